@@ -10,7 +10,9 @@ neighbour filter + flow pass + step-size pass) from the reference object's initi
 all clouds already resident in HBM, all registrations of the batch handed to ONE
 cvo_hip_align_many call (three engines of up to 32 slots each share the GPU; a slot's registration
 is one blockIdx.z slice of every kernel launch of its engine; a slot that falls free takes
-the next pair of the batch -- continuous batching).  `value` = registrations completed per second.  Side legs of the same run
+the next pair of the batch -- continuous batching).  `value` = registrations completed per second.  A plain run
+sets up, warms up, times `--steps` steps, writes the results of the last one under `--dump-outputs DIR` if given,
+and prints the line.  With `--full`, side legs of the same run
 (rank 0, N = 1; none of them inside the timed region): the same batch size with copies of
 ONE pair (`identical_pairs`), one registration at a time (`single_stream`), kernel
 durations by HIP events for the roofline objects, BASELINE configs[4] per GPU
@@ -19,7 +21,7 @@ this box (`cpu_baseline`) -- whose result for pair 0 is compared with the GPU's
 (`parity_vs_oracle`).
 
 One process per GPU; for N > 1 every rank runs its own batches (independent frame pairs:
-weak scaling, no data-path collective), and -- as a separately reported leg -- all ranks
+weak scaling, no data-path collective), and -- with `--full`, as a separately reported leg -- all ranks
 also run the target-sharded mode of BASELINE configs[3] (200k x 200k, rows split over the
 ranks, partial sums exchanged through peer mailboxes over xGMI, RCCL as the fall-back).
 
@@ -236,8 +238,13 @@ def emit(out):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every side leg as well (one-at-a-time rate, roofline, CPU "
+                         "baseline and parity, other modes and sizes, the sharded leg under N ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the results of the last timed step (iteration counts, final states) as DIR/<name>.npy")
     ap.add_argument("--points", type=int, default=10000, help="N = M of the synthetic pairs")
     ap.add_argument("--batch", type=int, default=64, help="frame pairs handed to one align_many call per step")
     ap.add_argument("--identical", action="store_true",
@@ -247,7 +254,7 @@ def parse():
                     help="budget of the main cpu_baseline sample (rank 0, N=1 only)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-frontend", action="store_true", help="skip the RGB-D front end side leg")
-    ap.add_argument("--no-side-legs", action="store_true", help="timed region + roofline only (profiling runs)")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: timed region + roofline only (profiling runs)")
     ap.add_argument("--saturation-batch", type=int, default=256,
                     help="side leg: distinct pairs per call with the tail of a call amortised (0 = skip)")
     ap.add_argument("--config4-points", type=int, default=20000, help="N = M of the BASELINE configs[4] leg")
@@ -264,13 +271,18 @@ def parse():
     ap.add_argument("--force-sharded-leg", action="store_true",
                     help="run the sharded leg even on one GPU (world size 1): exercises the "
                          "multi-rank code path where only one GPU is available")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def respawn_under_torchrun(gpus, torch):
-    """`python bench.py --gpus N` without a launcher: replace this process by
+    """`python bench.py --gpus N` without a launcher: run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`
-    (the driver's command for N > 1), so that both launch conventions run the same ranks."""
+    (the driver's command for N > 1) as a child and exit with its status, so that both launch conventions
+    run the same ranks.  A child, not exec: this process has initialised the GPU already, and replacing
+    such a process's program can take the GPU driver down."""
     on_dev0 = os.environ.get("CVO_BENCH_RANKS_ON_DEVICE0", "") not in ("", "0")
     have = torch.cuda.device_count()
     if have < gpus and not on_dev0:
@@ -287,11 +299,31 @@ def respawn_under_torchrun(gpus, torch):
            "--master-addr", "127.0.0.1", "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    rc = subprocess.call(cmd)
+    raise SystemExit(rc if rc >= 0 else 128 - rc)   # (a launcher killed by a signal: the shell's 128 + signal)
 
 
 def pair_seed(pkg, i):
     return pkg.data.SEED_CFG2 if i == 0 else pkg.data.SEED_CFG5_BASE + i
+
+
+def dump_outputs(path, pkg, its, states):
+    """What a caller of align_many received from the last timed step, registrations in batch order: the
+    iteration counts (`iterations.npy`) and every field of the final states (`<field>.npy`: R as B x 3 x 3,
+    the transforms as B x 4 x 4).  The inputs are seeded, so two builds can be compared file for file."""
+    import ctypes
+    os.makedirs(path, exist_ok=True)
+    arrays = {"iterations": np.array(its, np.float64)}
+    shapes = {"R": (3, 3), "transform": (4, 4), "prev_transform": (4, 4), "accum_transform": (4, 4)}
+    for name, ctype in pkg.capi.State._fields_:
+        if name == "pad_":
+            continue
+        dtype = np.float64 if ctype is ctypes.c_int32 else np.float32
+        a = np.array([np.array(getattr(s, name), dtype) for s in states])
+        arrays[name] = a.reshape((len(states),) + shapes.get(name, a.shape[1:]))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -441,8 +473,10 @@ def main():
                           "most pair tests are proven unnecessary, not executed",
             "batched_TFLOPs": sweep_flop_per_iter * float(it_sum.item()) / elapsed / 1e12,
             "peak_TFLOPs": PEAK_F32_TFLOPS}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, pkg, last_its, last_states)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- one registration at a time (latency view): the configs[1] pair on context 0, through
         # cvo_hip_align -- the call a sequential VO loop makes (ref src/cvo.cpp:361-420), BASELINE configs[1] read
         # literally.  Under N ranks: rank 0's GPU, the others wait at the next barrier.  The figures also go into
@@ -475,7 +509,7 @@ def main():
         out["equivalent_sweep_rate"]["single_stream_TFLOPs"] = \
             sweep_flop_per_iter / (out["single_stream"]["ms_per_iteration"] * 1e-3) / 1e12
         gpu_state0, gpu_iters0 = st1[0], its[0]
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # ---- the path that produced `value`, checked in this run: every registration of the last timed
         # step (engines, 32-slot tables, candidate lists) against the same pair registered on its own
         # (cvo_hip_align), bit for bit; four of them against the oracle in the cpu leg below
@@ -561,7 +595,7 @@ def main():
             out["parity_vs_oracle"] = parity
             batched_parity.update(batched_vs_oracle(pkg, pairs, last_states, last_its, acvo, cpu["cores"]))
         out.setdefault("parity_vs_oracle", {})["batched"] = batched_parity
-    if world > 1 and not args.no_side_legs:
+    if world > 1 and args.full and not args.no_side_legs:
         # BASELINE configs[4] IS "64 concurrent 20k x 20k across 8 GPUs": under N ranks every rank runs the leg on its own
         # registrations (collective: all ranks, or none -- an exception on one rank is agreed on before anybody waits)
         import threading
@@ -588,7 +622,7 @@ def main():
                 out["config"]["config4_registrations_per_s"] = c4["registrations_per_s"]
     # The target-sharded leg runs last and under a watchdog: the headline line above it must
     # not depend on it, not even if an exchange hangs.
-    if (world > 1 or args.force_sharded_leg) and args.sharded_steps > 0:
+    if ((world > 1 and args.full) or args.force_sharded_leg) and args.sharded_steps > 0:
         import threading
 
         def give_up():

@@ -199,7 +199,7 @@ def test_bench_multi_rank_rehearsal_on_one_gpu(launcher):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CVO_BENCH_RANKS_ON_DEVICE0="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    bench_args = [os.path.join(root, "bench.py"),
+    bench_args = [os.path.join(root, "bench.py"), "--full",
                   "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--points", "3000",
                   "--sharded-points", "20000", "--sharded-steps", "1", "--sharded-timeout", "120",
                   "--config4-points", "4000", "--config4-count", "4"]
@@ -239,3 +239,44 @@ def test_bench_multi_rank_rehearsal_on_one_gpu(launcher):
     assert "error" not in sh, sh
     assert sh["exchange"] == "mailbox" and sh["registrations_per_s"] > 0, sh
     assert sh["iterations"] > 0
+
+
+def test_bench_plain_run_dumps_its_last_step(pkg, po, tmp_path):
+    """A plain `bench.py` (no --full): the timed steps and the line, no side leg.  --dump-outputs writes what
+    the last timed step's align_many call returned; a second run of the same command writes the same bytes,
+    and pair 0 of the dump is the oracle's registration of the seeded pair."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+               "--points", "3000", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]
+        head = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in head, key
+        assert head["steps"] == 3 and head["value"] > 0 and head["ms_per_step"] > 0
+        assert head["value"] == pytest.approx(8 * 1e3 / head["ms_per_step"], rel=1e-5)
+        for key in ("roofline", "cpu_baseline", "parity_vs_oracle", "leg_errors"):
+            assert key not in head, key
+        runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = runs
+    assert sorted(a) == sorted(b) and {"iterations", "R", "T", "transform"} <= set(a)
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and a[name].shape[0] == 8, name
+        assert a[name].tobytes() == b[name].tobytes(), name
+    assert a["R"].shape == (8, 3, 3) and a["transform"].shape == (8, 4, 4)
+    xf, ff, xm, fm = pkg.data.synthetic_pair(3000, 3000, seed=pkg.data.SEED_CFG2)
+    p = po.default_params(po.MODE_CVO)
+    so = po.init_state(p)
+    n_or, _ = po.align(p, so, xf, ff, xm, fm, search=po.SEARCH_GRID, trace_cap=1)
+    assert a["iterations"][0] == n_or
+    assert np.array_equal(a["R"][0].ravel(), np.array(so.R, np.float32))
+    assert np.array_equal(a["T"][0], np.array(so.T, np.float32))

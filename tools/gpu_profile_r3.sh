@@ -6,7 +6,7 @@ ROOTDIR=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOTDIR/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOTDIR
-python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json; echo
 cd /tmp && export TMPDIR=/tmp
 # ---- the roofline object's own command: one engine of 22 pairs, flow-pass dispatches bracketed by HIP events
@@ -17,14 +17,14 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_r -o fetch -- $
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_r -o write -- $R > $OUT/pmc_write_r.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq_r -o sq -- $R > $OUT/pmc_sq_r.log 2>&1
 # ---- the timed region (three engines, 64 distinct pairs): kernel time shares
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_batch -o stats -- python $ROOTDIR/bench.py --steps 5 --warmup 1 --no-cpu --no-side-legs > $OUT/stats_batch.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_batch -o stats -- python $ROOTDIR/bench.py --full --steps 5 --warmup 1 --no-cpu --no-side-legs > $OUT/stats_batch.log 2>&1
 # ---- VALU issue of the batched run at saturation (256 distinct pairs per call), and its wall time without counters
 export CVO_HIP_GRAPH=1
 DISTINCT=1 python $ROOTDIR/tools/gpu_batch.py 10000 4 256 > $OUT/valu_wall.log 2>&1
 DISTINCT=1 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_valu -o p -- python $ROOTDIR/tools/gpu_batch.py 10000 1 256 > $OUT/pmc_valu.log 2>&1
 unset CVO_HIP_GRAPH
 # ---- one registration at a time (head mode): kernel trace + the wait counters of the post-step part
-S="python $ROOTDIR/bench.py --batch 1 --steps 5 --warmup 1 --no-cpu --no-side-legs"
+S="python $ROOTDIR/bench.py --full --batch 1 --steps 5 --warmup 1 --no-cpu --no-side-legs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- $S > $OUT/stats.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc_sq -o sq -- $S > $OUT/pmc_sq.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o fetch -- $S > $OUT/pmc_fetch.log 2>&1
