@@ -1,4 +1,5 @@
 """ctypes binding of include/cvo_hip.h (csrc/libcvo_hip.so)."""
+import collections
 import ctypes as C
 import os
 
@@ -20,7 +21,7 @@ SYMBOLS = [
     "cvo_hip_swap_moving_to_fixed", "cvo_hip_set_pcd_many", "cvo_hip_get_device_cloud", "cvo_hip_range_filter_grid_average", "cvo_hip_set_shard", "cvo_hip_shard_range",
     "cvo_hip_comm_unique_id", "cvo_hip_comm_init", "cvo_hip_set_allreduce",
     "cvo_hip_mailbox_create", "cvo_hip_mailbox_connect",
-    "cvo_hip_transform_pcd", "cvo_hip_flow", "cvo_hip_step_coeffs", "cvo_hip_pick_step",
+    "cvo_hip_transform_pcd", "cvo_hip_flow", "cvo_hip_step_coeffs", "cvo_hip_pose_hessian", "cvo_hip_pick_step",
     "cvo_hip_exp_se3", "cvo_hip_dist_se3", "cvo_hip_align", "cvo_hip_align_many",
     "cvo_hip_function_inner_product", "cvo_hip_function_inner_product_clouds",
     "cvo_hip_engine_profiling", "cvo_hip_get_engine_profile", "cvo_hip_get_engine_flow_trace", "cvo_hip_get_wave_load", "cvo_hip_set_graph_capture", "cvo_hip_set_profiling", "cvo_hip_get_profile", "cvo_hip_get_graph_stats", "cvo_hip_get_run_stats", "cvo_hip_get_run_clocks", "cvo_hip_get_mirror_retries", "cvo_hip_synchronize",
@@ -67,6 +68,22 @@ class Profile(C.Structure):
         ("self_ms", C.c_double), ("self_launches", C.c_int64), ("self_pairs", C.c_double),
         ("proc_flow_ms", C.c_double), ("proc_flow_launches", C.c_int64),
     ]
+
+
+class PoseHessianC(C.Structure):
+    """struct cvo_hip_pose_hessian."""
+    _fields_ = [
+        ("f", C.c_double), ("g", C.c_double * 6), ("H", C.c_double * 36),
+        ("nnz", C.c_int64), ("ell", C.c_float), ("pad_", C.c_int32),
+    ]
+
+
+# Context.pose_hessian's answer: f = sum a (float), g (6,), H (6, 6) float64 in (omega, v) order, nnz = |A| (int)
+PoseHessian = collections.namedtuple("PoseHessian", "f g H nnz")
+
+
+def pose_hessian_from_c(h):
+    return PoseHessian(float(h.f), np.array(h.g[:], np.float64), np.array(h.H[:], np.float64).reshape(6, 6), int(h.nnz))
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
@@ -122,6 +139,7 @@ def lib():
     L.cvo_hip_transform_pcd.argtypes = [vp, fp, fp]
     L.cvo_hip_flow.argtypes = [vp, C.c_float, dp]
     L.cvo_hip_step_coeffs.argtypes = [vp, fp, fp, C.c_float, dp]
+    L.cvo_hip_pose_hessian.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseHessianC)]
     L.cvo_hip_pick_step.argtypes = [dp, C.c_float, fp]
     L.cvo_hip_exp_se3.argtypes = [fp, fp, C.c_float, fp, fp]
     L.cvo_hip_dist_se3.argtypes = [fp, fp, C.c_float, fp]
@@ -375,6 +393,19 @@ class Context:
         self._chk(self._L.cvo_hip_step_coeffs(self._ctx, fptr(omega), fptr(v), np.float32(ell),
                                               dptr(out)), "step_coeffs")
         return out
+
+    def pose_hessian_raw(self, R, T, ell):
+        """cvo_hip_pose_hessian: the C struct as the library filled it (PoseHessianC)."""
+        R, T = f32(R).reshape(9), f32(T).reshape(3)
+        out = PoseHessianC()
+        self._chk(self._L.cvo_hip_pose_hessian(self._ctx, fptr(R), fptr(T), np.float32(ell), C.byref(out)),
+                  "pose_hessian")
+        return out
+
+    def pose_hessian(self, R, T, ell):
+        """The 6x6 Hessian of the CVO objective at the pose (R, T) and length scale ell (include/cvo_hip.h
+        cvo_hip_pose_hessian): PoseHessian(f, g, H, nnz).  The context is left as transform_pcd(R, T) leaves it."""
+        return pose_hessian_from_c(self.pose_hessian_raw(R, T, ell))
 
     def align(self, state, trace_cap=2000):
         tr = (Trace * trace_cap)() if trace_cap > 0 else None

@@ -368,7 +368,7 @@ int cvo_hip_destroy(cvo_hip_ctx *ctx)
                     (void *)ctx->moving.feat, (void *)ctx->fixed.seg, (void *)ctx->moving.seg,
                     (void *)ctx->scratch_a.pos, (void *)ctx->scratch_a.feat, (void *)ctx->scratch_a.seg,
                     (void *)ctx->scratch_b.pos, (void *)ctx->scratch_b.feat, (void *)ctx->scratch_b.seg, (void *)ctx->st, (void *)ctx->st2, ctx->part_flow.p, ctx->part_xx.p,
-                    ctx->part_yy.p, ctx->part_step.p, ctx->run_mail.p, (void *)ctx->trace_dev, ctx->kept_cnt.p, ctx->pos_bt.p, ctx->cand[0].p, ctx->cand[1].p, ctx->cand[2].p, ctx->cand_xyb.p, ctx->cand_cnt_xyb.p, ctx->cand_sfb[0].p, ctx->cand_sfb[1].p, ctx->cand_cnt_sfb[0].p, ctx->cand_cnt_sfb[1].p, ctx->cand_cnt[0].p,
+                    ctx->part_yy.p, ctx->part_step.p, ctx->part_hess.p, ctx->run_mail.p, (void *)ctx->trace_dev, ctx->kept_cnt.p, ctx->pos_bt.p, ctx->cand[0].p, ctx->cand[1].p, ctx->cand[2].p, ctx->cand_xyb.p, ctx->cand_cnt_xyb.p, ctx->cand_sfb[0].p, ctx->cand_sfb[1].p, ctx->cand_cnt_sfb[0].p, ctx->cand_cnt_sfb[1].p, ctx->cand_cnt[0].p,
                     ctx->cand_cnt[1].p, ctx->cand_cnt[2].p})
         if (p) (void)hipFree(p);
     for (int l = 0; l < LIST_N; ++l) {
@@ -658,6 +658,87 @@ int cvo_hip_step_coeffs(cvo_hip_ctx *ctx, const float omega[3], const float v[3]
     rc = fetch_red(ctx, RED_STEP, 4, bcde);
     if (!rc && ctx->profiling) rc = drain_events(ctx);
     return rc;
+}
+
+int cvo_hip_pose_hessian(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
+                         cvo_hip_pose_hessian_t *out)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (!R || !T || !out) return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_hessian: null argument");
+    if (!(std::isfinite(ell) && ell > 0.0f))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_hessian: ell must be finite and > 0");
+    if (ctx->fixed.n <= 0 || ctx->moving.n <= 0)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_hessian: both clouds must be set");
+    if (multi_rank(ctx) || ctx->mailbox)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_hessian: not with a communicator, mailboxes or an all-reduce "
+                                              "hook attached (sums over ranks are the caller's)");
+    int rc = cvo_hip_transform_pcd(ctx, R, T);
+    if (rc) return rc;
+    DevState *h = &ctx->st_host[kPollSlots];
+    h->kc = make_kconsts(ctx->dprm, ell);
+    h->kc_ell = -1.0f;   // (never equal to an ell: prepare_iteration recomputes)
+    rc = fill_filter_geometry(ctx, h);
+    if (rc) return rc;
+    compute_filter_bounds(h, false);
+    rc = push_state_fields(ctx, offsetof(DevState, kc), offsetof(DevState, xi) - offsetof(DevState, kc));
+    if (rc) return rc;
+    // A and its weights exactly as cvo_hip_flow keeps them: filter + PROC_FLOW, which records the kept list
+    // (outside the loop the flow pass sums a: ProcessArgs::need_d2)
+    int rlo, rhi, slo, shi;
+    shard_ranges(ctx, rlo, rhi, slo, shi);
+    for (bool redo = true; redo;) {
+        rc = zero_counters(ctx);
+        if (!rc) rc = enqueue_filter(ctx, LIST_XY, ctx->fixed, rlo, rhi, 0, ctx->moving, 1, 0);
+        if (!rc) rc = enqueue_process(ctx, PROC_FLOW, LIST_XY, ctx->part_flow, ctx->fixed.pos,
+                                      ctx->fixed.feat, 0, ctx->moving.pos, ctx->moving.feat, 1, 0, 0);
+        if (!rc) rc = check_overflow_and_grow(ctx, &redo);
+        if (rc) return rc;
+    }
+    // f and nnz: the flow partials reduced as cvo_hip_function_inner_product reduces them
+    PostFlowArgs pa{};
+    pa.st = ctx->st;
+    pa.prm = ctx->dprm;
+    pa.prm.mode = CVO_HIP_MODE_CVO;   // no self terms here
+    pa.nblk = ctx->proc_blocks;
+    pa.flags = POST_REDUCE;
+    pa.part_flow = (const double *)ctx->part_flow.p;
+    launch_post_flow(pa, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    // the Hessian pass over the kept list, then its fixed-order reduction
+    rc = ensure_buf(ctx, ctx->part_hess, (size_t)(PROC_BLOCKS + 1) * NACC_HESS * sizeof(double));
+    if (rc) return rc;
+    HessArgs ha{};
+    ha.pos_a = ctx->fixed.pos;
+    ha.pos_b = ctx->moving.pos;
+    ha.kept_ij = (const uint2 *)ctx->lists[LIST_KEPT].a.p;
+    ha.kept_a = (const float *)ctx->lists[LIST_KEPT].b.p;
+    ha.kept_cnt = (const uint32_t *)ctx->kept_cnt.p;
+    ha.st = ctx->st;
+    ha.partials = (double *)ctx->part_hess.p;
+    ha.out = ha.partials + (size_t)PROC_BLOCKS * NACC_HESS;
+    ha.nblk = ctx->proc_blocks;
+    ha.kept_wcap = ctx->lists[LIST_KEPT].cap / (uint32_t)(4 * ctx->proc_blocks);   // (enqueue_process's slice)
+    ha.kept_packed = kept_format(ctx, &ha.kept_ebase);
+    ha.inv_l2 = 1.0f / (ell * ell);
+    ha.inv_l = 1.0f / ell;
+    launch_pose_hessian(ha, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    double sums[NACC_HESS];
+    HIP_TRY(ctx, hipMemcpyAsync(sums, ha.out, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
+    double red[9];
+    rc = fetch_red(ctx, RED_FLOW, 9, red);   // (synchronises the stream)
+    if (rc) return rc;
+    cvo_hip_pose_hessian_t r{};
+    r.f = red[6];
+    r.nnz = (int64_t)red[8];
+    r.ell = ell;
+    for (int k = 0; k < 6; ++k) r.g[k] = sums[k];
+    for (int k = 0, q = 6; k < 6; ++k)
+        for (int l = k; l < 6; ++l, ++q) r.H[6 * k + l] = r.H[6 * l + k] = sums[q];
+    *out = r;
+    if (ctx->profiling) return drain_events(ctx);
+    return CVO_HIP_OK;
 }
 
 int cvo_hip_pick_step(const double bcde[4], float min_step, float *step)

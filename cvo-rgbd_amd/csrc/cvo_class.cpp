@@ -169,6 +169,20 @@ void registration::align()
     publish();
 }
 
+void registration::align(cvo_hip_pose_hessian_t *out)
+{
+    if (!out) {
+        align();
+        return;
+    }
+    if (!have_moving_) throw std::runtime_error("align(): set_pcd() must precede each align()");
+    check(cvo_hip_align(ctx_, &state_, nullptr, 0, &n_iter_), "cvo_hip_align");
+    check(cvo_hip_pose_hessian(ctx_, state_.R, state_.T, state_.ell, out), "cvo_hip_pose_hessian");
+    check(cvo_hip_swap_moving_to_fixed(ctx_), "cvo_hip_swap_moving_to_fixed");
+    have_moving_ = false;
+    publish();
+}
+
 void registration::align_many(registration *const *objects, int count)
 {
     std::vector<cvo_hip_ctx *> ctxs((size_t)count);

@@ -817,6 +817,182 @@ struct PrepareInit {
     int32_t iter, n_fixed, done;
     float center[3], xmax, y0max;
 };
+// ---------------------------------------------------------------------------
+// Device helpers shared by the list kernels (cvo_kernels.hip) and the pose-Hessian pass (cvo_hessian.hip)
+// ---------------------------------------------------------------------------
+// (CVO_GLOBAL: the explicit global address space, see PairSrc in cvo_kernels.hip)
+#define CVO_GLOBAL __attribute__((address_space(1)))
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+// Eigen: transform.linear()*p + translation, coefficient order, no FMA
+__device__ __forceinline__ float4 apply_tf(const float *Rt, const float *t, const float4 p)
+{
+    float4 o;
+    o.x = ((Rt[0] * p.x + Rt[1] * p.y) + Rt[2] * p.z) + t[0];
+    o.y = ((Rt[3] * p.x + Rt[4] * p.y) + Rt[5] * p.z) + t[1];
+    o.z = ((Rt[6] * p.x + Rt[7] * p.y) + Rt[8] * p.z) + t[2];
+    o.w = p.w;   // the point's 5th feature rides along
+    return o;
+}
+
+template <bool W>
+__device__ __forceinline__ float4 load_pos(const void *base, unsigned byte_off)
+{
+    return *reinterpret_cast<const float4 *>(static_cast<const char *>(base) + byte_off);   // (.w unused: the compiler narrows the load itself)
+}
+template <bool W>
+__device__ __forceinline__ float4 load_pos(const CVO_GLOBAL char *base, unsigned byte_off)
+{
+    if (W) {
+        const f32x4_t v = *reinterpret_cast<const CVO_GLOBAL f32x4_t *>(base + byte_off);
+        return make_float4(v.x, v.y, v.z, v.w);
+    }
+    typedef float f32x3_t __attribute__((ext_vector_type(3)));
+    const f32x3_t v = *reinterpret_cast<const CVO_GLOBAL f32x3_t *>(base + byte_off);   // (12 of the row's 16 bytes)
+    return make_float4(v.x, v.y, v.z, 0.0f);
+}
+__device__ __forceinline__ uint2 load8(const CVO_GLOBAL char *base, unsigned idx)
+{
+#ifdef CVO_NT_LISTS
+    const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const CVO_GLOBAL u32x2_t *>(base) + idx);
+#else
+    const u32x2_t v = reinterpret_cast<const CVO_GLOBAL u32x2_t *>(base)[idx];
+#endif
+    return make_uint2(v.x, v.y);
+}
+// Kept-list entries (ProcessArgs::kept_packed).  `raw_w`: the entry's word of the weight array (mode 0 only).
+__device__ __forceinline__ uint2 kept_pack(const int mode, const unsigned ebase, const unsigned i, const unsigned j, const float w)
+{
+    if (mode == 1) return make_uint2(i | (j << 16), __float_as_uint(w));
+    const unsigned wb = __float_as_uint(w);
+    return make_uint2(i | (j << 18), (j >> 14) | (((wb >> 23) - ebase) << 4) | ((wb & 0x7fffffu) << 8));
+}
+__device__ __forceinline__ void kept_unpack(const int mode, const unsigned ebase, const uint2 e, const float raw_w, unsigned &i,
+                                            unsigned &j, float &w)
+{
+    if (mode == 0) { i = e.x; j = e.y; w = raw_w; }
+    else if (mode == 1) { i = e.x & 0xffffu; j = e.x >> 16; w = __uint_as_float(e.y); }
+    else {
+        i = e.x & 0x3ffffu;
+        j = (e.x >> 18) | ((e.y & 0xfu) << 14);
+        w = __uint_as_float(((((e.y >> 4) & 0xfu) + ebase) << 23) | ((e.y >> 8) & 0x7fffffu));
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Wave-wide float64 sums of N per-lane values, written to dst[0..N).
+//
+// A butterfly per value costs 6 exchanges (12 ds_bpermute for a double), and the
+// LDS pipe -- not the VALU -- was what the list kernels waited on.  This is a
+// reduce-scatter instead: at the level with lane mask OFF the lower lane of each
+// pair keeps the first half of the values and the upper lane the second half,
+// each adding what its partner held of its own half, so the number of live
+// values halves per level (9 -> 5 -> 3 -> 2 -> 1: 13 exchanges instead of 54).
+// Levels 32 and 16 use gfx950's v_permlane32_swap / v_permlane16_swap, levels 8,
+// 4, 2, 1 DPP moves (row_mirror, row_half_mirror, quad_perm: partners l^15, l^7,
+// l^2, l^1 -- the masks 32,16,15,7,2,1 are independent, so every level joins two
+// disjoint halves): nothing goes through the LDS crossbar.  The order of the
+// additions is fixed: results are reproducible.
+template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double x)
+{
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+template <int OFF> __device__ __forceinline__ double wave_xchg(double x)
+{
+    if constexpr (OFF == 8) return dpp_mov_f64<0x140>(x);        // row_mirror
+    else if constexpr (OFF == 4) return dpp_mov_f64<0x141>(x);   // row_half_mirror
+    else if constexpr (OFF == 2) return dpp_mov_f64<0x4E>(x);    // quad_perm [2,3,0,1]
+    else if constexpr (OFF == 1) return dpp_mov_f64<0xB1>(x);    // quad_perm [1,0,3,2]
+    else return __shfl_xor(x, OFF, 64);
+}
+
+template <int N, int OFF> struct WaveRS {
+    static constexpr int H = (N + 1) / 2;
+    static __device__ __forceinline__ void run(double *v, int lane)
+    {
+        if constexpr (N > 1) {
+            const bool upper = (lane & OFF) != 0;
+#pragma unroll
+            for (int q = 0; q < H; ++q) {
+                const double hi = (q + H < N) ? v[q + H] : 0.0;
+                if constexpr (OFF >= 16) {
+                    // gfx950 v_permlane{32,16}_swap: the upper half (odd rows) of the
+                    // first operand trades places with the lower half (even rows) of
+                    // the second, so {kept, received} come out without any select
+                    const unsigned xl = (unsigned)__double2loint(v[q]), xh = (unsigned)__double2hiint(v[q]);
+                    const unsigned yl = (unsigned)__double2loint(hi), yh = (unsigned)__double2hiint(hi);
+                    double k0, k1;
+                    if constexpr (OFF == 32) {
+                        const auto rl = __builtin_amdgcn_permlane32_swap(xl, yl, false, false);
+                        const auto rh = __builtin_amdgcn_permlane32_swap(xh, yh, false, false);
+                        k0 = __hiloint2double((int)rh[0], (int)rl[0]);
+                        k1 = __hiloint2double((int)rh[1], (int)rl[1]);
+                    } else {
+                        const auto rl = __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
+                        const auto rh = __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
+                        k0 = __hiloint2double((int)rh[0], (int)rl[0]);
+                        k1 = __hiloint2double((int)rh[1], (int)rl[1]);
+                    }
+                    v[q] = k0 + k1;
+                } else {
+                    const double send = upper ? v[q] : hi;
+                    const double keep = upper ? hi : v[q];
+                    v[q] = keep + wave_xchg<OFF>(send);
+                }
+            }
+        } else {
+            v[0] += wave_xchg<OFF>(v[0]);
+        }
+        if constexpr (OFF > 1) WaveRS<(N > 1 ? H : 1), OFF / 2>::run(v, lane);
+    }
+    // which of the N sums this lane ends up holding in v[0] (-1: none / a duplicate)
+    static __device__ __forceinline__ int slot(int lane)
+    {
+        int p = 0;
+        if constexpr (OFF > 1) p = WaveRS<(N > 1 ? H : 1), OFF / 2>::slot(lane);
+        if (p < 0) return -1;
+        if constexpr (N > 1) {
+            p += (lane & OFF) ? H : 0;
+            return p < N ? p : -1;
+        } else {
+            return (lane & OFF) ? -1 : p;   // plain butterfly level: one writer per pair
+        }
+    }
+};
+
+template <int N>
+__device__ __forceinline__ void wave_sums(double (&v)[N], int lane, double *dst)
+{
+    WaveRS<N, 32>::run(v, lane);
+    const int p = WaveRS<N, 32>::slot(lane);
+    if (p >= 0) dst[p] = v[0];
+}
+
+
+// The pose Hessian of the CVO objective (cvo_hessian.hip, include/cvo_hip.h cvo_hip_pose_hessian): one pass over the
+// kept list a PROC_FLOW pass recorded, then a one-block fixed-order reduction of its block partials.
+constexpr int NACC_HESS = 27;   // g[6], then H's upper triangle row by row (21)
+struct HessArgs {
+    const float4 *pos_a;        // the fixed cloud (x)
+    const float4 *pos_b;        // the moving cloud as set (z): y = [Rt|t] z with the state's Rt, t
+    const uint2 *kept_ij;       // the kept list, its weights (kept_packed == 0) and per-wave counts (ProcessArgs)
+    const float *kept_a;
+    const uint32_t *kept_cnt;
+    const DevState *st;
+    double *partials;           // [NACC_HESS][nblk]
+    double *out;                // [NACC_HESS]
+    uint32_t kept_wcap;
+    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
+    int kept_packed;
+    unsigned kept_ebase;
+    float inv_l2, inv_l;        // 1 / ell^2, 1 / ell
+};
+void launch_pose_hessian(const HessArgs &a, hipStream_t s);
+
 void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t *build_masks = nullptr, const PrepareInit *init = nullptr);
 void launch_filter(const FilterArgs &a, dim3 grid, hipStream_t s, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);

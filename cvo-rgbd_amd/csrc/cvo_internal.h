@@ -336,6 +336,7 @@ struct cvo_hip_ctx {
     int cur_trace_cap = 0;
     hipEvent_t poll_ev[kPollSlots]{};
     DevBuf part_flow, part_xx, part_yy, part_step;   // [PROC_BLOCKS][NACC_MAX] float64
+    DevBuf part_hess;                    // cvo_hip_pose_hessian: [NACC_HESS][nblk] block partials, then the [NACC_HESS] sums
     List lists[LIST_N];
     DevBuf kept_cnt;                 // uint32[PROC_WAVES]
     cvo_hip_trace *trace_dev = nullptr;
@@ -429,6 +430,7 @@ bool multi_rank(const cvo_hip_ctx *ctx);
 DevParams loop_params(const cvo_hip_ctx *ctx);
 hipStream_t loop_stream(const cvo_hip_ctx *ctx);
 int enqueue_filter(cvo_hip_ctx *ctx, int list, const Cloud &ca, int row_lo, int row_hi, int tf_a, const Cloud &cb, int tf_b, int check_done);
+int kept_format(const cvo_hip_ctx *ctx, unsigned *ebase);
 int enqueue_process(cvo_hip_ctx *ctx, int mode, int list, DevBuf &part, const float4 *pos_a, const float *feat_a, int tf_a,
                     const float4 *pos_b, const float *feat_b, int tf_b, int first_counted, int check_done);
 int drain_events(cvo_hip_ctx *ctx, int n_exec = -1, const DevState *fin = nullptr);

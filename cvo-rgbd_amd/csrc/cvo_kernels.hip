@@ -42,17 +42,6 @@ namespace cvo_dev {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Eigen: transform.linear()*p + translation, coefficient order, no FMA
-__device__ __forceinline__ float4 apply_tf(const float *Rt, const float *t, const float4 p)
-{
-    float4 o;
-    o.x = ((Rt[0] * p.x + Rt[1] * p.y) + Rt[2] * p.z) + t[0];
-    o.y = ((Rt[3] * p.x + Rt[4] * p.y) + Rt[5] * p.z) + t[1];
-    o.z = ((Rt[6] * p.x + Rt[7] * p.y) + Rt[8] * p.z) + t[2];
-    o.w = p.w;   // the point's 5th feature rides along
-    return o;
-}
-
 __device__ __forceinline__ float mv_row(const float *m, float x, float y, float z)
 {
     return (m[0] * x + m[1] * y) + m[2] * z;
@@ -554,99 +543,7 @@ __device__ __forceinline__ float weight_from_ck(const KernConsts &kc, float d2, 
     return a > kc.sp ? a : 0.0f;
 }
 
-
-// ---------------------------------------------------------------------------
-// Wave-wide float64 sums of N per-lane values, written to dst[0..N).
-//
-// A butterfly per value costs 6 exchanges (12 ds_bpermute for a double), and the
-// LDS pipe -- not the VALU -- was what the list kernels waited on.  This is a
-// reduce-scatter instead: at the level with lane mask OFF the lower lane of each
-// pair keeps the first half of the values and the upper lane the second half,
-// each adding what its partner held of its own half, so the number of live
-// values halves per level (9 -> 5 -> 3 -> 2 -> 1: 13 exchanges instead of 54).
-// Levels 32 and 16 use gfx950's v_permlane32_swap / v_permlane16_swap, levels 8,
-// 4, 2, 1 DPP moves (row_mirror, row_half_mirror, quad_perm: partners l^15, l^7,
-// l^2, l^1 -- the masks 32,16,15,7,2,1 are independent, so every level joins two
-// disjoint halves): nothing goes through the LDS crossbar.  The order of the
-// additions is fixed: results are reproducible.
-template <int CTRL> __device__ __forceinline__ double dpp_mov_f64(double x)
-{
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-template <int OFF> __device__ __forceinline__ double wave_xchg(double x)
-{
-    if constexpr (OFF == 8) return dpp_mov_f64<0x140>(x);        // row_mirror
-    else if constexpr (OFF == 4) return dpp_mov_f64<0x141>(x);   // row_half_mirror
-    else if constexpr (OFF == 2) return dpp_mov_f64<0x4E>(x);    // quad_perm [2,3,0,1]
-    else if constexpr (OFF == 1) return dpp_mov_f64<0xB1>(x);    // quad_perm [1,0,3,2]
-    else return __shfl_xor(x, OFF, 64);
-}
-
-template <int N, int OFF> struct WaveRS {
-    static constexpr int H = (N + 1) / 2;
-    static __device__ __forceinline__ void run(double *v, int lane)
-    {
-        if constexpr (N > 1) {
-            const bool upper = (lane & OFF) != 0;
-#pragma unroll
-            for (int q = 0; q < H; ++q) {
-                const double hi = (q + H < N) ? v[q + H] : 0.0;
-                if constexpr (OFF >= 16) {
-                    // gfx950 v_permlane{32,16}_swap: the upper half (odd rows) of the
-                    // first operand trades places with the lower half (even rows) of
-                    // the second, so {kept, received} come out without any select
-                    const unsigned xl = (unsigned)__double2loint(v[q]), xh = (unsigned)__double2hiint(v[q]);
-                    const unsigned yl = (unsigned)__double2loint(hi), yh = (unsigned)__double2hiint(hi);
-                    double k0, k1;
-                    if constexpr (OFF == 32) {
-                        const auto rl = __builtin_amdgcn_permlane32_swap(xl, yl, false, false);
-                        const auto rh = __builtin_amdgcn_permlane32_swap(xh, yh, false, false);
-                        k0 = __hiloint2double((int)rh[0], (int)rl[0]);
-                        k1 = __hiloint2double((int)rh[1], (int)rl[1]);
-                    } else {
-                        const auto rl = __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
-                        const auto rh = __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
-                        k0 = __hiloint2double((int)rh[0], (int)rl[0]);
-                        k1 = __hiloint2double((int)rh[1], (int)rl[1]);
-                    }
-                    v[q] = k0 + k1;
-                } else {
-                    const double send = upper ? v[q] : hi;
-                    const double keep = upper ? hi : v[q];
-                    v[q] = keep + wave_xchg<OFF>(send);
-                }
-            }
-        } else {
-            v[0] += wave_xchg<OFF>(v[0]);
-        }
-        if constexpr (OFF > 1) WaveRS<(N > 1 ? H : 1), OFF / 2>::run(v, lane);
-    }
-    // which of the N sums this lane ends up holding in v[0] (-1: none / a duplicate)
-    static __device__ __forceinline__ int slot(int lane)
-    {
-        int p = 0;
-        if constexpr (OFF > 1) p = WaveRS<(N > 1 ? H : 1), OFF / 2>::slot(lane);
-        if (p < 0) return -1;
-        if constexpr (N > 1) {
-            p += (lane & OFF) ? H : 0;
-            return p < N ? p : -1;
-        } else {
-            return (lane & OFF) ? -1 : p;   // plain butterfly level: one writer per pair
-        }
-    }
-};
-
-template <int N>
-__device__ __forceinline__ void wave_sums(double (&v)[N], int lane, double *dst)
-{
-    WaveRS<N, 32>::run(v, lane);
-    const int p = WaveRS<N, 32>::slot(lane);
-    if (p >= 0) dst[p] = v[0];
-}
+// (the wave-wide float64 sums, WaveRS / wave_sums, live in cvo_device.h)
 
 template <int MODE> struct NAcc;
 template <> struct NAcc<PROC_FLOW> { static constexpr int n = NACC_FLOW; };
@@ -730,24 +627,7 @@ __device__ __forceinline__ ProcHead proc_head_global(const ProcessArgs &a, const
     return h;
 }
 
-// Kept-list entries (ProcessArgs::kept_packed).  `raw_w`: the entry's word of the weight array (mode 0 only).
-__device__ __forceinline__ uint2 kept_pack(const int mode, const unsigned ebase, const unsigned i, const unsigned j, const float w)
-{
-    if (mode == 1) return make_uint2(i | (j << 16), __float_as_uint(w));
-    const unsigned wb = __float_as_uint(w);
-    return make_uint2(i | (j << 18), (j >> 14) | (((wb >> 23) - ebase) << 4) | ((wb & 0x7fffffu) << 8));
-}
-__device__ __forceinline__ void kept_unpack(const int mode, const unsigned ebase, const uint2 e, const float raw_w, unsigned &i,
-                                            unsigned &j, float &w)
-{
-    if (mode == 0) { i = e.x; j = e.y; w = raw_w; }
-    else if (mode == 1) { i = e.x & 0xffffu; j = e.x >> 16; w = __uint_as_float(e.y); }
-    else {
-        i = e.x & 0x3ffffu;
-        j = (e.x >> 18) | ((e.y & 0xfu) << 14);
-        w = __uint_as_float(((((e.y >> 4) & 0xfu) + ebase) << 23) | ((e.y >> 8) & 0x7fffffu));
-    }
-}
+// (kept-list entries, kept_pack / kept_unpack, and the gathers load_pos / load8: cvo_device.h)
 
 // One pair of the exact pass.  PROC_FLOW / PROC_SELF: membership test of
 // se_kernel (ref cvo.cpp:125-152) and the flow / self sums; returns the weight
@@ -760,9 +640,6 @@ __device__ __forceinline__ void kept_unpack(const int mode, const unsigned ebase
 // through the scalar cache that the round's gathers wait for.
 // (A pointer that went through the pin is an opaque value to the compiler: without the explicit global address
 // space its loads would become flat ones.)
-#define CVO_GLOBAL __attribute__((address_space(1)))
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 struct PairSrc {
     const CVO_GLOBAL char *pos_a; const float *feat_a;
     const CVO_GLOBAL char *pos_b; const float *feat_b;
@@ -799,31 +676,6 @@ template <bool PIN> __device__ __forceinline__ PairSrc pin_pair_src(const Proces
     p.feat_a = a.feat_a; p.feat_b = a.feat_b;
     p.tf_a = (int)pin_u32<PIN>((unsigned)a.tf_a); p.tf_b = (int)pin_u32<PIN>((unsigned)a.tf_b);
     return p;
-}
-template <bool W>
-__device__ __forceinline__ float4 load_pos(const void *base, unsigned byte_off)
-{
-    return *reinterpret_cast<const float4 *>(static_cast<const char *>(base) + byte_off);   // (.w unused: the compiler narrows the load itself)
-}
-template <bool W>
-__device__ __forceinline__ float4 load_pos(const CVO_GLOBAL char *base, unsigned byte_off)
-{
-    if (W) {
-        const f32x4_t v = *reinterpret_cast<const CVO_GLOBAL f32x4_t *>(base + byte_off);
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    typedef float f32x3_t __attribute__((ext_vector_type(3)));
-    const f32x3_t v = *reinterpret_cast<const CVO_GLOBAL f32x3_t *>(base + byte_off);   // (12 of the row's 16 bytes)
-    return make_float4(v.x, v.y, v.z, 0.0f);
-}
-__device__ __forceinline__ uint2 load8(const CVO_GLOBAL char *base, unsigned idx)
-{
-#ifdef CVO_NT_LISTS
-    const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const CVO_GLOBAL u32x2_t *>(base) + idx);
-#else
-    const u32x2_t v = reinterpret_cast<const CVO_GLOBAL u32x2_t *>(base)[idx];
-#endif
-    return make_uint2(v.x, v.y);
 }
 __device__ __forceinline__ void store8(const CVO_GLOBAL char *base, unsigned idx, unsigned x, unsigned y)
 {

@@ -214,6 +214,31 @@ int enqueue_filter(cvo_hip_ctx *ctx, int list, const Cloud &ca, int row_lo, int 
     return CVO_HIP_OK;
 }
 
+// The form of the kept list's entries for the clouds and parameters set (ProcessArgs::kept_packed; *ebase: its
+// kept_ebase).  The flow pass that records the list and every pass that streams it back take it from here.
+int kept_format(const cvo_hip_ctx *ctx, unsigned *ebase)
+{
+    const bool no_pack = ctx->opt.no_pack;   // (test switch "kept_pack" = 0: 8 + 4 byte kept entries)
+    const int weight = ctx->prm.color_scale > 0.0f ? 1 : 0;   // (the MATLAB object's weight: ProcessArgs::weight)
+    *ebase = 0;
+    if (!no_pack && ctx->fixed.np <= 65536 && ctx->moving.np <= 65536) return 1;
+    if (!no_pack && weight == 0 && ctx->fixed.np <= 262144 && ctx->moving.np <= 262144) {
+        // 8 bytes for larger clouds too (ProcessArgs::kept_packed == 2): a member's weight a = ck * k is a positive
+        // float32 with sp < a <= fl(fl(c_sigma^2) fl(sigma^2)) -- the two exp are <= 1 (ref cvo.cpp:143-153 as
+        // pair_weight computes it); if those two bounds lie within 16 binades, 4 bits of exponent do
+        const float amax = (float)ctx->dprm.cs2_d * (float)ctx->dprm.s2_d;
+        uint32_t blo, bhi;
+        std::memcpy(&blo, &ctx->dprm.sp, sizeof(blo));
+        std::memcpy(&bhi, &amax, sizeof(bhi));
+        const uint32_t elo = blo >> 23, ehi = bhi >> 23;   // (both positive: the sign bit is clear)
+        if (ctx->dprm.sp > 0.0f && amax > ctx->dprm.sp && elo >= 1 && ehi < 255 && ehi - elo <= 15) {
+            *ebase = elo;
+            return 2;
+        }
+    }
+    return 0;
+}
+
 int enqueue_process(cvo_hip_ctx *ctx, int mode, int list, DevBuf &part, const float4 *pos_a,
                     const float *feat_a, int tf_a, const float4 *pos_b, const float *feat_b,
                     int tf_b, int first_counted, int check_done)
@@ -255,22 +280,7 @@ int enqueue_process(cvo_hip_ctx *ctx, int mode, int list, DevBuf &part, const fl
     a.check_done = check_done;
     a.need_d2 = (ctx->prm.mode == CVO_HIP_MODE_ACVO || !ctx->in_loop || ctx->cur_trace_cap > 0) ? 1 : 0;   // (a trace record holds the sum of the weights)
     a.weight = ctx->prm.color_scale > 0.0f ? 1 : 0;   // the MATLAB object's weight: its own instantiation
-    const bool no_pack = ctx->opt.no_pack;   // (test switch "kept_pack" = 0: 8 + 4 byte kept entries)
-    a.kept_packed = (!no_pack && ctx->fixed.np <= 65536 && ctx->moving.np <= 65536) ? 1 : 0;
-    if (!a.kept_packed && !no_pack && a.weight == 0 && ctx->fixed.np <= 262144 && ctx->moving.np <= 262144) {
-        // 8 bytes for larger clouds too (ProcessArgs::kept_packed == 2): a member's weight a = ck * k is a positive
-        // float32 with sp < a <= fl(fl(c_sigma^2) fl(sigma^2)) -- the two exp are <= 1 (ref cvo.cpp:143-153 as
-        // pair_weight computes it); if those two bounds lie within 16 binades, 4 bits of exponent do
-        const float amax = (float)ctx->dprm.cs2_d * (float)ctx->dprm.s2_d;
-        uint32_t blo, bhi;
-        std::memcpy(&blo, &ctx->dprm.sp, sizeof(blo));
-        std::memcpy(&bhi, &amax, sizeof(bhi));
-        const uint32_t elo = blo >> 23, ehi = bhi >> 23;   // (both positive: the sign bit is clear)
-        if (ctx->dprm.sp > 0.0f && amax > ctx->dprm.sp && elo >= 1 && ehi < 255 && ehi - elo <= 15) {
-            a.kept_packed = 2;
-            a.kept_ebase = elo;
-        }
-    }
+    a.kept_packed = kept_format(ctx, &a.kept_ebase);
     if ((mode == PROC_FLOW && list == LIST_XY) || (mode == PROC_SELF && (list == LIST_XX || list == LIST_YY))) {
         const bool no_cand = ctx->opt.no_cand;
         ctx->ck_nblk[list] = 0;

@@ -26,6 +26,7 @@ class _Registration:
         self.accum_transform = np.eye(4, dtype=np.float32)
         self.num_iterations = 0
         self.trace = []
+        self.hessian = None   # align(hessian=True) publishes the pose Hessian here
         self._have_moving = False
 
     def _publish(self):
@@ -59,34 +60,44 @@ class _Registration:
         if not first:
             self.align(trace_cap=trace_cap)
 
-    def align(self, trace_cap=0):
-        """ref src/cvo.cpp:361-420."""
+    def align(self, trace_cap=0, hessian=False):
+        """ref src/cvo.cpp:361-420.
+
+        hessian=True: after the loop, evaluate the pose Hessian of the CVO objective at the final R, T and
+        length scale (capi.Context.pose_hessian, include/cvo_hip.h cvo_hip_pose_hessian) before the moving
+        cloud becomes the fixed one, and publish it as ``self.hessian`` (a capi.PoseHessian: f, g, H, nnz).
+        -H is the information-like quantity of the registration; no noise model is implied.  The
+        registration itself is the same bit for bit either way."""
         if not self._have_moving:
             raise capi.CvoHipError("align(): set_pcd() must precede each align()")
         self.num_iterations, self.trace = self.ctx.align(self.state, trace_cap=trace_cap)
+        if hessian:
+            s = self.state
+            self.hessian = self.ctx.pose_hessian(np.array(s.R, np.float32), np.array(s.T, np.float32), s.ell)
         self.ctx.swap_moving_to_fixed()   # ptr_fixed_pcd = std::move(ptr_moving_pcd)
         self._have_moving = False
         self._publish()
 
-    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0):
-        """ref src/cvo.cpp:422-435."""
+    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False):
+        """ref src/cvo.cpp:422-435 (hessian: see align())."""
         if not self.init:
             self.set_pcd(positions, features, layout)
         else:
             self.set_pcd(positions, features, layout)
-            self.align(trace_cap=trace_cap)
+            self.align(trace_cap=trace_cap, hessian=hessian)
 
-    def run_sequence(self, frames, writer=None, trace_cap=0):
+    def run_sequence(self, frames, writer=None, trace_cap=0, hessian=False):
         """The loop of the reference's drivers (ref src/cvo_main.cpp:36-66): every
         frame goes through run_cvo() and then gets a pose line of `accum_transform`
         in `writer` (a trajectory.TrajectoryWriter) -- the first frame too (the
         identity): `init` is already true after the first run_cvo()
         (ref cvo_main.cpp:52,58).  `frames` yields (name,
-        positions, features).  Returns the per-pair iteration counts."""
+        positions, features).  Returns the per-pair iteration counts.  hessian=True: every
+        pair's align() evaluates the pose Hessian (align()); the last one stays in ``self.hessian``."""
         iters = []
         for name, positions, features in frames:
             first = not self.init
-            self.run_cvo(positions, features, trace_cap=trace_cap)
+            self.run_cvo(positions, features, trace_cap=trace_cap, hessian=hessian)
             if not first:
                 iters.append(self.num_iterations)
             if writer is not None and self.init:

@@ -74,6 +74,10 @@ class registration {
 
     void set_pcd(const point_cloud_view &pc);
     void align();
+    // align() that also evaluates the pose Hessian of the CVO objective at the final pose and length scale, before
+    // the moving cloud becomes the fixed one (cvo_hip_pose_hessian; -H is the information-like quantity, no noise
+    // model implied).  out == nullptr: plain align().  The registration is the same bit for bit either way.
+    void align(cvo_hip_pose_hessian_t *out);
     void run_cvo(const point_cloud_view &pc);
     // The reference's own signatures (ref include/cvo.hpp:171-192): images in, the front
     // end (pcd_generator) runs first -- on the GPU.  The two paths are dead parameters

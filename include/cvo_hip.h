@@ -259,6 +259,52 @@ int cvo_hip_flow(cvo_hip_ctx *ctx, float ell, double out13[13]);
 int cvo_hip_step_coeffs(cvo_hip_ctx *ctx, const float omega[3], const float v[3], float ell,
                         double bcde[4]);
 
+/* The 6x6 pose Hessian of the CVO objective at a pose (R, T) and length scale ell.
+ *
+ * Transformed cloud: y_j = R^T (z_j - T), bit for bit what cvo_hip_transform_pcd(ctx, R, T)
+ * makes.  Member set: A with weights a_ij is exactly the member set and the float32 weights
+ * cvo_hip_flow(ctx, ell, ...) keeps at that pose (the same filter, exact test and weights; cvo,
+ * acvo with its own parameters, and the MATLAB weight).  acvo's self terms Axx, Ayy do not
+ * depend on the pose and are not part of it.
+ *
+ * Perturbation on the right, as align() updates the pose: (R, T) <- (R, T) Exp(xi), xi =
+ * (omega, v) in cvo_hip_exp_se3's order, so y_j(xi) = exp(-xi^) y_j.  Objective:
+ *     F(xi) = sum_{(i,j) in A} a_ij exp(-(|x_i - y_j(xi)|^2 - |x_i - y_j|^2) / (2 ell^2))
+ * with A and every member's colour factor frozen at xi = 0: the thresholded sum jumps at every
+ * change of membership, only the frozen-set objective has a derivative (the flow is its gradient).
+ *   f = F(0) = sum a;  g = dF/dxi (0);  H = d2F/dxi2 (0), the exact second derivative
+ *   (the exponential map's second-order term included, not a Gauss-Newton J^T J).
+ * Per member, with r = y - x, J = [[y]x, -I] (dy = J xi to first order), u = J^T r = (y x x, x - y):
+ *   grad a = -(a / ell^2) u, so g = (1 / ell^2) (sum a x x y, sum a (y - x));
+ *   hess a = (a / ell^4) u u^T - (a / ell^2) (J^T J + S), S the Hessian of r . 1/2 (w x (w x y) + w x v):
+ *   J^T J = [[|y|^2 I - y y^T, [y]x], [-[y]x, I]],
+ *   S_ww = 1/2 (r y^T + y r^T) - (r . y) I,  S_wv = -1/2 [r]x,  S_vw = 1/2 [r]x,  S_vv = 0.
+ * Cross-check with cvo_hip_flow: g_omega = (c / ell^2) out13[0..2], g_v = (d / ell^2) out13[3..5]
+ * up to per-pair float32 rounding; f = out13[6], nnz = out13[8].
+ *
+ * -H is the information-like quantity of the registration at that pose; no noise model is implied.
+ * Per-member terms are float32, summed in float64 in a fixed order: repeated calls give the same
+ * bits.  The context is left as cvo_hip_transform_pcd(ctx, R, T) leaves it; a following
+ * cvo_hip_align is unaffected.  A sharded context (cvo_hip_set_shard) with no communication
+ * attached returns the sums over its own rows (they add up over the shards).  An empty A gives
+ * zeros and CVO_HIP_OK.  CVO_HIP_ERR_INVALID: a null argument, ell not finite or not > 0, a cloud
+ * missing, or a communicator, mailboxes or an all-reduce hook attached (sums over ranks are the
+ * caller's).
+ *
+ * (The struct tag and the function share the name, as struct stat and stat() do; the typedef is
+ * cvo_hip_pose_hessian_t.) */
+struct cvo_hip_pose_hessian {
+    double f;          /* sum of a over A (cvo_hip_flow's sum_a) */
+    double g[6];       /* dF/dxi, (omega, v) order */
+    double H[36];      /* d2F/dxi2, row-major, symmetric */
+    int64_t nnz;       /* |A| */
+    float ell;         /* the length scale used */
+    int32_t pad_;
+};
+typedef struct cvo_hip_pose_hessian cvo_hip_pose_hessian_t;
+int cvo_hip_pose_hessian(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
+                         cvo_hip_pose_hessian_t *out);
+
 /* Root selection + clamps (ref src/cvo.cpp:291-307), Exp_SEK3
  * (ref src/LieGroup.cpp:159-186) and dist_se3 (ref src/cvo.cpp:71-81): the O(1)
  * host maths of the loop, exported for tests and for callers that drive the

@@ -2,9 +2,9 @@
 """Register / scratch / LDS table of every kernel of cvo_kernels.hip, from the compiler's own
 metadata (no GPU needed):
 
-    python tools/isa_resources.py [out.txt]
+    python tools/isa_resources.py [out.txt] [--src cvo_hessian.hip]
 
-compiles cvo-rgbd_amd/csrc/cvo_kernels.hip with the Makefile's flags + -save-temps into a scratch
+compiles cvo-rgbd_amd/csrc/cvo_kernels.hip (or the --src file of that directory) with the Makefile's flags + -save-temps into a scratch
 directory and reads the amdhsa.kernels notes of the gfx950 assembly."""
 import os
 import re
@@ -40,16 +40,22 @@ def table(asm):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else None
+    args = sys.argv[1:]
+    src = "cvo_kernels.hip"
+    if "--src" in args:
+        k = args.index("--src")
+        src = args[k + 1]
+        del args[k:k + 2]
+    out = args[0] if args else None
     with tempfile.TemporaryDirectory() as tmp:
-        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-c", os.path.join(SRC, "cvo_kernels.hip"), "-o",
+        subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-c", os.path.join(SRC, src), "-o",
                                                            os.path.join(tmp, "k.o")], cwd=tmp, check=True)
         asm = [f for f in os.listdir(tmp) if f.endswith(".s") and "gfx950" in f]
         text = open(os.path.join(tmp, asm[0])).read()
     rows, keys = table(text)
     mfma = len(re.findall(r"^\s*v_mfma_", text, re.M))
     swaps = len(re.findall(r"^\s*v_permlane\d+_swap", text, re.M))
-    lines = ["# ISA resources of cvo_kernels.hip (hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=8 -save-temps)",
+    lines = ["# ISA resources of %s (hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-kernarg-preload-count=8 -save-temps)" % src,
              "# %d v_mfma_*, %d v_permlane*_swap in the file" % (mfma, swaps),
              "# kernel | sgpr | sgpr spilled (to vector lanes, no memory) | vgpr | vgpr spilled | scratch bytes | static LDS bytes"]
     for r in rows:
