@@ -21,7 +21,8 @@ SYMBOLS = [
     "cvo_hip_swap_moving_to_fixed", "cvo_hip_set_pcd_many", "cvo_hip_get_device_cloud", "cvo_hip_range_filter_grid_average", "cvo_hip_set_shard", "cvo_hip_shard_range",
     "cvo_hip_comm_unique_id", "cvo_hip_comm_init", "cvo_hip_set_allreduce",
     "cvo_hip_mailbox_create", "cvo_hip_mailbox_connect",
-    "cvo_hip_transform_pcd", "cvo_hip_flow", "cvo_hip_step_coeffs", "cvo_hip_pose_hessian", "cvo_hip_pick_step",
+    "cvo_hip_transform_pcd", "cvo_hip_flow", "cvo_hip_step_coeffs", "cvo_hip_pose_hessian", "cvo_hip_pose_score",
+    "cvo_hip_pose_score_many", "cvo_hip_pick_step",
     "cvo_hip_exp_se3", "cvo_hip_dist_se3", "cvo_hip_align", "cvo_hip_align_many",
     "cvo_hip_function_inner_product", "cvo_hip_function_inner_product_clouds",
     "cvo_hip_engine_profiling", "cvo_hip_get_engine_profile", "cvo_hip_get_engine_flow_trace", "cvo_hip_get_wave_load", "cvo_hip_set_graph_capture", "cvo_hip_set_profiling", "cvo_hip_get_profile", "cvo_hip_get_graph_stats", "cvo_hip_get_run_stats", "cvo_hip_get_run_clocks", "cvo_hip_get_mirror_retries", "cvo_hip_synchronize",
@@ -86,6 +87,34 @@ def pose_hessian_from_c(h):
     return PoseHessian(float(h.f), np.array(h.g[:], np.float64), np.array(h.H[:], np.float64).reshape(6, 6), int(h.nnz))
 
 
+class PoseScoreC(C.Structure):
+    """struct cvo_hip_pose_score."""
+    _fields_ = [
+        ("inner", C.c_double), ("self_fixed", C.c_double), ("self_moving", C.c_double), ("cos_angle", C.c_double),
+        ("mean_d2", C.c_double), ("nnz", C.c_int64), ("nnz_fixed", C.c_int64), ("nnz_moving", C.c_int64),
+        ("fixed_matched", C.c_int32), ("moving_matched", C.c_int32), ("n_fixed", C.c_int32), ("n_moving", C.c_int32),
+        ("ell", C.c_float), ("pad_", C.c_int32),
+    ]
+
+
+class PoseScore(collections.namedtuple("PoseScore", "inner self_fixed self_moving cos_angle mean_d2 nnz nnz_fixed nnz_moving "
+                                                    "fixed_matched moving_matched n_fixed n_moving ell")):
+    """Context.pose_score's answer (include/cvo_hip.h cvo_hip_pose_score): the CVO inner product at the pose, the two
+    norms, their cosine, the weighted mean squared distance of the members, the member counts and the matched points."""
+    __slots__ = ()
+
+    @property
+    def rms(self):
+        """sqrt(mean_d2): the weighted rms distance of the members of A."""
+        return float(np.sqrt(self.mean_d2))
+
+
+def pose_score_from_c(s):
+    return PoseScore(float(s.inner), float(s.self_fixed), float(s.self_moving), float(s.cos_angle), float(s.mean_d2),
+                     int(s.nnz), int(s.nnz_fixed), int(s.nnz_moving), int(s.fixed_matched), int(s.moving_matched),
+                     int(s.n_fixed), int(s.n_moving), float(s.ell))
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
 
@@ -140,6 +169,8 @@ def lib():
     L.cvo_hip_flow.argtypes = [vp, C.c_float, dp]
     L.cvo_hip_step_coeffs.argtypes = [vp, fp, fp, C.c_float, dp]
     L.cvo_hip_pose_hessian.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseHessianC)]
+    L.cvo_hip_pose_score.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseScoreC)]
+    L.cvo_hip_pose_score_many.argtypes = [C.POINTER(vp), fp, fp, fp, C.POINTER(PoseScoreC), C.c_int]
     L.cvo_hip_pick_step.argtypes = [dp, C.c_float, fp]
     L.cvo_hip_exp_se3.argtypes = [fp, fp, C.c_float, fp, fp]
     L.cvo_hip_dist_se3.argtypes = [fp, fp, C.c_float, fp]
@@ -407,6 +438,18 @@ class Context:
         cvo_hip_pose_hessian): PoseHessian(f, g, H, nnz).  The context is left as transform_pcd(R, T) leaves it."""
         return pose_hessian_from_c(self.pose_hessian_raw(R, T, ell))
 
+    def pose_score_raw(self, R, T, ell):
+        """cvo_hip_pose_score: the C struct as the library filled it (PoseScoreC)."""
+        R, T = f32(R).reshape(9), f32(T).reshape(3)
+        out = PoseScoreC()
+        self._chk(self._L.cvo_hip_pose_score(self._ctx, fptr(R), fptr(T), np.float32(ell), C.byref(out)), "pose_score")
+        return out
+
+    def pose_score(self, R, T, ell):
+        """The normalised CVO inner product and the overlap of the two clouds at the pose (R, T) and length scale ell
+        (include/cvo_hip.h cvo_hip_pose_score): a PoseScore.  The context is left as transform_pcd(R, T) leaves it."""
+        return pose_score_from_c(self.pose_score_raw(R, T, ell))
+
     def align(self, state, trace_cap=2000):
         tr = (Trace * trace_cap)() if trace_cap > 0 else None
         n_it = C.c_int(0)
@@ -531,6 +574,25 @@ def align_many(contexts, states):
     its = (C.c_int * n)()
     check(lib().cvo_hip_align_many(arr_c, arr_s, its, n), what="align_many")
     return list(its)
+
+
+def pose_score_many_raw(contexts, Rs, Ts, ells):
+    """cvo_hip_pose_score_many: the C structs as the library filled them."""
+    n = len(contexts)
+    arr_c = (C.c_void_p * n)(*[c._ctx for c in contexts])
+    R = f32(np.asarray(Rs, np.float32).reshape(n * 9) if n else np.zeros(0, np.float32))
+    T = f32(np.asarray(Ts, np.float32).reshape(n * 3) if n else np.zeros(0, np.float32))
+    E = f32(np.asarray(ells, np.float32).reshape(n) if n else np.zeros(0, np.float32))
+    out = (PoseScoreC * max(n, 1))()
+    check(lib().cvo_hip_pose_score_many(arr_c, fptr(R), fptr(T), fptr(E), out, n),
+          contexts[0]._ctx if n else None, what="pose_score_many")
+    return list(out)[:n]
+
+
+def pose_score_many(contexts, Rs, Ts, ells):
+    """The scores of many contexts of one device in one call (cvo_hip_pose_score_many): Rs (n, 3, 3), Ts (n, 3), ells
+    (n,).  Every context's work is enqueued before the one wait; each PoseScore is what Context.pose_score gives."""
+    return [pose_score_from_c(s) for s in pose_score_many_raw(contexts, Rs, Ts, ells)]
 
 
 def mirror_retries():

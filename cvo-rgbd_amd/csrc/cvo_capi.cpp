@@ -186,6 +186,249 @@ DevParams make_dev_params(const cvo_hip_params &p)
 
 }   // namespace cvo_impl
 
+// ---- cvo_hip_pose_score (include/cvo_hip.h)
+// Pinned staging of a context's score: its three passes go out back to back, each with its own image of the state
+// fields it pushes and its own words to come back, so that a call -- or a batch of contexts -- waits once, at the end.
+struct ScorePin {
+    DevHead img[3];        // the state in front of pass p (0: the fixed cloud against itself, 1: the moving one, 2: the pose)
+    double red[3][9];      // RED_FLOW .. RED_FLOW + 8 after pass p: [6] sum a, [8] members
+    uint32_t ovf[3][16];   // DevState::ovf after pass p
+    double out[3];         // k_pose_score_reduce: sum a d2, fixed rows matched, moving rows matched
+};
+static_assert(offsetof(DevState, xi) <= sizeof(DevHead) && offsetof(DevState, done) + sizeof(int32_t) <= sizeof(DevHead),
+              "the pushed fields are fields of the head");
+
+namespace cvo_impl {
+namespace {
+
+enum { kScoreFixed = 0, kScoreMoving = 1, kScorePose = 2 };
+
+struct ScoreJob {
+    float R[9], T[3], ell;
+    bool self_pass[2];   // the norm of the fixed / moving cloud is computed (not the cloud's cached one)
+};
+
+bool self_norm_valid(const cvo_hip_ctx *ctx, const Cloud &c, float ell)
+{
+    uint32_t bits;
+    std::memcpy(&bits, &ell, sizeof(bits));
+    return c.self.valid && c.self.gen == c.gen && c.self.ell_bits == bits &&
+           std::memcmp(&c.self.prm, &ctx->prm, sizeof(cvo_hip_params)) == 0;
+}
+
+// Everything a score is refused for, checked before anything is enqueued.
+int score_check(cvo_hip_ctx *ctx, const float *R, const float *T, float ell, const void *out)
+{
+    if (!R || !T || !out) return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: null argument");
+    if (!(std::isfinite(ell) && ell > 0.0f))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: ell must be finite and > 0");
+    if (ctx->fixed.n <= 0 || ctx->moving.n <= 0)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: both clouds must be set");
+    if (ctx->sharded && (ctx->row_lo > 0 || ctx->row_hi < ctx->fixed.n || ctx->srow_lo > 0 || ctx->srow_hi < ctx->moving.n))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: not on a sharded context (the overlap counts do not add "
+                                              "up over shards)");
+    if (multi_rank(ctx) || ctx->mailbox)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: not with a communicator, mailboxes or an all-reduce "
+                                              "hook attached");
+    return CVO_HIP_OK;
+}
+
+// One pass: the state fields of the host image, then the filter and PROC_FLOW over rows [rlo, rhi) of ca against cb
+// (cb under [Rt|t] if tf_b) and POST_REDUCE -- cvo_hip_flow's member set and sums; the sums and the overflow flags
+// go to pinned words of the pass's own.
+int score_pass(cvo_hip_ctx *ctx, int p, const Cloud &ca, int rlo, int rhi, const Cloud &cb, int tf_b)
+{
+    ScorePin *pin = ctx->score_pin;
+    std::memcpy(static_cast<void *>(&pin->img[p]), static_cast<const void *>(&ctx->st_host[kPollSlots]), sizeof(DevHead));
+    const char *img = reinterpret_cast<const char *>(&pin->img[p]);
+    char *dev = reinterpret_cast<char *>(ctx->st);
+    const size_t ranges[4][2] = {{offsetof(DevState, R), offsetof(DevState, ell)},
+                                 {offsetof(DevState, Rt), offsetof(DevState, used_Rt)},
+                                 {offsetof(DevState, kc), offsetof(DevState, xi)},
+                                 {offsetof(DevState, done), offsetof(DevState, done) + sizeof(int32_t)}};
+    for (const auto &r : ranges)
+        HIP_TRY(ctx, hipMemcpyAsync(dev + r[0], img + r[0], r[1] - r[0], hipMemcpyHostToDevice, ctx->stream));
+    int rc = zero_counters(ctx);
+    if (!rc) rc = enqueue_filter(ctx, LIST_XY, ca, rlo, rhi, 0, cb, tf_b, 0);
+    if (!rc) rc = enqueue_process(ctx, PROC_FLOW, LIST_XY, ctx->part_flow, ca.pos, ca.feat, 0, cb.pos, cb.feat, tf_b, 0, 0);
+    if (rc) return rc;
+    PostFlowArgs pa{};
+    pa.st = ctx->st;
+    pa.prm = ctx->dprm;
+    pa.prm.mode = CVO_HIP_MODE_CVO;   // no self terms here
+    pa.nblk = ctx->proc_blocks;
+    pa.flags = POST_REDUCE;
+    pa.part_flow = (const double *)ctx->part_flow.p;
+    launch_post_flow(pa, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(pin->red[p], dev + offsetof(DevState, red) + RED_FLOW * sizeof(double), sizeof(pin->red[p]),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(pin->ovf[p], dev + offsetof(DevState, ovf), sizeof(pin->ovf[p]), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    return CVO_HIP_OK;
+}
+
+// A context's whole score, enqueued on its stream without a wait: the self passes its clouds' cached norms do not
+// cover, the pass at the pose, the score pass over the pose's kept list.
+int score_enqueue(cvo_hip_ctx *ctx, ScoreJob &job)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = cloud_ready(ctx, ctx->fixed);
+    if (!rc) rc = cloud_ready(ctx, ctx->moving);
+    if (rc) return rc;
+    if (!ctx->score_pin) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->score_pin, sizeof(ScorePin), hipHostMallocDefault));
+    // the context ends as cvo_hip_transform_pcd(ctx, R, T) leaves it
+    DevState *h = &ctx->st_host[kPollSlots];
+    std::memcpy(h->R, job.R, sizeof(h->R));
+    std::memcpy(h->T, job.T, sizeof(h->T));
+    cvo_math::inverse_tf(job.R, job.T, h->Rt, h->t);
+    h->done = 0;
+    h->kc = make_kconsts(ctx->dprm, job.ell);
+    h->kc_ell = -1.0f;   // (never equal to an ell: prepare_iteration recomputes)
+    job.self_pass[0] = !self_norm_valid(ctx, ctx->fixed, job.ell);
+    job.self_pass[1] = !self_norm_valid(ctx, ctx->moving, job.ell);
+    // A cloud against itself, untransformed: the cloud stands in as both clouds of the context for the pass, so that the
+    // filter geometry, the kept-list sizes and the entry form are its own -- the same bits whichever side it is on
+    // (the fixed cloud's norm after cvo_hip_swap_moving_to_fixed is the moving cloud's one frame earlier).  Only the
+    // cloud's own rows are listed: the padding rows (cvo_cloud.h, NaN features) are never a row of the pass, and as
+    // columns they lie ~10 km from every row.
+    for (int s = 0; s < 2; ++s) {
+        if (!job.self_pass[s]) continue;
+        const Cloud keep_f = ctx->fixed, keep_m = ctx->moving;
+        const Cloud c = s == 0 ? keep_f : keep_m;
+        ctx->fixed = c;
+        ctx->moving = c;
+        rc = fill_filter_geometry(ctx, h);
+        if (!rc) {
+            compute_filter_bounds(h, true);
+            rc = score_pass(ctx, s, ctx->fixed, 0, c.n, ctx->moving, 0);
+        }
+        ctx->fixed = keep_f;
+        ctx->moving = keep_m;
+        if (rc) return rc;
+    }
+    // A at the pose exactly as cvo_hip_pose_hessian rebuilds it (the same filter and PROC_FLOW pass): last, so that the
+    // kept list the score pass streams is its
+    rc = fill_filter_geometry(ctx, h);
+    if (rc) return rc;
+    compute_filter_bounds(h, false);
+    int rlo, rhi, slo, shi;
+    shard_ranges(ctx, rlo, rhi, slo, shi);
+    rc = score_pass(ctx, kScorePose, ctx->fixed, rlo, rhi, ctx->moving, 1);
+    if (rc) return rc;
+    const size_t flag_off = (size_t)(PROC_BLOCKS + 4) * sizeof(double);
+    const size_t nflag = (size_t)ctx->fixed.np + (size_t)ctx->moving.np;   // (both multiples of CLOUD_PAD)
+    rc = ensure_buf(ctx, ctx->part_score, flag_off + nflag);
+    if (rc) return rc;
+    char *ps = static_cast<char *>(ctx->part_score.p);
+    HIP_TRY(ctx, hipMemsetAsync(ps + flag_off, 0, nflag, ctx->stream));
+    ScoreArgs sa{};
+    sa.pos_a = ctx->fixed.pos;
+    sa.pos_b = ctx->moving.pos;
+    sa.kept_ij = (const uint2 *)ctx->lists[LIST_KEPT].a.p;
+    sa.kept_a = (const float *)ctx->lists[LIST_KEPT].b.p;
+    sa.kept_cnt = (const uint32_t *)ctx->kept_cnt.p;
+    sa.st = ctx->st;
+    sa.partials = reinterpret_cast<double *>(ps);
+    sa.out = sa.partials + PROC_BLOCKS;
+    sa.flag_a = reinterpret_cast<uint8_t *>(ps + flag_off);
+    sa.flag_b = sa.flag_a + ctx->fixed.np;
+    sa.na = ctx->fixed.np;
+    sa.nb = ctx->moving.np;
+    sa.nblk = ctx->proc_blocks;
+    sa.kept_wcap = ctx->lists[LIST_KEPT].cap / (uint32_t)(4 * ctx->proc_blocks);   // (enqueue_process's slice)
+    sa.kept_packed = kept_format(ctx, &sa.kept_ebase);
+    launch_pose_score(sa, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->score_pin->out, sa.out, sizeof(ctx->score_pin->out), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->have_tf = true;
+    return CVO_HIP_OK;
+}
+
+// After the wait: a pass whose tile or kept list overflowed grows that list and the score is enqueued again (*redo);
+// otherwise the result, and the norms the self passes computed go to their clouds.
+int score_collect(cvo_hip_ctx *ctx, const ScoreJob &job, cvo_hip_pose_score_t *out, bool *redo)
+{
+    const ScorePin *pin = ctx->score_pin;
+    *redo = false;
+    for (int p = 0; p < 3; ++p) {
+        if (p < 2 && !job.self_pass[p]) continue;
+        for (int l = 0; l < LIST_N; ++l) {
+            if (!(pin->ovf[p][l] | pin->ovf[p][8 + l])) continue;
+            const uint32_t cap = ctx->lists[l].cap;
+            int rc = ensure_list(ctx, l, 0, 0, std::min(4.0e9, 2.0 * (double)cap + 1024.0));
+            if (rc) return rc;
+            if (ctx->lists[l].cap <= cap) return fail(ctx, CVO_HIP_ERR_NOMEM, "cvo_hip_pose_score: a list cannot grow further");
+            *redo = true;
+        }
+    }
+    if (*redo) return CVO_HIP_OK;
+    uint32_t bits;
+    std::memcpy(&bits, &job.ell, sizeof(bits));
+    for (int s = 0; s < 2; ++s) {
+        if (!job.self_pass[s]) continue;
+        Cloud &c = s == 0 ? ctx->fixed : ctx->moving;
+        c.self.valid = true;
+        c.self.gen = c.gen;
+        c.self.prm = ctx->prm;
+        c.self.ell_bits = bits;
+        c.self.sum = pin->red[s][6];
+        c.self.nnz = (int64_t)pin->red[s][8];
+    }
+    cvo_hip_pose_score_t r{};
+    r.inner = pin->red[kScorePose][6];
+    r.nnz = (int64_t)pin->red[kScorePose][8];
+    r.self_fixed = ctx->fixed.self.sum;
+    r.nnz_fixed = ctx->fixed.self.nnz;
+    r.self_moving = ctx->moving.self.sum;
+    r.nnz_moving = ctx->moving.self.nnz;
+    r.cos_angle = (r.self_fixed > 0.0 && r.self_moving > 0.0) ? r.inner / std::sqrt(r.self_fixed * r.self_moving) : 0.0;
+    r.mean_d2 = r.nnz > 0 ? pin->out[0] / r.inner : 0.0;
+    r.fixed_matched = (int32_t)pin->out[1];
+    r.moving_matched = (int32_t)pin->out[2];
+    r.n_fixed = ctx->fixed.n;
+    r.n_moving = ctx->moving.n;
+    r.ell = job.ell;
+    *out = r;
+    if (ctx->profiling) return drain_events(ctx);
+    return CVO_HIP_OK;
+}
+
+// The scores of `count` checked contexts: every chain is enqueued, then the streams are waited for, once.
+int score_batch(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, const float *ell, cvo_hip_pose_score_t *out,
+                int count)
+{
+    std::vector<ScoreJob> jobs((size_t)count);
+    std::vector<char> todo((size_t)count, 1);
+    for (int k = 0; k < count; ++k) {
+        std::memcpy(jobs[k].R, R9 + 9 * (size_t)k, sizeof(jobs[k].R));
+        std::memcpy(jobs[k].T, T3 + 3 * (size_t)k, sizeof(jobs[k].T));
+        jobs[k].ell = ell[k];
+    }
+    for (bool any = true; any;) {
+        for (int k = 0; k < count; ++k) {
+            if (!todo[k]) continue;
+            const int rc = score_enqueue(ctxs[k], jobs[k]);
+            if (rc) return rc;
+        }
+        for (int k = 0; k < count; ++k)
+            if (todo[k]) HIP_TRY(ctxs[k], hipStreamSynchronize(ctxs[k]->stream));
+        any = false;
+        for (int k = 0; k < count; ++k) {
+            if (!todo[k]) continue;
+            bool redo = false;
+            const int rc = score_collect(ctxs[k], jobs[k], &out[k], &redo);
+            if (rc) return rc;
+            todo[k] = redo ? 1 : 0;
+            any = any || redo;
+        }
+    }
+    return CVO_HIP_OK;
+}
+
+}   // namespace
+}   // namespace cvo_impl
+
 extern "C" {
 
 
@@ -368,7 +611,7 @@ int cvo_hip_destroy(cvo_hip_ctx *ctx)
                     (void *)ctx->moving.feat, (void *)ctx->fixed.seg, (void *)ctx->moving.seg,
                     (void *)ctx->scratch_a.pos, (void *)ctx->scratch_a.feat, (void *)ctx->scratch_a.seg,
                     (void *)ctx->scratch_b.pos, (void *)ctx->scratch_b.feat, (void *)ctx->scratch_b.seg, (void *)ctx->st, (void *)ctx->st2, ctx->part_flow.p, ctx->part_xx.p,
-                    ctx->part_yy.p, ctx->part_step.p, ctx->part_hess.p, ctx->run_mail.p, (void *)ctx->trace_dev, ctx->kept_cnt.p, ctx->pos_bt.p, ctx->cand[0].p, ctx->cand[1].p, ctx->cand[2].p, ctx->cand_xyb.p, ctx->cand_cnt_xyb.p, ctx->cand_sfb[0].p, ctx->cand_sfb[1].p, ctx->cand_cnt_sfb[0].p, ctx->cand_cnt_sfb[1].p, ctx->cand_cnt[0].p,
+                    ctx->part_yy.p, ctx->part_step.p, ctx->part_hess.p, ctx->part_score.p, ctx->run_mail.p, (void *)ctx->trace_dev, ctx->kept_cnt.p, ctx->pos_bt.p, ctx->cand[0].p, ctx->cand[1].p, ctx->cand[2].p, ctx->cand_xyb.p, ctx->cand_cnt_xyb.p, ctx->cand_sfb[0].p, ctx->cand_sfb[1].p, ctx->cand_cnt_sfb[0].p, ctx->cand_cnt_sfb[1].p, ctx->cand_cnt[0].p,
                     ctx->cand_cnt[1].p, ctx->cand_cnt[2].p})
         if (p) (void)hipFree(p);
     for (int l = 0; l < LIST_N; ++l) {
@@ -376,6 +619,7 @@ int cvo_hip_destroy(cvo_hip_ctx *ctx)
         if (ctx->lists[l].b.p) (void)hipFree(ctx->lists[l].b.p);
     }
     if (ctx->st_host) (void)hipHostFree(ctx->st_host);
+    if (ctx->score_pin) (void)hipHostFree(ctx->score_pin);
     for (Cloud *c : {&ctx->fixed, &ctx->moving, &ctx->scratch_a, &ctx->scratch_b}) {
         if (c->pending && (c->wait_ev || c->ready_ev)) (void)hipEventSynchronize(c->wait_ev ? c->wait_ev : c->ready_ev);
         if (c->stage) (void)hipHostFree(c->stage);
@@ -401,6 +645,7 @@ int cvo_hip_set_params(cvo_hip_ctx *ctx, const cvo_hip_params *p)
     drop_graphs(ctx);   // (captured batches hold the parameter block by value)
     ctx->prm = *p;
     ctx->dprm = make_dev_params(*p);
+    for (Cloud *c : {&ctx->fixed, &ctx->moving, &ctx->scratch_a, &ctx->scratch_b}) c->self.valid = false;   // (cvo_hip_pose_score)
     return CVO_HIP_OK;
 }
 
@@ -739,6 +984,35 @@ int cvo_hip_pose_hessian(cvo_hip_ctx *ctx, const float R[9], const float T[3], f
     *out = r;
     if (ctx->profiling) return drain_events(ctx);
     return CVO_HIP_OK;
+}
+
+int cvo_hip_pose_score(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell, cvo_hip_pose_score_t *out)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    int rc = score_check(ctx, R, T, ell, out);
+    if (rc) return rc;
+    return score_batch(&ctx, R, T, &ell, out, 1);
+}
+
+int cvo_hip_pose_score_many(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, const float *ell,
+                            cvo_hip_pose_score_t *out, int count)
+{
+    cvo_lock::Api api_guard;
+    if (count < 0) return CVO_HIP_ERR_INVALID;
+    if (count == 0) return CVO_HIP_OK;
+    if (!ctxs || !R9 || !T3 || !ell || !out) return CVO_HIP_ERR_INVALID;
+    // (every context and argument before any context is touched)
+    for (int k = 0; k < count; ++k) {
+        if (!ctxs[k] || ctxs[k]->device != ctxs[0]->device) return CVO_HIP_ERR_INVALID;
+        for (int q = 0; q < k; ++q)
+            if (ctxs[q] == ctxs[k]) return fail(ctxs[0], CVO_HIP_ERR_INVALID, "cvo_hip_pose_score_many: a context twice");
+    }
+    for (int k = 0; k < count; ++k) {
+        const int rc = score_check(ctxs[k], R9 + 9 * (size_t)k, T3 + 3 * (size_t)k, ell[k], out + k);
+        if (rc) return rc;
+    }
+    return score_batch(ctxs, R9, T3, ell, out, count);
 }
 
 int cvo_hip_pick_step(const double bcde[4], float min_step, float *step)

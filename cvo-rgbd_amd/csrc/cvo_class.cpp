@@ -183,6 +183,24 @@ void registration::align(cvo_hip_pose_hessian_t *out)
     publish();
 }
 
+void registration::align(cvo_hip_pose_score_t *score, float score_ell, cvo_hip_pose_hessian_t *hessian)
+{
+    if (!have_moving_) throw std::runtime_error("align(): set_pcd() must precede each align()");
+    check(cvo_hip_align(ctx_, &state_, nullptr, 0, &n_iter_), "cvo_hip_align");
+    if (hessian) check(cvo_hip_pose_hessian(ctx_, state_.R, state_.T, state_.ell, hessian), "cvo_hip_pose_hessian");
+    if (score)
+        check(cvo_hip_pose_score(ctx_, state_.R, state_.T, score_ell > 0.0f ? score_ell : params_.ell_init, score),
+              "cvo_hip_pose_score");
+    check(cvo_hip_swap_moving_to_fixed(ctx_), "cvo_hip_swap_moving_to_fixed");
+    have_moving_ = false;
+    publish();
+}
+
+void registration::pose_score(const float R[9], const float T[3], float ell, cvo_hip_pose_score_t *out)
+{
+    check(cvo_hip_pose_score(ctx_, R, T, ell, out), "cvo_hip_pose_score");
+}
+
 void registration::align_many(registration *const *objects, int count)
 {
     std::vector<cvo_hip_ctx *> ctxs((size_t)count);

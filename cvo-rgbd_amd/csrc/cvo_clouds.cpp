@@ -87,6 +87,7 @@ int cloud_reserve(cvo_hip_ctx *ctx, Cloud &c, const float *xyz, const float *fea
     }
     c.n = n;
     c.np = np;
+    ++c.gen;   // (the arrays change: cvo_hip_pose_score's norm of the cloud is stale)
     c.pad_axis = (other.n > 0) ? 1 - other.pad_axis : 0;
     for (int a = 0; a < 3; ++a) { c.lo[a] = 0.0f; c.hi[a] = 0.0f; }
     if (n == 0) return CVO_HIP_OK;

@@ -993,6 +993,27 @@ struct HessArgs {
 };
 void launch_pose_hessian(const HessArgs &a, hipStream_t s);
 
+// The pose score (cvo_score.hip, include/cvo_hip.h cvo_hip_pose_score): one pass over the kept list a PROC_FLOW pass
+// recorded -- sum a d2 per block, a matched flag per fixed and per moving row -- then a one-block fixed-order reduction.
+struct ScoreArgs {
+    const float4 *pos_a;        // the fixed cloud (x)
+    const float4 *pos_b;        // the moving cloud as set (z): y = [Rt|t] z with the state's Rt, t
+    const uint2 *kept_ij;       // the kept list, its weights (kept_packed == 0) and per-wave counts (ProcessArgs)
+    const float *kept_a;
+    const uint32_t *kept_cnt;
+    const DevState *st;
+    uint8_t *flag_a;            // [na] 1: fixed row i has a member (zeroed on the stream before the pass)
+    uint8_t *flag_b;            // [nb] likewise for the moving rows
+    double *partials;           // [nblk] sum a d2 per block
+    double *out;                // [3]: sum a d2, fixed rows matched, moving rows matched
+    uint32_t kept_wcap;
+    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
+    int kept_packed;
+    unsigned kept_ebase;
+    int na, nb;                 // rows of the two clouds' device arrays (multiples of CLOUD_PAD, so of 4)
+};
+void launch_pose_score(const ScoreArgs &a, hipStream_t s);
+
 void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t *build_masks = nullptr, const PrepareInit *init = nullptr);
 void launch_filter(const FilterArgs &a, dim3 grid, hipStream_t s, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);

@@ -58,6 +58,18 @@ struct Cloud {
     hipEvent_t ready_ev = nullptr;
     hipEvent_t wait_ev = nullptr;     // what `pending` waits for: ready_ev, or the event of a batched hand-over (borrowed)
     bool pending = false;
+    // cvo_hip_pose_score's |f|^2 of this cloud against itself: valid while `gen` is what it was made at (every write of
+    // the arrays, cloud_reserve, bumps it) and for the parameters and ell it was made with.  A member of the cloud,
+    // so that cvo_hip_swap_moving_to_fixed carries it along with the arrays.
+    uint64_t gen = 0;
+    struct SelfNorm {
+        bool valid = false;
+        uint64_t gen = 0;
+        cvo_hip_params prm{};
+        uint32_t ell_bits = 0;
+        double sum = 0.0;
+        int64_t nnz = 0;
+    } self;
 };
 
 struct EventPair {
@@ -337,6 +349,8 @@ struct cvo_hip_ctx {
     hipEvent_t poll_ev[kPollSlots]{};
     DevBuf part_flow, part_xx, part_yy, part_step;   // [PROC_BLOCKS][NACC_MAX] float64
     DevBuf part_hess;                    // cvo_hip_pose_hessian: [NACC_HESS][nblk] block partials, then the [NACC_HESS] sums
+    DevBuf part_score;                   // cvo_hip_pose_score: [PROC_BLOCKS] block partials, [4] sums, the matched bytes
+    struct ScorePin *score_pin = nullptr;   // cvo_hip_pose_score: pinned staging of its passes (cvo_capi.cpp)
     List lists[LIST_N];
     DevBuf kept_cnt;                 // uint32[PROC_WAVES]
     cvo_hip_trace *trace_dev = nullptr;

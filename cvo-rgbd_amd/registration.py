@@ -27,6 +27,8 @@ class _Registration:
         self.num_iterations = 0
         self.trace = []
         self.hessian = None   # align(hessian=True) publishes the pose Hessian here
+        self.score = None     # align(score=...) publishes the pose score here
+        self.scores = []      # run_sequence(score=...): one pose score per pair
         self._have_moving = False
 
     def _publish(self):
@@ -54,52 +56,67 @@ class _Registration:
         self.ctx.set_moving_device(d_positions, d_features, n, layout)
         self._have_moving = True
 
-    def run_cvo_device(self, d_positions, d_features, n, layout=capi.FEAT_ROWMAJOR, trace_cap=0):
+    def run_cvo_device(self, d_positions, d_features, n, layout=capi.FEAT_ROWMAJOR, trace_cap=0, score=False):
         first = not self.init
         self.set_pcd_device(d_positions, d_features, n, layout)
         if not first:
-            self.align(trace_cap=trace_cap)
+            self.align(trace_cap=trace_cap, score=score)
 
-    def align(self, trace_cap=0, hessian=False):
+    def align(self, trace_cap=0, hessian=False, score=False):
         """ref src/cvo.cpp:361-420.
 
         hessian=True: after the loop, evaluate the pose Hessian of the CVO objective at the final R, T and
         length scale (capi.Context.pose_hessian, include/cvo_hip.h cvo_hip_pose_hessian) before the moving
         cloud becomes the fixed one, and publish it as ``self.hessian`` (a capi.PoseHessian: f, g, H, nnz).
-        -H is the information-like quantity of the registration; no noise model is implied.  The
-        registration itself is the same bit for bit either way."""
+        -H is the information-like quantity of the registration; no noise model is implied.
+
+        score=True: after the loop, score the registration at the final R, T (capi.Context.pose_score,
+        include/cvo_hip.h cvo_hip_pose_score) at ``params.ell_init`` -- one fixed length scale per object, so
+        that the scores of a sequence can be compared and each cloud's norm is computed once -- and publish it
+        as ``self.score`` (a capi.PoseScore; cos_angle is the normalised inner product).  A float: score at
+        that length scale.  The registration itself is the same bit for bit with or without either."""
         if not self._have_moving:
             raise capi.CvoHipError("align(): set_pcd() must precede each align()")
         self.num_iterations, self.trace = self.ctx.align(self.state, trace_cap=trace_cap)
         if hessian:
             s = self.state
             self.hessian = self.ctx.pose_hessian(np.array(s.R, np.float32), np.array(s.T, np.float32), s.ell)
+        if score is not False and score is not None:
+            s = self.state
+            ell = self.params.ell_init if score is True else float(score)
+            self.score = self.ctx.pose_score(np.array(s.R, np.float32), np.array(s.T, np.float32), ell)
         self.ctx.swap_moving_to_fixed()   # ptr_fixed_pcd = std::move(ptr_moving_pcd)
         self._have_moving = False
         self._publish()
 
-    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False):
-        """ref src/cvo.cpp:422-435 (hessian: see align())."""
+    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False, score=False):
+        """ref src/cvo.cpp:422-435 (hessian, score: see align())."""
         if not self.init:
             self.set_pcd(positions, features, layout)
         else:
             self.set_pcd(positions, features, layout)
-            self.align(trace_cap=trace_cap, hessian=hessian)
+            self.align(trace_cap=trace_cap, hessian=hessian, score=score)
 
-    def run_sequence(self, frames, writer=None, trace_cap=0, hessian=False):
+    def run_sequence(self, frames, writer=None, trace_cap=0, hessian=False, score=False):
         """The loop of the reference's drivers (ref src/cvo_main.cpp:36-66): every
         frame goes through run_cvo() and then gets a pose line of `accum_transform`
         in `writer` (a trajectory.TrajectoryWriter) -- the first frame too (the
         identity): `init` is already true after the first run_cvo()
         (ref cvo_main.cpp:52,58).  `frames` yields (name,
         positions, features).  Returns the per-pair iteration counts.  hessian=True: every
-        pair's align() evaluates the pose Hessian (align()); the last one stays in ``self.hessian``."""
+        pair's align() evaluates the pose Hessian (align()); the last one stays in ``self.hessian``.
+        score=True (or a length scale): every pair is scored (align()) and ``self.scores`` holds one
+        capi.PoseScore per pair of this call, in order."""
         iters = []
+        if score is not False and score is not None:
+            self.scores = []
         for name, positions, features in frames:
             first = not self.init
-            self.run_cvo(positions, features, trace_cap=trace_cap, hessian=hessian)
+            self.run_cvo(positions, features, trace_cap=trace_cap, hessian=hessian, score=score)
             if not first:
                 iters.append(self.num_iterations)
+                if score is not False and score is not None:
+                    self.scores.append(self.score)
             if writer is not None and self.init:
                 writer.append(name, self.accum_transform)
         return iters

@@ -78,6 +78,13 @@ class registration {
     // the moving cloud becomes the fixed one (cvo_hip_pose_hessian; -H is the information-like quantity, no noise
     // model implied).  out == nullptr: plain align().  The registration is the same bit for bit either way.
     void align(cvo_hip_pose_hessian_t *out);
+    // align() that also scores the registration at the final pose (cvo_hip_pose_score: the normalised CVO inner
+    // product and the overlap) at length scale score_ell -- 0: params' ell_init, one scale for every pair of a
+    // sequence -- and, if hessian is not null, evaluates the pose Hessian as align(hessian) does.  score == nullptr:
+    // no score.  The registration is the same bit for bit either way.
+    void align(cvo_hip_pose_score_t *score, float score_ell, cvo_hip_pose_hessian_t *hessian = nullptr);
+    // cvo_hip_pose_score of the clouds set, at the pose (R, T) and length scale ell
+    void pose_score(const float R[9], const float T[3], float ell, cvo_hip_pose_score_t *out);
     void run_cvo(const point_cloud_view &pc);
     // The reference's own signatures (ref include/cvo.hpp:171-192): images in, the front
     // end (pcd_generator) runs first -- on the GPU.  The two paths are dead parameters

@@ -305,6 +305,68 @@ typedef struct cvo_hip_pose_hessian cvo_hip_pose_hessian_t;
 int cvo_hip_pose_hessian(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
                          cvo_hip_pose_hessian_t *out);
 
+/* A normalised score of a registration at a pose (R, T) and length scale ell: the cosine of the
+ * angle between the two functions of the CVO objective, and how much of each cloud overlaps.
+ *
+ * Member rule: every sum below uses exactly the member set and the float32 weights a that
+ * cvo_hip_flow(ctx, ell, ...) keeps (the same filter, exact test and weights; cvo, acvo with its
+ * c_sp_thres colour cut, and the MATLAB weight).  Neither function_inner_product's threshold nor
+ * acvo's Ayy tail-row rule is used.
+ *   A       = the members (i, j) of the fixed cloud x against y_j = R^T (z_j - T), bit for bit
+ *             what cvo_hip_transform_pcd(ctx, R, T) makes;
+ *   A_X     = all ordered pairs (i, i') of the fixed cloud, the diagonal included, that pass the
+ *             rule against the fixed cloud itself, untransformed;
+ *   A_Y     = the same for the moving cloud as set (a rigid motion keeps the norm).
+ *   inner       = <f_X, f_{T.Y}> = sum_{A} a            (cvo_hip_flow's sum_a, cvo_hip_pose_hessian's f)
+ *   self_fixed  = |f_X|^2        = sum_{A_X} a
+ *   self_moving = |f_Y|^2        = sum_{A_Y} a
+ *   cos_angle   = inner / sqrt(self_fixed * self_moving); 0 if either is 0
+ *   mean_d2     = sum_{A} a d2 / sum_{A} a, d2 the float32 squared distance the member test
+ *                 used; 0 if A is empty.  sqrt(mean_d2) is a weighted residual.
+ *   fixed_matched / moving_matched: points of either cloud with at least one member in A.
+ * cos_angle lies in [0, 1] for real data, is 1 for a cloud against itself and does not depend on
+ * the cloud sizes: a threshold on it tells a registration that worked from one that did not.
+ * With thresholding the truncated Gram matrix is not guaranteed to be positive semi-definite, so
+ * cos_angle can exceed 1 in contrived inputs; it is reported as computed, not clamped.
+ *
+ * Per-member terms are float32, summed in float64 in a fixed order: repeated calls give the same
+ * bits.  Counts are exact integers.  |f_X|^2 depends on a cloud, the parameters and ell only: the
+ * context keeps it with the cloud (cvo_hip_swap_moving_to_fixed carries it along, every hand-over
+ * of the cloud and cvo_hip_set_params drop it), so in an odometry loop scored at one ell the fixed
+ * cloud's norm was the moving cloud's one frame earlier and costs nothing.
+ *
+ * The context is left as cvo_hip_transform_pcd(ctx, R, T) leaves it; a following cvo_hip_align is
+ * unaffected.  An empty A gives inner = cos_angle = mean_d2 = 0 and CVO_HIP_OK.
+ * CVO_HIP_ERR_INVALID: a null argument, ell not finite or not > 0, a cloud missing, a sharded
+ * context (cvo_hip_set_shard narrower than the whole clouds: the overlap counts do not add up over
+ * shards), or a communicator, mailboxes or an all-reduce hook attached.
+ *
+ * cvo_hip_pose_score_many: count distinct contexts of one device (anything else is refused before
+ * any context is touched), R9 count x 9, T3 count x 3, ell count values.  Every context's work is
+ * enqueued before the call waits, once, at the end; each result is bit for bit what a lone
+ * cvo_hip_pose_score on that context gives.  count == 0: CVO_HIP_OK.
+ *
+ * (The struct tag and the function share the name, as for cvo_hip_pose_hessian; the typedef is
+ * cvo_hip_pose_score_t.) */
+struct cvo_hip_pose_score {
+    double inner;          /* sum of a over A */
+    double self_fixed;     /* |f_X|^2: sum of a over A_X */
+    double self_moving;    /* |f_Y|^2: sum of a over A_Y */
+    double cos_angle;      /* inner / sqrt(self_fixed * self_moving); 0 if either is 0; not clamped */
+    double mean_d2;        /* sum a d2 / sum a over A; 0 if A is empty */
+    int64_t nnz, nnz_fixed, nnz_moving;   /* |A|, |A_X|, |A_Y| */
+    int32_t fixed_matched;  /* fixed points with at least one member in A */
+    int32_t moving_matched; /* moving points with at least one member in A */
+    int32_t n_fixed, n_moving;
+    float ell;             /* the length scale used */
+    int32_t pad_;
+};
+typedef struct cvo_hip_pose_score cvo_hip_pose_score_t;
+int cvo_hip_pose_score(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
+                       cvo_hip_pose_score_t *out);
+int cvo_hip_pose_score_many(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, const float *ell,
+                            cvo_hip_pose_score_t *out, int count);
+
 /* Root selection + clamps (ref src/cvo.cpp:291-307), Exp_SEK3
  * (ref src/LieGroup.cpp:159-186) and dist_se3 (ref src/cvo.cpp:71-81): the O(1)
  * host maths of the loop, exported for tests and for callers that drive the
