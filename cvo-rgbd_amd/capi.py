@@ -22,7 +22,7 @@ SYMBOLS = [
     "cvo_hip_comm_unique_id", "cvo_hip_comm_init", "cvo_hip_set_allreduce",
     "cvo_hip_mailbox_create", "cvo_hip_mailbox_connect",
     "cvo_hip_transform_pcd", "cvo_hip_flow", "cvo_hip_step_coeffs", "cvo_hip_pose_hessian", "cvo_hip_pose_score",
-    "cvo_hip_pose_score_many", "cvo_hip_pick_step",
+    "cvo_hip_pose_score_many", "cvo_hip_pose_matches", "cvo_hip_pick_step",
     "cvo_hip_exp_se3", "cvo_hip_dist_se3", "cvo_hip_align", "cvo_hip_align_many",
     "cvo_hip_function_inner_product", "cvo_hip_function_inner_product_clouds",
     "cvo_hip_engine_profiling", "cvo_hip_get_engine_profile", "cvo_hip_get_engine_flow_trace", "cvo_hip_get_wave_load", "cvo_hip_set_graph_capture", "cvo_hip_set_profiling", "cvo_hip_get_profile", "cvo_hip_get_graph_stats", "cvo_hip_get_run_stats", "cvo_hip_get_run_clocks", "cvo_hip_get_mirror_retries", "cvo_hip_synchronize",
@@ -115,6 +115,35 @@ def pose_score_from_c(s):
                      int(s.n_fixed), int(s.n_moving), float(s.ell))
 
 
+class PoseMatchesC(C.Structure):
+    """cvo_hip_pose_matches_t: the summary of cvo_hip_pose_matches."""
+    _fields_ = [
+        ("inner", C.c_double), ("nnz", C.c_int64), ("n_fixed", C.c_int32), ("n_moving", C.c_int32),
+        ("fixed_matched", C.c_int32), ("moving_matched", C.c_int32), ("ell", C.c_float), ("exact", C.c_int32),
+    ]
+
+
+class PointMatchesC(C.Structure):
+    """struct cvo_hip_point_matches: one side's host arrays (a null pointer: not wanted)."""
+    _fields_ = [("support", C.POINTER(C.c_double)), ("count", C.POINTER(C.c_int32)), ("best", C.POINTER(C.c_int32)),
+                ("best_w", C.POINTER(C.c_float))]
+
+
+class PointMatches(collections.namedtuple("PointMatches", "support count best best_w")):
+    """One cloud's side of Context.pose_matches: numpy arrays over the points in the caller's order -- support (float64:
+    the sum of the weights of the point's members), count (int32), best (int32: the index in the OTHER cloud of the
+    member with the largest weight, -1 if none) and best_w (float32)."""
+    __slots__ = ()
+
+
+class PoseMatches(collections.namedtuple("PoseMatches", "inner nnz n_fixed n_moving fixed_matched moving_matched ell exact "
+                                                        "fixed moving")):
+    """Context.pose_matches's answer (include/cvo_hip.h cvo_hip_pose_matches): the summary fields (pose_score's of the
+    same name; exact: every support is the correctly rounded sum of its weights) and ``fixed`` / ``moving``, a
+    PointMatches each, or None for a side not asked for."""
+    __slots__ = ()
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
 
@@ -171,6 +200,8 @@ def lib():
     L.cvo_hip_pose_hessian.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseHessianC)]
     L.cvo_hip_pose_score.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseScoreC)]
     L.cvo_hip_pose_score_many.argtypes = [C.POINTER(vp), fp, fp, fp, C.POINTER(PoseScoreC), C.c_int]
+    L.cvo_hip_pose_matches.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PointMatchesC), C.POINTER(PointMatchesC),
+                                       C.POINTER(PoseMatchesC)]
     L.cvo_hip_pick_step.argtypes = [dp, C.c_float, fp]
     L.cvo_hip_exp_se3.argtypes = [fp, fp, C.c_float, fp, fp]
     L.cvo_hip_dist_se3.argtypes = [fp, fp, C.c_float, fp]
@@ -449,6 +480,35 @@ class Context:
         """The normalised CVO inner product and the overlap of the two clouds at the pose (R, T) and length scale ell
         (include/cvo_hip.h cvo_hip_pose_score): a PoseScore.  The context is left as transform_pcd(R, T) leaves it."""
         return pose_score_from_c(self.pose_score_raw(R, T, ell))
+
+    def pose_matches(self, R, T, ell, fixed=True, moving=True):
+        """Which points matched at the pose (R, T) and length scale ell (include/cvo_hip.h cvo_hip_pose_matches): a
+        PoseMatches.  fixed / moving = False: that side's arrays are not made (no copy back) and the field is None.
+        The context is left as transform_pcd(R, T) leaves it."""
+        R, T = f32(R).reshape(9), f32(T).reshape(3)
+        out = PoseMatchesC()
+        n = []
+        for which in (0, 1):   # (the library's own counts: the arrays below must hold what it writes)
+            rows, pts = C.c_int(), C.c_int()
+            self._chk(self._L.cvo_hip_get_device_cloud(self._ctx, which, None, None, None, C.byref(rows), C.byref(pts)), "pose_matches")
+            n.append(max(pts.value, 0))
+        sides, structs = [], []
+        for want, k in ((fixed, n[0]), (moving, n[1])):
+            if not want:
+                sides.append(None)
+                structs.append(None)
+                continue
+            pm = PointMatches(np.zeros(k, np.float64), np.zeros(k, np.int32), np.full(k, -1, np.int32), np.zeros(k, np.float32))
+            sides.append(pm)
+            structs.append(PointMatchesC(pm.support.ctypes.data_as(C.POINTER(C.c_double)),
+                                         pm.count.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         pm.best.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         pm.best_w.ctypes.data_as(C.POINTER(C.c_float))))
+        self._chk(self._L.cvo_hip_pose_matches(self._ctx, fptr(R), fptr(T), np.float32(ell),
+                                               C.byref(structs[0]) if structs[0] else None,
+                                               C.byref(structs[1]) if structs[1] else None, C.byref(out)), "pose_matches")
+        return PoseMatches(float(out.inner), int(out.nnz), int(out.n_fixed), int(out.n_moving), int(out.fixed_matched),
+                           int(out.moving_matched), float(out.ell), bool(out.exact), sides[0], sides[1])
 
     def align(self, state, trace_cap=2000):
         tr = (Trace * trace_cap)() if trace_cap > 0 else None

@@ -54,6 +54,7 @@ const OptDef kOptions[] = {
     {"run_build_at", "CVO_HIP_RUN_BUILD_AT", 2, 0.0},         {"alone_max", "CVO_HIP_ALONE_MAX", 2, 0.0},
     {"narrow_merge", "CVO_HIP_NARROW_MERGE", 1, 1.0},     {"narrow_blocks", "CVO_HIP_NARROW_BLOCKS", 2, 0.0},
     {"engine_crowd", "CVO_HIP_ENGINE_CROWD", 2, 0.0},     {"engine_merge_max", "CVO_HIP_ENGINE_MERGE_MAX", 2, 0.0},
+    {"matches_combine", nullptr, 0, 0.0},
 };
 void env_defaults(cvo_hip_ctx *ctx)
 {
@@ -104,6 +105,7 @@ int apply_option(cvo_hip_ctx *ctx, const char *key, double v)
     else if (is("engines")) { if (v < 0.0 || v > 8.0) return CVO_HIP_ERR_INVALID; o.engines_force = (int)v; }
     else if (is("list_init")) { if (v < 0.0) return CVO_HIP_ERR_INVALID; o.list_init = v; }
     else if (is("kept_pack")) o.no_pack = !on;
+    else if (is("matches_combine")) o.matches_combine = on;
     else if (is("list_margin")) { if (v > 4.0) return CVO_HIP_ERR_INVALID; o.list_margin = v < 0.0 ? -1.0f : (float)v; }
     else if (is("final_mirror")) o.no_final_mirror = !on;
     else if (is("twist_on_shared_gpu")) o.twist_on_shared_gpu = on;
@@ -217,19 +219,18 @@ bool self_norm_valid(const cvo_hip_ctx *ctx, const Cloud &c, float ell)
 }
 
 // Everything a score is refused for, checked before anything is enqueued.
-int score_check(cvo_hip_ctx *ctx, const float *R, const float *T, float ell, const void *out)
+int score_check(cvo_hip_ctx *ctx, const char *who, const float *R, const float *T, float ell, const void *out)
 {
-    if (!R || !T || !out) return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: null argument");
+    auto refuse = [&](const char *why) { return fail(ctx, CVO_HIP_ERR_INVALID, (std::string(who) + why).c_str()); };
+    if (!R || !T || !out) return refuse(": null argument");
     if (!(std::isfinite(ell) && ell > 0.0f))
-        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: ell must be finite and > 0");
+        return refuse(": ell must be finite and > 0");
     if (ctx->fixed.n <= 0 || ctx->moving.n <= 0)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: both clouds must be set");
+        return refuse(": both clouds must be set");
     if (ctx->sharded && (ctx->row_lo > 0 || ctx->row_hi < ctx->fixed.n || ctx->srow_lo > 0 || ctx->srow_hi < ctx->moving.n))
-        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: not on a sharded context (the overlap counts do not add "
-                                              "up over shards)");
+        return refuse(": not on a sharded context (the overlap counts do not add up over shards)");
     if (multi_rank(ctx) || ctx->mailbox)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_score: not with a communicator, mailboxes or an all-reduce "
-                                              "hook attached");
+        return refuse(": not with a communicator, mailboxes or an all-reduce hook attached");
     return CVO_HIP_OK;
 }
 
@@ -426,6 +427,152 @@ int score_batch(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, cons
     return CVO_HIP_OK;
 }
 
+// ---- cvo_hip_pose_matches (include/cvo_hip.h)
+// Layout of one side's output arrays, on the device (after the accumulators) and in the pinned staging alike:
+// support [n] float64, count [n] int32, best [n] int32, best_w [n] float32, the side padded to 16 bytes.
+struct MatchSide {
+    size_t off, support, count, best, best_w, bytes;
+};
+MatchSide match_side(size_t off, int n)
+{
+    MatchSide m;
+    m.off = off;
+    m.support = off;
+    m.count = m.support + (size_t)n * sizeof(double);
+    m.best = m.count + (size_t)n * sizeof(int32_t);
+    m.best_w = m.best + (size_t)n * sizeof(int32_t);
+    m.bytes = (((size_t)n * 20) + 15) & ~(size_t)15;
+    return m;
+}
+
+// The pass at the pose (cvo_hip_pose_score's, without the self passes), the matches pass over its kept list, and the
+// copies of what the caller wants into pinned memory; no wait.
+int matches_enqueue(cvo_hip_ctx *ctx, const ScoreJob &job, const bool want[2])
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = cloud_ready(ctx, ctx->fixed);
+    if (!rc) rc = cloud_ready(ctx, ctx->moving);
+    if (rc) return rc;
+    if (!ctx->score_pin) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->score_pin, sizeof(ScorePin), hipHostMallocDefault));
+    // the context ends as cvo_hip_transform_pcd(ctx, R, T) leaves it
+    DevState *h = &ctx->st_host[kPollSlots];
+    std::memcpy(h->R, job.R, sizeof(h->R));
+    std::memcpy(h->T, job.T, sizeof(h->T));
+    cvo_math::inverse_tf(job.R, job.T, h->Rt, h->t);
+    h->done = 0;
+    h->kc = make_kconsts(ctx->dprm, job.ell);
+    h->kc_ell = -1.0f;   // (never equal to an ell: prepare_iteration recomputes)
+    rc = fill_filter_geometry(ctx, h);
+    if (rc) return rc;
+    compute_filter_bounds(h, false);
+    int rlo, rhi, slo, shi;
+    shard_ranges(ctx, rlo, rhi, slo, shi);
+    rc = score_pass(ctx, kScorePose, ctx->fixed, rlo, rhi, ctx->moving, 1);
+    if (rc) return rc;
+    const int na = ctx->fixed.np, nb = ctx->moving.np;
+    const size_t acc_off = sizeof(MatchCounters);
+    const size_t acc_bytes = ((size_t)na + (size_t)nb) * sizeof(MatchAcc);
+    const MatchSide sd[2] = {match_side(acc_off + acc_bytes, ctx->fixed.n),
+                             match_side(acc_off + acc_bytes + match_side(0, ctx->fixed.n).bytes, ctx->moving.n)};
+    rc = ensure_buf(ctx, ctx->part_matches, sd[1].off + sd[1].bytes);
+    if (rc) return rc;
+    // pinned: the counters, then the sides that are wanted
+    const size_t stage_off[2] = {sizeof(MatchCounters), sizeof(MatchCounters) + (want[0] ? sd[0].bytes : 0)};
+    const size_t stage_bytes = stage_off[1] + (want[1] ? sd[1].bytes : 0);
+    if (stage_bytes > ctx->match_stage_bytes) {
+        if (ctx->match_stage) HIP_TRY(ctx, hipHostFree(ctx->match_stage));
+        ctx->match_stage = nullptr;
+        ctx->match_stage_bytes = 0;
+        const size_t grown = stage_bytes * 5 / 4 + 4096;
+        if (hipHostMalloc(&ctx->match_stage, grown, hipHostMallocDefault) != hipSuccess) {
+            ctx->match_stage = nullptr;
+            (void)hipGetLastError();
+            return fail(ctx, CVO_HIP_ERR_NOMEM, "cvo_hip_pose_matches: no pinned memory for the staging");
+        }
+        ctx->match_stage_bytes = grown;
+    }
+    char *pm = static_cast<char *>(ctx->part_matches.p);
+    HIP_TRY(ctx, hipMemsetAsync(pm, 0, acc_off + acc_bytes, ctx->stream));
+    MatchArgs ma{};
+    ma.feat_a = ctx->fixed.feat;
+    ma.feat_b = ctx->moving.feat;
+    ma.kept_ij = (const uint2 *)ctx->lists[LIST_KEPT].a.p;
+    ma.kept_a = (const float *)ctx->lists[LIST_KEPT].b.p;
+    ma.kept_cnt = (const uint32_t *)ctx->kept_cnt.p;
+    ma.st = ctx->st;
+    ma.counters = reinterpret_cast<MatchCounters *>(pm);
+    ma.acc_a = reinterpret_cast<MatchAcc *>(pm + acc_off);
+    ma.acc_b = ma.acc_a + na;
+    for (int s = 0; s < 2; ++s) {
+        ma.out[s].support = reinterpret_cast<double *>(pm + sd[s].support);
+        ma.out[s].count = reinterpret_cast<int32_t *>(pm + sd[s].count);
+        ma.out[s].best = reinterpret_cast<int32_t *>(pm + sd[s].best);
+        ma.out[s].best_w = reinterpret_cast<float *>(pm + sd[s].best_w);
+    }
+    ma.na = na;
+    ma.nb = nb;
+    ma.n_fixed = ctx->fixed.n;
+    ma.n_moving = ctx->moving.n;
+    ma.blocks_a = (na + BLOCK - 1) / BLOCK;
+    ma.blocks_b = (nb + BLOCK - 1) / BLOCK;
+    ma.nblk = ctx->proc_blocks;
+    ma.kept_wcap = ctx->lists[LIST_KEPT].cap / (uint32_t)(4 * ctx->proc_blocks);   // (enqueue_process's slice)
+    ma.kept_packed = kept_format(ctx, &ma.kept_ebase);
+    launch_pose_matches(ma, ctx->opt.matches_combine, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    char *stage = static_cast<char *>(ctx->match_stage);
+    HIP_TRY(ctx, hipMemcpyAsync(stage, pm, sizeof(MatchCounters), hipMemcpyDeviceToHost, ctx->stream));
+    for (int s = 0; s < 2; ++s)
+        if (want[s] && sd[s].bytes)
+            HIP_TRY(ctx, hipMemcpyAsync(stage + stage_off[s], pm + sd[s].off, sd[s].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->have_tf = true;
+    return CVO_HIP_OK;
+}
+
+// After the wait: a tile or kept list that overflowed grows and the call is enqueued again (*redo), as score_collect
+// does; otherwise the summary and the caller's arrays.
+int matches_collect(cvo_hip_ctx *ctx, const ScoreJob &job, const cvo_hip_point_matches *const side[2],
+                    cvo_hip_pose_matches_t *summary, bool *redo)
+{
+    const ScorePin *pin = ctx->score_pin;
+    *redo = false;
+    for (int l = 0; l < LIST_N; ++l) {
+        if (!(pin->ovf[kScorePose][l] | pin->ovf[kScorePose][8 + l])) continue;
+        const uint32_t cap = ctx->lists[l].cap;
+        int rc = ensure_list(ctx, l, 0, 0, std::min(4.0e9, 2.0 * (double)cap + 1024.0));
+        if (rc) return rc;
+        if (ctx->lists[l].cap <= cap) return fail(ctx, CVO_HIP_ERR_NOMEM, "cvo_hip_pose_matches: a list cannot grow further");
+        *redo = true;
+    }
+    if (*redo) return CVO_HIP_OK;
+    const char *stage = static_cast<const char *>(ctx->match_stage);
+    MatchCounters cnt;
+    std::memcpy(&cnt, stage, sizeof(cnt));
+    cvo_hip_pose_matches_t r{};
+    r.inner = pin->red[kScorePose][6];
+    r.nnz = (int64_t)pin->red[kScorePose][8];
+    r.n_fixed = ctx->fixed.n;
+    r.n_moving = ctx->moving.n;
+    r.fixed_matched = (int32_t)cnt.matched_a;
+    r.moving_matched = (int32_t)cnt.matched_b;
+    r.ell = job.ell;
+    r.exact = cnt.inexact == 0 ? 1 : 0;
+    *summary = r;
+    size_t off = sizeof(MatchCounters);
+    for (int s = 0; s < 2; ++s) {
+        if (!side[s]) continue;
+        const int n = s == 0 ? ctx->fixed.n : ctx->moving.n;
+        const MatchSide m = match_side(off, n);
+        if (side[s]->support) std::memcpy(side[s]->support, stage + m.support, (size_t)n * sizeof(double));
+        if (side[s]->count) std::memcpy(side[s]->count, stage + m.count, (size_t)n * sizeof(int32_t));
+        if (side[s]->best) std::memcpy(side[s]->best, stage + m.best, (size_t)n * sizeof(int32_t));
+        if (side[s]->best_w) std::memcpy(side[s]->best_w, stage + m.best_w, (size_t)n * sizeof(float));
+        off += m.bytes;
+    }
+    if (ctx->profiling) return drain_events(ctx);
+    return CVO_HIP_OK;
+}
+
 }   // namespace
 }   // namespace cvo_impl
 
@@ -611,7 +758,7 @@ int cvo_hip_destroy(cvo_hip_ctx *ctx)
                     (void *)ctx->moving.feat, (void *)ctx->fixed.seg, (void *)ctx->moving.seg,
                     (void *)ctx->scratch_a.pos, (void *)ctx->scratch_a.feat, (void *)ctx->scratch_a.seg,
                     (void *)ctx->scratch_b.pos, (void *)ctx->scratch_b.feat, (void *)ctx->scratch_b.seg, (void *)ctx->st, (void *)ctx->st2, ctx->part_flow.p, ctx->part_xx.p,
-                    ctx->part_yy.p, ctx->part_step.p, ctx->part_hess.p, ctx->part_score.p, ctx->run_mail.p, (void *)ctx->trace_dev, ctx->kept_cnt.p, ctx->pos_bt.p, ctx->cand[0].p, ctx->cand[1].p, ctx->cand[2].p, ctx->cand_xyb.p, ctx->cand_cnt_xyb.p, ctx->cand_sfb[0].p, ctx->cand_sfb[1].p, ctx->cand_cnt_sfb[0].p, ctx->cand_cnt_sfb[1].p, ctx->cand_cnt[0].p,
+                    ctx->part_yy.p, ctx->part_step.p, ctx->part_hess.p, ctx->part_score.p, ctx->part_matches.p, ctx->run_mail.p, (void *)ctx->trace_dev, ctx->kept_cnt.p, ctx->pos_bt.p, ctx->cand[0].p, ctx->cand[1].p, ctx->cand[2].p, ctx->cand_xyb.p, ctx->cand_cnt_xyb.p, ctx->cand_sfb[0].p, ctx->cand_sfb[1].p, ctx->cand_cnt_sfb[0].p, ctx->cand_cnt_sfb[1].p, ctx->cand_cnt[0].p,
                     ctx->cand_cnt[1].p, ctx->cand_cnt[2].p})
         if (p) (void)hipFree(p);
     for (int l = 0; l < LIST_N; ++l) {
@@ -620,6 +767,7 @@ int cvo_hip_destroy(cvo_hip_ctx *ctx)
     }
     if (ctx->st_host) (void)hipHostFree(ctx->st_host);
     if (ctx->score_pin) (void)hipHostFree(ctx->score_pin);
+    if (ctx->match_stage) (void)hipHostFree(ctx->match_stage);
     for (Cloud *c : {&ctx->fixed, &ctx->moving, &ctx->scratch_a, &ctx->scratch_b}) {
         if (c->pending && (c->wait_ev || c->ready_ev)) (void)hipEventSynchronize(c->wait_ev ? c->wait_ev : c->ready_ev);
         if (c->stage) (void)hipHostFree(c->stage);
@@ -990,7 +1138,7 @@ int cvo_hip_pose_score(cvo_hip_ctx *ctx, const float R[9], const float T[3], flo
 {
     cvo_lock::Api api_guard;
     if (!ctx) return CVO_HIP_ERR_INVALID;
-    int rc = score_check(ctx, R, T, ell, out);
+    int rc = score_check(ctx, "cvo_hip_pose_score", R, T, ell, out);
     if (rc) return rc;
     return score_batch(&ctx, R, T, &ell, out, 1);
 }
@@ -1009,10 +1157,37 @@ int cvo_hip_pose_score_many(cvo_hip_ctx *const *ctxs, const float *R9, const flo
             if (ctxs[q] == ctxs[k]) return fail(ctxs[0], CVO_HIP_ERR_INVALID, "cvo_hip_pose_score_many: a context twice");
     }
     for (int k = 0; k < count; ++k) {
-        const int rc = score_check(ctxs[k], R9 + 9 * (size_t)k, T3 + 3 * (size_t)k, ell[k], out + k);
+        const int rc = score_check(ctxs[k], "cvo_hip_pose_score", R9 + 9 * (size_t)k, T3 + 3 * (size_t)k, ell[k], out + k);
         if (rc) return rc;
     }
     return score_batch(ctxs, R9, T3, ell, out, count);
+}
+
+int cvo_hip_pose_matches(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
+                         const cvo_hip_point_matches *fixed, const cvo_hip_point_matches *moving,
+                         cvo_hip_pose_matches_t *summary)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    int rc = score_check(ctx, "cvo_hip_pose_matches", R, T, ell, summary);
+    if (rc) return rc;
+    ScoreJob job{};
+    std::memcpy(job.R, R, sizeof(job.R));
+    std::memcpy(job.T, T, sizeof(job.T));
+    job.ell = ell;
+    const cvo_hip_point_matches *const side[2] = {fixed, moving};
+    // (a side none of whose arrays is wanted costs no copy back either)
+    const bool want[2] = {fixed && (fixed->support || fixed->count || fixed->best || fixed->best_w),
+                          moving && (moving->support || moving->count || moving->best || moving->best_w)};
+    const cvo_hip_point_matches *const copy[2] = {want[0] ? side[0] : nullptr, want[1] ? side[1] : nullptr};
+    for (bool redo = true; redo;) {
+        rc = matches_enqueue(ctx, job, want);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        rc = matches_collect(ctx, job, copy, summary, &redo);
+        if (rc) return rc;
+    }
+    return CVO_HIP_OK;
 }
 
 int cvo_hip_pick_step(const double bcde[4], float min_step, float *step)
@@ -1238,6 +1413,7 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     else if (is("engine_merge_max")) *value = o.engine_merge_max;
     else if (is("list_init")) *value = o.list_init;
     else if (is("kept_pack")) *value = !o.no_pack;
+    else if (is("matches_combine")) *value = o.matches_combine;
     else if (is("list_margin")) *value = o.list_margin;
     else if (is("final_mirror")) *value = !o.no_final_mirror;
     else if (is("twist_on_shared_gpu")) *value = o.twist_on_shared_gpu;

@@ -201,6 +201,12 @@ void registration::pose_score(const float R[9], const float T[3], float ell, cvo
     check(cvo_hip_pose_score(ctx_, R, T, ell, out), "cvo_hip_pose_score");
 }
 
+void registration::pose_matches(const float R[9], const float T[3], float ell, const cvo_hip_point_matches *fixed,
+                                const cvo_hip_point_matches *moving, cvo_hip_pose_matches_t *summary)
+{
+    check(cvo_hip_pose_matches(ctx_, R, T, ell, fixed, moving, summary), "cvo_hip_pose_matches");
+}
+
 void registration::align_many(registration *const *objects, int count)
 {
     std::vector<cvo_hip_ctx *> ctxs((size_t)count);

@@ -1014,6 +1014,48 @@ struct ScoreArgs {
 };
 void launch_pose_score(const ScoreArgs &a, hipStream_t s);
 
+// Per-point support and best match (cvo_matches.hip, include/cvo_hip.h cvo_hip_pose_matches): one pass over the kept list
+// a PROC_FLOW pass recorded accumulates per device row of either cloud with integer atomics; a finishing pass writes
+// the rows' results at their caller's indices.
+struct MatchAcc {               // one device row's accumulators: 32 bytes, one sector (zeroed on the stream before the pass)
+    unsigned long long best;    // (bits of the largest weight << 32) | (0xFFFFFFFF - caller's index of its other point); 0: none
+    unsigned long long units;   // the sum of the weights in units of 2^(floor(log2(inner)) - 61)
+    unsigned count;             // members
+    unsigned pad_[3];
+};
+static_assert(sizeof(MatchAcc) == 32, "a row's accumulators are one 32-byte sector");
+struct MatchCounters {          // zeroed with the accumulators
+    unsigned matched_a, matched_b;   // rows of either cloud with a member
+    unsigned inexact;           // members whose weight lost a bit below the unit (cvo_matches.hip)
+    unsigned pad_;
+};
+struct MatchOut {               // one side's results in the caller's order (device)
+    double *support;
+    int32_t *count;
+    int32_t *best;
+    float *best_w;
+};
+struct MatchArgs {
+    const float *feat_a;        // the fixed / moving cloud's feature rows: word FEAT_INDEX_SLOT is the caller's index
+    const float *feat_b;
+    const uint2 *kept_ij;       // the kept list, its weights (kept_packed == 0) and per-wave counts (ProcessArgs)
+    const float *kept_a;
+    const uint32_t *kept_cnt;
+    const DevState *st;         // red[RED_FLOW + 6]: the sum of all weights of the pass
+    MatchAcc *acc_a;            // [na]
+    MatchAcc *acc_b;            // [nb]
+    MatchCounters *counters;
+    MatchOut out[2];            // [0] the fixed cloud's [n_fixed], [1] the moving cloud's [n_moving]
+    uint32_t kept_wcap;
+    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
+    int kept_packed;
+    unsigned kept_ebase;
+    int na, nb;                 // rows of the two clouds' device arrays
+    int n_fixed, n_moving;      // points as the caller counts them
+    int blocks_a, blocks_b;     // blocks of the finishing pass per side
+};
+void launch_pose_matches(const MatchArgs &a, bool combine, hipStream_t s);
+
 void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t *build_masks = nullptr, const PrepareInit *init = nullptr);
 void launch_filter(const FilterArgs &a, dim3 grid, hipStream_t s, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);

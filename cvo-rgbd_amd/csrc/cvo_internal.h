@@ -249,6 +249,7 @@ struct CtxOptions {
     bool no_alone = false;            // "small_calls_alone" = 0: small align_many calls through the engines
     bool no_fuse = false;             // "fused_groups" = 0: align_many runs every registration on its own stream
     bool no_pack = false;             // "kept_pack" = 0: 8 + 4 byte kept entries
+    bool matches_combine = true;      // "matches_combine" = 0: cvo_hip_pose_matches sends every member's atomics of the fixed row on their own
     bool no_final_mirror = false;     // "final_mirror" = 0: the final state comes by a copy in stream order
     bool twist_on_shared_gpu = false; // "twist_on_shared_gpu": in-launch exchange although the ranks share a GPU
     bool comm_debug = false;          // "comm_debug"
@@ -351,6 +352,9 @@ struct cvo_hip_ctx {
     DevBuf part_hess;                    // cvo_hip_pose_hessian: [NACC_HESS][nblk] block partials, then the [NACC_HESS] sums
     DevBuf part_score;                   // cvo_hip_pose_score: [PROC_BLOCKS] block partials, [4] sums, the matched bytes
     struct ScorePin *score_pin = nullptr;   // cvo_hip_pose_score: pinned staging of its passes (cvo_capi.cpp)
+    DevBuf part_matches;                 // cvo_hip_pose_matches: MatchCounters, the rows' MatchAcc, the output arrays of both sides
+    void *match_stage = nullptr;         // ... its pinned staging: MatchCounters, then the arrays that come back
+    size_t match_stage_bytes = 0;
     List lists[LIST_N];
     DevBuf kept_cnt;                 // uint32[PROC_WAVES]
     cvo_hip_trace *trace_dev = nullptr;

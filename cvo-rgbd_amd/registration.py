@@ -29,6 +29,8 @@ class _Registration:
         self.hessian = None   # align(hessian=True) publishes the pose Hessian here
         self.score = None     # align(score=...) publishes the pose score here
         self.scores = []      # run_sequence(score=...): one pose score per pair
+        self.matches = None   # align(matches=...) publishes the per-point matches here
+        self.matches_list = []   # run_sequence(matches=...): one capi.PoseMatches per pair
         self._have_moving = False
 
     def _publish(self):
@@ -56,13 +58,13 @@ class _Registration:
         self.ctx.set_moving_device(d_positions, d_features, n, layout)
         self._have_moving = True
 
-    def run_cvo_device(self, d_positions, d_features, n, layout=capi.FEAT_ROWMAJOR, trace_cap=0, score=False):
+    def run_cvo_device(self, d_positions, d_features, n, layout=capi.FEAT_ROWMAJOR, trace_cap=0, score=False, matches=False):
         first = not self.init
         self.set_pcd_device(d_positions, d_features, n, layout)
         if not first:
-            self.align(trace_cap=trace_cap, score=score)
+            self.align(trace_cap=trace_cap, score=score, matches=matches)
 
-    def align(self, trace_cap=0, hessian=False, score=False):
+    def align(self, trace_cap=0, hessian=False, score=False, matches=False):
         """ref src/cvo.cpp:361-420.
 
         hessian=True: after the loop, evaluate the pose Hessian of the CVO objective at the final R, T and
@@ -74,7 +76,14 @@ class _Registration:
         include/cvo_hip.h cvo_hip_pose_score) at ``params.ell_init`` -- one fixed length scale per object, so
         that the scores of a sequence can be compared and each cloud's norm is computed once -- and publish it
         as ``self.score`` (a capi.PoseScore; cos_angle is the normalised inner product).  A float: score at
-        that length scale.  The registration itself is the same bit for bit with or without either."""
+        that length scale.
+
+        matches=True (or a length scale, as for score): after the loop, ask which points matched at the final R, T
+        (capi.Context.pose_matches, include/cvo_hip.h cvo_hip_pose_matches) and publish the answer as
+        ``self.matches`` (a capi.PoseMatches: per point of the fixed and of the moving cloud, in the caller's order,
+        the support, the number of members and the best match in the other cloud).
+
+        The registration itself is the same bit for bit with or without any of them."""
         if not self._have_moving:
             raise capi.CvoHipError("align(): set_pcd() must precede each align()")
         self.num_iterations, self.trace = self.ctx.align(self.state, trace_cap=trace_cap)
@@ -85,19 +94,23 @@ class _Registration:
             s = self.state
             ell = self.params.ell_init if score is True else float(score)
             self.score = self.ctx.pose_score(np.array(s.R, np.float32), np.array(s.T, np.float32), ell)
+        if matches is not False and matches is not None:
+            s = self.state
+            ell = self.params.ell_init if matches is True else float(matches)
+            self.matches = self.ctx.pose_matches(np.array(s.R, np.float32), np.array(s.T, np.float32), ell)
         self.ctx.swap_moving_to_fixed()   # ptr_fixed_pcd = std::move(ptr_moving_pcd)
         self._have_moving = False
         self._publish()
 
-    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False, score=False):
-        """ref src/cvo.cpp:422-435 (hessian, score: see align())."""
+    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False, score=False, matches=False):
+        """ref src/cvo.cpp:422-435 (hessian, score, matches: see align())."""
         if not self.init:
             self.set_pcd(positions, features, layout)
         else:
             self.set_pcd(positions, features, layout)
-            self.align(trace_cap=trace_cap, hessian=hessian, score=score)
+            self.align(trace_cap=trace_cap, hessian=hessian, score=score, matches=matches)
 
-    def run_sequence(self, frames, writer=None, trace_cap=0, hessian=False, score=False):
+    def run_sequence(self, frames, writer=None, trace_cap=0, hessian=False, score=False, matches=False):
         """The loop of the reference's drivers (ref src/cvo_main.cpp:36-66): every
         frame goes through run_cvo() and then gets a pose line of `accum_transform`
         in `writer` (a trajectory.TrajectoryWriter) -- the first frame too (the
@@ -106,15 +119,21 @@ class _Registration:
         positions, features).  Returns the per-pair iteration counts.  hessian=True: every
         pair's align() evaluates the pose Hessian (align()); the last one stays in ``self.hessian``.
         score=True (or a length scale): every pair is scored (align()) and ``self.scores`` holds one
-        capi.PoseScore per pair of this call, in order."""
+        capi.PoseScore per pair of this call, in order.  matches=True (or a length scale): likewise
+        ``self.matches_list`` holds one capi.PoseMatches per pair (fixed = the earlier frame of the pair)."""
         iters = []
+        want_matches = matches is not False and matches is not None
+        if want_matches:
+            self.matches_list = []
         if score is not False and score is not None:
             self.scores = []
         for name, positions, features in frames:
             first = not self.init
-            self.run_cvo(positions, features, trace_cap=trace_cap, hessian=hessian, score=score)
+            self.run_cvo(positions, features, trace_cap=trace_cap, hessian=hessian, score=score, matches=matches)
             if not first:
                 iters.append(self.num_iterations)
+                if want_matches:
+                    self.matches_list.append(self.matches)
                 if score is not False and score is not None:
                     self.scores.append(self.score)
             if writer is not None and self.init:

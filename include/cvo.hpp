@@ -85,6 +85,11 @@ class registration {
     void align(cvo_hip_pose_score_t *score, float score_ell, cvo_hip_pose_hessian_t *hessian = nullptr);
     // cvo_hip_pose_score of the clouds set, at the pose (R, T) and length scale ell
     void pose_score(const float R[9], const float T[3], float ell, cvo_hip_pose_score_t *out);
+    // cvo_hip_pose_matches of the clouds set, at the pose (R, T) and length scale ell: which points matched.  fixed /
+    // moving: the caller's arrays of one entry per point of that cloud, in the order the cloud was handed over (null: that
+    // side is not wanted); summary: the counts and the inner product, cvo_hip_pose_score's of the same name.
+    void pose_matches(const float R[9], const float T[3], float ell, const cvo_hip_point_matches *fixed,
+                      const cvo_hip_point_matches *moving, cvo_hip_pose_matches_t *summary);
     void run_cvo(const point_cloud_view &pc);
     // The reference's own signatures (ref include/cvo.hpp:171-192): images in, the front
     // end (pcd_generator) runs first -- on the GPU.  The two paths are dead parameters

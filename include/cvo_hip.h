@@ -367,6 +367,61 @@ int cvo_hip_pose_score(cvo_hip_ctx *ctx, const float R[9], const float T[3], flo
 int cvo_hip_pose_score_many(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, const float *ell,
                             cvo_hip_pose_score_t *out, int count);
 
+/* Which points matched: per point of either cloud, its share of the CVO inner product at a pose
+ * (R, T) and length scale ell, and its best match in the other cloud.
+ *
+ * Member rule: the member set A and the float32 weights a are exactly those cvo_hip_flow(ctx,
+ * ell, ...) keeps at the pose -- the set cvo_hip_pose_hessian and cvo_hip_pose_score sum over; the
+ * summary's inner, nnz, fixed_matched and moving_matched are cvo_hip_pose_score's, bit for bit.
+ * For point i of the fixed cloud (for point j of the moving cloud likewise, with the roles swapped):
+ *   count[i]   = the members (i, j) of A;
+ *   support[i] = the sum of their weights: sum_i support[i] = sum_j support[j] = inner;
+ *   best[i]    = the j of the member with the largest weight, the smallest such j if several
+ *                share it; -1 if the point has no member;
+ *   best_w[i]  = that weight; 0 if none.
+ * Indices are the caller's on both sides: array position i is point i of the cloud as it was
+ * handed over (host or device arrays, a batched hand-over, the front end's cloud; a cloud that
+ * cvo_hip_swap_moving_to_fixed moved keeps its indices), and best holds such an index of the
+ * other cloud.
+ *
+ * Arithmetic: counts and best are exact.  A support is accumulated in 64-bit fixed point with a
+ * unit of 2^-61 of the binade of inner, in which a float32 weight of at least inner * 2^-38 is
+ * an exact integer and no sum can overflow (cvo_matches.hip); the sum is then rounded once to
+ * float64.  summary.exact = 1 says every weight was such an integer: each support is the
+ * correctly rounded sum of its weights -- and the sum itself wherever that fits a float64,
+ * as it does for cvo and acvo weights (sp_thres < a <= sigma^2 c_sigma^2) of realistic clouds.
+ * exact = 0 (weights more than 38 binades below inner, conceivable with the MATLAB weight only):
+ * each such weight was cut to the unit, an error below inner * 2^-61 per member.  Nothing depends
+ * on the order in which the device meets the members: repeated calls give the same bytes.
+ *
+ * fixed / moving: the caller's host arrays of n_fixed / n_moving elements; a null array is not
+ * wanted, a null struct wants none of that side and costs no copy back.  Device memory and the
+ * pinned staging are the context's and grow with the clouds.
+ *
+ * The context is left as cvo_hip_transform_pcd(ctx, R, T) leaves it; a cvo_hip_align before or
+ * after is unaffected.  An empty A is CVO_HIP_OK: zeros, and -1 in best.
+ * CVO_HIP_ERR_INVALID: as cvo_hip_pose_score -- null R, T or summary, ell not finite or not > 0, a
+ * cloud missing, a sharded context (cvo_hip_set_shard narrower than the whole clouds), or a
+ * communicator, mailboxes or an all-reduce hook attached. */
+typedef struct cvo_hip_pose_matches_summary {
+    double inner;           /* sum of a over A (cvo_hip_pose_score's inner) */
+    int64_t nnz;            /* |A| */
+    int32_t n_fixed, n_moving;
+    int32_t fixed_matched;  /* fixed points with at least one member */
+    int32_t moving_matched; /* moving points with at least one member */
+    float ell;              /* the length scale used */
+    int32_t exact;          /* 1: every support is the correctly rounded sum of its weights */
+} cvo_hip_pose_matches_t;
+typedef struct cvo_hip_point_matches {   /* one side; every pointer may be NULL (not wanted) */
+    double *support;        /* [n] sum of the weights of the point's members, 0 if none */
+    int32_t *count;         /* [n] number of members */
+    int32_t *best;          /* [n] index, in the OTHER cloud, of the member with the largest weight; -1 if none */
+    float *best_w;          /* [n] that weight, 0 if none */
+} cvo_hip_point_matches;
+int cvo_hip_pose_matches(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
+                         const cvo_hip_point_matches *fixed, const cvo_hip_point_matches *moving,
+                         cvo_hip_pose_matches_t *summary);
+
 /* Root selection + clamps (ref src/cvo.cpp:291-307), Exp_SEK3
  * (ref src/LieGroup.cpp:159-186) and dist_se3 (ref src/cvo.cpp:71-81): the O(1)
  * host maths of the loop, exported for tests and for callers that drive the

@@ -2,7 +2,7 @@
 """Register / scratch / LDS table of every kernel of cvo_kernels.hip, from the compiler's own
 metadata (no GPU needed):
 
-    python tools/isa_resources.py [out.txt] [--src cvo_hessian.hip]
+    python tools/isa_resources.py [out.txt] [--src cvo_hessian.hip | cvo_score.hip | cvo_matches.hip]
 
 compiles cvo-rgbd_amd/csrc/cvo_kernels.hip (or the --src file of that directory) with the Makefile's flags + -save-temps into a scratch
 directory and reads the amdhsa.kernels notes of the gfx950 assembly."""
