@@ -25,7 +25,7 @@ SYMBOLS = [
     "cvo_hip_pose_score_many", "cvo_hip_pose_matches", "cvo_hip_pick_step",
     "cvo_hip_exp_se3", "cvo_hip_dist_se3", "cvo_hip_align", "cvo_hip_align_many",
     "cvo_hip_function_inner_product", "cvo_hip_function_inner_product_clouds",
-    "cvo_hip_engine_profiling", "cvo_hip_get_engine_profile", "cvo_hip_get_engine_flow_trace", "cvo_hip_get_wave_load", "cvo_hip_set_graph_capture", "cvo_hip_set_profiling", "cvo_hip_get_profile", "cvo_hip_get_graph_stats", "cvo_hip_get_run_stats", "cvo_hip_get_run_clocks", "cvo_hip_get_mirror_retries", "cvo_hip_synchronize",
+    "cvo_hip_engine_profiling", "cvo_hip_get_engine_profile", "cvo_hip_get_engine_flow_trace", "cvo_hip_get_wave_load", "cvo_hip_set_graph_capture", "cvo_hip_set_profiling", "cvo_hip_get_profile", "cvo_hip_get_graph_stats", "cvo_hip_get_run_stats", "cvo_hip_get_list_stats", "cvo_hip_get_run_clocks", "cvo_hip_get_mirror_retries", "cvo_hip_synchronize",
     "cvo_hip_set_option", "cvo_hip_get_option",
 ]
 
@@ -224,6 +224,7 @@ def lib():
     L.cvo_hip_get_mirror_retries.argtypes = []
     L.cvo_hip_get_mirror_retries.restype = C.c_longlong
     L.cvo_hip_get_run_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.cvo_hip_get_list_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.cvo_hip_synchronize.argtypes = [vp]
     L.cvo_hip_set_option.argtypes = [vp, C.c_char_p, C.c_double]
     L.cvo_hip_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double)]
@@ -559,6 +560,12 @@ class Context:
         a, b, c, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         self._chk(self._L.cvo_hip_get_run_stats(self._ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "run_stats")
         return a.value, b.value, c.value, d.value
+
+    def list_stats(self):
+        """(all-pairs xy builds, narrowings of the candidate record, re-expansions) of this context's last registration."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self._L.cvo_hip_get_list_stats(self._ctx, C.byref(a), C.byref(b), C.byref(c)), "list_stats")
+        return a.value, b.value, c.value
 
     def run_clocks(self):
         buf = (C.c_longlong * 16)()

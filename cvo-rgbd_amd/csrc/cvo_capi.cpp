@@ -55,6 +55,7 @@ const OptDef kOptions[] = {
     {"narrow_merge", "CVO_HIP_NARROW_MERGE", 1, 1.0},     {"narrow_blocks", "CVO_HIP_NARROW_BLOCKS", 2, 0.0},
     {"engine_crowd", "CVO_HIP_ENGINE_CROWD", 2, 0.0},     {"engine_merge_max", "CVO_HIP_ENGINE_MERGE_MAX", 2, 0.0},
     {"matches_combine", nullptr, 0, 0.0},
+    {"record_narrow", "CVO_HIP_NO_RECORD_NARROW", 1, 0.0}, {"list_stale_max", "CVO_HIP_LIST_STALE_MAX", 2, 0.0},
 };
 void env_defaults(cvo_hip_ctx *ctx)
 {
@@ -107,6 +108,8 @@ int apply_option(cvo_hip_ctx *ctx, const char *key, double v)
     else if (is("kept_pack")) o.no_pack = !on;
     else if (is("matches_combine")) o.matches_combine = on;
     else if (is("list_margin")) { if (v > 4.0) return CVO_HIP_ERR_INVALID; o.list_margin = v < 0.0 ? -1.0f : (float)v; }
+    else if (is("record_narrow")) o.record_narrow = on;
+    else if (is("list_stale_max")) { if (!(v >= 1.0 && v <= 64.0)) return CVO_HIP_ERR_INVALID; o.list_stale_max = (float)v; }
     else if (is("final_mirror")) o.no_final_mirror = !on;
     else if (is("twist_on_shared_gpu")) o.twist_on_shared_gpu = on;
     else if (is("comm_debug")) o.comm_debug = on;
@@ -181,6 +184,8 @@ DevParams make_dev_params(const cvo_hip_params &p)
     d.color_scale = p.color_scale;
     // tile-list re-use (cvo_device.h plan_lists); CVO_HIP_LIST_MARGIN=0 rebuilds every iteration
     d.build_at = 0.7f;   // (measured 0.3 / 0.5 / 0.7: 1.80 / 1.77 / 1.73 ms per 10k x 10k registration)
+    d.record_narrow = 1;
+    d.list_stale_max = 3.0f;
     d.list_margin = 0.15f;   // (loop_params picks the margin of an align() by size; CVO_HIP_LIST_MARGIN overrides it there)
     return d;
 }
@@ -1358,6 +1363,16 @@ int cvo_hip_get_run_stats(cvo_hip_ctx *ctx, int *runs, int *declined, int *itera
     return CVO_HIP_OK;
 }
 
+int cvo_hip_get_list_stats(const cvo_hip_ctx *ctx, int *builds, int *narrowings, int *reexpansions)
+{
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    // (the counters travel in the state's head: the host's copy of the final state has them, job_finish)
+    if (builds) *builds = ctx->list_stats[0];
+    if (narrowings) *narrowings = ctx->list_stats[1];
+    if (reexpansions) *reexpansions = ctx->list_stats[2];
+    return CVO_HIP_OK;
+}
+
 int cvo_hip_get_run_clocks(cvo_hip_ctx *ctx, long long clocks16[16])
 {
     cvo_lock::Api api_guard;
@@ -1415,6 +1430,8 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     else if (is("kept_pack")) *value = !o.no_pack;
     else if (is("matches_combine")) *value = o.matches_combine;
     else if (is("list_margin")) *value = o.list_margin;
+    else if (is("record_narrow")) *value = o.record_narrow;
+    else if (is("list_stale_max")) *value = o.list_stale_max;
     else if (is("final_mirror")) *value = !o.no_final_mirror;
     else if (is("twist_on_shared_gpu")) *value = o.twist_on_shared_gpu;
     else if (is("comm_debug")) *value = o.comm_debug;

@@ -194,6 +194,8 @@ struct DevParams {
     int32_t async_self;  // acvo: the xx / yy lists are double-buffered too and PROC_SELF rides in the flow launch
     float color_scale;   // cvo_hip_params::color_scale
     float run_cand_cap;  // > 0: the plan has resident runs (kt_run) that hold this many candidates in registers
+    int32_t record_narrow;   // the synchronous plan narrows the xy record when the length scale drops instead of building anew (plan_lists)
+    float list_stale_max;    // ... and lets the tile list behind a narrowed record get this many times wider than a fresh one would be
     double s2_d, cs2_d, dl_step;
 };
 
@@ -223,6 +225,15 @@ struct alignas(16) DevHead {
     int32_t ck_nblk[3];         // candidate list of tile list l (ProcessArgs::cand): recorded by a pass of this many
                                 // blocks over the tile list as it stands; 0 = none (tile list rebuilt / to be rebuilt)
     float list_Rt[9], list_t[3];
+    // The candidate record of the synchronous xy list has a radius and a pose of its own (plan_lists "narrowing"): it holds every
+    // pair closer than rec_r with the moving cloud at [rec_Rt | rec_t].  A fresh build sets them to the tile list's; a narrowing
+    // pass and an expansion of a bounded record set them to the radius and pose of the iteration whose flow pass wrote the record.
+    float rec_r;
+    int32_t narrow;             // REC_NARROW: this iteration's streaming flow pass writes the record back narrowed to rec_r;
+                                // REC_BOUNDED: an expanding pass records only the candidates with d2 < rec_r^2
+    float rec_Rt[9], rec_t[3];
+    int32_t list_stat[3];       // since align() began: all-pairs xy builds named, narrowings named, re-expansions seen (cvo_hip_get_list_stats)
+    int32_t rec_pad_[3];
     // Asynchronous xy builds (DevParams::async_xy): two buffers; FLOW consumes `xy_active`; the
     // k_filter blocks of the launch that READS this state build `xy_target` (-1: none) at the
     // transform recorded for it (xy_Rt / xy_t[target]); `xy_fresh`: the buffer whose build ran in
@@ -262,6 +273,7 @@ struct alignas(16) DevHead {
 };
 // Check word of a head that went to the host's pinned copy (head_publish -> job_pump): every 16-byte piece mixed with its index,
 // summed; DevHead::head_check_ counts as zero and then holds the sum.
+enum { REC_NARROW = 1, REC_BOUNDED = 2 };   // DevHead::narrow
 CVO_HD unsigned head_check_mix(unsigned x, unsigned y, unsigned z, unsigned w, unsigned piece)
 {
     return (x * 0x9E3779B1u + y * 0x85EBCA77u + z * 0xC2B2AE3Du + w * 0x27D4EB2Fu) ^ (piece * 0x165667B1u + 0x9E3779B9u);
@@ -552,6 +564,33 @@ CVO_HD void compute_filter_bounds(DevHead *s, bool identity)
 // above the float32 rounding of the coordinates and of d2 (<= ~1e-5 m here) and
 // far below the margin (>= 1 mm at ell_min): decisions change performance only.
 constexpr float LIST_LOOSE = 1.3f;
+// Narrowing (DevParams::record_narrow; the synchronous xy list of clouds that keep a candidate record).  The record has a
+// radius and a pose of its own, rec_r and [rec_Rt | rec_t], and is re-used while
+//     sqrt(tau_now) + (travel since the RECORD's pose) <= rec_r.
+// When the length scale drops, a record that is still valid but too wide is not thrown away with its tile list: with
+// rb = (1 + margin) sqrt(tau_now), a pair closer than rb now was closer than rb + travel at the record's pose, so if
+//     rb + travel <= rec_r
+// the candidates with d2 < rb^2 of the old record ARE the record of radius rb at the current pose.  The plan names a
+// NARROWING: no build, and the iteration's streaming flow pass writes those candidates back (stream_candidates).  The tile
+// list stays the old, wide one.  The flow pass expands it again when the launch geometry changes (process_body), so it must
+// stay a superset by its own radius and pose as well, and an expansion of a bounded record keeps only d2 < rec_r^2 (the post
+// kernel then moves the record's pose to that iteration's, head_plan).  An expansion over a list many times too wide costs
+// more than a build: beyond list_stale_max x the width of a fresh list the plan builds.
+// (travel of y = Rt y0 + t since the pose [Rt0 | t0])
+CVO_HD float pose_travel(const DevHead *s, const float *Rt0, const float *t0, const float ymax)
+{
+    float f2 = 0.0f, c2 = 0.0f;
+    for (int r = 0; r < 3; ++r) {
+        float dc = s->t[r] - t0[r];
+        for (int q = 0; q < 3; ++q) {
+            const float d = s->Rt[3 * r + q] - Rt0[3 * r + q];
+            f2 += d * d;
+            dc += d * s->center[q];
+        }
+        c2 += dc * dc;
+    }
+    return sqrtf(0.5f * f2) * 1.001f * ymax + sqrtf(c2);
+}
 // (`bulk`: where the transform records and the kernel constants are stored -- the state itself; the post
 // kernels run the plan on a private copy in registers, every lane of a wave the same, and send these few
 // large, rarely written fields straight to the shared copy instead of carrying them along: `store` =
@@ -561,20 +600,8 @@ CVO_HD void plan_lists(DevHead *s, DevHead *bulk, const bool store, const DevPar
     const float ymax = s->y0max;
     const float slack = 1.0e-4f * (1.0f + s->xmax + ymax);
     const float margin = p.list_margin;
-    float travel = 0.0f;
-    if (s->list_ok[LIST_XY] && !p.async_xy) {
-        float f2 = 0.0f, c2 = 0.0f;
-        for (int r = 0; r < 3; ++r) {
-            float dc = s->t[r] - s->list_t[r];
-            for (int q = 0; q < 3; ++q) {
-                const float d = s->Rt[3 * r + q] - s->list_Rt[3 * r + q];
-                f2 += d * d;
-                dc += d * s->center[q];
-            }
-            c2 += dc * dc;
-        }
-        travel = sqrtf(0.5f * f2) * 1.001f * ymax + sqrtf(c2);
-    }
+    const bool sync_xy = s->list_ok[LIST_XY] && !p.async_xy;
+    const float travel = sync_xy ? pose_travel(s, s->list_Rt, s->list_t, ymax) : 0.0f;
 #pragma unroll
     for (int l = 0; l < 3; ++l) {
         if (l == LIST_XY && p.async_xy) continue;   // planned by plan_xy_async (and tauf[XY] must stay
@@ -583,19 +610,46 @@ CVO_HD void plan_lists(DevHead *s, DevHead *bulk, const bool store, const DevPar
         if (l != LIST_XY && p.mode != CVO_HIP_MODE_ACVO) { s->reuse[l] = 1; continue; }   // cvo has no self lists
         const float need = (r_now + (l == LIST_XY ? travel : 0.0f)) * 1.0001f + slack;
         const float lr = s->list_r[l];
-        const bool keep = margin > 0.0f && s->list_ok[l] && need <= lr &&
-                          lr <= LIST_LOOSE * (1.0f + margin) * (r_now * 1.0001f + slack);
+        const float r0 = r_now * 1.0001f + slack;
+        const float rb = r0 * (1.0f + margin);
+        bool keep = margin > 0.0f && s->list_ok[l] && need <= lr;
+        if (l == LIST_XY && p.record_narrow && keep && s->ck_nblk[LIST_XY] != 0) {
+            // a record exists: it is judged by its own radius and pose, the tile list behind it by the staleness bound
+            const float tr = pose_travel(s, s->rec_Rt, s->rec_t, ymax);
+            const float rr = s->rec_r;
+            keep = (r_now + tr) * 1.0001f + slack <= rr && lr <= fmaxf(p.list_stale_max, LIST_LOOSE) * (1.0f + margin) * r0;
+            s->narrow &= REC_BOUNDED;
+            if (keep && !(rr <= LIST_LOOSE * (1.0f + margin) * r0)) {   // valid, but too wide: narrow it if it has the room
+                keep = (rb + tr) * 1.0001f + slack <= rr;
+                if (keep) {
+                    s->rec_r = rb * 1.000001f;
+                    s->narrow = REC_NARROW | REC_BOUNDED;
+                    s->list_stat[1] += 1;
+                    if (store) {
+                        for (int q = 0; q < 9; ++q) bulk->rec_Rt[q] = s->Rt[q];
+                        for (int q = 0; q < 3; ++q) bulk->rec_t[q] = s->t[q];
+                    }
+                }
+            }
+        } else {
+            keep = keep && lr <= LIST_LOOSE * (1.0f + margin) * r0;
+            if (l == LIST_XY) s->narrow &= REC_BOUNDED;
+        }
         s->reuse[l] = keep ? 1 : 0;
         if (keep) continue;
         s->ck_nblk[l] = 0;   // a new tile list: the candidate list recorded from the old one is void
-        const float rb = (r_now * 1.0001f + slack) * (1.0f + margin);
         s->list_r[l] = rb * 1.000001f;   // rounded up: the list holds at least this radius
         s->list_ok[l] = 1;
         if (margin > 0.0f)   // tauf of compute_filter_bounds is tau + rounding slack: widen tau
             s->tauf[l] = (s->list_r[l] * s->list_r[l] + (s->tauf[l] - s->kc.tau)) * 1.000001f;
-        if (l == LIST_XY && store) {
-            for (int q = 0; q < 9; ++q) bulk->list_Rt[q] = s->Rt[q];
-            for (int q = 0; q < 3; ++q) bulk->list_t[q] = s->t[q];
+        if (l == LIST_XY) {
+            s->rec_r = s->list_r[l];   // the record of a fresh list: the list's radius and pose
+            s->narrow = p.record_narrow ? REC_BOUNDED : 0;
+            s->list_stat[0] += 1;
+            if (store) {
+                for (int q = 0; q < 9; ++q) bulk->list_Rt[q] = bulk->rec_Rt[q] = s->Rt[q];
+                for (int q = 0; q < 3; ++q) bulk->list_t[q] = bulk->rec_t[q] = s->t[q];
+            }
         }
     }
 }
@@ -793,7 +847,7 @@ CVO_HD void prepare_iteration(DevHead *s, DevHead *bulk, const bool store, const
         const float q = s->r_last > 0.0f ? r_now / s->r_last : 1.0f;
         // (a build named or in flight: the record that list will give -- the host queues a RUN batch two slots ahead)
         const int coming = p.async_xy ? (s->xy_target >= 0 ? s->xy_target : s->xy_fresh) : -1;
-        const float rr = p.async_xy ? ((coming >= 0 ? coming : s->xy_active) ? s->xy_r[1] : s->xy_r[0]) : s->list_r[LIST_XY];
+        const float rr = p.async_xy ? ((coming >= 0 ? coming : s->xy_active) ? s->xy_r[1] : s->xy_r[0]) : s->rec_r;
         const float w = rr / r_now;
         // (x 1 / 0.95: the host compares with what a run holds, and an estimate wants room -- the publishing block of a head-mode
         // flow launch replaces it by the record's count where that is known, head_body)

@@ -269,6 +269,8 @@ struct CtxOptions {
     int engine_merge_max = 2;         // "engine_merge_max" (tuning probe): engines of up to this many slots launch the step pass with the twist in front
     double list_init = 0.0;           // "list_init": first capacity of every list (0: by the clouds)
     float list_margin = -1.0f;        // "list_margin": width of the tile lists (< 0: by the clouds)
+    bool record_narrow = true;        // "record_narrow" = 0: a record too wide for the length scale is thrown away with its tile list (cvo_device.h plan_lists)
+    float list_stale_max = 3.0f;      // "list_stale_max": how many times wider than a fresh one the tile list behind a narrowed record may get
     int run_cand = 0;                 // "run_candidates_max" (0: what the runs hold)
     double mailbox_timeout_s = 5.0;   // "mailbox_timeout_s": read by the next cvo_hip_mailbox_connect
     double run_timeout_ms = 0.0;      // "run_timeout_ms": a resident run's exchange gives up after this long (0: 1 s)
@@ -283,6 +285,7 @@ struct cvo_hip_ctx {
     long long side_builds_launched = 0;  // side builds launched by this context ("side_builds_launched")
     long long tail_handovers = 0;        // times this context's registration left an engine for runs of its own ("tail_handovers")
     long long run_aborts = 0;            // resident runs of this context that gave up at their entry hand-shake ("run_aborts")
+    int list_stats[3] = {0, 0, 0};       // the last registration's all-pairs xy builds, narrowings, re-expansions (cvo_hip_get_list_stats)
     long long run_timeouts = 0;          // resident runs of this context that gave up on an exchange (cvo_hip_get_option "run_timeouts")
     int device = 0;
     hipStream_t stream = nullptr;

@@ -222,6 +222,7 @@ int job_finish(AlignJob &j)
     if (f.done == RUNNING || f.done == NEED_BIGGER_LIST)
         return fail(ctx, CVO_HIP_ERR_INVALID, "align loop ended without a verdict");
     const int executed = f.n_exec;
+    for (int q = 0; q < 3; ++q) ctx->list_stats[q] = f.list_stat[q];
     if (j.trace_cap > 0 && executed > 0)
         HIP_TRY(ctx, hipMemcpy(j.trace, ctx->trace_dev,
                                (size_t)std::min(executed, j.trace_cap) * sizeof(cvo_hip_trace),

@@ -598,6 +598,8 @@ struct ProcHead {
     uint2 *cand;                   // the candidate record of the list (buffer) the pass reads, its per-wave counts
     uint32_t *cand_cnt;
     int need_d2;                   // ProcessArgs::need_d2 -- or 0 where the kernel is built for loops that never read that sum
+    int narrow;                    // DevHead::narrow of the synchronous xy list (PROC_FLOW, else 0) ...
+    float rec_lim;                 // ... and the square of its record's radius where the record is bounded by it, else PAD_BIG
 };
 
 template <int MODE>
@@ -624,6 +626,8 @@ __device__ __forceinline__ ProcHead proc_head_global(const ProcessArgs &a, const
     h.par = par;
     h.cand = a.cand; h.cand_cnt = a.cand_cnt;
     h.need_d2 = a.need_d2;
+    h.narrow = (MODE == PROC_FLOW && !a.async_xy) ? st->narrow : 0;
+    h.rec_lim = (h.narrow & REC_BOUNDED) ? st->rec_r * st->rec_r : PAD_BIG;
     return h;
 }
 
@@ -840,7 +844,8 @@ __device__ __forceinline__ float eval_pair(const ARGS &a, const ProcHead &hd, co
                                            unsigned j, float w, double *acc,
                                            const cvo_math::XiConsts &xc, const double *etab = nullptr,
                                            const int first_counted = 0, float *ck_io = nullptr,
-                                           uint2 *pf_out = nullptr, const CVO_GLOBAL char *pf_base = nullptr, unsigned pf_idx = 0)
+                                           uint2 *pf_out = nullptr, const CVO_GLOBAL char *pf_base = nullptr, unsigned pf_idx = 0,
+                                           float *d2_out = nullptr /* PROC_FLOW / PROC_SELF: the pair's squared distance, member or not */)
 {
     const float *Rt = hd.Rt;
     const float *tt = hd.tt;
@@ -870,6 +875,7 @@ __device__ __forceinline__ float eval_pair(const ARGS &a, const ProcHead &hd, co
     float d2 = 0.0f;
     if (MODE != PROC_STEP) {
         d2 = __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, e0 * e0));
+        if (d2_out) *d2_out = d2;
         if (CK == 0) {
             w = (d2 < kc.tau) ? pair_weight<WEIGHT>(kc, d2, fa0, fa4, fb0, fb4, etab) : 0.0f;
         } else {
@@ -986,11 +992,27 @@ __device__ __forceinline__ bool expand_lists(const ProcessArgs &a, const ProcHea
             float w = 0.0f;
             uint2 pr = make_uint2(0u, 0u);
             float ck = 0.0f;
+            float d2 = 0.0f;
             if (lane < cnt) {
                 pr = pairq[base + lane];
-                w = eval_pair<MODE, WEIGHT, REC>(src, hd, kc, pr.x, pr.y, 0.0f, acc, *hd.xi, s_etab, first_counted, &ck);   // (xi: PROC_STEP only)
+                w = eval_pair<MODE, WEIGHT, REC>(src, hd, kc, pr.x, pr.y, 0.0f, acc, *hd.xi, s_etab, first_counted, &ck,   // (xi: PROC_STEP only)
+                                                 nullptr, nullptr, 0, (REC && MODE == PROC_FLOW) ? &d2 : nullptr);
             }
-            if (REC) {   // every candidate goes on record, at the place the wave met it (its colour weight with it)
+            if (REC && MODE == PROC_FLOW) {
+                // every candidate inside the record's radius goes on record, in the order the wave met them (its colour weight with
+                // it); a record that is not bounded (hd.rec_lim = PAD_BIG) takes them all
+                const unsigned long long cm = __ballot(lane < cnt && !(d2 >= hd.rec_lim));
+                const unsigned add = (unsigned)__popcll(cm);
+                if (co + add <= a.kept_wcap) {
+                    if (lane < cnt && !(d2 >= hd.rec_lim)) {
+                        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
+                        hd.cand[kbase + co + below] = make_uint2(pr.x | (pr.y << 16), __float_as_uint(ck));
+                    }
+                } else if (lane == 0) {
+                    atomicOr(&a.st->ovf[hd.par][LIST_KEPT], 1u);   // slice full: grow and redo
+                }
+                co += add;
+            } else if (REC) {   // every candidate goes on record, at the place the wave met it
                 if (co + (unsigned)cnt <= a.kept_wcap) {
                     if (lane < cnt) hd.cand[kbase + co + lane] = make_uint2(pr.x | (pr.y << 16), __float_as_uint(ck));
                 } else if (lane == 0) {
@@ -1082,7 +1104,12 @@ __device__ __forceinline__ bool expand_lists(const ProcessArgs &a, const ProcHea
 // The candidate list of one registration, streamed by the wave that recorded it: lane l takes the
 // wave's l-th candidate of the round -- nothing to expand, full rounds but the last, the colour weight
 // read back with the pair.  PROC_FLOW: the members of A of THIS iteration go to the kept list as always.
-template <int MODE, bool PIPE>
+// NARROW (PROC_FLOW, a narrowing named by plan_lists): the candidates with d2 < rec_lim -- the record of the new, smaller radius
+// at this iteration's pose -- are written back as well, INTO THE SAME SLICE, compacted, in order, and their count replaces the
+// slice's.  In place is safe: the round that holds candidates b0 .. b0 + 63 in registers writes indices co + below <= b0 + lane
+// only, all of them read in this round or before, and the records of the next round (b0 + 64 ...) were requested in front of
+// this round's stores and are waited for before the next round's.
+template <int MODE, bool PIPE, bool NARROW = false>
 __device__ __forceinline__ bool stream_candidates(const ProcessArgs &a, const ProcHead &hd, const KernConsts &kc, const int lane,
                                                   const unsigned wave, const int done_word, const double *s_etab,
                                                   double (&acc)[NAcc<MODE>::n])
@@ -1094,6 +1121,7 @@ __device__ __forceinline__ bool stream_candidates(const ProcessArgs &a, const Pr
     if (done_word != 0) return false;
     if (n > wcap) n = wcap;
     unsigned nk = 0;
+    unsigned co = 0;   // wave-uniform (NARROW): candidates written back so far
     // (the loop's addresses and switches in scalar registers: PairSrc)
     const PairSrc src = pin_pair_src<PIPE>(a);
     const CVO_GLOBAL char *cand_w = pin_global<PIPE>(hd.cand + base);
@@ -1106,10 +1134,22 @@ __device__ __forceinline__ bool stream_candidates(const ProcessArgs &a, const Pr
         uint2 *const pf = PF ? &e_next : nullptr;
         const unsigned ci = e.x & 0xffffu, cj = e.x >> 16;
         float w = 0.0f;
+        float d2 = PAD_BIG;
         if (b0 + (unsigned)lane < n) {
             float ck = __uint_as_float(e.y);
             w = eval_pair<MODE, 0, 2>(src, hd, kc, ci, cj, 0.0f, acc, *hd.xi, s_etab, 0, &ck, pf, cand_w,
-                                      min(b0 + 64u + (unsigned)lane, wcap - 1u));
+                                      min(b0 + 64u + (unsigned)lane, wcap - 1u), NARROW ? &d2 : nullptr);
+        }
+        // (the wait for the next round's record in front of this round's two stores, not behind them at the loop's end: loads and stores
+        // count in one counter, and there the wait would be for the stores as well)
+        if (NARROW && PF) asm volatile("" : "+v"(e_next.x), "+v"(e_next.y));
+        if (NARROW) {   // (d2 = PAD_BIG past the slice's end: never below the limit)
+            const unsigned long long cm = __ballot(d2 < hd.rec_lim);
+            if (d2 < hd.rec_lim) {
+                const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
+                store8(cand_w, co + below, e.x, e.y);
+            }
+            co += (unsigned)__popcll(cm);
         }
         const unsigned long long km = __ballot(w > 0.0f);
         if (MODE == PROC_FLOW && w > 0.0f) {   // (members <= candidates <= the slice: it cannot overflow here)
@@ -1130,6 +1170,7 @@ __device__ __forceinline__ bool stream_candidates(const ProcessArgs &a, const Pr
         if (MODE == PROC_FLOW) a.kept_cnt[wave] = nk;
 #endif
         acc[MODE == PROC_FLOW ? 8 : 1] = (double)nk;
+        if (NARROW) hd.cand_cnt[wave] = co;
     }
     return true;
 }
@@ -1208,7 +1249,10 @@ __device__ __forceinline__ void process_body(const ProcessArgs &a, const unsigne
         // (lists built ahead: only the xy list of a head-mode plan keeps records, one per buffer -- cand_b)
         if (CAND && WEIGHT == 0 && hd.cand && (MODE == PROC_FLOW ? (!a.async_xy || a.cand_b != nullptr)
                                                                  : (!a.async_self || a.cand_b != nullptr))) {
-            if (hd.ck_nblk == a.nblk) alive = stream_candidates<MODE, PIPE>(a, hd, kc, lane, wave, done_word, s_etab, acc);
+            // (a narrowing: wave-uniform, decided once in front of the loop -- the plain loop carries nothing of it)
+            if (hd.ck_nblk == a.nblk && MODE == PROC_FLOW && (hd.narrow & REC_NARROW))
+                alive = stream_candidates<MODE, PIPE, MODE == PROC_FLOW>(a, hd, kc, lane, wave, done_word, s_etab, acc);
+            else if (hd.ck_nblk == a.nblk) alive = stream_candidates<MODE, PIPE>(a, hd, kc, lane, wave, done_word, s_etab, acc);
             else alive = expand_lists<MODE, WEIGHT, WEIGHT == 0 ? 1 : 0, PIPE>(a, hd, kc, bid, wid, lane, wave, done_word, list_bad, in_list, in_tiles, first_counted, s_etab, pairq_all, acc);
         } else {
             alive = expand_lists<MODE, WEIGHT, 0, PIPE>(a, hd, kc, bid, wid, lane, wave, done_word, list_bad, in_list, in_tiles, first_counted, s_etab, pairq_all, acc);
@@ -1429,6 +1473,7 @@ __device__ __forceinline__ bool step_twist_body(const ProcessArgs &a, DevState *
     // ---- compute_step_size sums over this wave's slice of the kept list
     ProcHead phd;
     phd.need_d2 = 0;
+    phd.narrow = 0; phd.rec_lim = PAD_BIG;
     phd.Rt = hd->Rt; phd.tt = hd->t;   // (eval_pair<PROC_STEP> reads nothing else of it)
     double acc[NACC];
 #pragma unroll
@@ -1992,6 +2037,17 @@ __device__ __forceinline__ void head_plan(DevHead *lds, const PostStepArgs &a, c
         DevHead L;
         __builtin_memcpy(&L, lds, sizeof(DevHead));
         if (HM == HM_CLASSIC) {
+            // the flow pass of the slot that ended expanded the xy tile list (its record was void or of another geometry): where it
+            // did not follow a build that is a re-expansion, and a bounded record now holds the pairs within rec_r at THAT slot's pose
+            if (ck_ok[LIST_XY] && L.ck_nblk[LIST_XY] != a.ck_nblk[LIST_XY] && !p.async_xy) {
+                if (L.reuse[LIST_XY]) L.list_stat[2] += 1;
+                if (L.narrow & REC_BOUNDED) {
+#pragma unroll
+                    for (int q = 0; q < 9; ++q) { L.rec_Rt[q] = L.Rt[q]; if (lane0) lds->rec_Rt[q] = L.Rt[q]; }
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) { L.rec_t[q] = L.t[q]; if (lane0) lds->rec_t[q] = L.t[q]; }
+                }
+            }
 #pragma unroll
             for (int l = 0; l < 3; ++l)
                 if (ck_ok[l]) L.ck_nblk[l] = a.ck_nblk[l];
@@ -2013,6 +2069,9 @@ __device__ __forceinline__ void head_plan(DevHead *lds, const PostStepArgs &a, c
             for (int q = 0; q < 3; ++q) { lds->t[q] = L.t[q]; lds->tauf[q] = L.tauf[q]; lds->list_r[q] = L.list_r[q];
                                           lds->list_ok[q] = L.list_ok[q]; lds->reuse[q] = L.reuse[q]; lds->ck_nblk[q] = L.ck_nblk[q]; }
             lds->kc_ell = L.kc_ell; lds->run_hint = L.run_hint; lds->r_last = L.r_last;
+            lds->rec_r = L.rec_r; lds->narrow = L.narrow;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) lds->list_stat[q] = L.list_stat[q];
             lds->xy_active = L.xy_active; lds->xy_target = L.xy_target; lds->stall = L.stall; lds->xy_fresh = L.xy_fresh;
             lds->tauf_build = L.tauf_build;
 #pragma unroll
@@ -2088,16 +2147,20 @@ __device__ __forceinline__ void head_publish(const PostStepArgs &a, const DevHea
         const uint4 *src = reinterpret_cast<const uint4 *>(s_st);
         uint4 *dst = reinterpret_cast<uint4 *>(a.final_mirror);
         constexpr int pieces = (int)(DEVSTATE_HEAD_BYTES / 16);
-        static_assert(pieces <= 64 && offsetof(DevHead, head_check_) == DEVSTATE_HEAD_BYTES - 12, "one wave copies the head; the check word is the last piece's second word");
+        static_assert(pieces > 64 && pieces <= 128 && offsetof(DevHead, head_check_) == DEVSTATE_HEAD_BYTES - 12,
+                      "one wave copies the head, two pieces per lane; the check word is the last piece's second word, held by the lanes' second pieces");
         if (threadIdx.x < 64) {
+            const int p1 = (int)threadIdx.x + 64;   // the lane's second piece
+            const uint4 v0 = src[threadIdx.x];
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if ((int)threadIdx.x < pieces) v = src[threadIdx.x];
-            if ((int)threadIdx.x == pieces - 1) v.y = 0u;   // (the word itself counts as zero)
-            unsigned sum = (int)threadIdx.x < pieces ? head_check_mix(v.x, v.y, v.z, v.w, threadIdx.x) : 0u;
+            if (p1 < pieces) v = src[p1];
+            if (p1 == pieces - 1) v.y = 0u;   // (the word itself counts as zero)
+            unsigned sum = head_check_mix(v0.x, v0.y, v0.z, v0.w, threadIdx.x) + (p1 < pieces ? head_check_mix(v.x, v.y, v.z, v.w, (unsigned)p1) : 0u);
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) sum += (unsigned)__shfl_xor((int)sum, off, 64);
-            if ((int)threadIdx.x == pieces - 1) v.y = sum;
-            if ((int)threadIdx.x < pieces) dst[threadIdx.x] = v;
+            if (p1 == pieces - 1) v.y = sum;
+            dst[threadIdx.x] = v0;
+            if (p1 < pieces) dst[p1] = v;
         }
         __threadfence_system();
         __syncthreads();
@@ -2523,6 +2586,7 @@ __device__ __forceinline__ ProcHead proc_head_lds(const ProcessArgs &a, const De
     hd.par = par;
     hd.cand = nullptr; hd.cand_cnt = nullptr;
     hd.need_d2 = a.need_d2;
+    hd.narrow = 0; hd.rec_lim = PAD_BIG;   // (lists built ahead: their records are not narrowed)
     if (a.cand_b) {   // the record of the buffer in use (xy list; acvo: xx / yy)
         const int l = a.async_self == 2 ? 1 : 0;
         const int ck = MODE == PROC_FLOW ? (hd.second ? h->xy_ck[1] : h->xy_ck[0]) : (hd.second ? h->sf_ck[l][1] : h->sf_ck[l][0]);
@@ -4007,6 +4071,7 @@ kt_side_record(const Slot *__restrict__ tab, const int q)
         hd.cand = t ? pa.cand_b : pa.cand;
         hd.cand_cnt = t ? pa.cand_cnt_b : pa.cand_cnt;
         hd.need_d2 = 0;
+        hd.narrow = 0; hd.rec_lim = PAD_BIG;
         process_body<PROC_FLOW, 0, true, false>(pa, blockIdx.x, scratch, hd);
     }
     // (the record is in memory before the count that says so)

@@ -472,9 +472,12 @@ DevParams loop_params(const cvo_hip_ctx *ctx)
     if (ctx->use_async && ctx->lone && ctx->allow_head && !multi_rank(ctx)) dp.build_at = 0.9f;
     // (plans with resident runs, the conditions of enqueue_step: what a run's registers hold -- the plan keeps a list that has become
     // wide while its record still fits, plan_xy_async)
-    if (ctx->use_async && ctx->lone && ctx->allow_head && ctx->allow_run && !multi_rank(ctx) && ctx->prm.mode == CVO_HIP_MODE_CVO &&
+    if (ctx->use_async && ctx->lone && ctx->allow_head && runs_allowed(ctx) && !multi_rank(ctx) && ctx->prm.mode == CVO_HIP_MODE_CVO &&
         !(ctx->prm.color_scale > 0.0f) && !ctx->post_dbg && ctx->allow_merge && ctx->fixed.np <= 65536 && ctx->moving.np <= 65536 && !ctx->opt.no_cand)
         dp.run_cand_cap = (float)ctx->run_g_max * (float)(RUN_BLOCK * (RUN_R + RUN_L));
+    // (narrowing: the synchronous xy plan -- engines, large and sharded registrations; cvo_device.h plan_lists)
+    dp.record_narrow = ctx->opt.record_narrow ? 1 : 0;
+    dp.list_stale_max = ctx->opt.list_stale_max;
     return dp;
 }
 

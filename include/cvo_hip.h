@@ -487,7 +487,7 @@ int cvo_hip_set_graph_capture(cvo_hip_ctx *ctx, int enable);
  *                        times out costs that wait, not the frame: the pair is registered again without runs, and the context
  *                        goes without runs for its next 64 registrations ("run_timeouts" counts them, read-only)
  * and the test switches of tests/ ("head_mode", "merged_launches", "async_builds", "candidate_records", "kept_pack",
- * "list_init", "list_margin", "final_mirror", "one_launch_hand_over", "small_calls_alone", "fused_groups", "engines",
+ * "list_init", "list_margin", "record_narrow", "list_stale_max", "final_mirror", "one_launch_hand_over", "small_calls_alone", "fused_groups", "engines",
  * "run_candidates_max", "run_fault", "sync_upload", "no_graph", "twist_on_shared_gpu", "comm_debug", "engine_debug"; the
  * measured probes "engine_crowd", "engine_merge_max", "narrow_merge", "narrow_blocks", all off: profiles/r06_ab.txt 16).
  * The environment variables of the same switches only set the DEFAULTS, read once when a context is
@@ -527,6 +527,10 @@ int cvo_hip_get_graph_stats(const cvo_hip_ctx *ctx, long long *launches_from_cac
  * that declined, iterations executed inside runs, candidate pairs of the record the last run looked at.  Diagnostics; any
  * pointer may be null. */
 int cvo_hip_get_run_stats(cvo_hip_ctx *ctx, int *runs, int *declined, int *iterations, int *candidates);
+/* The synchronous xy list of the context's last registration (cvo_hip_align, or its member of a cvo_hip_align_many call): all-pairs
+ * builds, narrowings of the candidate record (option "record_narrow") and re-expansions of the tile list after a change of launch
+ * geometry, counted on the device since the registration began.  Diagnostics; any pointer may be null. */
+int cvo_hip_get_list_stats(const cvo_hip_ctx *ctx, int *builds, int *narrowings, int *reexpansions);
 /* ... and, in builds with -DCVO_RUN_CLOCKS, the ticks the first solver block of the runs spent in each phase of the loop
  * (csrc/cvo_kernels.hip kt_run: RUN_CLK; zeros otherwise). */
 int cvo_hip_get_run_clocks(cvo_hip_ctx *ctx, long long clocks16[16]);
