@@ -22,7 +22,7 @@ SYMBOLS = [
     "cvo_hip_comm_unique_id", "cvo_hip_comm_init", "cvo_hip_set_allreduce",
     "cvo_hip_mailbox_create", "cvo_hip_mailbox_connect",
     "cvo_hip_transform_pcd", "cvo_hip_flow", "cvo_hip_step_coeffs", "cvo_hip_pose_hessian", "cvo_hip_pose_score",
-    "cvo_hip_pose_score_many", "cvo_hip_pose_matches", "cvo_hip_pick_step",
+    "cvo_hip_pose_score_many", "cvo_hip_pose_scan", "cvo_hip_pose_matches", "cvo_hip_pick_step",
     "cvo_hip_exp_se3", "cvo_hip_dist_se3", "cvo_hip_align", "cvo_hip_align_many",
     "cvo_hip_function_inner_product", "cvo_hip_function_inner_product_clouds",
     "cvo_hip_engine_profiling", "cvo_hip_get_engine_profile", "cvo_hip_get_engine_flow_trace", "cvo_hip_get_wave_load", "cvo_hip_set_graph_capture", "cvo_hip_set_profiling", "cvo_hip_get_profile", "cvo_hip_get_graph_stats", "cvo_hip_get_run_stats", "cvo_hip_get_list_stats", "cvo_hip_get_run_clocks", "cvo_hip_get_mirror_retries", "cvo_hip_synchronize",
@@ -115,6 +115,31 @@ def pose_score_from_c(s):
                      int(s.n_fixed), int(s.n_moving), float(s.ell))
 
 
+class PoseScanEntryC(C.Structure):
+    """cvo_hip_pose_scan_entry: one candidate pose of cvo_hip_pose_scan."""
+    _fields_ = [("inner", C.c_double), ("cos_angle", C.c_double), ("mean_d2", C.c_double), ("nnz", C.c_int64)]
+
+
+class PoseScanC(C.Structure):
+    """cvo_hip_pose_scan_t: the summary of cvo_hip_pose_scan."""
+    _fields_ = [
+        ("self_fixed", C.c_double), ("self_moving", C.c_double), ("nnz_fixed", C.c_int64), ("nnz_moving", C.c_int64),
+        ("count", C.c_int32), ("best", C.c_int32), ("n_fixed", C.c_int32), ("n_moving", C.c_int32),
+        ("ell", C.c_float), ("pad_", C.c_int32),
+    ]
+
+
+POSE_SCAN_ENTRY = np.dtype([("inner", "<f8"), ("cos_angle", "<f8"), ("mean_d2", "<f8"), ("nnz", "<i8")])
+
+
+class PoseScan(collections.namedtuple("PoseScan", "inner cos_angle mean_d2 nnz self_fixed self_moving nnz_fixed nnz_moving "
+                                                  "count best n_fixed n_moving ell")):
+    """Context.pose_scan's answer (include/cvo_hip.h cvo_hip_pose_scan): numpy arrays over the candidate poses -- inner,
+    cos_angle, mean_d2 (float64) and nnz (int64) -- the summary's fields, and ``best``: the index of the largest inner
+    (-1: no pose has a member)."""
+    __slots__ = ()
+
+
 class PoseMatchesC(C.Structure):
     """cvo_hip_pose_matches_t: the summary of cvo_hip_pose_matches."""
     _fields_ = [
@@ -200,6 +225,7 @@ def lib():
     L.cvo_hip_pose_hessian.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseHessianC)]
     L.cvo_hip_pose_score.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PoseScoreC)]
     L.cvo_hip_pose_score_many.argtypes = [C.POINTER(vp), fp, fp, fp, C.POINTER(PoseScoreC), C.c_int]
+    L.cvo_hip_pose_scan.argtypes = [vp, fp, fp, C.c_int, C.c_float, C.POINTER(PoseScanEntryC), C.POINTER(PoseScanC)]
     L.cvo_hip_pose_matches.argtypes = [vp, fp, fp, C.c_float, C.POINTER(PointMatchesC), C.POINTER(PointMatchesC),
                                        C.POINTER(PoseMatchesC)]
     L.cvo_hip_pick_step.argtypes = [dp, C.c_float, fp]
@@ -481,6 +507,27 @@ class Context:
         """The normalised CVO inner product and the overlap of the two clouds at the pose (R, T) and length scale ell
         (include/cvo_hip.h cvo_hip_pose_score): a PoseScore.  The context is left as transform_pcd(R, T) leaves it."""
         return pose_score_from_c(self.pose_score_raw(R, T, ell))
+
+    def pose_scan_raw(self, Rs, Ts, ell):
+        """cvo_hip_pose_scan: (the entries' bytes, 32 per pose; the summary as the library filled it, a PoseScanC)."""
+        R = np.ascontiguousarray(np.asarray(Rs, np.float32).reshape(-1, 9))
+        T = np.ascontiguousarray(np.asarray(Ts, np.float32).reshape(-1, 3))
+        if len(R) != len(T):
+            raise ValueError("pose_scan: as many rotations as translations")
+        n = len(R)
+        out = (PoseScanEntryC * max(n, 1))()
+        summary = PoseScanC()
+        self._chk(self._L.cvo_hip_pose_scan(self._ctx, fptr(R), fptr(T), n, np.float32(ell), out, C.byref(summary)), "pose_scan")
+        return bytes(out)[:n * C.sizeof(PoseScanEntryC)], summary
+
+    def pose_scan(self, Rs, Ts, ell):
+        """The scores of many candidate poses of the pair that is set (include/cvo_hip.h cvo_hip_pose_scan): Rs (n, 3, 3),
+        Ts (n, 3) -> a PoseScan.  The context is left as transform_pcd(Rs[best], Ts[best]) leaves it."""
+        raw, s = self.pose_scan_raw(Rs, Ts, ell)
+        e = np.frombuffer(raw, POSE_SCAN_ENTRY)
+        return PoseScan(e["inner"].copy(), e["cos_angle"].copy(), e["mean_d2"].copy(), e["nnz"].copy(), float(s.self_fixed),
+                        float(s.self_moving), int(s.nnz_fixed), int(s.nnz_moving), int(s.count), int(s.best), int(s.n_fixed),
+                        int(s.n_moving), float(s.ell))
 
     def pose_matches(self, R, T, ell, fixed=True, moving=True):
         """Which points matched at the pose (R, T) and length scale ell (include/cvo_hip.h cvo_hip_pose_matches): a

@@ -54,7 +54,7 @@ const OptDef kOptions[] = {
     {"run_build_at", "CVO_HIP_RUN_BUILD_AT", 2, 0.0},         {"alone_max", "CVO_HIP_ALONE_MAX", 2, 0.0},
     {"narrow_merge", "CVO_HIP_NARROW_MERGE", 1, 1.0},     {"narrow_blocks", "CVO_HIP_NARROW_BLOCKS", 2, 0.0},
     {"engine_crowd", "CVO_HIP_ENGINE_CROWD", 2, 0.0},     {"engine_merge_max", "CVO_HIP_ENGINE_MERGE_MAX", 2, 0.0},
-    {"matches_combine", nullptr, 0, 0.0},
+    {"matches_combine", nullptr, 0, 0.0},                 {"scan_chunk", nullptr, 0, 0.0},
     {"record_narrow", "CVO_HIP_NO_RECORD_NARROW", 1, 0.0}, {"list_stale_max", "CVO_HIP_LIST_STALE_MAX", 2, 0.0},
 };
 void env_defaults(cvo_hip_ctx *ctx)
@@ -107,6 +107,7 @@ int apply_option(cvo_hip_ctx *ctx, const char *key, double v)
     else if (is("list_init")) { if (v < 0.0) return CVO_HIP_ERR_INVALID; o.list_init = v; }
     else if (is("kept_pack")) o.no_pack = !on;
     else if (is("matches_combine")) o.matches_combine = on;
+    else if (is("scan_chunk")) { if (v < 0.0 || v > (double)SCAN_CHUNK) return CVO_HIP_ERR_INVALID; o.scan_chunk = (int)v; }
     else if (is("list_margin")) { if (v > 4.0) return CVO_HIP_ERR_INVALID; o.list_margin = v < 0.0 ? -1.0f : (float)v; }
     else if (is("record_narrow")) o.record_narrow = on;
     else if (is("list_stale_max")) { if (!(v >= 1.0 && v <= 64.0)) return CVO_HIP_ERR_INVALID; o.list_stale_max = (float)v; }
@@ -274,20 +275,12 @@ int score_pass(cvo_hip_ctx *ctx, int p, const Cloud &ca, int rlo, int rhi, const
     return CVO_HIP_OK;
 }
 
-// A context's whole score, enqueued on its stream without a wait: the self passes its clouds' cached norms do not
-// cover, the pass at the pose, the score pass over the pose's kept list.
-int score_enqueue(cvo_hip_ctx *ctx, ScoreJob &job)
+// The norms |f_X|^2, |f_Y|^2 of a context's clouds (cvo_hip_pose_score's self_fixed / self_moving; cvo_hip_pose_scan's, the same
+// passes and the same per-cloud cache): the self passes the clouds' cached norms do not cover, enqueued without a wait.
+// Sets job.self_pass and the kernel constants of the host's state image `h` for job.ell.
+int self_norms_enqueue(cvo_hip_ctx *ctx, ScoreJob &job, DevState *h)
 {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = cloud_ready(ctx, ctx->fixed);
-    if (!rc) rc = cloud_ready(ctx, ctx->moving);
-    if (rc) return rc;
     if (!ctx->score_pin) HIP_TRY(ctx, hipHostMalloc((void **)&ctx->score_pin, sizeof(ScorePin), hipHostMallocDefault));
-    // the context ends as cvo_hip_transform_pcd(ctx, R, T) leaves it
-    DevState *h = &ctx->st_host[kPollSlots];
-    std::memcpy(h->R, job.R, sizeof(h->R));
-    std::memcpy(h->T, job.T, sizeof(h->T));
-    cvo_math::inverse_tf(job.R, job.T, h->Rt, h->t);
     h->done = 0;
     h->kc = make_kconsts(ctx->dprm, job.ell);
     h->kc_ell = -1.0f;   // (never equal to an ell: prepare_iteration recomputes)
@@ -304,7 +297,7 @@ int score_enqueue(cvo_hip_ctx *ctx, ScoreJob &job)
         const Cloud c = s == 0 ? keep_f : keep_m;
         ctx->fixed = c;
         ctx->moving = c;
-        rc = fill_filter_geometry(ctx, h);
+        int rc = fill_filter_geometry(ctx, h);
         if (!rc) {
             compute_filter_bounds(h, true);
             rc = score_pass(ctx, s, ctx->fixed, 0, c.n, ctx->moving, 0);
@@ -313,6 +306,57 @@ int score_enqueue(cvo_hip_ctx *ctx, ScoreJob &job)
         ctx->moving = keep_m;
         if (rc) return rc;
     }
+    return CVO_HIP_OK;
+}
+
+// After the wait: pass p of the staging overflowed a tile or kept list -- the list grows and the caller enqueues again (*redo)
+int score_pass_grow(cvo_hip_ctx *ctx, int p, const char *who, bool *redo)
+{
+    const ScorePin *pin = ctx->score_pin;
+    for (int l = 0; l < LIST_N; ++l) {
+        if (!(pin->ovf[p][l] | pin->ovf[p][8 + l])) continue;
+        const uint32_t cap = ctx->lists[l].cap;
+        int rc = ensure_list(ctx, l, 0, 0, std::min(4.0e9, 2.0 * (double)cap + 1024.0));
+        if (rc) return rc;
+        if (ctx->lists[l].cap <= cap) return fail(ctx, CVO_HIP_ERR_NOMEM, (std::string(who) + ": a list cannot grow further").c_str());
+        *redo = true;
+    }
+    return CVO_HIP_OK;
+}
+
+// ... and when none did: the norms the self passes computed go to their clouds
+void self_norms_store(cvo_hip_ctx *ctx, const ScoreJob &job)
+{
+    const ScorePin *pin = ctx->score_pin;
+    uint32_t bits;
+    std::memcpy(&bits, &job.ell, sizeof(bits));
+    for (int s = 0; s < 2; ++s) {
+        if (!job.self_pass[s]) continue;
+        Cloud &c = s == 0 ? ctx->fixed : ctx->moving;
+        c.self.valid = true;
+        c.self.gen = c.gen;
+        c.self.prm = ctx->prm;
+        c.self.ell_bits = bits;
+        c.self.sum = pin->red[s][6];
+        c.self.nnz = (int64_t)pin->red[s][8];
+    }
+}
+
+// A context's whole score, enqueued on its stream without a wait: the self passes its clouds' cached norms do not
+// cover, the pass at the pose, the score pass over the pose's kept list.
+int score_enqueue(cvo_hip_ctx *ctx, ScoreJob &job)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = cloud_ready(ctx, ctx->fixed);
+    if (!rc) rc = cloud_ready(ctx, ctx->moving);
+    if (rc) return rc;
+    // the context ends as cvo_hip_transform_pcd(ctx, R, T) leaves it
+    DevState *h = &ctx->st_host[kPollSlots];
+    std::memcpy(h->R, job.R, sizeof(h->R));
+    std::memcpy(h->T, job.T, sizeof(h->T));
+    cvo_math::inverse_tf(job.R, job.T, h->Rt, h->t);
+    rc = self_norms_enqueue(ctx, job, h);
+    if (rc) return rc;
     // A at the pose exactly as cvo_hip_pose_hessian rebuilds it (the same filter and PROC_FLOW pass): last, so that the
     // kept list the score pass streams is its
     rc = fill_filter_geometry(ctx, h);
@@ -359,28 +403,11 @@ int score_collect(cvo_hip_ctx *ctx, const ScoreJob &job, cvo_hip_pose_score_t *o
     *redo = false;
     for (int p = 0; p < 3; ++p) {
         if (p < 2 && !job.self_pass[p]) continue;
-        for (int l = 0; l < LIST_N; ++l) {
-            if (!(pin->ovf[p][l] | pin->ovf[p][8 + l])) continue;
-            const uint32_t cap = ctx->lists[l].cap;
-            int rc = ensure_list(ctx, l, 0, 0, std::min(4.0e9, 2.0 * (double)cap + 1024.0));
-            if (rc) return rc;
-            if (ctx->lists[l].cap <= cap) return fail(ctx, CVO_HIP_ERR_NOMEM, "cvo_hip_pose_score: a list cannot grow further");
-            *redo = true;
-        }
+        const int rc = score_pass_grow(ctx, p, "cvo_hip_pose_score", redo);
+        if (rc) return rc;
     }
     if (*redo) return CVO_HIP_OK;
-    uint32_t bits;
-    std::memcpy(&bits, &job.ell, sizeof(bits));
-    for (int s = 0; s < 2; ++s) {
-        if (!job.self_pass[s]) continue;
-        Cloud &c = s == 0 ? ctx->fixed : ctx->moving;
-        c.self.valid = true;
-        c.self.gen = c.gen;
-        c.self.prm = ctx->prm;
-        c.self.ell_bits = bits;
-        c.self.sum = pin->red[s][6];
-        c.self.nnz = (int64_t)pin->red[s][8];
-    }
+    self_norms_store(ctx, job);
     cvo_hip_pose_score_t r{};
     r.inner = pin->red[kScorePose][6];
     r.nnz = (int64_t)pin->red[kScorePose][8];
@@ -430,6 +457,187 @@ int score_batch(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, cons
         }
     }
     return CVO_HIP_OK;
+}
+
+// ---- cvo_hip_pose_scan (include/cvo_hip.h)
+// Per pose: [Rt | t] as cvo_hip_transform_pcd makes it, and the two constants of the culling test of k_pose_scan
+// (cvo_scan.hip scan_near): scale >= |Rt|_2 and reach = sqrt(tau) + slack.
+//   scale: |Rt|_2^2 = lambda_max(Rt Rt^T) <= 1 + |Rt Rt^T - I|_F -- 1 + ~1e-7 for a float32 rotation, and a bound for any matrix.
+//   slack: with u = 2^-24, X = the largest |coordinate| of the fixed cloud, Z of the moving cloud, S = 3 max|Rt| Z + max|t|:
+//     every partial sum of a row of apply_tf is at most S, so its six roundings leave a component within 6 u S and the row
+//     within 6 sqrt(3) u S < 11 u S of the exact image; the kernel's transformed centre likewise: 22 u S together.  The kernel's
+//     left-hand side -- three differences of numbers up to X and S, their squares' sum, a square root, two subtractions of
+//     radii no larger than the clouds -- is within 12 u sqrt(3) (X + S) of its exact value.  A member's computed d2 < tau
+//     bounds the distance of the computed rows by sqrt(tau) (1 + 4 u).  Needed: below 34 u sqrt(3) (X + S) + 4 u sqrt(tau);
+//     taken: 64 u sqrt(3) (X + S) + 1e-6 sqrt(tau), rounded up.  (1e-5 m for clouds 1.5 m from the origin: culling loses nothing.)
+void scan_pose_consts(const float *R, const float *T, float tau, double xabs, double zabs, float *tf)
+{
+    cvo_math::inverse_tf(R, T, tf, tf + 9);
+    double g2 = 0.0, rmax = 0.0, tmax = 0.0;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) {
+            double g = r == c ? -1.0 : 0.0;
+            for (int q = 0; q < 3; ++q) g += (double)tf[3 * r + q] * (double)tf[3 * c + q];
+            g2 += g * g;
+            rmax = std::max(rmax, std::fabs((double)tf[3 * r + c]));
+        }
+        tmax = std::max(tmax, std::fabs((double)tf[9 + r]));
+    }
+    const double S = 3.0 * rmax * zabs + tmax;
+    const double u = 1.0 / 16777216.0;
+    const double rt = std::sqrt((double)tau);
+    tf[12] = (float)(std::sqrt(1.0 + std::sqrt(g2)) * 1.000001);
+    tf[13] = (float)((rt * 1.000001 + 64.0 * u * std::sqrt(3.0) * (xabs + S)) * 1.000001);
+    tf[14] = tf[15] = 0.0f;
+}
+
+double cloud_abs_max(const Cloud &c)
+{
+    double m = 0.0;
+    for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::fabs((double)c.lo[a]), std::fabs((double)c.hi[a])));
+    return m;
+}
+
+// Pinned staging of a scan: the state image the winner's pose is pushed from, the chunk's poses going up, its sums coming back
+struct ScanStage {
+    DevHead *img;
+    float *tf;       // [m][SCAN_TF]
+    double *out;     // [m][3]
+};
+size_t scan_stage_off_tf() { return (sizeof(DevHead) + 63) & ~(size_t)63; }
+size_t scan_stage_bytes(int m) { return scan_stage_off_tf() + (size_t)m * (SCAN_TF * sizeof(float) + 3 * sizeof(double)); }
+ScanStage scan_stage(cvo_hip_ctx *ctx, int m)
+{
+    char *b = static_cast<char *>(ctx->scan_stage);
+    ScanStage st;
+    st.img = reinterpret_cast<DevHead *>(b);
+    st.tf = reinterpret_cast<float *>(b + scan_stage_off_tf());
+    st.out = reinterpret_cast<double *>(b + scan_stage_off_tf() + (size_t)m * SCAN_TF * sizeof(float));
+    return st;
+}
+
+int scan_run(cvo_hip_ctx *ctx, const float *R9, const float *T3, int count, float ell, cvo_hip_pose_scan_entry *out,
+             cvo_hip_pose_scan_t *summary)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = cloud_ready(ctx, ctx->fixed);
+    if (!rc) rc = cloud_ready(ctx, ctx->moving);
+    if (rc) return rc;
+    const int chunk = ctx->opt.scan_chunk > 0 ? ctx->opt.scan_chunk : SCAN_CHUNK;
+    const int m = std::max(1, std::min(count, chunk));   // poses per launch: what the buffers are sized for
+    const int nseg_a = (ctx->fixed.n + SEG - 1) / SEG, nseg_b = (ctx->moving.n + SEG - 1) / SEG;
+    const int nblk = (nseg_a + 3) / 4;
+    if (scan_stage_bytes(m) > ctx->scan_stage_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the last scan's state image may still be on its way)
+        if (ctx->scan_stage) (void)hipHostFree(ctx->scan_stage);
+        ctx->scan_stage = nullptr;
+        ctx->scan_stage_bytes = 0;
+        HIP_TRY(ctx, hipHostMalloc(&ctx->scan_stage, scan_stage_bytes(m), hipHostMallocDefault));
+        ctx->scan_stage_bytes = scan_stage_bytes(m);
+    }
+    const size_t dev_tf = (size_t)m * SCAN_TF * sizeof(float), dev_out = (size_t)m * 3 * sizeof(double);
+    rc = ensure_buf(ctx, ctx->scan_dev, dev_tf + dev_out + (size_t)3 * nblk * m * sizeof(double));
+    if (rc) return rc;
+    const ScanStage st = scan_stage(ctx, m);
+    // the norms: the passes and the per-cloud cache of cvo_hip_pose_score, in front of the first chunk and behind the same wait
+    DevState *h = &ctx->st_host[kPollSlots];
+    ScoreJob job{};
+    job.ell = ell;
+    rc = self_norms_enqueue(ctx, job, h);
+    if (rc) return rc;
+    ScanArgs sa{};
+    sa.pos_a = ctx->fixed.pos;
+    sa.feat_a = ctx->fixed.feat;
+    sa.seg_a = ctx->fixed.seg;
+    sa.pos_b = ctx->moving.pos;
+    sa.feat_b = ctx->moving.feat;
+    sa.seg_b = ctx->moving.seg;
+    char *dev = static_cast<char *>(ctx->scan_dev.p);
+    sa.tf = reinterpret_cast<const float *>(dev);
+    sa.out = reinterpret_cast<double *>(dev + dev_tf);
+    sa.partials = reinterpret_cast<double *>(dev + dev_tf + dev_out);
+    sa.kc = make_kconsts(ctx->dprm, ell);
+    sa.nseg_a = nseg_a;
+    sa.nseg_b = nseg_b;
+    sa.nblk = nblk;
+    const int weight = ctx->prm.color_scale > 0.0f ? 1 : 0;   // (the MATLAB object's weight, as enqueue_process picks it)
+    const double xabs = cloud_abs_max(ctx->fixed), zabs = cloud_abs_max(ctx->moving);
+    bool norms_done = false;
+    for (int k0 = 0; k0 < count || !norms_done; k0 += m) {
+        const int nk = std::max(0, std::min(m, count - k0));
+        if (nk > 0) {
+            for (int k = 0; k < nk; ++k)
+                scan_pose_consts(R9 + 9 * (size_t)(k0 + k), T3 + 3 * (size_t)(k0 + k), sa.kc.tau, xabs, zabs, st.tf + (size_t)k * SCAN_TF);
+            HIP_TRY(ctx, hipMemcpyAsync(dev, st.tf, (size_t)nk * SCAN_TF * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            sa.count = nk;
+            launch_pose_scan(sa, weight, ctx->stream);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(st.out, sa.out, (size_t)nk * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the chunk's one wait
+        while (!norms_done) {   // (a self pass that overflowed a list: the list grows, the self passes alone go out again)
+            bool redo = false;
+            for (int p = 0; p < 2; ++p) {
+                if (!job.self_pass[p]) continue;
+                rc = score_pass_grow(ctx, p, "cvo_hip_pose_scan", &redo);
+                if (rc) return rc;
+            }
+            if (!redo) {
+                self_norms_store(ctx, job);
+                norms_done = true;
+                break;
+            }
+            rc = self_norms_enqueue(ctx, job, h);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        for (int k = 0; k < nk; ++k) {
+            cvo_hip_pose_scan_entry e{};
+            e.inner = st.out[3 * (size_t)k];
+            e.nnz = (int64_t)st.out[3 * (size_t)k + 2];
+            e.mean_d2 = e.nnz > 0 ? st.out[3 * (size_t)k + 1] / e.inner : 0.0;
+            out[k0 + k] = e;
+        }
+    }
+    cvo_hip_pose_scan_t r{};
+    r.self_fixed = ctx->fixed.self.sum;
+    r.nnz_fixed = ctx->fixed.self.nnz;
+    r.self_moving = ctx->moving.self.sum;
+    r.nnz_moving = ctx->moving.self.nnz;
+    r.count = count;
+    r.best = -1;
+    r.n_fixed = ctx->fixed.n;
+    r.n_moving = ctx->moving.n;
+    r.ell = ell;
+    const bool normed = r.self_fixed > 0.0 && r.self_moving > 0.0;
+    const double norm = normed ? std::sqrt(r.self_fixed * r.self_moving) : 1.0;
+    double top = 0.0;
+    for (int k = 0; k < count; ++k) {
+        out[k].cos_angle = normed ? out[k].inner / norm : 0.0;
+        if (out[k].nnz > 0 && (r.best < 0 || out[k].inner > top)) {   // the largest inner, the first of equals
+            r.best = k;
+            top = out[k].inner;
+        }
+    }
+    *summary = r;
+    if (r.best < 0) return ctx->profiling ? drain_events(ctx) : CVO_HIP_OK;
+    // the context ends as cvo_hip_transform_pcd(ctx, R_best, T_best) leaves it.  The fields go up from the scan's own pinned image,
+    // in stream order behind the scan and without a wait: the image is next written behind the next scan's wait.
+    std::memcpy(h->R, R9 + 9 * (size_t)r.best, sizeof(h->R));
+    std::memcpy(h->T, T3 + 3 * (size_t)r.best, sizeof(h->T));
+    cvo_math::inverse_tf(h->R, h->T, h->Rt, h->t);
+    h->done = 0;
+    rc = fill_filter_geometry(ctx, h);
+    if (rc) return rc;
+    std::memcpy(static_cast<void *>(st.img), static_cast<const void *>(h), sizeof(DevHead));
+    const size_t ranges[3][2] = {{offsetof(DevState, R), offsetof(DevState, ell)},
+                                 {offsetof(DevState, Rt), offsetof(DevState, used_Rt)},
+                                 {offsetof(DevState, done), offsetof(DevState, done) + sizeof(int32_t)}};
+    for (const auto &g : ranges)
+        HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(ctx->st) + g[0], reinterpret_cast<const char *>(st.img) + g[0], g[1] - g[0],
+                                    hipMemcpyHostToDevice, ctx->stream));
+    ctx->have_tf = true;
+    return ctx->profiling ? drain_events(ctx) : CVO_HIP_OK;
 }
 
 // ---- cvo_hip_pose_matches (include/cvo_hip.h)
@@ -773,6 +981,8 @@ int cvo_hip_destroy(cvo_hip_ctx *ctx)
     if (ctx->st_host) (void)hipHostFree(ctx->st_host);
     if (ctx->score_pin) (void)hipHostFree(ctx->score_pin);
     if (ctx->match_stage) (void)hipHostFree(ctx->match_stage);
+    if (ctx->scan_stage) (void)hipHostFree(ctx->scan_stage);
+    if (ctx->scan_dev.p) (void)hipFree(ctx->scan_dev.p);
     for (Cloud *c : {&ctx->fixed, &ctx->moving, &ctx->scratch_a, &ctx->scratch_b}) {
         if (c->pending && (c->wait_ev || c->ready_ev)) (void)hipEventSynchronize(c->wait_ev ? c->wait_ev : c->ready_ev);
         if (c->stage) (void)hipHostFree(c->stage);
@@ -1168,6 +1378,26 @@ int cvo_hip_pose_score_many(cvo_hip_ctx *const *ctxs, const float *R9, const flo
     return score_batch(ctxs, R9, T3, ell, out, count);
 }
 
+int cvo_hip_pose_scan(cvo_hip_ctx *ctx, const float *R9, const float *T3, int count, float ell, cvo_hip_pose_scan_entry *out,
+                      cvo_hip_pose_scan_t *summary)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (count < 0 || count > (1 << 20)) return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_scan: count must be 0 .. 2^20");
+    if (count == 0 && !summary) return CVO_HIP_OK;
+    const void *some = ctx;   // (count == 0: no arrays to hand over)
+    int rc = score_check(ctx, "cvo_hip_pose_scan", count ? R9 : (const float *)some, count ? T3 : (const float *)some, ell,
+                         (count && !out) ? nullptr : (const void *)summary);
+    if (rc) return rc;
+    if (ctx->fixed.n > SCAN_MAX_POINTS || ctx->moving.n > SCAN_MAX_POINTS)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_scan: a cloud of more than 65536 points");
+    for (size_t q = 0; q < (size_t)count * 9; ++q)
+        if (!std::isfinite(R9[q])) return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_scan: a non-finite entry in R9");
+    for (size_t q = 0; q < (size_t)count * 3; ++q)
+        if (!std::isfinite(T3[q])) return fail(ctx, CVO_HIP_ERR_INVALID, "cvo_hip_pose_scan: a non-finite entry in T3");
+    return scan_run(ctx, R9, T3, count, ell, out, summary);
+}
+
 int cvo_hip_pose_matches(cvo_hip_ctx *ctx, const float R[9], const float T[3], float ell,
                          const cvo_hip_point_matches *fixed, const cvo_hip_point_matches *moving,
                          cvo_hip_pose_matches_t *summary)
@@ -1429,6 +1659,7 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     else if (is("list_init")) *value = o.list_init;
     else if (is("kept_pack")) *value = !o.no_pack;
     else if (is("matches_combine")) *value = o.matches_combine;
+    else if (is("scan_chunk")) *value = o.scan_chunk;
     else if (is("list_margin")) *value = o.list_margin;
     else if (is("record_narrow")) *value = o.record_narrow;
     else if (is("list_stale_max")) *value = o.list_stale_max;

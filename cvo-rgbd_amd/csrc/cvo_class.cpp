@@ -201,6 +201,12 @@ void registration::pose_score(const float R[9], const float T[3], float ell, cvo
     check(cvo_hip_pose_score(ctx_, R, T, ell, out), "cvo_hip_pose_score");
 }
 
+void registration::pose_scan(const float *R9, const float *T3, int count, float ell, cvo_hip_pose_scan_entry *out,
+                             cvo_hip_pose_scan_t *summary)
+{
+    check(cvo_hip_pose_scan(ctx_, R9, T3, count, ell, out, summary), "cvo_hip_pose_scan");
+}
+
 void registration::pose_matches(const float R[9], const float T[3], float ell, const cvo_hip_point_matches *fixed,
                                 const cvo_hip_point_matches *moving, cvo_hip_pose_matches_t *summary)
 {

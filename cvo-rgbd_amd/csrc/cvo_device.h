@@ -1110,6 +1110,29 @@ struct MatchArgs {
 };
 void launch_pose_matches(const MatchArgs &a, bool combine, hipStream_t s);
 
+// The pose scan (cvo_scan.hip, include/cvo_hip.h cvo_hip_pose_scan): many candidate poses of one pair in one launch, no
+// lists.  Block (b, k) sweeps the fixed cloud's segments 4 b .. 4 b + 3 against the moving cloud under pose k and leaves
+// three float64 sums; a second launch adds a pose's block sums in block order.
+constexpr int SCAN_TF = 16;      // floats per pose in ScanArgs::tf: Rt[9], t[3], the culling's radius scale and reach, 2 pad
+constexpr int SCAN_CHUNK = 4096; // poses per launch at most (the grid's second dimension; 24 bytes of partials per pose and block)
+constexpr int SCAN_MAX_POINTS = 65536;   // per cloud: 1024 segments, 256 blocks
+struct ScanArgs {
+    const float4 *pos_a;        // the fixed cloud (x), its feature rows and its segments' bounding spheres
+    const float *feat_a;
+    const float4 *seg_a;
+    const float4 *pos_b;        // the moving cloud as set (z)
+    const float *feat_b;
+    const float4 *seg_b;
+    const float *tf;            // [count][SCAN_TF]
+    double *partials;           // [3][nblk][count]: sum a, sum a d2, members
+    double *out;                // [count][3]: the same, added over the blocks in block order
+    KernConsts kc;              // make_kconsts(dprm, ell)
+    int nseg_a, nseg_b;         // segments that hold points of the clouds (the runs of nothing but padding rows are never visited)
+    int nblk;                   // blocks per pose: ceil(nseg_a / 4)
+    int count;                  // poses of this launch
+};
+void launch_pose_scan(const ScanArgs &a, int weight, hipStream_t s);
+
 void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t *build_masks = nullptr, const PrepareInit *init = nullptr);
 void launch_filter(const FilterArgs &a, dim3 grid, hipStream_t s, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);

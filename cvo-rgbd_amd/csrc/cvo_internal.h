@@ -250,6 +250,7 @@ struct CtxOptions {
     bool no_fuse = false;             // "fused_groups" = 0: align_many runs every registration on its own stream
     bool no_pack = false;             // "kept_pack" = 0: 8 + 4 byte kept entries
     bool matches_combine = true;      // "matches_combine" = 0: cvo_hip_pose_matches sends every member's atomics of the fixed row on their own
+    int scan_chunk = 0;               // "scan_chunk" (test switch): poses per launch of cvo_hip_pose_scan (0: SCAN_CHUNK)
     bool no_final_mirror = false;     // "final_mirror" = 0: the final state comes by a copy in stream order
     bool twist_on_shared_gpu = false; // "twist_on_shared_gpu": in-launch exchange although the ranks share a GPU
     bool comm_debug = false;          // "comm_debug"
@@ -358,6 +359,9 @@ struct cvo_hip_ctx {
     DevBuf part_matches;                 // cvo_hip_pose_matches: MatchCounters, the rows' MatchAcc, the output arrays of both sides
     void *match_stage = nullptr;         // ... its pinned staging: MatchCounters, then the arrays that come back
     size_t match_stage_bytes = 0;
+    DevBuf scan_dev;                     // cvo_hip_pose_scan: a chunk's poses, its [count][3] sums, the block partials
+    void *scan_stage = nullptr;          // ... its pinned staging (cvo_capi.cpp ScanStage)
+    size_t scan_stage_bytes = 0;
     List lists[LIST_N];
     DevBuf kept_cnt;                 // uint32[PROC_WAVES]
     cvo_hip_trace *trace_dev = nullptr;

@@ -12,6 +12,19 @@ import numpy as np
 from . import capi
 
 
+def pose_grid(R0, T0, rotations, translations):
+    """Candidate poses around (R0, T0) for align(init_candidates=...): every (R0 @ dR, T0 + dT) of the two lists, in
+    row-major product order (rotations outer, translations inner).  Returns (Rs, Ts): float32 arrays of shape
+    (len(rotations) * len(translations), 3, 3) and (..., 3); the products and sums are formed in float64."""
+    R0 = np.asarray(R0, np.float64).reshape(3, 3)
+    T0 = np.asarray(T0, np.float64).reshape(3)
+    rot = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
+    tr = np.asarray(translations, np.float64).reshape(-1, 3)
+    Rs = np.repeat(R0 @ rot, len(tr), axis=0)
+    Ts = np.tile(T0 + tr, (len(rot), 1))
+    return Rs.astype(np.float32), Ts.astype(np.float32)
+
+
 class _Registration:
     MODE = capi.MODE_CVO
 
@@ -31,6 +44,7 @@ class _Registration:
         self.scores = []      # run_sequence(score=...): one pose score per pair
         self.matches = None   # align(matches=...) publishes the per-point matches here
         self.matches_list = []   # run_sequence(matches=...): one capi.PoseMatches per pair
+        self.scan = None      # align(init_candidates=...) publishes the scan of the starting poses here
         self._have_moving = False
 
     def _publish(self):
@@ -58,14 +72,22 @@ class _Registration:
         self.ctx.set_moving_device(d_positions, d_features, n, layout)
         self._have_moving = True
 
-    def run_cvo_device(self, d_positions, d_features, n, layout=capi.FEAT_ROWMAJOR, trace_cap=0, score=False, matches=False):
+    def run_cvo_device(self, d_positions, d_features, n, layout=capi.FEAT_ROWMAJOR, trace_cap=0, score=False, matches=False,
+                       init_candidates=None, scan_ell=None):
         first = not self.init
         self.set_pcd_device(d_positions, d_features, n, layout)
         if not first:
-            self.align(trace_cap=trace_cap, score=score, matches=matches)
+            self.align(trace_cap=trace_cap, score=score, matches=matches, init_candidates=init_candidates, scan_ell=scan_ell)
 
-    def align(self, trace_cap=0, hessian=False, score=False, matches=False):
+    def align(self, trace_cap=0, hessian=False, score=False, matches=False, init_candidates=None, scan_ell=None):
         """ref src/cvo.cpp:361-420.
+
+        init_candidates=(Rs, Ts): before the loop, score the pose the object carries and these candidate poses -- (n, 3, 3)
+        and (n, 3), e.g. from pose_grid() -- in one call (capi.Context.pose_scan, include/cvo_hip.h cvo_hip_pose_scan) at
+        ``scan_ell`` (default ``params.ell_init``), and start the loop from the one with the largest inner product.
+        Index 0 of the scanned list is the carried pose, the candidates follow: by the scan's own measure the start is
+        never worse than without it.  The scan is published as ``self.scan`` (a capi.PoseScan; ``best`` 0: the carried
+        pose stayed, -1: no pose has a member and the carried pose stayed).  None: nothing changes, bit for bit.
 
         hessian=True: after the loop, evaluate the pose Hessian of the CVO objective at the final R, T and
         length scale (capi.Context.pose_hessian, include/cvo_hip.h cvo_hip_pose_hessian) before the moving
@@ -86,6 +108,15 @@ class _Registration:
         The registration itself is the same bit for bit with or without any of them."""
         if not self._have_moving:
             raise capi.CvoHipError("align(): set_pcd() must precede each align()")
+        if init_candidates is not None:
+            Rs, Ts = init_candidates
+            st = self.state
+            Rs = np.concatenate([np.array(st.R, np.float32).reshape(1, 3, 3), np.asarray(Rs, np.float32).reshape(-1, 3, 3)])
+            Ts = np.concatenate([np.array(st.T, np.float32).reshape(1, 3), np.asarray(Ts, np.float32).reshape(-1, 3)])
+            self.scan = self.ctx.pose_scan(Rs, Ts, self.params.ell_init if scan_ell is None else float(scan_ell))
+            if self.scan.best > 0:
+                st.R[:] = [float(v) for v in Rs[self.scan.best].ravel()]
+                st.T[:] = [float(v) for v in Ts[self.scan.best]]
         self.num_iterations, self.trace = self.ctx.align(self.state, trace_cap=trace_cap)
         if hessian:
             s = self.state
@@ -102,13 +133,15 @@ class _Registration:
         self._have_moving = False
         self._publish()
 
-    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False, score=False, matches=False):
-        """ref src/cvo.cpp:422-435 (hessian, score, matches: see align())."""
+    def run_cvo(self, positions, features, layout=capi.FEAT_ROWMAJOR, trace_cap=0, hessian=False, score=False, matches=False,
+                init_candidates=None, scan_ell=None):
+        """ref src/cvo.cpp:422-435 (hessian, score, matches, init_candidates, scan_ell: see align())."""
         if not self.init:
             self.set_pcd(positions, features, layout)
         else:
             self.set_pcd(positions, features, layout)
-            self.align(trace_cap=trace_cap, hessian=hessian, score=score, matches=matches)
+            self.align(trace_cap=trace_cap, hessian=hessian, score=score, matches=matches, init_candidates=init_candidates,
+                       scan_ell=scan_ell)
 
     def run_sequence(self, frames, writer=None, trace_cap=0, hessian=False, score=False, matches=False):
         """The loop of the reference's drivers (ref src/cvo_main.cpp:36-66): every

@@ -85,6 +85,11 @@ class registration {
     void align(cvo_hip_pose_score_t *score, float score_ell, cvo_hip_pose_hessian_t *hessian = nullptr);
     // cvo_hip_pose_score of the clouds set, at the pose (R, T) and length scale ell
     void pose_score(const float R[9], const float T[3], float ell, cvo_hip_pose_score_t *out);
+    // cvo_hip_pose_scan of the clouds set: the scores of `count` candidate poses (R9 count x 9, T3 count x 3) at length scale
+    // ell in one call -- out[k] belongs to pose k, summary->best is the index of the largest inner product (-1: no pose has
+    // a member).  Where to start an align() whose true motion may be out of the kernel's reach.
+    void pose_scan(const float *R9, const float *T3, int count, float ell, cvo_hip_pose_scan_entry *out,
+                   cvo_hip_pose_scan_t *summary);
     // cvo_hip_pose_matches of the clouds set, at the pose (R, T) and length scale ell: which points matched.  fixed /
     // moving: the caller's arrays of one entry per point of that cloud, in the order the cloud was handed over (null: that
     // side is not wanted); summary: the counts and the inner product, cvo_hip_pose_score's of the same name.

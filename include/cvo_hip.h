@@ -367,6 +367,68 @@ int cvo_hip_pose_score(cvo_hip_ctx *ctx, const float R[9], const float T[3], flo
 int cvo_hip_pose_score_many(cvo_hip_ctx *const *ctxs, const float *R9, const float *T3, const float *ell,
                             cvo_hip_pose_score_t *out, int count);
 
+/* Where to start: the score of MANY candidate poses of the pair that is set, in one call -- the step in
+ * front of a registration whose true motion may lie outside the kernel's reach (dropped frames,
+ * re-attachment to a keyframe, loop-closure candidates, a motion model with several hypotheses).
+ * R9 is count x 9, T3 count x 3 (row-major rotations, as everywhere); entry k of `out` belongs to
+ * pose k.  Both clouds are read once per launch and stay on chip; nothing is listed or recorded
+ * between the poses (cvo_scan.hip).
+ *
+ * Member rule: A_k and every float32 weight a are exactly what cvo_hip_flow(ctx, ell, ...) keeps at
+ * pose k -- y_j = Rt z_j + t with [Rt | t] the inverse of (R_k, T_k) as cvo_hip_transform_pcd makes
+ * it, d2 = fma(e2, e2, fma(e1, e1, e0 e0)), member iff d2 < tau and the pair weight > 0; cvo, acvo
+ * with its own parameters, and the MATLAB weight.  nnz is therefore EQUAL to
+ * cvo_hip_pose_score(ctx, R_k, T_k, ell).nnz, for every k.
+ *
+ * Sums: per-member terms are float32 (a, and the float32 product a d2 as cvo_hip_pose_score forms
+ * it), accumulated in float64.  The order differs from cvo_hip_pose_score's, so inner is not bit-
+ * equal to it; both are sums of the same nnz positive float32 numbers, hence
+ *   |inner_scan - inner_score| <= 2 g inner,  g = nnz u / (1 - nnz u),  u = 2^-53,
+ * and mean_d2 agrees to 4 g + 4 u relative.  self_fixed, self_moving, nnz_fixed and nnz_moving come
+ * from cvo_hip_pose_score's own self passes and per-cloud cache: bit-equal, and a scan warms the
+ * cache for a following score and the other way round.
+ *
+ * Independence: the 32 bytes of entry k are a function of the two clouds as handed over, the
+ * parameters, ell and pose k -- not of count, of k's position in the call, of how the call is cut
+ * into launches or of earlier calls.  There are no float atomics; culling only removes pairs that
+ * are not members, and the order in which members are added is fixed by the clouds' device order.
+ *
+ * best: the index of the largest inner, the smallest such index if several share it; -1 if count
+ * is 0 or every A_k is empty.  The context is left as cvo_hip_transform_pcd(ctx, R_best, T_best)
+ * leaves it; its pose is untouched if best is -1.  A cvo_hip_align before or after is unaffected.
+ * Device and pinned memory are the context's, grow with the clouds and with min(count, 4096) and
+ * are freed by cvo_hip_destroy.  The call waits once per 4096 poses.
+ *
+ * What it leaves out: fixed_matched / moving_matched (a flag byte per point per pose and a pass
+ * over them) -- run cvo_hip_pose_score or cvo_hip_pose_matches on the winner.
+ *
+ * CVO_HIP_ERR_INVALID, before anything is enqueued: as cvo_hip_pose_score -- null R9, T3, out or
+ * summary with count > 0, ell not finite or not > 0, a cloud missing, a sharded context narrower
+ * than the whole clouds, a communicator, mailboxes or an all-reduce hook attached -- and count < 0,
+ * count > 2^20, a non-finite entry in R9 or T3, or a cloud of more than 65536 points (the scan is a
+ * segment-by-segment sweep tuned for the clouds the front end and the drivers make).  count == 0
+ * with a valid context: CVO_HIP_OK, best = -1, the norms still filled.  A null ctx:
+ * CVO_HIP_ERR_INVALID. */
+typedef struct cvo_hip_pose_scan_entry {   /* one candidate pose */
+    double inner;        /* sum of a over A_k (cvo_hip_pose_score's inner at that pose) */
+    double cos_angle;    /* inner / sqrt(self_fixed * self_moving); 0 if either is 0; not clamped */
+    double mean_d2;      /* sum a d2 / sum a over A_k; 0 if A_k is empty */
+    int64_t nnz;         /* |A_k| */
+} cvo_hip_pose_scan_entry;
+typedef struct cvo_hip_pose_scan_summary {
+    double self_fixed, self_moving;      /* |f_X|^2, |f_Y|^2: cvo_hip_pose_score's, bit for bit */
+    int64_t nnz_fixed, nnz_moving;
+    int32_t count;                       /* poses scored */
+    int32_t best;                        /* index of the largest inner, the smallest such index if several
+                                            share it; -1 if count == 0 or every A_k is empty */
+    int32_t n_fixed, n_moving;
+    float ell;                           /* the length scale used */
+    int32_t pad_;
+} cvo_hip_pose_scan_t;
+int cvo_hip_pose_scan(cvo_hip_ctx *ctx, const float *R9 /* count x 9 */, const float *T3 /* count x 3 */,
+                      int count, float ell, cvo_hip_pose_scan_entry *out /* count */,
+                      cvo_hip_pose_scan_t *summary);
+
 /* Which points matched: per point of either cloud, its share of the CVO inner product at a pose
  * (R, T) and length scale ell, and its best match in the other cloud.
  *
