@@ -1,5 +1,6 @@
 // cvo_device.h -- device-resident state and argument blocks shared by the HIP
-// kernels (cvo_kernels.hip) and their host driver (cvo_capi.cpp).
+// kernels (cvo_kernels.hip, the pose queries' cvo_hessian / _score / _matches / _scan.hip) and their host driver
+// (cvo_capi.cpp, cvo_plan.cpp, cvo_pose.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -871,8 +872,20 @@ struct PrepareInit {
     int32_t iter, n_fixed, done;
     float center[3], xmax, y0max;
 };
+// A kept list as a PROC_FLOW pass recorded it, for the passes that stream it back outside the loop (the pose queries): the
+// fields of the recording pass's ProcessArgs, filled by kept_view (cvo_plan.cpp), read through kept_slice / kept_entry below.
+struct KeptView {
+    const uint2 *kept_ij;       // the entries, their weights (kept_packed == 0) and the per-wave counts
+    const float *kept_a;
+    const uint32_t *kept_cnt;
+    const DevState *st;         // the state the pass ran at: [Rt | t], red[RED_FLOW ..]
+    uint32_t kept_wcap;         // slice of one wave (entries)
+    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
+    int kept_packed;
+    unsigned kept_ebase;
+};
 // ---------------------------------------------------------------------------
-// Device helpers shared by the list kernels (cvo_kernels.hip) and the pose-Hessian pass (cvo_hessian.hip)
+// Device helpers shared by the list kernels (cvo_kernels.hip) and the passes of the pose queries
 // ---------------------------------------------------------------------------
 // (CVO_GLOBAL: the explicit global address space, see PairSrc in cvo_kernels.hip)
 #define CVO_GLOBAL __attribute__((address_space(1)))
@@ -931,6 +944,24 @@ __device__ __forceinline__ void kept_unpack(const int mode, const unsigned ebase
         j = (e.x >> 18) | ((e.y & 0xfu) << 14);
         w = __uint_as_float(((((e.y >> 4) & 0xfu) + ebase) << 23) | ((e.y >> 8) & 0x7fffffu));
     }
+}
+// Streaming a KeptView: wave `wid` of block b takes slice 4 b + wid -- what wave 4 b + wid of the PROC_FLOW pass recorded,
+// exactly as the PROC_STEP pass does.  Returns the slice; base: the index of its first entry, n: its entries.
+__device__ __forceinline__ const CVO_GLOBAL char *kept_slice(const KeptView &k, const int wid, size_t &base, unsigned &n)
+{
+    const unsigned wave = blockIdx.x * 4u + (unsigned)wid;
+    base = (size_t)wave * k.kept_wcap;
+    n = k.kept_cnt[wave];
+    if (n > k.kept_wcap) n = k.kept_wcap;
+    return (const CVO_GLOBAL char *)(unsigned long long)(k.kept_ij + base);
+}
+// ... and entry `off` of the slice, in any of the three entry forms: its rows and its weight
+__device__ __forceinline__ void kept_entry(const KeptView &k, const CVO_GLOBAL char *slice, const size_t base, const unsigned off,
+                                           unsigned &i, unsigned &j, float &w)
+{
+    const uint2 e = load8(slice, off);
+    const float raw_w = k.kept_packed ? 0.0f : k.kept_a[base + off];
+    kept_unpack(k.kept_packed, k.kept_ebase, e, raw_w, i, j, w);
 }
 
 // ---------------------------------------------------------------------------
@@ -1026,6 +1057,34 @@ __device__ __forceinline__ void wave_sums(double (&v)[N], int lane, double *dst)
     if (p >= 0) dst[p] = v[0];
 }
 
+// The block's sums of N per-thread values, in a fixed order: the waves' sums (wave_sums), then the four of them in wave
+// order.  red: 4 N doubles of LDS; thread t < N returns sum t.
+template <int N>
+__device__ __forceinline__ double block_sums(double (&v)[N], double *red)
+{
+    const int tid = threadIdx.x;
+    wave_sums<N>(v, tid & 63, red + __builtin_amdgcn_readfirstlane(tid >> 6) * N);
+    __syncthreads();
+    return tid < N ? ((red[tid] + red[N + tid]) + red[2 * N + tid]) + red[3 * N + tid] : 0.0;
+}
+// One block adds [N][nblk] block partials: thread t those of blocks t, t + 256, ... in that order, then block_sums.
+// (A fixed trip count, unrolled: all of a thread's loads are in flight together; the partials are [value][block], so
+// that every load of a wave is one contiguous 512-byte run.)
+template <int N>
+__device__ __forceinline__ double block_partials_sum(const double *partials, const int nblk, double *red)
+{
+    static_assert(PROC_BLOCKS % BLOCK == 0, "partials per thread must be whole");
+    double s[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k] = 0.0;
+#pragma unroll
+    for (int u = 0; u < PROC_BLOCKS / BLOCK; ++u) {
+        const int b = (int)threadIdx.x + u * BLOCK;
+#pragma unroll
+        for (int k = 0; k < N; ++k) s[k] += (b < nblk) ? partials[(size_t)k * nblk + b] : 0.0;
+    }
+    return block_sums<N>(s, red);
+}
 
 // The pose Hessian of the CVO objective (cvo_hessian.hip, include/cvo_hip.h cvo_hip_pose_hessian): one pass over the
 // kept list a PROC_FLOW pass recorded, then a one-block fixed-order reduction of its block partials.
@@ -1033,16 +1092,9 @@ constexpr int NACC_HESS = 27;   // g[6], then H's upper triangle row by row (21)
 struct HessArgs {
     const float4 *pos_a;        // the fixed cloud (x)
     const float4 *pos_b;        // the moving cloud as set (z): y = [Rt|t] z with the state's Rt, t
-    const uint2 *kept_ij;       // the kept list, its weights (kept_packed == 0) and per-wave counts (ProcessArgs)
-    const float *kept_a;
-    const uint32_t *kept_cnt;
-    const DevState *st;
+    KeptView kept;
     double *partials;           // [NACC_HESS][nblk]
     double *out;                // [NACC_HESS]
-    uint32_t kept_wcap;
-    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
-    int kept_packed;
-    unsigned kept_ebase;
     float inv_l2, inv_l;        // 1 / ell^2, 1 / ell
 };
 void launch_pose_hessian(const HessArgs &a, hipStream_t s);
@@ -1052,18 +1104,11 @@ void launch_pose_hessian(const HessArgs &a, hipStream_t s);
 struct ScoreArgs {
     const float4 *pos_a;        // the fixed cloud (x)
     const float4 *pos_b;        // the moving cloud as set (z): y = [Rt|t] z with the state's Rt, t
-    const uint2 *kept_ij;       // the kept list, its weights (kept_packed == 0) and per-wave counts (ProcessArgs)
-    const float *kept_a;
-    const uint32_t *kept_cnt;
-    const DevState *st;
+    KeptView kept;
     uint8_t *flag_a;            // [na] 1: fixed row i has a member (zeroed on the stream before the pass)
     uint8_t *flag_b;            // [nb] likewise for the moving rows
     double *partials;           // [nblk] sum a d2 per block
     double *out;                // [3]: sum a d2, fixed rows matched, moving rows matched
-    uint32_t kept_wcap;
-    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
-    int kept_packed;
-    unsigned kept_ebase;
     int na, nb;                 // rows of the two clouds' device arrays (multiples of CLOUD_PAD, so of 4)
 };
 void launch_pose_score(const ScoreArgs &a, hipStream_t s);
@@ -1092,18 +1137,11 @@ struct MatchOut {               // one side's results in the caller's order (dev
 struct MatchArgs {
     const float *feat_a;        // the fixed / moving cloud's feature rows: word FEAT_INDEX_SLOT is the caller's index
     const float *feat_b;
-    const uint2 *kept_ij;       // the kept list, its weights (kept_packed == 0) and per-wave counts (ProcessArgs)
-    const float *kept_a;
-    const uint32_t *kept_cnt;
-    const DevState *st;         // red[RED_FLOW + 6]: the sum of all weights of the pass
+    KeptView kept;              // (its st->red[RED_FLOW + 6]: the sum of all weights of the pass)
     MatchAcc *acc_a;            // [na]
     MatchAcc *acc_b;            // [nb]
     MatchCounters *counters;
     MatchOut out[2];            // [0] the fixed cloud's [n_fixed], [1] the moving cloud's [n_moving]
-    uint32_t kept_wcap;
-    int nblk;                   // blocks of the PROC_FLOW pass that recorded the list
-    int kept_packed;
-    unsigned kept_ebase;
     int na, nb;                 // rows of the two clouds' device arrays
     int n_fixed, n_moving;      // points as the caller counts them
     int blocks_a, blocks_b;     // blocks of the finishing pass per side

@@ -70,74 +70,48 @@ __device__ __forceinline__ void member_hessian_terms(const float4 x, const float
     }
 }
 
-// Block b, wave w streams slice 4 b + w of the kept list -- what wave 4 b + w of the PROC_FLOW pass recorded, in any of
-// the three entry forms (kept_unpack) -- exactly as the PROC_STEP pass does.  y is the moving row through apply_tf with
-// the state's [Rt|t]: the bits the flow pass tested.
+// Block b, wave w streams slice 4 b + w of the kept list (kept_slice).  y is the moving row through apply_tf with the
+// state's [Rt|t]: the bits the flow pass tested.
 __global__ void __launch_bounds__(BLOCK) k_pose_hessian(const HessArgs a)
 {
     __shared__ double red[4 * NACC_HESS];
-    if ((int)blockIdx.x >= a.nblk) return;
+    if ((int)blockIdx.x >= a.kept.nblk) return;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned wave = blockIdx.x * 4u + (unsigned)wid;
     float Rt[9], tt[3];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) Rt[q] = a.st->Rt[q];
+    for (int q = 0; q < 9; ++q) Rt[q] = a.kept.st->Rt[q];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) tt[q] = a.st->t[q];
-    const size_t base = (size_t)wave * a.kept_wcap;
-    unsigned n = a.kept_cnt[wave];
-    if (n > a.kept_wcap) n = a.kept_wcap;
-    const CVO_GLOBAL char *kept_w = (const CVO_GLOBAL char *)(unsigned long long)(a.kept_ij + base);
+    for (int q = 0; q < 3; ++q) tt[q] = a.kept.st->t[q];
+    size_t base;
+    unsigned n;
+    const CVO_GLOBAL char *kept_w = kept_slice(a.kept, __builtin_amdgcn_readfirstlane(tid >> 6), base, n);
     const CVO_GLOBAL char *pos_a = (const CVO_GLOBAL char *)(unsigned long long)a.pos_a;
     const CVO_GLOBAL char *pos_b = (const CVO_GLOBAL char *)(unsigned long long)a.pos_b;
-    const int packed = a.kept_packed;
     double acc[NACC_HESS];
 #pragma unroll
     for (int k = 0; k < NACC_HESS; ++k) acc[k] = 0.0;
     for (unsigned off = (unsigned)lane; off < n; off += 64u) {
-        const uint2 e = load8(kept_w, off);
-        const float raw_w = packed ? 0.0f : a.kept_a[base + off];
         unsigned i, j;
         float w;
-        kept_unpack(packed, a.kept_ebase, e, raw_w, i, j, w);
+        kept_entry(a.kept, kept_w, base, off, i, j, w);
         const float4 x = load_pos<false>(pos_a, i * 16u);
         const float4 y = apply_tf(Rt, tt, load_pos<false>(pos_b, j * 16u));
         member_hessian_terms(x, y, w, a.inv_l2, a.inv_l, acc);
     }
-    wave_sums<NACC_HESS>(acc, lane, red + wid * NACC_HESS);
-    __syncthreads();
-    if (tid < NACC_HESS)   // [value][block]: coalesced for the reader
-        a.partials[(size_t)tid * a.nblk + blockIdx.x] =
-            ((red[tid] + red[NACC_HESS + tid]) + red[2 * NACC_HESS + tid]) + red[3 * NACC_HESS + tid];
+    const double sum = block_sums<NACC_HESS>(acc, red);
+    if (tid < NACC_HESS) a.partials[(size_t)tid * a.kept.nblk + blockIdx.x] = sum;   // [value][block]: coalesced for the reader
 }
 
-// thread t adds the partials of blocks t, t + 256, ... in that order; then the waves, then the four wave sums in order.
-// (A fixed trip count, unrolled: all of a thread's loads are in flight together; the partials are [value][block], so
-// that every load of a wave is one contiguous 512-byte run.)
 __global__ void __launch_bounds__(BLOCK) k_pose_hessian_reduce(const HessArgs a)
 {
     __shared__ double red[4 * NACC_HESS];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    static_assert(PROC_BLOCKS % BLOCK == 0, "partials per thread must be whole");
-    double s[NACC_HESS];
-#pragma unroll
-    for (int k = 0; k < NACC_HESS; ++k) s[k] = 0.0;
-#pragma unroll
-    for (int u = 0; u < PROC_BLOCKS / BLOCK; ++u) {
-        const int b = tid + u * BLOCK;
-#pragma unroll
-        for (int k = 0; k < NACC_HESS; ++k) s[k] += (b < a.nblk) ? a.partials[(size_t)k * a.nblk + b] : 0.0;
-    }
-    wave_sums<NACC_HESS>(s, lane, red + wid * NACC_HESS);
-    __syncthreads();
-    if (tid < NACC_HESS)
-        a.out[tid] = ((red[tid] + red[NACC_HESS + tid]) + red[2 * NACC_HESS + tid]) + red[3 * NACC_HESS + tid];
+    const double sum = block_partials_sum<NACC_HESS>(a.partials, a.kept.nblk, red);
+    if (threadIdx.x < NACC_HESS) a.out[threadIdx.x] = sum;
 }
 
 void launch_pose_hessian(const HessArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_pose_hessian, dim3((unsigned)a.nblk), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_pose_hessian, dim3((unsigned)a.kept.nblk), dim3(BLOCK), 0, s, a);
     hipLaunchKernelGGL(k_pose_hessian_reduce, dim3(1), dim3(BLOCK), 0, s, a);
 }
 

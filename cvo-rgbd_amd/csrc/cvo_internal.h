@@ -1,7 +1,8 @@
 // cvo_internal.h -- what the translation units of the host library share: the context, the growable device
 // arrays, argument tables and captured batches, the recorded launches of an iteration, the resumable align() job.
-//   cvo_capi.cpp    entry points that are not listed below (create / destroy, parameters, sharding, mailboxes, the
-//                   low-level calls of the loop body, function_inner_product, profiling getters)
+//   cvo_capi.cpp    entry points that are not listed below (create / destroy, parameters and options, sharding, mailboxes,
+//                   the low-level calls of the loop body, function_inner_product, profiling getters)
+//   cvo_pose.cpp    the pose queries: cvo_hip_pose_hessian, _pose_score (_many), _pose_scan, _pose_matches
 //   cvo_clouds.cpp  the cloud hand-over (tail of set_pcd(), ref src/cvo.cpp:344-356): one cloud, a batch
 //   cvo_plan.cpp    from the launches of ONE iteration (recorded, not issued) to launch plans, argument tables and
 //                   captured batches; the eager launches of the low-level entry points
@@ -85,6 +86,11 @@ struct FilterPlan {
 };
 
 struct DevBuf {   // a growable device array
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
+struct PinBuf {   // a growable pinned staging buffer
     void *p = nullptr;
     size_t bytes = 0;
 };
@@ -355,13 +361,11 @@ struct cvo_hip_ctx {
     DevBuf part_flow, part_xx, part_yy, part_step;   // [PROC_BLOCKS][NACC_MAX] float64
     DevBuf part_hess;                    // cvo_hip_pose_hessian: [NACC_HESS][nblk] block partials, then the [NACC_HESS] sums
     DevBuf part_score;                   // cvo_hip_pose_score: [PROC_BLOCKS] block partials, [4] sums, the matched bytes
-    struct ScorePin *score_pin = nullptr;   // cvo_hip_pose_score: pinned staging of its passes (cvo_capi.cpp)
+    struct ScorePin *score_pin = nullptr;   // cvo_hip_pose_score: pinned staging of its passes (cvo_pose.cpp)
     DevBuf part_matches;                 // cvo_hip_pose_matches: MatchCounters, the rows' MatchAcc, the output arrays of both sides
-    void *match_stage = nullptr;         // ... its pinned staging: MatchCounters, then the arrays that come back
-    size_t match_stage_bytes = 0;
+    PinBuf match_stage;                  // ... its pinned staging: MatchCounters, then the arrays that come back
     DevBuf scan_dev;                     // cvo_hip_pose_scan: a chunk's poses, its [count][3] sums, the block partials
-    void *scan_stage = nullptr;          // ... its pinned staging (cvo_capi.cpp ScanStage)
-    size_t scan_stage_bytes = 0;
+    PinBuf scan_stage;                   // ... its pinned staging (cvo_pose.cpp ScanStage)
     List lists[LIST_N];
     DevBuf kept_cnt;                 // uint32[PROC_WAVES]
     cvo_hip_trace *trace_dev = nullptr;
@@ -456,6 +460,7 @@ DevParams loop_params(const cvo_hip_ctx *ctx);
 hipStream_t loop_stream(const cvo_hip_ctx *ctx);
 int enqueue_filter(cvo_hip_ctx *ctx, int list, const Cloud &ca, int row_lo, int row_hi, int tf_a, const Cloud &cb, int tf_b, int check_done);
 int kept_format(const cvo_hip_ctx *ctx, unsigned *ebase);
+KeptView kept_view(const cvo_hip_ctx *ctx);
 int enqueue_process(cvo_hip_ctx *ctx, int mode, int list, DevBuf &part, const float4 *pos_a, const float *feat_a, int tf_a,
                     const float4 *pos_b, const float *feat_b, int tf_b, int first_counted, int check_done);
 int drain_events(cvo_hip_ctx *ctx, int n_exec = -1, const DevState *fin = nullptr);
@@ -482,6 +487,8 @@ constexpr int kShortBatch = 2;      // classic slots of a batch of a plan that h
 constexpr int kRunBatchSlots = 2;   // classic slots behind the resident run of a RUN batch (an even number, see kBatch)
 int zero_counters(cvo_hip_ctx *ctx);
 int push_state_fields(cvo_hip_ctx *ctx, size_t off, size_t bytes);
+int push_pose_fields(cvo_hip_ctx *ctx, const DevHead *img, bool with_consts);
+int enqueue_flow_reduce(cvo_hip_ctx *ctx, const CommTable *comm);
 int fetch_red(cvo_hip_ctx *ctx, int off, int count, double *out);
 // ---- cvo_job.cpp
 void decide_scheme(cvo_hip_ctx *ctx);

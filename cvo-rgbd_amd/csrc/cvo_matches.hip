@@ -70,22 +70,17 @@ __device__ __forceinline__ void row_atomics(MatchAcc *acc, unsigned row, unsigne
     atomicAdd(&r->count, count);
 }
 
-// Block b, wave w streams slice 4 b + w of the kept list -- what wave 4 b + w of the PROC_FLOW pass recorded, in any of
-// the three entry forms (kept_unpack) -- as k_pose_score and k_pose_hessian do.
+// Block b, wave w streams slice 4 b + w of the kept list (kept_slice).
 template <bool COMBINE>
 __global__ void __launch_bounds__(BLOCK) k_pose_matches(const MatchArgs a)
 {
-    if ((int)blockIdx.x >= a.nblk) return;
+    if ((int)blockIdx.x >= a.kept.nblk) return;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned wave = blockIdx.x * 4u + (unsigned)wid;
-    const size_t base = (size_t)wave * a.kept_wcap;
-    unsigned n = a.kept_cnt[wave];
-    if (n > a.kept_wcap) n = a.kept_wcap;
+    size_t base;
+    unsigned n;
+    const CVO_GLOBAL char *kept_w = kept_slice(a.kept, __builtin_amdgcn_readfirstlane(tid >> 6), base, n);
     if (n == 0) return;
-    const int E = f64_exponent(a.st->red[RED_FLOW + 6]);   // (n > 0: the pass has members, inner > 0)
-    const CVO_GLOBAL char *kept_w = (const CVO_GLOBAL char *)(unsigned long long)(a.kept_ij + base);
-    const int packed = a.kept_packed;
+    const int E = f64_exponent(a.kept.st->red[RED_FLOW + 6]);   // (n > 0: the pass has members, inner > 0)
     unsigned inexact = 0;
     for (unsigned off0 = 0; off0 < n; off0 += 64u) {   // (wave-uniform trips: the scan below needs every lane)
         const unsigned off = off0 + (unsigned)lane;
@@ -93,9 +88,7 @@ __global__ void __launch_bounds__(BLOCK) k_pose_matches(const MatchArgs a)
         unsigned i = 0, j = 0;
         float w = 0.0f;
         if (live) {
-            const uint2 e = load8(kept_w, off);
-            const float raw_w = packed ? 0.0f : a.kept_a[base + off];
-            kept_unpack(packed, a.kept_ebase, e, raw_w, i, j, w);
+            kept_entry(a.kept, kept_w, base, off, i, j, w);
             live = i < (unsigned)a.na && j < (unsigned)a.nb;   // (always: a member's rows are rows of the clouds)
         }
         unsigned ci = 0, cj = 0;
@@ -153,7 +146,7 @@ __global__ void __launch_bounds__(BLOCK) k_pose_matches_finish(const MatchArgs a
         if (c >= 0 && c < npts) {
             const MatchAcc v = acc[r];
             matched = v.count != 0;
-            const int E = matched ? f64_exponent(a.st->red[RED_FLOW + 6]) : 0;
+            const int E = matched ? f64_exponent(a.kept.st->red[RED_FLOW + 6]) : 0;
             // (unsigned 64-bit to float64 rounds to nearest: the float64 nearest the sum; the scaling is exact)
             o.support[c] = matched ? __builtin_ldexp((double)v.units, E - (MATCH_UNIT_BITS - 1)) : 0.0;
             o.count[c] = (int32_t)v.count;
@@ -168,9 +161,9 @@ __global__ void __launch_bounds__(BLOCK) k_pose_matches_finish(const MatchArgs a
 void launch_pose_matches(const MatchArgs &a, bool combine, hipStream_t s)
 {
     if (combine)
-        hipLaunchKernelGGL(k_pose_matches<true>, dim3((unsigned)a.nblk), dim3(BLOCK), 0, s, a);
+        hipLaunchKernelGGL(k_pose_matches<true>, dim3((unsigned)a.kept.nblk), dim3(BLOCK), 0, s, a);
     else
-        hipLaunchKernelGGL(k_pose_matches<false>, dim3((unsigned)a.nblk), dim3(BLOCK), 0, s, a);
+        hipLaunchKernelGGL(k_pose_matches<false>, dim3((unsigned)a.kept.nblk), dim3(BLOCK), 0, s, a);
     hipLaunchKernelGGL(k_pose_matches_finish, dim3((unsigned)(a.blocks_a + a.blocks_b)), dim3(BLOCK), 0, s, a);
 }
 

@@ -239,6 +239,20 @@ int kept_format(const cvo_hip_ctx *ctx, unsigned *ebase)
     return 0;
 }
 
+// ... and the list itself as the last PROC_FLOW pass of the context recorded it, for a pass that streams it back
+KeptView kept_view(const cvo_hip_ctx *ctx)
+{
+    KeptView v{};
+    v.kept_ij = (const uint2 *)ctx->lists[LIST_KEPT].a.p;
+    v.kept_a = (const float *)ctx->lists[LIST_KEPT].b.p;
+    v.kept_cnt = (const uint32_t *)ctx->kept_cnt.p;
+    v.st = ctx->st;
+    v.nblk = ctx->proc_blocks;
+    v.kept_wcap = ctx->lists[LIST_KEPT].cap / (uint32_t)(4 * ctx->proc_blocks);   // (enqueue_process's slice)
+    v.kept_packed = kept_format(ctx, &v.kept_ebase);
+    return v;
+}
+
 int enqueue_process(cvo_hip_ctx *ctx, int mode, int list, DevBuf &part, const float4 *pos_a,
                     const float *feat_a, int tf_a, const float4 *pos_b, const float *feat_b,
                     int tf_b, int first_counted, int check_done)
@@ -1203,6 +1217,39 @@ int push_state_fields(cvo_hip_ctx *ctx, size_t off, size_t bytes)
     HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(ctx->st) + off,
                                 reinterpret_cast<char *>(&ctx->st_host[kPollSlots]) + off, bytes,
                                 hipMemcpyHostToDevice, ctx->stream));
+    return CVO_HIP_OK;
+}
+
+// The state fields a pose pushes -- R, T; Rt, t; `done`; with_consts: the kernel constants and the filter's geometry and
+// bounds (kc .. xi) as well -- from a pinned image of the state's head (null: staging slot 0), in stream order, no wait.
+int push_pose_fields(cvo_hip_ctx *ctx, const DevHead *img, bool with_consts)
+{
+    if (!img) img = &ctx->st_host[kPollSlots];
+    const size_t ranges[4][2] = {{offsetof(DevState, R), offsetof(DevState, ell)},
+                                 {offsetof(DevState, Rt), offsetof(DevState, used_Rt)},
+                                 {offsetof(DevState, kc), with_consts ? offsetof(DevState, xi) : offsetof(DevState, kc)},
+                                 {offsetof(DevState, done), offsetof(DevState, done) + sizeof(int32_t)}};
+    for (const auto &r : ranges)
+        if (r[1] > r[0])
+            HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(ctx->st) + r[0], reinterpret_cast<const char *>(img) + r[0], r[1] - r[0],
+                                        hipMemcpyHostToDevice, ctx->stream));
+    return CVO_HIP_OK;
+}
+
+// The flow partials of a PROC_FLOW pass outside the loop reduced into DevState::red[RED_FLOW ..], without self terms whatever
+// the context's mode; comm: not null -- the sums go over the ranks' mailboxes.
+int enqueue_flow_reduce(cvo_hip_ctx *ctx, const CommTable *comm)
+{
+    PostFlowArgs pa{};
+    pa.st = ctx->st;
+    pa.prm = ctx->dprm;
+    pa.prm.mode = CVO_HIP_MODE_CVO;   // no self terms here
+    pa.nblk = ctx->proc_blocks;
+    pa.flags = POST_REDUCE;
+    pa.comm = comm;
+    pa.part_flow = (const double *)ctx->part_flow.p;
+    launch_post_flow(pa, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
     return CVO_HIP_OK;
 }
 

@@ -26,7 +26,7 @@ namespace cvo_dev {
 //     |c_x - c_y'| - r_x - scale r_y > reach          (all float32, c_y' = apply_tf(Rt, t, c_y))
 // with (c_x, r_x), (c_y, r_y) the segments' spheres (cvo_cloud.hip k_cloud_seg: every real row of the segment lies within
 // r of c, r already rounded up), scale >= |Rt|_2 and reach = sqrt(tau) + slack, both made per pose by the host
-// (cvo_capi.cpp scan_pose_consts, where the slack is derived).  A member (i, j) has a computed d2 < tau, hence
+// (cvo_pose.cpp scan_pose_consts, where the slack is derived).  A member (i, j) has a computed d2 < tau, hence
 // |x_i - y^_j| < sqrt(tau) (1 + 4 u) for the computed row y^_j, and
 //     |c_x - c_y*| <= |c_x - x_i| + |x_i - y^_j| + |y^_j - y_j*| + |y_j* - c_y*| <= r_x + sqrt(tau)(1 + 4 u) + err + |Rt|_2 r_y
 // (* = in exact arithmetic); the slack covers err, the rounding of c_y' and of the left-hand side.  So a skipped

@@ -14,34 +14,27 @@
 
 namespace cvo_dev {
 
-// Block b, wave w streams slice 4 b + w of the kept list -- what wave 4 b + w of the PROC_FLOW pass recorded, in any of
-// the three entry forms (kept_unpack) -- as k_pose_hessian does.
+// Block b, wave w streams slice 4 b + w of the kept list (kept_slice).
 __global__ void __launch_bounds__(BLOCK) k_pose_score(const ScoreArgs a)
 {
     __shared__ double red[4];
-    if ((int)blockIdx.x >= a.nblk) return;
+    if ((int)blockIdx.x >= a.kept.nblk) return;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned wave = blockIdx.x * 4u + (unsigned)wid;
     float Rt[9], tt[3];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) Rt[q] = a.st->Rt[q];
+    for (int q = 0; q < 9; ++q) Rt[q] = a.kept.st->Rt[q];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) tt[q] = a.st->t[q];
-    const size_t base = (size_t)wave * a.kept_wcap;
-    unsigned n = a.kept_cnt[wave];
-    if (n > a.kept_wcap) n = a.kept_wcap;
-    const CVO_GLOBAL char *kept_w = (const CVO_GLOBAL char *)(unsigned long long)(a.kept_ij + base);
+    for (int q = 0; q < 3; ++q) tt[q] = a.kept.st->t[q];
+    size_t base;
+    unsigned n;
+    const CVO_GLOBAL char *kept_w = kept_slice(a.kept, __builtin_amdgcn_readfirstlane(tid >> 6), base, n);
     const CVO_GLOBAL char *pos_a = (const CVO_GLOBAL char *)(unsigned long long)a.pos_a;
     const CVO_GLOBAL char *pos_b = (const CVO_GLOBAL char *)(unsigned long long)a.pos_b;
-    const int packed = a.kept_packed;
     double acc[1] = {0.0};
     for (unsigned off = (unsigned)lane; off < n; off += 64u) {
-        const uint2 e = load8(kept_w, off);
-        const float raw_w = packed ? 0.0f : a.kept_a[base + off];
         unsigned i, j;
         float w;
-        kept_unpack(packed, a.kept_ebase, e, raw_w, i, j, w);
+        kept_entry(a.kept, kept_w, base, off, i, j, w);
         if (i >= (unsigned)a.na || j >= (unsigned)a.nb) continue;   // (never: a member's rows are rows of the clouds)
         const float4 x = load_pos<false>(pos_a, i * 16u);
         const float4 y = apply_tf(Rt, tt, load_pos<false>(pos_b, j * 16u));
@@ -51,9 +44,8 @@ __global__ void __launch_bounds__(BLOCK) k_pose_score(const ScoreArgs a)
         a.flag_a[i] = 1;
         a.flag_b[j] = 1;
     }
-    wave_sums<1>(acc, lane, red + wid);
-    __syncthreads();
-    if (tid == 0) a.partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    const double sum = block_sums<1>(acc, red);
+    if (tid == 0) a.partials[blockIdx.x] = sum;
 }
 
 // the matched bytes of words tid, tid + BLOCK, ... of a flag array (every byte is 0 or 1: the byte sum of a word is
@@ -73,29 +65,20 @@ __device__ __forceinline__ unsigned wave_sum_u32(unsigned v)
     return v;
 }
 
-// thread t adds the partials of blocks t, t + 256, ... in that order; then the waves, then the four wave sums in order
 __global__ void __launch_bounds__(BLOCK) k_pose_score_reduce(const ScoreArgs a)
 {
     __shared__ double red[4];
     __shared__ unsigned cnt[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    static_assert(PROC_BLOCKS % BLOCK == 0, "partials per thread must be whole");
-    double s[1] = {0.0};
-#pragma unroll
-    for (int u = 0; u < PROC_BLOCKS / BLOCK; ++u) {
-        const int b = tid + u * BLOCK;
-        s[0] += (b < a.nblk) ? a.partials[b] : 0.0;
-    }
-    wave_sums<1>(s, lane, red + wid);
     const unsigned ca = wave_sum_u32(count_flags(a.flag_a, a.na, tid));
     const unsigned cb = wave_sum_u32(count_flags(a.flag_b, a.nb, tid));
     if (lane == 0) {
         cnt[0][wid] = ca;
         cnt[1][wid] = cb;
     }
-    __syncthreads();
+    const double sum = block_partials_sum<1>(a.partials, a.kept.nblk, red);   // (its barrier: the counts are in place)
     if (tid == 0) {
-        a.out[0] = ((red[0] + red[1]) + red[2]) + red[3];
+        a.out[0] = sum;
         a.out[1] = (double)(cnt[0][0] + cnt[0][1] + cnt[0][2] + cnt[0][3]);
         a.out[2] = (double)(cnt[1][0] + cnt[1][1] + cnt[1][2] + cnt[1][3]);
     }
@@ -103,7 +86,7 @@ __global__ void __launch_bounds__(BLOCK) k_pose_score_reduce(const ScoreArgs a)
 
 void launch_pose_score(const ScoreArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_pose_score, dim3((unsigned)a.nblk), dim3(BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_pose_score, dim3((unsigned)a.kept.nblk), dim3(BLOCK), 0, s, a);
     hipLaunchKernelGGL(k_pose_score_reduce, dim3(1), dim3(BLOCK), 0, s, a);
 }
 

@@ -15,32 +15,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pose_hessian_ref as ref  # noqa: E402
+from pose_cases import case as _case, ctx as _ctx, pose as _pose, stream as _stream, trace_bits as _trace_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL = 1e-6
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _pose():
-    ax = np.array([0.3, -0.5, 0.8])
-    ax /= np.linalg.norm(ax)
-    th = 0.02
-    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
-    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
-    return R.astype(np.float32), np.array([0.01, -0.02, 0.015], np.float32)
-
-
-def _ctx(pkg, params, xf, ff, xm, fm):
-    c = pkg.capi.Context(params=params, device=0, stream=_stream())
-    c.set_fixed(xf, ff)
-    c.set_moving(xm, fm)
-    return c
 
 
 def _oracle(po, pmode, ell, xf, ff, xm, fm, R, T, search):
@@ -57,21 +37,6 @@ def _check(got, want, rtol=RTOL):
     assert np.all(np.abs(got.g - want["g"]) <= rtol * want["sg"]), (got.g, want["g"])
     assert np.all(np.abs(got.H - want["H"]) <= rtol * want["sH"]), np.abs(got.H - want["H"]) / want["sH"]
     assert np.array_equal(got.H, got.H.T)
-
-
-def _case(pkg, desk, name):
-    """(capi mode, oracle mode, params, clouds, ell, oracle search) of a named case."""
-    capi = pkg.capi
-    if name == "desk":
-        xf, ff = desk["xyz0"], pkg.data.cvo_features(desk["rgb0"])
-        xm, fm = desk["xyz1"], pkg.data.cvo_features(desk["rgb1"])
-        return capi.MODE_CVO, 0, (xf, ff, xm, fm), 0.1
-    kind, n = name.split("_")
-    n = int(n)
-    acvo = kind == "acvo"
-    clouds = pkg.data.synthetic_pair(n, n, seed=n % 97 + 3, acvo=acvo)
-    return {"cvo": capi.MODE_CVO, "acvo": capi.MODE_ACVO, "matlab": capi.MODE_MATLAB}[kind], \
-        {"cvo": 0, "acvo": 1, "matlab": 2}[kind], clouds, (0.15 if kind == "matlab" else 0.1)
 
 
 @pytest.mark.parametrize("name", ["cvo_3000", "cvo_10000", "desk", "acvo_10000", "matlab_3000"])
@@ -142,13 +107,6 @@ def test_repeated_calls_are_bit_identical(pkg):
     b = bytes(c.pose_hessian_raw(R, T, 0.1))
     c.close()
     assert a == b
-
-
-def _trace_bits(tr):
-    """A trace as tests/test_gpu_paths.py compares traces bit for bit: the members and the float32 twist and step of every
-    iteration (the float64 sums and the bookkeeping fields of a record depend on which launch path an iteration took --
-    resident runs or not, a matter of timing -- not on the registration)."""
-    return [(t["nnz"], t["step"], tuple(t["omega"]), tuple(t["v"])) for t in tr]
 
 
 @pytest.mark.parametrize("mode_name", ["cvo", "acvo"])

@@ -19,7 +19,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pose_scan_ref as sref  # noqa: E402
-from test_gpu_pose_score import _case, _ctx, _pose, _stream, _trace_bits  # noqa: E402
+from pose_cases import case as _case, ctx as _ctx, pose as _pose, stream as _stream, trace_bits as _trace_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

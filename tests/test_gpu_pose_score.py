@@ -13,46 +13,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pose_score_ref as ref  # noqa: E402
+from pose_cases import case as _case, ctx as _ctx, pose as _pose, stream as _stream, trace_bits as _trace_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I3, Z3 = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _pose():
-    ax = np.array([0.3, -0.5, 0.8])
-    ax /= np.linalg.norm(ax)
-    th = 0.02
-    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
-    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
-    return R.astype(np.float32), np.array([0.01, -0.02, 0.015], np.float32)
-
-
-def _ctx(pkg, params, xf, ff, xm, fm):
-    c = pkg.capi.Context(params=params, device=0, stream=_stream())
-    c.set_fixed(xf, ff)
-    c.set_moving(xm, fm)
-    return c
-
-
-def _case(pkg, desk, name):
-    """(capi mode, oracle mode, clouds, ell) of a named case."""
-    capi = pkg.capi
-    if name == "desk":
-        xf, ff = desk["xyz0"], pkg.data.cvo_features(desk["rgb0"])
-        xm, fm = desk["xyz1"], pkg.data.cvo_features(desk["rgb1"])
-        return capi.MODE_CVO, 0, (xf, ff, xm, fm), 0.1
-    kind, n = name.split("_")
-    n = int(n)
-    clouds = pkg.data.synthetic_pair(n, n, seed=n % 97 + 3, acvo=kind == "acvo")
-    return {"cvo": capi.MODE_CVO, "acvo": capi.MODE_ACVO, "matlab": capi.MODE_MATLAB}[kind], \
-        {"cvo": 0, "acvo": 1, "matlab": 2}[kind], clouds, (0.15 if kind == "matlab" else 0.1)
 
 
 def _check(got, want):
@@ -205,11 +171,6 @@ def test_many_equals_lone_calls(pkg):
     finally:
         for c in ctxs:
             c.close()
-
-
-def _trace_bits(tr):
-    """A trace as tests/test_gpu_pose_hessian.py compares them: members, float32 twist and step of every iteration."""
-    return [(t["nnz"], t["step"], tuple(t["omega"]), tuple(t["v"])) for t in tr]
 
 
 @pytest.mark.parametrize("mode_name", ["cvo", "acvo"])
