@@ -912,6 +912,7 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     else if (is("alone_max")) *value = o.alone_max;
     // read-only counters
     else if (is("run_timeouts")) *value = (double)ctx->run_timeouts;
+    else if (is("list_grows")) *value = (double)ctx->list_grows;
     else if (is("run_aborts")) *value = (double)ctx->run_aborts;
     else if (is("no_run_backoff")) *value = ctx->no_run_backoff;
     else return CVO_HIP_ERR_INVALID;

@@ -553,6 +553,33 @@ CVO_HD void compute_filter_bounds(DevHead *s, bool identity)
     s->tauf[LIST_YY] = (tau + u16 * syy) * 1.000001f;
 }
 
+// The bounding-sphere cull of k_filter: can a point of sphere a be within `reach` of a point of sphere b?  (x, y, z) = the
+// centre of a 64-point Morton run (k_cloud_seg), moved by apply_tf where the run's cloud is, w = its radius.  The factors
+// carry the relative rounding of the test's own arithmetic (a few u of d and of the radii) and |Rt|_2 <= 1 + 1e-5; what
+// apply_tf's rounding does to the centre and to the points is absolute, grows with the coordinates, and is part of `reach`
+// (cull_slack below).  Host-and-device: tests/cpp/cull_host.cpp drives it on the CPU.
+CVO_HD bool spheres_near(const float4 sa, const float4 sb, float reach)
+{
+    const float ex = sa.x - sb.x, ey = sa.y - sb.y, ez = sa.z - sb.z;
+    const float d2 = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+    const float rr = (sa.w + sb.w + reach) * 1.00001f + 1e-5f;
+    return d2 * 0.99999f <= rr * rr;
+}
+// What `reach` holds on top of sqrt(tauf) ("The cull's slack").  With u = 2^-24, W = the largest
+// |coordinate| of either cloud (<= max|center| + max(xmax, y0max)) and S = 3 max|Rt| W + max|t|: every partial sum of a row
+// of apply_tf is at most S, so its six roundings leave a component within 6 u S and the point within 6 sqrt(3) u S < 11 u S
+// of its exact image Rt p + t.  The run's centre is moved by the same expressions and rounds on its own: the image of a
+// point of the run lies within r |Rt|_2 + 22 u S of the COMPUTED centre, not within r.  A member's computed d2 < tau puts
+// the computed rows within sqrt(tau) (1 + 4 u) < sqrt(tauf) of each other.  Needed: 22 u S per transformed side, 44 u S when
+// both are (the yy list); taken: 64 u S', S' >= S made of sums in place of the maxima (few operands, all of them in the
+// filter's registers already) and max|Rt| <= 1.0001 for the rotation spheres_near takes Rt for.  4e-5 m for the synthetic
+// pairs 1.5 m from the origin, 3 cm at 1500 m.
+CVO_HD float cull_slack(const float *t, const float cx, const float cy, const float cz, const float xmax, const float y0max)
+{
+    const float W = ((fabsf(cx) + fabsf(cy)) + fabsf(cz)) + (xmax + y0max);
+    return (64.0f / 16777216.0f) * (3.0003f * W + ((fabsf(t[0]) + fabsf(t[1])) + fabsf(t[2])));
+}
+
 // Tile-list re-use.  k_filter is conservative and membership in A is decided by
 // the exact test of k_process, so a list stays valid for as long as it is a
 // superset of {pairs with d2 < tau}.  A list is therefore built for the radius
@@ -892,7 +919,7 @@ struct KeptView {
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // Eigen: transform.linear()*p + translation, coefficient order, no FMA
-__device__ __forceinline__ float4 apply_tf(const float *Rt, const float *t, const float4 p)
+CVO_HD float4 apply_tf(const float *Rt, const float *t, const float4 p)
 {
     float4 o;
     o.x = ((Rt[0] * p.x + Rt[1] * p.y) + Rt[2] * p.z) + t[0];

@@ -300,6 +300,7 @@ struct Engine {
                         const double grown = std::min(
                             4.0e9, std::max((double)worst * NSUB, (double)c->lists[l].cap) * 1.5 + 1024.0);
                         rc = ensure_list(c, l, 0, 0, grown);
+                        ++c->list_grows;
                     }
                 for (int qq = 0; qq < 3 && !rc; ++qq) {   // the two buffers of a list share one capacity
                     const int la = qq == 0 ? LIST_XY : (qq == 1 ? LIST_XX : LIST_YY), lb = qq == 0 ? LIST_XYB : (qq == 1 ? LIST_XXB : LIST_YYB);

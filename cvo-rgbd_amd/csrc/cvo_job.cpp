@@ -497,6 +497,7 @@ int job_pump(AlignJob &j, bool block)
             const double grown =
                 std::min(4.0e9, std::max((double)worst * NSUB, (double)ctx->lists[l].cap) * 1.5 + 1024.0);
             rc = ensure_list(ctx, l, 0, 0, grown);
+            ++ctx->list_grows;
         }
     for (int q = 0; q < 3 && !rc; ++q) {   // the two buffers of a list share one capacity
         const int la = q == 0 ? LIST_XY : (q == 1 ? LIST_XX : LIST_YY), lb = q == 0 ? LIST_XYB : (q == 1 ? LIST_XXB : LIST_YYB);

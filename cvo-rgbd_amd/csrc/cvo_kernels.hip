@@ -64,16 +64,6 @@ size_t filter_smem_bytes(int jt)
            FILTER_KMAX * 4 * 4;
 }
 
-// Can a point of sphere a be within sqrt(tauf) of a point of sphere b?
-// Conservative against float32 rounding (relative and absolute slack).
-__device__ __forceinline__ bool spheres_near(const float4 sa, const float4 sb, float reach)
-{
-    const float ex = sa.x - sb.x, ey = sa.y - sb.y, ez = sa.z - sb.z;
-    const float d2 = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-    const float rr = (sa.w + sb.w + reach) * 1.00001f + 1e-5f;
-    return d2 * 0.99999f <= rr * rr;
-}
-
 // Append the wave's `n` staged tile entries (n <= TILE_STAGE = 128) to the 32 sub-lists of its row
 // region, DEALT in runs of L = 1 << DEAL_SHIFT = 4 entries (64-byte stores; runs of 1, 2, 4 measured alike,
 // whole flushes 3 % slower: profiles/r02_ab.txt): run c (entries cL .. cL+L-1) goes to
@@ -189,7 +179,8 @@ __device__ __forceinline__ void filter_body(const FilterArgs &a, const unsigned 
     // items that hold nothing cost no round trip of their own.
     const int k_all = (nitems - slot + nslot - 1) / nslot;
     const int ncf = a.jt / SEG;   // column segments of a full item
-    const float reach = sqrtf(tauf);
+    // (spheres_near and cull_slack: cvo_device.h)
+    const float reach = sqrtf(tauf) + cull_slack(tt, cx, cy, cz, hd->xmax, hd->y0max);
     for (int k0 = 0; k0 < k_all; k0 += FILTER_KMAX) {
     const int kn = min(FILTER_KMAX, k_all - k0);
     for (int q = tid; q < FILTER_KMAX * 4; q += BLOCK) nearmask[q] = 0u;

@@ -685,6 +685,7 @@ int check_overflow_and_grow(cvo_hip_ctx *ctx, bool *redo)
             const double grown = std::min(4.0e9, need * 1.25 + 1024.0);
             int rc = ensure_list(ctx, l, 0, 0, grown);
             if (rc) return rc;
+            ++ctx->list_grows;
             *redo = true;
         }
     return CVO_HIP_OK;

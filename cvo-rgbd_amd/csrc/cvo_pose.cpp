@@ -141,6 +141,7 @@ int score_pass_grow(cvo_hip_ctx *ctx, int p, const char *who, bool *redo)
         int rc = ensure_list(ctx, l, 0, 0, std::min(4.0e9, 2.0 * (double)cap + 1024.0));
         if (rc) return rc;
         if (ctx->lists[l].cap <= cap) return fail(ctx, CVO_HIP_ERR_NOMEM, (std::string(who) + ": a list cannot grow further").c_str());
+        ++ctx->list_grows;
         *redo = true;
     }
     return CVO_HIP_OK;

@@ -548,6 +548,9 @@ int cvo_hip_set_graph_capture(cvo_hip_ctx *ctx, int enable);
  *   "run_timeout_ms"     how long an exchange inside a resident run waits for a block of its launch (default 1000).  A run that
  *                        times out costs that wait, not the frame: the pair is registered again without runs, and the context
  *                        goes without runs for its next 64 registrations ("run_timeouts" counts them, read-only)
+ *   "list_grows"         read-only: how many times a tile or kept list of this context overflowed in a pass and was grown (the
+ *                        loop parks, the host grows the list and resumes; the low-level entry points and the pose queries redo
+ *                        their launches), since the context was created
  * and the test switches of tests/ ("head_mode", "merged_launches", "async_builds", "candidate_records", "kept_pack",
  * "list_init", "list_margin", "record_narrow", "list_stale_max", "final_mirror", "one_launch_hand_over", "small_calls_alone", "fused_groups", "engines",
  * "run_candidates_max", "run_fault", "sync_upload", "no_graph", "twist_on_shared_gpu", "comm_debug", "engine_debug"; the

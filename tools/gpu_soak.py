@@ -4,10 +4,12 @@
 one-by-one and through align_many.  usage: gpu_soak.py [n_cases] [max_points]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 import torch
 import __graft_entry__ as ge
 from oracle import pyoracle as po
+import hostile_cases as hc   # the degenerate kinds below: ONE definition, shared with tests/test_gpu_hostile.py
 
 pkg = ge.load_package()
 capi = pkg.capi
@@ -33,29 +35,16 @@ for case in range(n_cases):
     K = np.array([[0, -ang[2], ang[1]], [ang[2], 0, -ang[0]], [-ang[1], ang[0], 0]])
     R = np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th**2 * K @ K
     xm = (xm.astype(np.float64) @ R.T + rng.normal(size=3) * 0.004).astype(np.float32)
-    if os.environ.get("SOAK_DEGENERATE"):   # hostile inputs, one kind per case
-        kind = case % 8
+    if os.environ.get("SOAK_DEGENERATE"):   # hostile inputs, one kind per case: tests/hostile_cases.py (what each is for is said there)
+        kind = case % 12
         if kind == 0:      # identical clouds: converged at once
             xm, fm = xf.copy(), ff.copy()
-        elif kind == 1:    # a handful of points
-            k1, k2 = int(rng.integers(1, 20)), int(rng.integers(1, 20))
-            xf, ff, xm, fm = xf[:k1], ff[:k1], xm[:k2], fm[:k2]
-        elif kind == 2:    # a large motion: lists die young, stall slots
-            xm = (xm.astype(np.float64) + np.array([0.05, -0.04, 0.06])).astype(np.float32)
-        elif kind == 3:    # nothing in reach: empty A
+        elif kind == 1:    # nothing in reach: empty A
             xm = (xm.astype(np.float64) + 50.0).astype(np.float32)
-        elif kind == 4:    # everything in one small blob: dense tiles, overflowing lists
-            xf = (xf.astype(np.float64) * 0.08 + np.array([0.0, 0.0, 1.2])).astype(np.float32)
-            xm = (xm.astype(np.float64) * 0.08 + np.array([0.0, 0.0, 1.2])).astype(np.float32)
-        elif kind == 5:    # far from the origin: the rounding slack of the MFMA filter
-            off = np.array([80.0, -120.0, 60.0])
-            xf = (xf.astype(np.float64) + off).astype(np.float32)
-            xm = (xm.astype(np.float64) + off).astype(np.float32)
-        elif kind == 6:    # duplicated points
-            xf = np.concatenate([xf, xf[: len(xf) // 3]]); ff = np.concatenate([ff, ff[: len(ff) // 3]])
-            xm = np.concatenate([xm, xm[: len(xm) // 2]]); fm = np.concatenate([fm, fm[: len(fm) // 2]])
-        else:              # very unequal sizes
-            xm, fm = xm[: max(8, len(xm) // 40)], fm[: max(8, len(fm) // 40)]
+        else:              # the named kinds of tests/hostile_cases.py, applied to this case's random pair
+            name = (list(hc.FAR) + ["blob", "dup", "plane", "point", "unequal", "jump"])[kind - 2] if kind < 11 else \
+                "tiny_%dx%d" % (int(rng.integers(1, 20)), int(rng.integers(1, 20)))
+            xf, ff, xm, fm = hc.shape(name, xf, ff, xm, fm)
         n, m = len(xf), len(xm)
     mode = po.MODE_ACVO if acvo else po.MODE_CVO
     p = po.default_params(mode)
