@@ -5,9 +5,9 @@
 // ordering is this back end's data layout)
 //
 // Results are defined by the arithmetic below, not by the device: every step is either
-// exact (min / max, integer keys, a stable sort) or a fixed float sequence; a host
-// implementation of the same steps (the first version of upload_cloud) gave the same
-// bytes.
+// exact (min / max, integer keys, a stable sort) or a fixed float sequence (the float64
+// sqrt of the radius correctly rounded).  tests/cloud_layout_ref.py is the same steps in
+// numpy; tests/test_gpu_cloud_layout.py compares the device arrays with it by bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -197,3 +197,155 @@ def test_matlab_prep_oracle_known_answers():
     assert gc.tolist() == [[11, 21, 31], [0, 101, 128], [200, 0, 0]]      # floor(mean + 0.5): 10.5 -> 11, 100.5 -> 101, 127.5 -> 128
     e = mp.grid_average(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8))
     assert e[0].shape == (0, 3) and e[1].shape == (0, 3)
+
+
+def _prep_cases():
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import matlab_prep_cases
+    return matlab_prep_cases
+
+
+def _f32_range(p):
+    """sqrt((x*x + y*y) + z*z), every step rounded to float32, one point at a time."""
+    import numpy as np
+    f = np.float32
+    x, y, z = (f(v) for v in p)
+    return f(np.sqrt(f(f(f(x * x) + f(y * y)) + f(z * z))))
+
+
+def test_matlab_prep_oracle_on_non_finite_points_and_range_limits():
+    """The edge cases of tests/matlab_prep_cases.py that tests/test_gpu_matlab_edges.py runs on the device, on the
+    oracle, with their answers written down: points with a NaN / Inf coordinate never come out and do not move the
+    box; a range of exactly max_range or min_range is kept, one float32 step beyond is dropped."""
+    import numpy as np
+    from oracle import matlab_prep as mp
+    pc = _prep_cases()
+    bad = sorted({r for r, _, _ in pc.NONFINITE_ROWS})
+    assert len(bad) == 7
+    for label, xyz, rgb, rmax, rmin, grid in pc.nonfinite():
+        good = np.delete(np.arange(500), bad)
+        assert np.isfinite(xyz[good]).all() and not np.isfinite(xyz[bad]).all(1).any()
+        with np.errstate(invalid="ignore", over="ignore"):
+            got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+            # the oracle's own steps drop them too: handing it all 500 points changes nothing
+            f = mp.pc_range_filter(xyz, rgb, rmax, rmin) if rmax > 0 else (xyz, rgb)
+            if grid > 0:
+                whole = mp.grid_average(f[0], f[1], grid)
+                assert np.array_equal(whole[0], got[0]) and np.array_equal(whole[1], got[1]), label
+        assert np.isfinite(got[0]).all(), label
+        r = np.array([_f32_range(p) for p in xyz[good]])
+        kept = good[(r <= np.float32(rmax)) & (r >= np.float32(rmin))] if rmax > 0 else good
+        if grid > 0:   # the box is the finite kept points' box: every output lies inside it
+            assert np.all(got[0] >= xyz[kept].min(0)) and np.all(got[0] <= xyz[kept].max(0)), label
+            assert 0 < len(got[0]) <= len(kept)
+        else:
+            assert np.array_equal(got[0], xyz[kept]) and np.array_equal(got[1], rgb[kept]), label
+    xyz, rgb = pc.range_points()
+    r = [_f32_range(p) for p in xyz]
+    assert [float(v) for v in r[:6]] == [5.0, 5.0, 5.0, 0.75, 0.75, 0.75] and r[7] == np.float32(5.0) and len(r) == 14
+    assert np.linalg.norm(xyz[7].astype(np.float64)) > 5.0      # (kept by the float32 range, which rounds to 5)
+    assert all(v > np.float32(5.0) for v in r[8:11]) and all(v < np.float32(0.75) for v in r[11:14])
+    answers = {"limits kept": list(pc.RANGE_KEPT), "min above max": [], "max_range 0, min_range 5": list(range(14)),
+               "max_range -1, min_range 5": list(range(14))}
+    for label, x, c, rmax, rmin, grid in pc.range_limits():
+        got = pc.expected(mp, x, c, rmax, rmin, grid)
+        assert np.array_equal(got[0], xyz[answers[label]]) and np.array_equal(got[1], rgb[answers[label]]), label
+
+
+def test_matlab_prep_oracle_sums_the_range_as_x_y_then_z():
+    """32 points whose float32 range differs between (x*x + y*y) + z*z and x*x + (y*y + z*z), found by a seeded search:
+    with max_range = min_range = the range in the first order, the oracle keeps the point (and the other order would not)."""
+    import numpy as np
+    from oracle import matlab_prep as mp
+    pc = _prep_cases()
+    xyz, r_spec, r_other = pc.sum_order_points()
+    assert xyz.shape == (32, 3) and np.all(r_spec != r_other)
+    assert (r_other > r_spec).any() and (r_other < r_spec).any()
+    for i, (label, x, c, rmax, rmin, grid) in enumerate(pc.sum_order()):
+        assert _f32_range(xyz[i]) == r_spec[i] == np.float32(rmax) == np.float32(rmin)
+        got = pc.expected(mp, x, c, rmax, rmin, grid)
+        want = [j for j in range(32) if _f32_range(xyz[j]) == r_spec[i]]
+        assert i in want and np.array_equal(got[0], xyz[want]) and np.array_equal(got[1], c[want]), label
+
+
+def test_matlab_prep_oracle_on_voxel_faces_and_wide_keys():
+    """Points on voxel faces and one float32 step either side of them: with grid = 1/16 the coordinates origin + k / 16 are
+    exact, so the voxel of a point is k, or k - 1 one step below a face -- near the origin, 1.5 km away and with negative
+    coordinates.  3000 points in 3001^3 and in 300001^3 voxels: every point its own voxel, in lexicographic voxel order."""
+    import numpy as np
+    from oracle import matlab_prep as mp
+    pc = _prep_cases()
+    for label, xyz, rgb, rmax, rmin, grid in pc.voxel_faces():
+        got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+        name = label.split()[1]
+        x, k, nudge = pc.face_points(pc.FACE_ORIGINS[name], grid)
+        assert np.array_equal(x, xyz)
+        if grid == 0.0625:
+            assert np.array_equal((pc.FACE_ORIGINS[name] + k * grid).astype(np.float32).astype(np.float64), pc.FACE_ORIGINS[name] + k * grid)
+            assert np.array_equal(xyz.min(0).astype(np.float64), pc.FACE_ORIGINS[name])   # the anchor
+            vox = np.where(nudge < 0, k - 1, k)
+            assert vox.min() == 0
+            cells, inverse, count = np.unique(vox, axis=0, return_inverse=True, return_counts=True)   # lexicographic
+            assert len(got[0]) == len(cells), label
+            inverse = inverse.ravel()
+            mean = np.stack([np.bincount(inverse, weights=xyz[:, a].astype(np.float64)) / count for a in range(3)], 1)
+            assert np.array_equal(got[0], mean.astype(np.float32)), label
+        else:   # 0.05 is not a float32 step: the voxels by the definition, floor((x - min) / grid) in float64, point by point
+            import math
+            lo = [float(v) for v in xyz.min(0)]
+            cells = {tuple(math.floor((float(p[a]) - lo[a]) / grid) for a in range(3)) for p in xyz}
+            assert len(got[0]) == len(cells) > 500, label
+    for label, xyz, rgb, rmax, rmin, grid in pc.wide_keys():
+        got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+        x64 = xyz.astype(np.float64)
+        cell = np.floor((x64 - x64.min(0)) / grid).astype(np.int64)
+        span = cell.max(0) + 1
+        assert int(span[0]) * int(span[1]) * int(span[2]) > (2 ** 32 if grid == 1e-3 else 2 ** 53)
+        assert int(span[0]) * int(span[1]) * int(span[2]) < 2 ** 62
+        assert len(np.unique(cell, axis=0)) == 3000
+        by_cell = sorted(range(3000), key=lambda i: tuple(cell[i]))   # Python integers: no key to overflow
+        assert np.array_equal(got[0], xyz[by_cell]) and np.array_equal(got[1], rgb[by_cell]), label
+
+
+def test_matlab_prep_oracle_on_heavy_voxels_and_switches():
+    """70 000 points in one voxel whose colour means are 100.5, 254.5 and 0.49 -> 101, 255, 0 (floor(mean + 0.5)), beside
+    300 voxels of one point; one voxel for a whole cloud; one point; grid_size 0, negative and NaN switch the
+    downsampling off; no points in, no points out."""
+    import numpy as np
+    from oracle import matlab_prep as mp
+    pc = _prep_cases()
+    heavy, one_voxel, one_point, one_kept = pc.heavy_voxels()
+    _, xyz, rgb, rmax, rmin, grid = heavy
+    got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+    assert len(got[0]) == 301 and tuple(got[1][0]) == pc.HEAVY_COLOUR
+    inside = np.all(xyz < 1.0, axis=1)
+    assert inside.sum() == pc.HEAVY_N and np.allclose(got[0][0], xyz[inside].astype(np.float64).mean(0), atol=1e-6)
+    assert rgb[inside].astype(np.float64).mean(0).tolist() == [100.5, 254.5, 0.49]
+    singles = xyz[~inside]
+    by_cell = sorted(range(300), key=lambda i: tuple(np.floor(singles[i].astype(np.float64)).astype(int)))
+    assert np.array_equal(got[0][1:], singles[by_cell]) and np.array_equal(got[1][1:], rgb[~inside][by_cell])
+    _, xyz, rgb, rmax, rmin, grid = one_voxel
+    got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+    assert len(got[0]) == 1 and np.allclose(got[0][0], xyz.astype(np.float64).mean(0), atol=1e-6)
+    assert np.all(np.abs(got[1][0] - rgb.astype(np.float64).mean(0)) <= 0.5)
+    _, xyz, rgb, rmax, rmin, grid = one_point
+    got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+    assert np.array_equal(got[0], xyz) and np.array_equal(got[1], rgb) and rmin <= _f32_range(xyz[0]) <= rmax
+    _, xyz, rgb, rmax, rmin, grid = one_kept
+    got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+    assert np.array_equal(got[0], xyz[17:18]) and np.array_equal(got[1], rgb[17:18])
+    for label, xyz, rgb, rmax, rmin, grid in pc.switches():
+        got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+        if len(xyz) == 0:
+            assert got[0].shape == (0, 3) and got[1].shape == (0, 3)
+            continue
+        r = np.array([_f32_range(p) for p in xyz])
+        kept = (r <= np.float32(rmax)) & (r >= np.float32(rmin))
+        assert 0 < kept.sum() < len(xyz) and np.array_equal(got[0], xyz[kept]) and np.array_equal(got[1], rgb[kept]), label
+    for label, xyz, rgb, rmax, rmin, grid in pc.arena():   # the large and the small call: one output per occupied voxel
+        f = mp.pc_range_filter(xyz, rgb, rmax, rmin)
+        got = pc.expected(mp, xyz, rgb, rmax, rmin, grid)
+        x64 = f[0].astype(np.float64)
+        assert len(got[0]) == len(np.unique(np.floor((x64 - x64.min(0)) / grid).astype(np.int64), axis=0)) > 0, label

@@ -13,7 +13,11 @@ does not grow with the coordinates), the same stream loses members from 600 m on
     offset (300, -500, 200)    23 of 14 497   (0.16 %)
     offset (800, -1200, 600)   83 of 13 564   (0.61 %)
     offset (2000, -3000, 1500) 29 of 14 344   (0.20 %)
-(profiles/r08_ab.txt).  The second test keeps that visible: the stream must stay sharp enough to catch the old bound."""
+(profiles/r08_ab.txt).  The second test keeps that visible: the stream must stay sharp enough to catch the old bound.
+
+The spheres (b) culls with are cull_host.cpp's own restatement of k_cloud_seg (run_sphere).  That the device's spheres are
+those -- centre, radius and padding by bits, and every live row inside its run's sphere -- is pinned by
+tests/test_gpu_cloud_layout.py against tests/cloud_layout_ref.py."""
 import os
 import shutil
 import subprocess
