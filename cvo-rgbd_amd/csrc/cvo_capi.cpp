@@ -913,6 +913,8 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     // read-only counters
     else if (is("run_timeouts")) *value = (double)ctx->run_timeouts;
     else if (is("list_grows")) *value = (double)ctx->list_grows;
+    else if (is("async_builds_named")) *value = (double)ctx->async_stats[0];
+    else if (is("async_stalls")) *value = (double)ctx->async_stats[1];
     else if (is("run_aborts")) *value = (double)ctx->run_aborts;
     else if (is("no_run_backoff")) *value = ctx->no_run_backoff;
     else return CVO_HIP_ERR_INVALID;

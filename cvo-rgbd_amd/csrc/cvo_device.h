@@ -234,7 +234,9 @@ struct alignas(16) DevHead {
                                 // REC_BOUNDED: an expanding pass records only the candidates with d2 < rec_r^2
     float rec_Rt[9], rec_t[3];
     int32_t list_stat[3];       // since align() began: all-pairs xy builds named, narrowings named, re-expansions seen (cvo_hip_get_list_stats)
-    int32_t rec_pad_[3];
+    int32_t async_stat[2];      // ... and of the asynchronous plans: xy builds plan_xy_async named, stall slots (a slot that only builds: no buffer of the
+                                // xy list or of a self list was valid) -- cvo_hip_get_option "async_builds_named", "async_stalls"
+    int32_t rec_pad_;
     // Asynchronous xy builds (DevParams::async_xy): two buffers; FLOW consumes `xy_active`; the
     // k_filter blocks of the launch that READS this state build `xy_target` (-1: none) at the
     // transform recorded for it (xy_Rt / xy_t[target]); `xy_fresh`: the buffer whose build ran in
@@ -580,6 +582,31 @@ CVO_HD float cull_slack(const float *t, const float cx, const float cy, const fl
     return (64.0f / 16777216.0f) * (3.0003f * W + ((fabsf(t[0]) + fabsf(t[1])) + fabsf(t[2])));
 }
 
+// What the re-use bounds below hold on top of sqrt(tau) + travel ("The re-use bounds' slack").  A list or a
+// record is a set of pairs judged by their COMPUTED d2 at the pose of its build; a member is judged by its computed d2 at the current
+// pose; the travel bound speaks of the exact images.  With S as at cull_slack, a computed image lies within 11 u S of the exact one at
+// either pose, so a pair that is a member now, computed distance < sqrt(tau) (1 + 4 u), had at the build a computed distance below
+//     sqrt(tau) (1 + 4 u) + 11 u S + travel + 11 u S'           one point of the pair moved (the xy tile list, the xy record)
+//     sqrt(tau) (1 + 4 u) + 22 u S + 0 + 22 u S0                both points moved at both poses (the yy list; rigid: no travel)
+// (S of the current pose, S0 of the build's) and is in the list if that is at most its radius.  The xx list is never transformed
+// (sides = 0: the old slack alone).  The xy plans take 22 u S' (sides = 1) with cull_slack's S', made of the CURRENT pose's t: it covers
+// the build's pose as well, because the partial sums of apply_tf that matter end in the image itself, which lies within the list's
+// radius of a fixed point, so they stay below 3.0003 W + the radius whatever t is.  The yy list's points need not lie near the fixed
+// cloud and nothing ties the build's t to the current one, so there each pose pays for itself: the need holds 22 u S' of the current
+// pose (sides = 1: two points), and a BUILD widens its own filter bound by the 22 u S' of its pose on top of the radius it records
+// (plan_lists, plan_self_async_one: `wide`).
+// All of it on top of the old 1e-4 (1 + xmax + y0max), which keeps carrying the relative terms: the rounding of the plan's own ~20
+// float32 operations, of d2 and of pose_travel (whose dc cancels metres far from the origin: six roundings of at most
+// u (|dRt c| + |dt|) each, below 1e-5 m at 4 km for a change of 1e-2 rad; tests/cpp/reuse_host.cpp asserts the bound).  1.4e-5 m
+// for the synthetic pairs 1.5 m from the origin, 1 cm at 1500 m, 2.6 cm at 3700 m: there the lists are built that much wider and
+// serve as long as before.  Membership is the exact test's, so the slack changes which pairs are looked at, never a result.
+CVO_HD float reuse_slack(const float *t, const float *c, const float xmax, const float y0max, const float sides)
+{
+    const float W = ((fabsf(c[0]) + fabsf(c[1])) + fabsf(c[2])) + (xmax + y0max);
+    const float S = 3.0003f * W + ((fabsf(t[0]) + fabsf(t[1])) + fabsf(t[2]));
+    return 1.0e-4f * (1.0f + xmax + y0max) + sides * (22.0f / 16777216.0f) * S;
+}
+
 // Tile-list re-use.  k_filter is conservative and membership in A is decided by
 // the exact test of k_process, so a list stays valid for as long as it is a
 // superset of {pairs with d2 < tau}.  A list is therefore built for the radius
@@ -588,9 +615,10 @@ CVO_HD float cull_slack(const float *t, const float cx, const float cy, const fl
 // (triangle inequality; the xx / yy lists of acvo are rigid: only tau matters).
 // The travel of y = Rt y0 + t is bounded by |dRt|_2 max|y0 - c| + |dRt c + dt| with
 // |dRt|_2 = |dRt|_F / sqrt(2) for a difference of rotations.  A list much wider
-// than needed (after ell dropped) is rebuilt as well.  All slack terms are far
-// above the float32 rounding of the coordinates and of d2 (<= ~1e-5 m here) and
-// far below the margin (>= 1 mm at ell_min): decisions change performance only.
+// than needed (after ell dropped) is rebuilt as well.  The slack (reuse_slack) carries
+// the float32 rounding of the coordinates under apply_tf at both poses, which grows with
+// their distance from the origin, and of d2; a list's radius is (1 + margin) times the
+// radius WITH the slack, so the slack never eats the margin: decisions change performance only.
 constexpr float LIST_LOOSE = 1.3f;
 // Narrowing (DevParams::record_narrow; the synchronous xy list of clouds that keep a candidate record).  The record has a
 // radius and a pose of its own, rec_r and [rec_Rt | rec_t], and is re-used while
@@ -626,7 +654,10 @@ CVO_HD float pose_travel(const DevHead *s, const float *Rt0, const float *t0, co
 CVO_HD void plan_lists(DevHead *s, DevHead *bulk, const bool store, const DevParams &p, const float r_now)
 {
     const float ymax = s->y0max;
-    const float slack = 1.0e-4f * (1.0f + s->xmax + ymax);
+    // (yy: both points of a pair are moved at this pose, 22 u S' for the two, and were at the build's, which has widened its own
+    // filter bound by its own 22 u S' -- `wide` below: neither pose's slack needs the other's t)
+    const float slack_xx = reuse_slack(s->t, s->center, s->xmax, ymax, 0.0f), slack_xy = reuse_slack(s->t, s->center, s->xmax, ymax, 1.0f);
+    const float wide_yy = slack_xy - slack_xx;
     const float margin = p.list_margin;
     const bool sync_xy = s->list_ok[LIST_XY] && !p.async_xy;
     const float travel = sync_xy ? pose_travel(s, s->list_Rt, s->list_t, ymax) : 0.0f;
@@ -636,6 +667,7 @@ CVO_HD void plan_lists(DevHead *s, DevHead *bulk, const bool store, const DevPar
                                                     // tau + rounding slack: tauf_build is made from it)
         if (l != LIST_XY && p.async_self) continue; // planned by plan_self_async
         if (l != LIST_XY && p.mode != CVO_HIP_MODE_ACVO) { s->reuse[l] = 1; continue; }   // cvo has no self lists
+        const float slack = l == LIST_XX ? slack_xx : slack_xy;   // (xx: never transformed)
         const float need = (r_now + (l == LIST_XY ? travel : 0.0f)) * 1.0001f + slack;
         const float lr = s->list_r[l];
         const float r0 = r_now * 1.0001f + slack;
@@ -668,8 +700,10 @@ CVO_HD void plan_lists(DevHead *s, DevHead *bulk, const bool store, const DevPar
         s->ck_nblk[l] = 0;   // a new tile list: the candidate list recorded from the old one is void
         s->list_r[l] = rb * 1.000001f;   // rounded up: the list holds at least this radius
         s->list_ok[l] = 1;
-        if (margin > 0.0f)   // tauf of compute_filter_bounds is tau + rounding slack: widen tau
-            s->tauf[l] = (s->list_r[l] * s->list_r[l] + (s->tauf[l] - s->kc.tau)) * 1.000001f;
+        if (margin > 0.0f) {   // tauf of compute_filter_bounds is tau + rounding slack: widen tau
+            const float rw = s->list_r[l] + (l == LIST_YY ? wide_yy : 0.0f);
+            s->tauf[l] = (rw * rw + (s->tauf[l] - s->kc.tau)) * 1.000001f;
+        }
         if (l == LIST_XY) {
             s->rec_r = s->list_r[l];   // the record of a fresh list: the list's radius and pose
             s->narrow = p.record_narrow ? REC_BOUNDED : 0;
@@ -718,7 +752,7 @@ template <int B> CVO_HD float xy_travel(const DevHead *s, const DevHead *rec)
 CVO_HD void plan_xy_async(DevHead *s, DevHead *bulk, const bool store, const DevParams &p, const float r_now, const int fresh,
                           const bool fresh_failed, const int inflight)
 {
-    const float slack = 1.0e-4f * (1.0f + s->xmax + s->y0max);
+    const float slack = reuse_slack(s->t, s->center, s->xmax, s->y0max, 1.0f);
     const float margin = p.list_margin;
     const float r0 = r_now * 1.0001f + slack;   // radius needed with no travel
     if (fresh == 0) s->xy_ok[0] = fresh_failed ? 0 : 1;   // the build that has just ended
@@ -781,7 +815,8 @@ CVO_HD void plan_xy_async(DevHead *s, DevHead *bulk, const bool store, const Dev
 // depend on the transform -- so only ell ages them: a list built for radius
 // (1 + margin) r serves until r_now outgrows it; the next one is built ahead when
 // most of that room is gone or ell has dropped far below.
-template <int L> CVO_HD void plan_self_async_one(DevHead *s, const DevParams &p, const float r0, const float margin,
+// (wide: what a build adds to its radius for the filter's bound alone -- the rounding of apply_tf at the build's pose, yy only)
+template <int L> CVO_HD void plan_self_async_one(DevHead *s, const DevParams &p, const float r0, const float margin, const float wide,
                                                  const int fresh, const bool fresh_failed, const int inflight)
 {
     if (fresh == 0) s->sf_ok[L][0] = fresh_failed ? 0 : 1;
@@ -809,7 +844,7 @@ template <int L> CVO_HD void plan_self_async_one(DevHead *s, const DevParams &p,
         const int tgt = use < 0 ? 0 : 1 - use;
         s->sf_target[L] = tgt;
         const float r = r0 * (1.0f + margin) * 1.000001f;
-        s->sf_tauf_build[L] = (r * r + (s->tauf[LIST_XX + L] - s->kc.tau)) * 1.000001f;
+        s->sf_tauf_build[L] = ((r + wide) * (r + wide) + (s->tauf[LIST_XX + L] - s->kc.tau)) * 1.000001f;
         if (tgt == 0) { s->sf_ok[L][0] = 0; s->sf_ck[L][0] = 0; s->sf_r[L][0] = r; }
         else { s->sf_ok[L][1] = 0; s->sf_ck[L][1] = 0; s->sf_r[L][1] = r; }
     }
@@ -883,11 +918,21 @@ CVO_HD void prepare_iteration(DevHead *s, DevHead *bulk, const bool store, const
         s->r_last = r_now;
     }
     if (p.async_self) {   // (after the xy plan: it may add a stall)
-        const float slack = 1.0e-4f * (1.0f + s->xmax + s->y0max);
-        const float r0 = r_now * 1.0001f + slack;
-        plan_self_async_one<0>(s, p, r0, p.list_margin, b.sf_fresh[0], b.sf_failed[0], b.sf_inflight[0]);
-        plan_self_async_one<1>(s, p, r0, p.list_margin, b.sf_fresh[1], b.sf_failed[1], b.sf_inflight[1]);
+        // (xx: never transformed; yy: both points of a pair moved at this pose, 22 u S', and at the build's, whose own 22 u S' widened
+        // its filter bound -- reuse_slack)
+        const float s_xx = reuse_slack(s->t, s->center, s->xmax, s->y0max, 0.0f), s_yy = reuse_slack(s->t, s->center, s->xmax, s->y0max, 1.0f);
+        plan_self_async_one<0>(s, p, r_now * 1.0001f + s_xx, p.list_margin, 0.0f, b.sf_fresh[0], b.sf_failed[0], b.sf_inflight[0]);
+        plan_self_async_one<1>(s, p, r_now * 1.0001f + s_yy, p.list_margin, s_yy - s_xx, b.sf_fresh[1], b.sf_failed[1], b.sf_inflight[1]);
     }
+}
+
+// What the asynchronous plans have just decided, counted (DevHead::async_stat).  Apart from the plan, on the copy of the head the
+// caller stores to: in the post kernels the plan runs on registers, and two more words carried through it cost the resident runs
+// vector registers they do not have (profiles/r09_ab.txt 2).
+CVO_HD void count_async_plan(DevHead *dst, const DevHead *planned, const DevParams &p)
+{
+    if (p.async_xy && planned->xy_target >= 0) dst->async_stat[0] += 1;
+    if ((p.async_xy || p.async_self) && planned->stall) dst->async_stat[1] += 1;
 }
 
 size_t filter_smem_bytes(int jt);

@@ -293,6 +293,7 @@ struct cvo_hip_ctx {
     long long tail_handovers = 0;        // times this context's registration left an engine for runs of its own ("tail_handovers")
     long long run_aborts = 0;            // resident runs of this context that gave up at their entry hand-shake ("run_aborts")
     int list_stats[3] = {0, 0, 0};       // the last registration's all-pairs xy builds, narrowings, re-expansions (cvo_hip_get_list_stats)
+    int async_stats[2] = {0, 0};         // ... and the asynchronous plans' xy builds named and stall slots (cvo_hip_get_option "async_builds_named", "async_stalls")
     long long list_grows = 0;            // tile / kept lists of this context grown after a pass overflowed one (cvo_hip_get_option "list_grows")
     long long run_timeouts = 0;          // resident runs of this context that gave up on an exchange (cvo_hip_get_option "run_timeouts")
     int device = 0;

@@ -1999,6 +1999,7 @@ __device__ __forceinline__ void head_plan(DevHead *lds, const PostStepArgs &a, c
             }
             lds->done = done;
             if (HM != HM_CLASSIC) lds->pending = pending;
+            count_async_plan(lds, lds, p);   // (what has just been stored)
         }
     }
 }
@@ -2234,6 +2235,7 @@ __global__ void k_prepare(DevState *st, const DevParams prm, uint32_t *build_mas
         st->pending = 0;
         st->mail_snap = st->mail_seq;
         prepare_iteration(st, st, true, prm, plan_builds_none());
+        count_async_plan(st, st, prm);
     }
 }
 
@@ -3823,7 +3825,7 @@ __device__ __forceinline__ void run_body(const Slot *__restrict__ tab, const int
                 if ((s_st.xy_active ? 1 : 0) != act_cur) {
                     // the plan has changed lists; the solvers hold the old one's candidates: this slot is the run's last.  Its passes stand if
                     // the old list still holds every pair for the slot's transform (plan_xy_async's own test), else they are void
-                    const float r_now = sqrtf(s_st.kc.tau), slack = 1.0e-4f * (1.0f + s_st.xmax + s_st.y0max);
+                    const float r_now = sqrtf(s_st.kc.tau), slack = reuse_slack(s_st.t, s_st.center, s_st.xmax, s_st.y0max, 1.0f);
                     const float need = (r_now + (act_cur ? xy_travel<1>(&s_st, &s_st) : xy_travel<0>(&s_st, &s_st))) * 1.0001f + slack;
                     const bool held = (act_cur ? s_st.xy_ok[1] : s_st.xy_ok[0]) != 0 && need <= (act_cur ? s_st.xy_r[1] : s_st.xy_r[0]);
                     // (... and the run goes on where the new record fits the solvers it has: every block loads its candidates anew)

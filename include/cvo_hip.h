@@ -551,6 +551,9 @@ int cvo_hip_set_graph_capture(cvo_hip_ctx *ctx, int enable);
  *   "list_grows"         read-only: how many times a tile or kept list of this context overflowed in a pass and was grown (the
  *                        loop parks, the host grows the list and resumes; the low-level entry points and the pose queries redo
  *                        their launches), since the context was created
+ *   "async_builds_named", "async_stalls"   read-only, of the context's last registration: the builds of the xy list the asynchronous
+ *                        plan named and the slots that only built (no valid buffer), counted on the device since the registration began --
+ *                        what cvo_hip_get_list_stats counts for the synchronous plan
  * and the test switches of tests/ ("head_mode", "merged_launches", "async_builds", "candidate_records", "kept_pack",
  * "list_init", "list_margin", "record_narrow", "list_stale_max", "final_mirror", "one_launch_hand_over", "small_calls_alone", "fused_groups", "engines",
  * "run_candidates_max", "run_fault", "sync_upload", "no_graph", "twist_on_shared_gpu", "comm_debug", "engine_debug"; the

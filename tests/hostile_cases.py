@@ -6,6 +6,9 @@ A).  Shared by tests/test_hostile_cpu.py, tests/test_gpu_hostile.py and tools/gp
 
     far150 / far600 / far1500   both clouds + (80, -120, 60) / (300, -500, 200) / (800, -1200, 600): coordinates whose ulp
                                 (8e-6 .. 1.2e-4 m) is what apply_tf's rounding costs the cull's spheres and the filter
+    far3700                     both clouds + (2000, -3000, 1500): ulp 2.4e-4 m.  Not in NAMES (which multiplies every hostile test):
+                                reached through FAR_REUSE by the registrations that re-use lists far out (tests/test_reuse_cpu.py,
+                                tests/test_gpu_reuse_far.py), 40 iterations each with the break tests off (long_params)
     blob                        both x 0.08 + (0, 0, 1.2): everything within reach of everything -- dense tiles, 700 000 members;
                                 with the lists started small (test switch "list_init") they overflow and grow
     dup                         the first third of fixed and the first half of moving once more: ties in `best`, equal keys
@@ -20,6 +23,9 @@ import numpy as np
 
 BASE = (1500, 1300, 21)
 FAR = {"far150": (80.0, -120.0, 60.0), "far600": (300.0, -500.0, 200.0), "far1500": (800.0, -1200.0, 600.0)}
+FAR_REUSE = {"far3700": (2000.0, -3000.0, 1500.0)}
+REUSE_NAMES = tuple(FAR) + tuple(FAR_REUSE)   # the registrations kept running while they re-use lists
+REUSE_ITERATIONS = 40
 EDGE_SIZES = (63, 64, 65, 255, 256, 257)
 # every size once as n and once as m, a boundary of one kind against a boundary of the other, and four pairs at one boundary
 # on both sides -- 10 of the 36 pairs of the product: every pair costs six primitive tests, two scans and two registrations
@@ -52,8 +58,9 @@ def clouds(data, name, acvo=False):
 
 def shape(name, xf, ff, xm, fm):
     """The named case made of any pair of clouds (tools/gpu_soak.py applies the kinds to random pairs)."""
-    if name in FAR:
-        xf, xm = _shift(xf, FAR[name]), _shift(xm, FAR[name])
+    if name in FAR or name in FAR_REUSE:
+        off = FAR[name] if name in FAR else FAR_REUSE[name]
+        xf, xm = _shift(xf, off), _shift(xm, off)
     elif name == "blob":
         xf, xm = _shift(xf, (0.0, 0.0, 1.2), 0.08), _shift(xm, (0.0, 0.0, 1.2), 0.08)
     elif name == "dup":
@@ -140,3 +147,30 @@ def cull_trial(rng, offset, gl, gh, theta_max, tau):
     R = rot(rng.normal(size=3), theta_max * 10.0 ** rng.uniform(-1.0, 0.0))
     T = rng.normal(0.0, 0.02, 3)
     return X.astype(np.float32), (Y @ R.T + T).astype(np.float32), R.astype(np.float32), T.astype(np.float32)
+
+
+# ---- registrations that keep running (tests/test_reuse_cpu.py, tests/test_gpu_reuse_far.py)
+def long_params(p):
+    """The parameters (the library's or the oracle's) with both break tests off and REUSE_ITERATIONS iterations: from the identity
+    the far* cases otherwise stop after 1 - 7 iterations, before any list is re-used.  cvo then walks its whole length-scale
+    schedule, 0.15 -> 0.03; acvo runs from 0.10 down to ell_min."""
+    p.eps = np.float32(0.0)
+    p.eps_2 = np.float32(0.0)
+    p.max_iter = REUSE_ITERATIONS
+    return p
+
+
+_LONG_ALIGN = {}
+
+
+def oracle_long_align(po, data, name, acvo, search=None):
+    """(iterations, trace, state bytes) of the oracle's registration of a REUSE_NAMES case under long_params; computed once per
+    (case, mode, search) and shared."""
+    search = po.SEARCH_GRID if search is None else search
+    key = (name, acvo, search)
+    if key not in _LONG_ALIGN:
+        p = long_params(po.default_params(po.MODE_ACVO if acvo else po.MODE_CVO))
+        st = po.init_state(p)
+        n_or, tr = po.align(p, st, *clouds(data, name, acvo), search=search, trace_cap=REUSE_ITERATIONS)
+        _LONG_ALIGN[key] = (n_or, tr, bytes(st))
+    return _LONG_ALIGN[key]
