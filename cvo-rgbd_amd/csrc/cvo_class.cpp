@@ -58,7 +58,7 @@ void Affine3f::quaternion(float q[4]) const
 
 registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
-      fe_points_(0), device_(device)
+      fe_points_(0), device_(device), camera_(), have_camera_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -80,10 +80,17 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
     if (!rgb.data || !dep.data || rgb.rows != dep.rows || rgb.cols != dep.cols)
         throw std::runtime_error("set_pcd(): colour and depth image must have the same size");
     if (!fe_) {
-        const int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
+        int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
         if (rc != CVO_HIP_OK) throw std::runtime_error(std::string("cvo_fe_create: ") + cvo_hip_error_string(rc));
         fe_w_ = rgb.cols; fe_h_ = rgb.rows;
         cvo_fe_set_device_output(fe_, 1);
+        if (have_camera_ && (rc = cvo_fe_set_camera(fe_, &camera_)) != CVO_HIP_OK) {
+            // (no front end without its model: the next image tries again instead of falling back to the table)
+            const std::string why = cvo_fe_last_error(fe_);
+            cvo_fe_destroy(fe_);
+            fe_ = nullptr;
+            throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" + why + ")");
+        }
     }
     if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
         throw std::runtime_error("set_pcd(): the image size changed within a sequence");
@@ -107,6 +114,33 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
           "cvo_hip_set_moving_device");
     have_moving_ = true;
     std::cout << "num moving: " << fe_points_ << std::endl;   // ref src/cvo.cpp:343-347
+}
+
+void registration::set_camera(const cvo_fe_camera_model &model)
+{
+    // (the host-only entry refuses what cvo_fe_set_camera refuses: the answer does not wait for the first image)
+    int32_t qu = 0, qv = 0;
+    if (cvo_fe_rectify_map(&model, 1, 1, &qu, &qv) != CVO_HIP_OK)
+        throw std::runtime_error("set_camera(): members must be finite and fx, fy, depth_scale positive");
+    if (fe_) {
+        const int rc = cvo_fe_set_camera(fe_, &model);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    }
+    camera_ = model;
+    have_camera_ = true;
+}
+
+void registration::clear_camera()
+{
+    if (fe_) {
+        const int rc = cvo_fe_set_camera(fe_, nullptr);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    }
+    have_camera_ = false;
 }
 
 void registration::set_pcd(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,

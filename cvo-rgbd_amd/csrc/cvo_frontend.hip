@@ -95,6 +95,67 @@ __device__ __forceinline__ int block_base(const int *cnt, int b)
     return s;
 }
 
+// The first stage of a frame whose camera has a lens distortion: both images resampled through
+// the context's map (the rectification contract of include/cvo_frontend.h; the map itself is
+// cvo_fe_rectify_map's, made on the host once per model).  Colour: bilinear at 1/32 pixel in
+// integers over four taps with replicated borders; depth: the nearest sample, 0 outside the
+// image.  A thread owns four consecutive output pixels: two 16-byte loads of the map, three
+// dword stores of colour and one 8-byte store of depth, so that a wave writes whole lines
+// instead of single bytes; the taps are gathers (neighbouring pixels share cache lines: the
+// map is smooth).  The last, partial group of an image whose size is no multiple of four goes
+// pixel by pixel.  No tap leaves the images whatever the map holds: every coordinate is
+// clamped or tested here.
+__device__ __forceinline__ void fe_rectify_pixel(const uint8_t *src, const uint16_t *dsrc, int w, int h, int qu, int qv,
+                                                 int out[3], uint16_t *dout)
+{
+    const int x0 = qu >> 5, y0 = qv >> 5;   // floor: arithmetic shift
+    const int ax = qu & 31, ay = qv & 31;
+    const int xa = min(max(x0, 0), w - 1), xb = min(max(x0 + 1, 0), w - 1);
+    const int ya = min(max(y0, 0), h - 1), yb = min(max(y0 + 1, 0), h - 1);
+    const uint8_t *p00 = src + 3 * ((size_t)ya * w + xa), *p01 = src + 3 * ((size_t)ya * w + xb);
+    const uint8_t *p10 = src + 3 * ((size_t)yb * w + xa), *p11 = src + 3 * ((size_t)yb * w + xb);
+    const int w00 = (32 - ax) * (32 - ay), w01 = ax * (32 - ay), w10 = (32 - ax) * ay, w11 = ax * ay;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        out[c] = (w00 * p00[c] + w01 * p01[c] + w10 * p10[c] + w11 * p11[c] + 512) >> 10;
+    const int xn = (qu + 16) >> 5, yn = (qv + 16) >> 5;
+    *dout = (xn >= 0 && xn < w && yn >= 0 && yn < h) ? dsrc[(size_t)yn * w + xn] : (uint16_t)0;
+}
+
+__global__ void __launch_bounds__(FE_BLOCK) k_fe_rectify(const uint8_t *src, const uint16_t *dsrc, const int32_t *qu,
+                                                         const int32_t *qv, int w, int h, uint8_t *dst, uint16_t *ddst)
+{
+    const int np = w * h;
+    const int i0 = 4 * (blockIdx.x * FE_BLOCK + threadIdx.x);
+    if (i0 >= np) return;
+    if (i0 + 4 <= np) {
+        const int4 u4 = *reinterpret_cast<const int4 *>(qu + i0), v4 = *reinterpret_cast<const int4 *>(qv + i0);
+        const int us[4] = {u4.x, u4.y, u4.z, u4.w}, vs[4] = {v4.x, v4.y, v4.z, v4.w};
+        uint32_t b[12];
+        uint16_t d[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int c[3];
+            fe_rectify_pixel(src, dsrc, w, h, us[q], vs[q], c, &d[q]);
+            b[3 * q] = (uint32_t)c[0]; b[3 * q + 1] = (uint32_t)c[1]; b[3 * q + 2] = (uint32_t)c[2];
+        }
+        uint32_t *o = reinterpret_cast<uint32_t *>(dst + 3 * (size_t)i0);   // 12 * (i0 / 4): dword aligned
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o[k] = b[4 * k] | (b[4 * k + 1] << 8) | (b[4 * k + 2] << 16) | (b[4 * k + 3] << 24);
+        *reinterpret_cast<uint2 *>(ddst + i0) =
+            make_uint2((uint32_t)d[0] | ((uint32_t)d[1] << 16), (uint32_t)d[2] | ((uint32_t)d[3] << 16));
+    } else {
+        for (int i = i0; i < np; ++i) {
+            int c[3];
+            uint16_t d;
+            fe_rectify_pixel(src, dsrc, w, h, qu[i], qv[i], c, &d);
+            dst[3 * (size_t)i] = (uint8_t)c[0]; dst[3 * (size_t)i + 1] = (uint8_t)c[1]; dst[3 * (size_t)i + 2] = (uint8_t)c[2];
+            ddst[i] = d;
+        }
+    }
+}
+
 // Level 0 in one pass.  load_image: cv::cvtColor RGB2GRAY and RGB2HSV on 8-bit data,
 // channel 0 taken as R (ref src/pcd_generator.cpp:389-390), OpenCV's fixed-point
 // definitions; the grey image as float is level 0 of the pyramid (ref :53-61); its
@@ -640,6 +701,7 @@ const float kCameras[6][5] = {{1000.0f, 616.368f, 616.745f, 319.935f, 243.639f},
 
 struct FeGraph {
     uint64_t key = 0;
+    uint64_t cam_gen = 0;   // the context's camera generation the graph was captured at
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
 };
@@ -672,6 +734,15 @@ struct cvo_fe_ctx {
     bool pending = false;      // a frame was submitted and not collected yet
     bool device_output = false;   // collect_device() will be used: no copy of the cloud to the host
     int p_seq = 0, p_ftype = 0;
+    // the caller's camera (cvo_fe_set_camera); without one the table row of dataset_seq
+    cvo_fe_camera_model cam{};
+    bool custom = false;
+    bool rectify = false;      // ... and its dist is not all zero: frames start with k_fe_rectify
+    uint64_t cam_gen = 0;      // counts the changes of camera: part of a captured graph's key
+    // with the first distorting model: the upload targets of such frames and the map (qu, then qv)
+    uint8_t *raw_img = nullptr;
+    uint16_t *raw_depth = nullptr;
+    int32_t *rect_map = nullptr;   // 2 planes of rect_plane(np) entries
     std::string err;
 };
 
@@ -696,6 +767,18 @@ template <class T> hipError_t dev_alloc(T **p, size_t n) { return hipMalloc((voi
 template <class T> hipError_t pin_alloc(T **p, size_t n) { return hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocDefault); }
 
 inline int blocks(int n) { return (n + FE_BLOCK - 1) / FE_BLOCK; }
+
+// the two planes of the device map lie this many entries apart: k_fe_rectify's 16-byte loads stay aligned
+inline size_t rect_plane(int np) { return ((size_t)np + 3) & ~(size_t)3; }
+
+// what cvo_fe_set_camera accepts
+bool model_ok(const cvo_fe_camera_model &m)
+{
+    const float v[10] = {m.depth_scale, m.fx, m.fy, m.cx, m.cy, m.dist[0], m.dist[1], m.dist[2], m.dist[3], m.dist[4]};
+    for (float x : v)
+        if (!std::isfinite(x)) return false;
+    return m.depth_scale > 0.0f && m.fx > 0.0f && m.fy > 0.0f;
+}
 
 // the Canny path of a frame whose selection came out short (host loop: rare)
 int run_canny(cvo_fe_ctx *ctx)
@@ -729,7 +812,10 @@ int run_emit(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     e.map = ctx->map; e.depth = ctx->depth; e.img = ctx->img; e.hsv = ctx->hsv; e.dx0 = ctx->dx0; e.dy0 = ctx->dy0;
     e.cnt = ctx->cnt; e.ctrl = ctx->ctrl; e.pos = ctx->pos; e.feat = ctx->feat;
     e.np = ctx->np; e.w = ctx->d.w; e.cap = ctx->cap; e.feature_type = feature_type; e.nblocks = ctx->nchunks;
-    cvo_fe_camera(dataset_seq, e.cam);
+    if (ctx->custom) {
+        const cvo_fe_camera_model &m = ctx->cam;
+        e.cam[0] = m.depth_scale; e.cam[1] = m.fx; e.cam[2] = m.fy; e.cam[3] = m.cx; e.cam[4] = m.cy;
+    } else cvo_fe_camera(dataset_seq, e.cam);
     hipLaunchKernelGGL(k_fe_emit, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, e);
     FE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->ctrl, sizeof(FeCtrl), hipMemcpyDeviceToHost, s));
     // the cloud follows optimistically (its size is not known yet): enough for any normal frame
@@ -762,6 +848,112 @@ int cvo_fe_camera(int dataset_seq, float cam[5])
     return CVO_HIP_OK;
 }
 
+int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, int32_t *qu, int32_t *qv)
+{
+    if (!model || !qu || !qv || width < 1 || height < 1 || !model_ok(*model)) return CVO_HIP_ERR_INVALID;
+    // the contract of include/cvo_frontend.h, operation by operation (float64, nothing contracted)
+    const double fx = model->fx, fy = model->fy, cx = model->cx, cy = model->cy;
+    const double k1 = model->dist[0], k2 = model->dist[1], p1 = model->dist[2], p2 = model->dist[3], k3 = model->dist[4];
+    const double wmax = (double)width, hmax = (double)height;
+    for (int v = 0; v < height; ++v) {
+        const double y = ((double)v - cy) / fy;
+        for (int u = 0; u < width; ++u) {
+            const double x = ((double)u - cx) / fx;
+            const double r2 = x * x + y * y;
+            const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+            const double xd = x * rad + ((2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x));
+            const double yd = y * rad + (p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y);
+            double us = fx * xd + cx, vs = fy * yd + cy;
+            if (!(us >= -1.0)) us = -1.0;   // (also what is not a number)
+            if (us > wmax) us = wmax;
+            if (!(vs >= -1.0)) vs = -1.0;
+            if (vs > hmax) vs = hmax;
+            const size_t i = (size_t)v * width + u;
+            qu[i] = (int32_t)std::nearbyint(32.0 * us);   // ties to even (the default rounding mode)
+            qv[i] = (int32_t)std::nearbyint(32.0 * vs);
+        }
+    }
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: a frame is in flight");
+    if (model && !model_ok(*model))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: members must be finite and fx, fy, depth_scale positive");
+    if (!model && !ctx->custom) return CVO_HIP_OK;
+    if (model && ctx->custom && std::memcmp(model, &ctx->cam, sizeof(*model)) == 0) return CVO_HIP_OK;
+    bool distorts = false;
+    if (model)
+        for (int q = 0; q < 5; ++q) distorts = distorts || model->dist[q] != 0.0f;
+    if (distorts) {
+        const size_t np = (size_t)ctx->np, plane = rect_plane(ctx->np);
+        std::vector<int32_t> map;
+        try { map.resize(2 * plane); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "set_camera"); }
+        if (cvo_fe_rectify_map(model, ctx->d.w, ctx->d.h, map.data(), map.data() + plane) != CVO_HIP_OK)
+            return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: rectify_map");
+        FE_HIP(hipSetDevice(ctx->device));
+        // the new map goes into a buffer of its own and replaces the old one only once it is whole:
+        // after any failure here the context still has the camera, the map and the graphs it had
+        int32_t *new_map = nullptr;
+        const bool first = !ctx->raw_img;   // (the two raw buffers come and go together)
+        auto undo = [&]() {
+            if (new_map) (void)hipFree(new_map);
+            if (first) {
+                if (ctx->raw_img) (void)hipFree(ctx->raw_img);
+                if (ctx->raw_depth) (void)hipFree(ctx->raw_depth);
+                ctx->raw_img = nullptr;
+                ctx->raw_depth = nullptr;
+            }
+        };
+        if ((first && (dev_alloc(&ctx->raw_img, np * 3) != hipSuccess || dev_alloc(&ctx->raw_depth, np) != hipSuccess)) ||
+            dev_alloc(&new_map, 2 * plane) != hipSuccess) {
+            (void)hipGetLastError();
+            undo();
+            return fail(ctx, CVO_HIP_ERR_NOMEM, "set_camera: device memory for the raw images and the map");
+        }
+        hipError_t e = hipMemcpy(new_map, map.data(), 2 * plane * sizeof(int32_t), hipMemcpyHostToDevice);
+        // (no frame is in flight: once the stream is idle nothing reads the old map any more)
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            undo();
+            return fail(ctx, CVO_HIP_ERR_HIP, "set_camera: upload of the map", e);
+        }
+        if (ctx->rect_map) (void)hipFree(ctx->rect_map);
+        ctx->rect_map = new_map;
+    }
+    ctx->custom = model != nullptr;
+    ctx->cam = model ? *model : cvo_fe_camera_model{};
+    ctx->rectify = distorts;
+    // A graph captured for the camera before holds its numbers, its buffers (the map's address too) and
+    // its first node.  Dropping those graphs here is what keeps them from being launched again -- and what
+    // keeps the cache of 8 from filling with dead entries; the generation in the key is the guard
+    // behind it, should a graph ever outlive a change of camera.
+    ctx->cam_gen++;
+    for (auto &g : ctx->graphs) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    ctx->graphs.clear();
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_camera(const cvo_fe_ctx *ctx, cvo_fe_camera_model *out, int *custom)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    if (ctx->custom) *out = ctx->cam;
+    else {
+        float cam[5];
+        cvo_fe_camera(ctx->p_seq, cam);
+        *out = cvo_fe_camera_model{cam[0], cam[1], cam[2], cam[3], cam[4], {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
+    }
+    if (custom) *custom = ctx->custom ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
 const char *cvo_fe_last_error(const cvo_fe_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int cvo_fe_destroy(cvo_fe_ctx *ctx)
@@ -773,7 +965,7 @@ int cvo_fe_destroy(cvo_fe_ctx *ctx)
     void *dev[] = {ctx->img, ctx->gray, ctx->pattern, ctx->tmp8, ctx->st8, ctx->edges, ctx->depth, ctx->hsv,
                    ctx->I[0], ctx->I[1], ctx->I[2], ctx->ag[0], ctx->ag[1], ctx->ag[2], ctx->dx0, ctx->dy0,
                    ctx->map, ctx->ths, ctx->ths_s, ctx->pos, ctx->feat, ctx->sdiv, ctx->hdiv, ctx->cnt,
-                   ctx->mag, ctx->grad, ctx->ctrl, ctx->blk_cnt};
+                   ctx->mag, ctx->grad, ctx->ctrl, ctx->blk_cnt, ctx->raw_img, ctx->raw_depth, ctx->rect_map};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (auto &g : ctx->graphs) {
@@ -923,15 +1115,18 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     // buffers, fixed pinned staging): captured once per (camera, feature type, num_want,
     // output mode) and launched as one hipGraph -- 3 copies in, 11 kernels, the copies out.
     static const bool no_graph = getenv("CVO_FE_NO_GRAPH") != nullptr;
+    const int seq_given = dataset_seq;
+    if (ctx->custom) dataset_seq = 0;   // (ignored: one key whatever the caller passed)
     const uint64_t key = ((uint64_t)(uint32_t)dataset_seq << 40) ^ ((uint64_t)feature_type << 36) ^
                          ((uint64_t)ctx->device_output << 32) ^ (uint64_t)(uint32_t)ctx->num_want;
     int rc = CVO_HIP_OK;
     FeGraph *g = nullptr;
     for (auto &e : ctx->graphs)
-        if (e.key == key) g = &e;
+        if (e.key == key && e.cam_gen == ctx->cam_gen) g = &e;
     if (!no_graph && !g && ctx->graphs.size() < 8) {
         FeGraph ng;
         ng.key = key;
+        ng.cam_gen = ctx->cam_gen;
         cvo_lock::Capture alone;   // (see cvo_lock.h)
         if (alone.ok && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
             rc = enqueue_frame(ctx, dataset_seq, feature_type);
@@ -955,7 +1150,7 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
         if (rc) return rc;
     }
     ctx->pending = true;
-    ctx->p_seq = dataset_seq;
+    ctx->p_seq = seq_given;
     ctx->p_ftype = feature_type;
     return CVO_HIP_OK;
 }
@@ -966,9 +1161,14 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
 {
     const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
     hipStream_t s = ctx->stream;
-    FE_HIP(hipMemcpyAsync(ctx->img, ctx->h_img, (size_t)np * 3, hipMemcpyHostToDevice, s));
-    FE_HIP(hipMemcpyAsync(ctx->depth, ctx->h_depth, (size_t)np * 2, hipMemcpyHostToDevice, s));
+    // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
+    FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img : ctx->img, ctx->h_img, (size_t)np * 3, hipMemcpyHostToDevice, s));
+    FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_depth : ctx->depth, ctx->h_depth, (size_t)np * 2, hipMemcpyHostToDevice,
+                          s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl, ctx->h_ctrl, sizeof(FeCtrl), hipMemcpyHostToDevice, s));
+    if (ctx->rectify)
+        hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img, ctx->raw_depth,
+                           ctx->rect_map, ctx->rect_map + rect_plane(np), w, h, ctx->img, ctx->depth);
 
     const FeDims &d = ctx->d;
     hipLaunchKernelGGL(k_fe_level0, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->img, w, h, ctx->sdiv, ctx->hdiv,
@@ -1104,6 +1304,8 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_DX0: src = ctx->dx0; need = np * 4; break;
     case CVO_FE_STAGE_DY0: src = ctx->dy0; need = np * 4; break;
     case CVO_FE_STAGE_EDGES: src = ctx->edges; need = np; break;
+    case CVO_FE_STAGE_RECT_BGR: src = ctx->img; need = np * 3; break;
+    case CVO_FE_STAGE_RECT_DEPTH: src = ctx->depth; need = np * 2; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");

@@ -24,16 +24,50 @@ from . import capi
 
 FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
- STAGE_EDGES) = range(10)
+ STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH) = range(12)
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
-           "cvo_fe_camera")
+           "cvo_fe_camera", "cvo_fe_set_camera", "cvo_fe_get_camera", "cvo_fe_rectify_map")
 
 
 class Info(C.Structure):
     _fields_ = [("num_selected", C.c_int32), ("pot_used", C.c_int32), ("reselected", C.c_int32),
                 ("canny_used", C.c_int32), ("num_points", C.c_int32), ("pad_", C.c_int32)]
+
+
+class CameraModel(C.Structure):
+    """cvo_fe_camera_model: a caller's camera in place of the table row of `dataset_seq`.
+    `dist` is (k1, k2, p1, p2, k3) in OpenCV's / TUM's order; all zero: an ideal pinhole."""
+    _fields_ = [("depth_scale", C.c_float), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("dist", C.c_float * 5)]
+
+    def __init__(self, depth_scale=1000.0, fx=1.0, fy=1.0, cx=0.0, cy=0.0, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
+        if len(dist) != 5:
+            raise ValueError("dist holds k1, k2, p1, p2, k3")
+        super().__init__(depth_scale, fx, fy, cx, cy, (C.c_float * 5)(*dist))
+
+    def astuple(self):
+        return (self.depth_scale, self.fx, self.fy, self.cx, self.cy, tuple(self.dist))
+
+    def __eq__(self, other):
+        return isinstance(other, CameraModel) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "CameraModel(depth_scale=%r, fx=%r, fy=%r, cx=%r, cy=%r, dist=%r)" % self.astuple()
+
+
+# The published calibrations of the TUM RGB-D sequences (fx fy cx cy, d0..d4; depth 5000 per metre).
+# The reference's table (camera(1..3)) holds the same intrinsics without the distortion.  The entries are
+# shared by every user of the module: read them, hand them to set_camera() (which copies), and make a model of
+# your own -- CameraModel(*TUM_CAMERAS["fr1"].astuple()) -- before changing a member.
+TUM_CAMERAS = {
+    "fr1": CameraModel(5000.0, 517.3, 516.5, 318.6, 255.3, (0.2624, -0.9531, -0.0054, 0.0026, 1.1633)),
+    "fr2": CameraModel(5000.0, 520.9, 521.0, 325.1, 249.7, (0.2312, -0.7849, -0.0033, -0.0001, 0.9172)),
+    "fr3": CameraModel(5000.0, 535.4, 539.2, 320.1, 247.6),
+}
 
 
 _BOUND = False
@@ -61,6 +95,10 @@ def lib():
         L.cvo_fe_read_stage.argtypes = [vp, C.c_int, vp, C.c_size_t]
         L.cvo_fe_random_pattern.argtypes = [C.c_int, u8p]
         L.cvo_fe_camera.argtypes = [C.c_int, fp]
+        L.cvo_fe_set_camera.argtypes = [vp, C.POINTER(CameraModel)]
+        L.cvo_fe_get_camera.argtypes = [vp, C.POINTER(CameraModel), C.POINTER(C.c_int)]
+        L.cvo_fe_rectify_map.argtypes = [C.POINTER(CameraModel), C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -81,6 +119,18 @@ def camera(dataset_seq):
     cam = np.zeros(5, np.float32)
     capi.check(lib().cvo_fe_camera(int(dataset_seq), cam.ctypes.data_as(C.POINTER(C.c_float))), what="camera")
     return dict(zip(("scaling_factor", "fx", "fy", "cx", "cy"), (float(v) for v in cam)))
+
+
+def rectify_map(model, width, height):
+    """The map of the rectification contract (include/cvo_frontend.h) for a width x height image:
+    (qu, qv), int32 height x width, where each output pixel looks in the input, in 1/32 pixel.
+    Host only."""
+    qu = np.empty((int(height), int(width)), np.int32)
+    qv = np.empty_like(qu)
+    i32p = C.POINTER(C.c_int32)
+    capi.check(lib().cvo_fe_rectify_map(C.byref(model), int(width), int(height), qu.ctypes.data_as(i32p),
+                                        qv.ctypes.data_as(i32p)), what="rectify_map")
+    return qu, qv
 
 
 class PcdGenerator:
@@ -161,6 +211,20 @@ class PcdGenerator:
         """The following frames are taken with collect_device(): no copy of the cloud to the host."""
         self._chk(lib().cvo_fe_set_device_output(self._h, 1 if on else 0), "set_device_output")
 
+    def set_camera(self, model):
+        """A CameraModel for every following frame (their `dataset_seq` is then ignored); None: back
+        to the reference's table.  A model with distortion makes each frame start with the
+        rectification of both images on the device."""
+        self._chk(lib().cvo_fe_set_camera(self._h, None if model is None else C.byref(model)), "set_camera")
+
+    def camera(self):
+        """The CameraModel set, or None while the table is in use."""
+        out, custom = CameraModel(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_camera(self._h, C.byref(out), C.byref(custom)), "get_camera")
+        return out if custom.value else None
+
+    rectify_map = staticmethod(rectify_map)
+
     def info(self):
         out = Info()
         self._chk(lib().cvo_fe_get_info(self._h, C.byref(out)), "get_info")
@@ -172,7 +236,8 @@ class PcdGenerator:
         shapes = {STAGE_GRAY: ((h, w), np.uint8), STAGE_HSV: ((h, w, 3), np.uint8), STAGE_MAP: ((h, w), np.float32),
                   STAGE_AG0: ((h, w), np.float32), STAGE_AG1: ((h // 2, w // 2), np.float32),
                   STAGE_AG2: ((h // 4, w // 4), np.float32), STAGE_THS: ((h // 32, w // 32), np.float32),
-                  STAGE_DX0: ((h, w), np.float32), STAGE_DY0: ((h, w), np.float32), STAGE_EDGES: ((h, w), np.uint8)}
+                  STAGE_DX0: ((h, w), np.float32), STAGE_DY0: ((h, w), np.float32), STAGE_EDGES: ((h, w), np.uint8),
+                  STAGE_RECT_BGR: ((h, w, 3), np.uint8), STAGE_RECT_DEPTH: ((h, w), np.uint16)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -217,8 +282,11 @@ def load_img(rgb_path, depth_path):
     return np.ascontiguousarray(rgb[:, :, ::-1]), np.ascontiguousarray(dep)
 
 
-def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True):
+def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
+               camera=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
+    generator as it is -- a new one uses the table.
     `device`: the cloud goes from the front end to the registration in device memory
     (cvo_fe_collect_device -> cvo_hip_set_*_device) instead of through host arrays.
     `prefetch`: frame k+1 is in the front end (its own, low-priority stream) while frame k
@@ -234,6 +302,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         return 0
     if gen is None:
         gen = PcdGenerator(cur[1].shape[1], cur[1].shape[0])
+    if camera is not None:
+        gen.set_camera(camera)
     gen.set_device_output(device)
     gen.submit(cur[1], cur[2], dataset_seq, ftype)
     while cur is not None:
@@ -262,11 +332,12 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
-                  generator=None):
+                  generator=None, camera=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
-    features, acvo the HSV ones (ref src/cvo.cpp:329, src/adaptive_cvo.cpp:451)."""
+    features, acvo the HSV ones (ref src/cvo.cpp:329, src/adaptive_cvo.cpp:451).  `camera`: as in
+    run_frames, e.g. TUM_CAMERAS["fr1"] for a freiburg1 sequence with its lens distortion removed."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -276,4 +347,4 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
             bgr, depth = load_img(os.path.join(folder, r), os.path.join(folder, d))
             yield name, bgr, depth
 
-    return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator)
+    return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera)

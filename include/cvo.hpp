@@ -103,6 +103,12 @@ class registration {
                  const std::string &pcd_pth = std::string(), const std::string &pcd_dso_pth = std::string());
     void run_cvo(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,
                  const std::string &pcd_pth = std::string(), const std::string &pcd_dso_pth = std::string());
+    // A camera of the caller's for the image form of set_pcd() / run_cvo() in place of the table row of
+    // dataset_seq (which is then ignored): cvo_fe_set_camera.  A model with lens distortion makes every frame
+    // start with the rectification of both images on the device (the contract: cvo_frontend.h).  May be called
+    // before the first image; throws for a model the front end refuses.  clear_camera(): back to the table.
+    void set_camera(const cvo_fe_camera_model &model);
+    void clear_camera();
     int num_points_last_frame() const { return fe_points_; }
     // Batched mode: align() of `count` objects (each with its moving cloud set) in
     // one call, their kernel launches shared (cvo_hip_align_many).  The result of
@@ -122,6 +128,8 @@ class registration {
     cvo_fe_ctx *fe_;           // front end, created with the first image (its size is fixed then)
     int fe_w_, fe_h_, fe_points_;
     int device_;
+    cvo_fe_camera_model camera_;   // what set_camera() gave, for the front end created with the first image
+    bool have_camera_;
     void check(int status, const char *what);
     void publish();
     void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep);

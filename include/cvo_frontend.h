@@ -16,6 +16,12 @@
  * Every stage runs as HIP kernels on the context's stream; the images are
  * copied in, the cloud is copied out.  There is no CPU path: without a gfx950
  * device cvo_fe_create() fails with CVO_HIP_ERR_NODEVICE.
+ *
+ * Beyond the reference: a caller's own camera (cvo_fe_set_camera) in place of the
+ * six-row table, with the lens distortion removed on the device as the first
+ * stage of a frame.  The reference treats every camera as an ideal pinhole; its
+ * own run script's sequence (TUM fr1) is not one.  The rectification contract is
+ * stated at cvo_fe_camera_model below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -44,7 +50,10 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_AG2 = 5,      /* level 2: (w/4)*(h/4) float */
        CVO_FE_STAGE_THS = 6,      /* smoothed cell thresholds: (w/32)*(h/32) float */
        CVO_FE_STAGE_DX0 = 7, CVO_FE_STAGE_DY0 = 8,   /* level-0 gradients: w*h float */
-       CVO_FE_STAGE_EDGES = 9 };  /* Canny edges of the last top-up: w*h uint8 (0 / 255) */
+       CVO_FE_STAGE_EDGES = 9,    /* Canny edges of the last top-up: w*h uint8 (0 / 255) */
+       CVO_FE_STAGE_RECT_BGR = 10,    /* the colour image every later stage read: w*h*3 uint8 */
+       CVO_FE_STAGE_RECT_DEPTH = 11 };/* ... and the depth image: w*h uint16.  Without a distorting
+                                         camera model these two are the input images. */
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
@@ -54,6 +63,39 @@ typedef struct cvo_fe_info {
     int32_t num_points;     /* points in the cloud (selected and depth != 0) */
     int32_t pad_;
 } cvo_fe_info;
+
+/* A caller's camera: the five numbers of cvo_fe_camera() with the same meaning, and the
+ * lens distortion of the Brown-Conrady model in OpenCV's / TUM's order d0..d4.
+ *
+ * THE RECTIFICATION CONTRACT.  A model whose `dist` is not all zero makes every frame of
+ * the context start with a rectification of both images; grey, HSV, pyramid, selector,
+ * Canny top-up and back-projection then run on the rectified pair, unchanged.  The
+ * results are defined by the arithmetic below, not by the device.  It is this library's
+ * own definition -- the constant-camera-matrix convention of cv::undistort (the rectified
+ * image keeps fx fy cx cy; no new camera matrix, no cropping) and a fixed-point bilinear
+ * tap in the style of cv::remap (5 fractional bits) -- and it is NOT pinned against
+ * cv::remap: bytes may differ from OpenCV's in the last place.
+ *
+ * The map, once per (model, image size), in float64 on the model's floats widened
+ * exactly, no operation contracted into an FMA, in this order, for output pixel (u, v):
+ *     x = (u - cx) / fx;  y = (v - cy) / fy;  r2 = x*x + y*y;
+ *     rad = 1 + r2*(k1 + r2*(k2 + r2*k3));
+ *     xd = x*rad + ((2*p1)*x*y + p2*(r2 + (2*x)*x));
+ *     yd = y*rad + (p1*(r2 + (2*y)*y) + (2*p2)*x*y);
+ *     us = fx*xd + cx;  vs = fy*yd + cy;
+ *   us is clamped to [-1, w], vs to [-1, h] (a value that is not a number counts as -1);
+ *   qu = rint(32*us), qv = rint(32*vs), ties to even, as int32.
+ * Colour, per channel, in integers: x0 = floor(qu/32), ax = qu - 32*x0, likewise y0, ay;
+ *   the four taps (x0, x0+1) x (y0, y0+1), each coordinate clamped to the image
+ *   (replicated border: no black frame, no gradients made of it);
+ *   out = (sum of wx*wy*p + 512) >> 10, wx in {32 - ax, ax}, wy in {32 - ay, ay}.
+ * Depth is registered to the colour image and shares its map; it is never interpolated:
+ *   xn = floor((qu + 16)/32), yn likewise; out = source(xn, yn), or 0 (no point) when
+ *   (xn, yn) lies outside the image.  A zero stays a zero. */
+typedef struct cvo_fe_camera_model {
+    float depth_scale, fx, fy, cx, cy;   /* as cvo_fe_camera(): depth units per metre, focal lengths, centre */
+    float dist[5];                       /* k1 k2 p1 p2 k3; all 0: ideal pinhole, no rectification pass */
+} cvo_fe_camera_model;
 
 /* One context per image size, device and stream.  `stream` as in cvo_hip_create
  * (NULL: a stream of its own).  Images must be at least 64 x 64. */
@@ -70,6 +112,7 @@ int cvo_fe_set_num_want(cvo_fe_ctx *ctx, int num_want);
  *          to its RGB conversions unchanged, and so does this.
  *   depth: height rows of width uint16, `depth_stride` BYTES apart.
  *   dataset_seq: camera table index (ref src/pcd_generator.cpp:241-295); 1 = TUM fr1.
+ *          Ignored while the context has a camera model of its own (cvo_fe_set_camera).
  *   positions: capacity*3 floats (x y z per point); features: capacity*5 floats,
  *   ROW-major (CVO_HIP_FEAT_ROWMAJOR).  Points are in image scan order.
  *   *num_points: points found; if it exceeds `capacity` only the first `capacity`
@@ -103,6 +146,17 @@ int cvo_fe_collect_device(cvo_fe_ctx *ctx, const float **d_positions, const floa
  * start the (optimistic) copy of the cloud to the host.  cvo_fe_collect() still works. */
 int cvo_fe_set_device_output(cvo_fe_ctx *ctx, int on);
 
+/* While a model is set every frame of the context uses it and the `dataset_seq` argument of
+ * create_pointcloud() / submit() is ignored; model == NULL: back to the table (the state of a
+ * new context).  CVO_HIP_ERR_INVALID for a non-finite member, for fx, fy or depth_scale <= 0,
+ * and while a frame is submitted and not collected; the context keeps what it had.  The raw
+ * images and the map of the contract above take device memory only once a model with a
+ * non-zero `dist` has been set. */
+int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model);
+/* *custom = 1 and the model set, or *custom = 0 and the table row of the last frame's
+ * dataset_seq with zero distortion.  `custom` may be NULL. */
+int cvo_fe_get_camera(const cvo_fe_ctx *ctx, cvo_fe_camera_model *out, int *custom);
+
 /* what the last create_pointcloud / collect did */
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out);
 /* copy an intermediate image of the last create_pointcloud to host memory */
@@ -114,6 +168,10 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes);
 int cvo_fe_random_pattern(int n, uint8_t *out);
 /* The camera table: {depth scale, fx, fy, cx, cy}.  Host only. */
 int cvo_fe_camera(int dataset_seq, float cam[5]);
+/* The map of the rectification contract (see cvo_fe_camera_model) for a width x height image:
+ * qu and qv, width*height int32 each, row-major.  Host only.  CVO_HIP_ERR_INVALID for a null
+ * pointer, width or height < 1 and a model cvo_fe_set_camera() would refuse. */
+int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, int32_t *qu, int32_t *qv);
 
 #ifdef __cplusplus
 }
