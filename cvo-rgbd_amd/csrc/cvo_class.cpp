@@ -58,7 +58,7 @@ void Affine3f::quaternion(float q[4]) const
 
 registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
-      fe_points_(0), device_(device), camera_(), have_camera_(false)
+      fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -77,8 +77,10 @@ registration::~registration()
 // output arrays go straight into cvo_hip_set_*_device.
 void registration::cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep)
 {
-    if (!rgb.data || !dep.data || rgb.rows != dep.rows || rgb.cols != dep.cols)
+    if (!rgb.data || !dep.data || (!have_depth_camera_ && (rgb.rows != dep.rows || rgb.cols != dep.cols)))
         throw std::runtime_error("set_pcd(): colour and depth image must have the same size");
+    if (have_depth_camera_ && (dep.rows != depth_camera_.height || dep.cols != depth_camera_.width))
+        throw std::runtime_error("set_pcd(): the depth image must have the depth camera's size");
     if (!fe_) {
         int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
         if (rc != CVO_HIP_OK) throw std::runtime_error(std::string("cvo_fe_create: ") + cvo_hip_error_string(rc));
@@ -90,6 +92,12 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
             cvo_fe_destroy(fe_);
             fe_ = nullptr;
             throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" + why + ")");
+        }
+        if (have_depth_camera_ && (rc = cvo_fe_set_depth_camera(fe_, &depth_camera_)) != CVO_HIP_OK) {
+            const std::string why = cvo_fe_last_error(fe_);
+            cvo_fe_destroy(fe_);
+            fe_ = nullptr;
+            throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" + why + ")");
         }
     }
     if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
@@ -141,6 +149,34 @@ void registration::clear_camera()
                                      cvo_fe_last_error(fe_) + ")");
     }
     have_camera_ = false;
+}
+
+void registration::set_depth_camera(const cvo_fe_depth_camera &rig)
+{
+    if (fe_) {
+        const int rc = cvo_fe_set_depth_camera(fe_, &rig);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    } else {
+        // (the host-only entry refuses what cvo_fe_set_depth_camera refuses: the answer does not wait for the first image)
+        if (cvo_fe_check_depth_camera(&rig) != CVO_HIP_OK)
+            throw std::runtime_error("set_depth_camera(): size in [8, 8192], finite members, fx, fy, depth_scale "
+                                     "positive, max_range above min_range, R a rotation");
+    }
+    depth_camera_ = rig;
+    have_depth_camera_ = true;
+}
+
+void registration::clear_depth_camera()
+{
+    if (fe_) {
+        const int rc = cvo_fe_set_depth_camera(fe_, nullptr);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    }
+    have_depth_camera_ = false;
 }
 
 void registration::set_pcd(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,

@@ -104,7 +104,8 @@ __device__ __forceinline__ int block_base(const int *cnt, int b)
 // instead of single bytes; the taps are gathers (neighbouring pixels share cache lines: the
 // map is smooth).  The last, partial group of an image whose size is no multiple of four goes
 // pixel by pixel.  No tap leaves the images whatever the map holds: every coordinate is
-// clamped or tested here.
+// clamped or tested here.  A null `dsrc` (a context with a depth camera: k_fe_depth_warp brings
+// the raw depth into the rectified frame itself) leaves the depth plane alone.
 __device__ __forceinline__ void fe_rectify_pixel(const uint8_t *src, const uint16_t *dsrc, int w, int h, int qu, int qv,
                                                  int out[3], uint16_t *dout)
 {
@@ -119,7 +120,7 @@ __device__ __forceinline__ void fe_rectify_pixel(const uint8_t *src, const uint1
     for (int c = 0; c < 3; ++c)
         out[c] = (w00 * p00[c] + w01 * p01[c] + w10 * p10[c] + w11 * p11[c] + 512) >> 10;
     const int xn = (qu + 16) >> 5, yn = (qv + 16) >> 5;
-    *dout = (xn >= 0 && xn < w && yn >= 0 && yn < h) ? dsrc[(size_t)yn * w + xn] : (uint16_t)0;
+    *dout = (dsrc && xn >= 0 && xn < w && yn >= 0 && yn < h) ? dsrc[(size_t)yn * w + xn] : (uint16_t)0;
 }
 
 __global__ void __launch_bounds__(FE_BLOCK) k_fe_rectify(const uint8_t *src, const uint16_t *dsrc, const int32_t *qu,
@@ -143,15 +144,106 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_rectify(const uint8_t *src, con
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             o[k] = b[4 * k] | (b[4 * k + 1] << 8) | (b[4 * k + 2] << 16) | (b[4 * k + 3] << 24);
-        *reinterpret_cast<uint2 *>(ddst + i0) =
-            make_uint2((uint32_t)d[0] | ((uint32_t)d[1] << 16), (uint32_t)d[2] | ((uint32_t)d[3] << 16));
+        if (dsrc)
+            *reinterpret_cast<uint2 *>(ddst + i0) =
+                make_uint2((uint32_t)d[0] | ((uint32_t)d[1] << 16), (uint32_t)d[2] | ((uint32_t)d[3] << 16));
     } else {
         for (int i = i0; i < np; ++i) {
             int c[3];
             uint16_t d;
             fe_rectify_pixel(src, dsrc, w, h, qu[i], qv[i], c, &d);
             dst[3 * (size_t)i] = (uint8_t)c[0]; dst[3 * (size_t)i + 1] = (uint8_t)c[1]; dst[3 * (size_t)i + 2] = (uint8_t)c[2];
-            ddst[i] = d;
+            if (dsrc) ddst[i] = d;
+        }
+    }
+}
+
+// The first stage of a frame whose context has a depth camera (the registration contract of
+// include/cvo_frontend.h, at cvo_fe_depth_camera): a forward warp of the raw depth image into the
+// colour camera's frame with a z-buffer, nearest surface wins.  One thread per depth pixel: it lifts
+// the two opposite corners of its cell along the rig's rays (cvo_fe_depth_rays' table, interleaved as
+// float2 so that a wave reads whole lines), carries them into the colour frame, projects them, and
+// posts its depth to every colour pixel whose centre lies inside the projected cell -- at most 8 x 8
+// of them -- with an integer atomicMin whose result nobody reads (no-return, relaxed, agent scope:
+// integer minima commute, so the plane does not depend on the order of arrival).  Every write is
+// bounded here: x in [0, w), y in [0, h).
+constexpr uint32_t FE_Z_EMPTY = 0xFFFFFFFFu;   // a z-buffer entry nothing was written to
+constexpr int FE_FOOT = 8;                     // the footprint's cap per axis
+
+struct DepthWarpArgs {
+    const uint16_t *depth;   // dw * dh
+    const float2 *rays;      // (dh + 1) * (dw + 1): (xn, yn) of the cell corners
+    uint32_t *z;             // w * h, FE_Z_EMPTY where nothing was seen yet
+    int dw, dh, w, h;
+    float scale, min_range, max_range;
+    float R[9], T[3];
+    float cam[5];            // the colour camera: depth scale, fx, fy, cx, cy
+};
+
+__device__ __forceinline__ void fe_depth_corner(const DepthWarpArgs &a, float2 ray, float z, float Q[3])
+{
+    const float X = ray.x * z, Y = ray.y * z;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Q[k] = ((a.R[3 * k] * X + a.R[3 * k + 1] * Y) + a.R[3 * k + 2] * z) + a.T[k];
+}
+
+__device__ __forceinline__ void fe_depth_span(float pa, float pb, int n, int *lo, int *hi)
+{
+    const float top = (float)(n + 1);
+    const int p0 = (int)ceilf(fminf(fmaxf(fminf(pa, pb), -1.0f), top));
+    int p1 = (int)ceilf(fminf(fmaxf(fmaxf(pa, pb), -1.0f), top));
+    p1 = min(p1, p0 + FE_FOOT);
+    *lo = max(p0, 0);
+    *hi = min(p1, n);
+}
+
+__global__ void __launch_bounds__(FE_BLOCK) k_fe_depth_warp(const DepthWarpArgs a)
+{
+    const int i = blockIdx.x * FE_BLOCK + threadIdx.x;
+    if (i >= a.dw * a.dh) return;
+    const uint16_t d = a.depth[i];
+    if (d == 0) return;
+    const float z = (float)d / a.scale;
+    if ((a.min_range > 0.0f && z < a.min_range) || (a.max_range > 0.0f && z > a.max_range)) return;
+    const int v = i / a.dw, u = i - v * a.dw;
+    const size_t c = (size_t)v * (a.dw + 1) + u;
+    float Qa[3], Qb[3];
+    fe_depth_corner(a, a.rays[c], z, Qa);
+    fe_depth_corner(a, a.rays[c + a.dw + 2], z, Qb);
+    if (!(Qa[2] > 0.0f && Qb[2] > 0.0f)) return;   // (also a ray that is not a number)
+    const float ua = a.cam[1] * (Qa[0] / Qa[2]) + a.cam[3], va = a.cam[2] * (Qa[1] / Qa[2]) + a.cam[4];
+    const float ub = a.cam[1] * (Qb[0] / Qb[2]) + a.cam[3], vb = a.cam[2] * (Qb[1] / Qb[2]) + a.cam[4];
+    if (!(isfinite(ua) && isfinite(va) && isfinite(ub) && isfinite(vb))) return;
+    const float qf = rintf((0.5f * (Qa[2] + Qb[2])) * a.cam[0]);
+    if (!(qf >= 1.0f && qf <= 65535.0f)) return;
+    const uint32_t q = (uint32_t)qf;
+    int x0, x1, y0, y1;
+    fe_depth_span(ua, ub, a.w, &x0, &x1);
+    fe_depth_span(va, vb, a.h, &y0, &y1);
+    for (int y = y0; y < y1; ++y)
+        for (int x = x0; x < x1; ++x)
+            (void)__hip_atomic_fetch_min(a.z + ((size_t)y * a.w + x), q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ... and its second half: the z-buffer becomes the uint16 depth plane every later stage reads (0 where
+// nothing was written) and is armed again for the next frame in the same pass, so that a frame needs no
+// memset of its own.  Four pixels per thread: a 16-byte load, an 8-byte store of depth and a 16-byte
+// store of FE_Z_EMPTY; the last, partial group goes pixel by pixel.
+__global__ void __launch_bounds__(FE_BLOCK) k_fe_depth_final(uint32_t *z, int np, uint16_t *ddst)
+{
+    const int i0 = 4 * (blockIdx.x * FE_BLOCK + threadIdx.x);
+    if (i0 >= np) return;
+    if (i0 + 4 <= np) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(z + i0);
+        const uint32_t d0 = q.x == FE_Z_EMPTY ? 0u : q.x, d1 = q.y == FE_Z_EMPTY ? 0u : q.y;
+        const uint32_t d2 = q.z == FE_Z_EMPTY ? 0u : q.z, d3 = q.w == FE_Z_EMPTY ? 0u : q.w;
+        *reinterpret_cast<uint2 *>(ddst + i0) = make_uint2(d0 | (d1 << 16), d2 | (d3 << 16));
+        *reinterpret_cast<uint4 *>(z + i0) = make_uint4(FE_Z_EMPTY, FE_Z_EMPTY, FE_Z_EMPTY, FE_Z_EMPTY);
+    } else {
+        for (int i = i0; i < np; ++i) {
+            const uint32_t q = z[i];
+            ddst[i] = q == FE_Z_EMPTY ? (uint16_t)0 : (uint16_t)q;
+            z[i] = FE_Z_EMPTY;
         }
     }
 }
@@ -743,6 +835,14 @@ struct cvo_fe_ctx {
     uint8_t *raw_img = nullptr;
     uint16_t *raw_depth = nullptr;
     int32_t *rect_map = nullptr;   // 2 planes of rect_plane(np) entries
+    // the caller's depth camera (cvo_fe_set_depth_camera); without one depth is registered to colour
+    cvo_fe_depth_camera rig{};
+    bool has_rig = false;      // frames start with k_fe_depth_warp / k_fe_depth_final
+    int dw = 0, dh = 0;        // the size of the depth image a frame takes: the rig's, or the context's
+    // with the first rig: the upload target of the depth image, the ray table and the z-buffer
+    uint16_t *rig_depth = nullptr;
+    float2 *rays = nullptr;        // (dh + 1) * (dw + 1)
+    uint32_t *zbuf = nullptr;      // rect_plane(np) entries, FE_Z_EMPTY between frames
     std::string err;
 };
 
@@ -778,6 +878,28 @@ bool model_ok(const cvo_fe_camera_model &m)
     for (float x : v)
         if (!std::isfinite(x)) return false;
     return m.depth_scale > 0.0f && m.fx > 0.0f && m.fy > 0.0f;
+}
+
+// what cvo_fe_set_depth_camera accepts
+bool rig_ok(const cvo_fe_depth_camera &r)
+{
+    if (r.width < 8 || r.width > 8192 || r.height < 8 || r.height > 8192) return false;
+    const float *f = &r.depth_scale;   // the 24 floats after the two sizes
+    static_assert(sizeof(cvo_fe_depth_camera) == 2 * sizeof(int32_t) + 24 * sizeof(float), "no padding");
+    for (int q = 0; q < 24; ++q)
+        if (!std::isfinite(f[q])) return false;
+    if (!(r.depth_scale > 0.0f && r.fx > 0.0f && r.fy > 0.0f)) return false;
+    if (r.max_range > 0.0f && r.max_range <= r.min_range) return false;
+    double R[9];
+    for (int q = 0; q < 9; ++q) R[q] = (double)r.R[q];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double e = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2];
+            if (!(std::fabs(e - (i == j ? 1.0 : 0.0)) <= 1e-3)) return false;
+        }
+    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) +
+                       R[2] * (R[3] * R[7] - R[4] * R[6]);
+    return det > 0.0;
 }
 
 // the Canny path of a frame whose selection came out short (host loop: rare)
@@ -876,6 +998,147 @@ int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, 
     return CVO_HIP_OK;
 }
 
+int cvo_fe_check_depth_camera(const cvo_fe_depth_camera *rig)
+{
+    return rig && rig_ok(*rig) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID;
+}
+
+int cvo_fe_depth_rays(const cvo_fe_depth_camera *rig, float *xn, float *yn)
+{
+    if (!rig || !xn || !yn || !rig_ok(*rig)) return CVO_HIP_ERR_INVALID;
+    // the contract of include/cvo_frontend.h, operation by operation (float64, nothing contracted)
+    const double fx = rig->fx, fy = rig->fy, cx = rig->cx, cy = rig->cy;
+    const double k1 = rig->dist[0], k2 = rig->dist[1], p1 = rig->dist[2], p2 = rig->dist[3], k3 = rig->dist[4];
+    bool distorts = false;
+    for (int q = 0; q < 5; ++q) distorts = distorts || rig->dist[q] != 0.0f;
+    const double nan = std::nan("");
+    for (int j = 0; j <= rig->height; ++j) {
+        const double py = (double)j - 0.5, yd = (py - cy) / fy;
+        for (int i = 0; i <= rig->width; ++i) {
+            const double px = (double)i - 0.5, xd = (px - cx) / fx;
+            double x = xd, y = yd;
+            if (distorts) {
+                for (int it = 0; it < 20; ++it) {
+                    const double r2 = x * x + y * y;
+                    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+                    const double dx = (2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x);
+                    const double dy = p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y;
+                    x = (xd - dx) / rad;
+                    y = (yd - dy) / rad;
+                }
+                const double r2 = x * x + y * y;
+                const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+                const double xf = x * rad + ((2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x));
+                const double yf = y * rad + (p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y);
+                const double us = fx * xf + cx, vs = fy * yf + cy;
+                if (!(std::fabs(us - px) <= 1.0 / 32.0 && std::fabs(vs - py) <= 1.0 / 32.0)) x = y = nan;
+            }
+            const size_t c = (size_t)j * ((size_t)rig->width + 1) + i;
+            xn[c] = (float)x;
+            yn[c] = (float)y;
+        }
+    }
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: a frame is in flight");
+    if (rig && !rig_ok(*rig))
+        return fail(ctx, CVO_HIP_ERR_INVALID,
+                    "set_depth_camera: size in [8, 8192], finite members, fx, fy, depth_scale positive, "
+                    "max_range above min_range, R a rotation");
+    if (!rig && !ctx->has_rig) return CVO_HIP_OK;
+    if (rig && ctx->has_rig && std::memcmp(rig, &ctx->rig, sizeof(*rig)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    const int dw = rig ? rig->width : ctx->d.w, dh = rig ? rig->height : ctx->d.h;
+    const size_t dnp = (size_t)dw * dh;
+    // Everything new goes into buffers of its own and replaces what the context has only once it is
+    // whole: after any failure here the context still has the rig, the buffers and the graphs it had.
+    uint16_t *new_depth = nullptr, *new_host = nullptr;
+    float2 *new_rays = nullptr;
+    uint32_t *new_z = nullptr;
+    auto undo = [&]() {
+        if (new_depth) (void)hipFree(new_depth);
+        if (new_rays) (void)hipFree(new_rays);
+        if (new_z) (void)hipFree(new_z);
+        if (new_host) (void)hipHostFree(new_host);
+        (void)hipGetLastError();
+    };
+    const bool resize = dw != ctx->dw || dh != ctx->dh;   // the pinned staging image follows the depth size
+    if (resize && pin_alloc(&new_host, dnp) != hipSuccess) {
+        undo();
+        return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera: pinned memory for the depth image");
+    }
+    if (rig) {
+        const size_t nr = (size_t)(dw + 1) * (dh + 1), nz = rect_plane(ctx->np);
+        std::vector<float> t;
+        std::vector<float2> inter;
+        try { t.resize(2 * nr); inter.resize(nr); } catch (const std::bad_alloc &) {
+            undo();
+            return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera");
+        }
+        if (cvo_fe_depth_rays(rig, t.data(), t.data() + nr) != CVO_HIP_OK) {
+            undo();
+            return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: depth_rays");
+        }
+        for (size_t q = 0; q < nr; ++q) inter[q] = make_float2(t[q], t[nr + q]);
+        if (dev_alloc(&new_depth, dnp) != hipSuccess || dev_alloc(&new_rays, nr) != hipSuccess ||
+            (!ctx->zbuf && dev_alloc(&new_z, nz) != hipSuccess)) {
+            undo();
+            return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera: device memory for the raw depth, the rays and the z-buffer");
+        }
+        // (no frame is in flight: once the stream is idle nothing reads the old buffers any more)
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(new_rays, inter.data(), nr * sizeof(float2), hipMemcpyHostToDevice);
+        // the z-buffer is armed here and by every frame's k_fe_depth_final after it
+        if (e == hipSuccess) e = hipMemset(new_z ? new_z : ctx->zbuf, 0xFF, nz * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) {
+            undo();
+            return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera: upload of the rays", e);
+        }
+    } else {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            undo();
+            return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera", e);
+        }
+    }
+    if (ctx->rig_depth) (void)hipFree(ctx->rig_depth);
+    if (ctx->rays) (void)hipFree(ctx->rays);
+    ctx->rig_depth = new_depth;
+    ctx->rays = new_rays;
+    if (new_z) ctx->zbuf = new_z;
+    if (new_host) {
+        (void)hipHostFree(ctx->h_depth);
+        ctx->h_depth = new_host;
+    }
+    ctx->has_rig = rig != nullptr;
+    ctx->rig = rig ? *rig : cvo_fe_depth_camera{};
+    ctx->dw = dw;
+    ctx->dh = dh;
+    // as after a change of camera: the graphs captured before hold the old buffers and numbers
+    ctx->cam_gen++;
+    for (auto &g : ctx->graphs) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    ctx->graphs.clear();
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_depth_camera(const cvo_fe_ctx *ctx, cvo_fe_depth_camera *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_rig ? ctx->rig : cvo_fe_depth_camera{};
+    if (set) *set = ctx->has_rig ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
 int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
 {
     cvo_lock::Api api_guard;
@@ -965,7 +1228,8 @@ int cvo_fe_destroy(cvo_fe_ctx *ctx)
     void *dev[] = {ctx->img, ctx->gray, ctx->pattern, ctx->tmp8, ctx->st8, ctx->edges, ctx->depth, ctx->hsv,
                    ctx->I[0], ctx->I[1], ctx->I[2], ctx->ag[0], ctx->ag[1], ctx->ag[2], ctx->dx0, ctx->dy0,
                    ctx->map, ctx->ths, ctx->ths_s, ctx->pos, ctx->feat, ctx->sdiv, ctx->hdiv, ctx->cnt,
-                   ctx->mag, ctx->grad, ctx->ctrl, ctx->blk_cnt, ctx->raw_img, ctx->raw_depth, ctx->rect_map};
+                   ctx->mag, ctx->grad, ctx->ctrl, ctx->blk_cnt, ctx->raw_img, ctx->raw_depth, ctx->rect_map,
+                   ctx->rig_depth, ctx->rays, ctx->zbuf};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (auto &g : ctx->graphs) {
@@ -1008,6 +1272,7 @@ int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **
     }
     FeDims &d = ctx->d;
     d.w = width; d.h = height; d.w32 = width / 32; d.h32 = height / 32;
+    ctx->dw = width; ctx->dh = height;
     int wl = width, hl = height;
     for (int l = 0; l < FE_LEVELS; ++l) { d.wl[l] = wl; d.hl[l] = hl; wl /= 2; hl /= 2; }
     const size_t np = (size_t)width * height;
@@ -1090,7 +1355,8 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     cvo_lock::Api api_guard;
     if (!ctx) return CVO_HIP_ERR_INVALID;
     const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
-    if (!img || !depth || img_stride < (size_t)w * 3 || depth_stride < (size_t)w * 2 ||
+    const int dw = ctx->dw, dh = ctx->dh;   // (the depth camera's image, if the context has one)
+    if (!img || !depth || img_stride < (size_t)w * 3 || depth_stride < (size_t)dw * 2 ||
         (feature_type != CVO_FE_FEATURES_HSV && feature_type != CVO_FE_FEATURES_RGB))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit: bad argument");
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the previous frame was not collected");
@@ -1103,11 +1369,11 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     else
         for (int y = 0; y < h; ++y)
             std::memcpy(ctx->h_img + (size_t)y * w * 3, img + (size_t)y * img_stride, (size_t)w * 3);
-    if (depth == ctx->h_depth && depth_stride == (size_t)w * 2) {
-    } else if (depth_stride == (size_t)w * 2) std::memcpy(ctx->h_depth, depth, (size_t)np * 2);
+    if (depth == ctx->h_depth && depth_stride == (size_t)dw * 2) {
+    } else if (depth_stride == (size_t)dw * 2) std::memcpy(ctx->h_depth, depth, (size_t)dw * dh * 2);
     else
-        for (int y = 0; y < h; ++y)
-            std::memcpy(ctx->h_depth + (size_t)y * w, (const uint8_t *)depth + (size_t)y * depth_stride, (size_t)w * 2);
+        for (int y = 0; y < dh; ++y)
+            std::memcpy(ctx->h_depth + (size_t)y * dw, (const uint8_t *)depth + (size_t)y * depth_stride, (size_t)dw * 2);
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
     *ctx->h_ctrl = c0;
@@ -1163,12 +1429,30 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     hipStream_t s = ctx->stream;
     // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
     FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img : ctx->img, ctx->h_img, (size_t)np * 3, hipMemcpyHostToDevice, s));
-    FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_depth : ctx->depth, ctx->h_depth, (size_t)np * 2, hipMemcpyHostToDevice,
-                          s));
+    // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
+    uint16_t *depth_in = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : ctx->depth;
+    FE_HIP(hipMemcpyAsync(depth_in, ctx->h_depth, (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl, ctx->h_ctrl, sizeof(FeCtrl), hipMemcpyHostToDevice, s));
     if (ctx->rectify)
-        hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img, ctx->raw_depth,
-                           ctx->rect_map, ctx->rect_map + rect_plane(np), w, h, ctx->img, ctx->depth);
+        hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img,
+                           ctx->has_rig ? (const uint16_t *)nullptr : ctx->raw_depth, ctx->rect_map,
+                           ctx->rect_map + rect_plane(np), w, h, ctx->img, ctx->depth);
+    if (ctx->has_rig) {
+        const cvo_fe_depth_camera &r = ctx->rig;
+        DepthWarpArgs a{};
+        a.depth = ctx->rig_depth; a.rays = ctx->rays; a.z = ctx->zbuf;
+        a.dw = r.width; a.dh = r.height; a.w = w; a.h = h;
+        a.scale = r.depth_scale; a.min_range = r.min_range; a.max_range = r.max_range;
+        for (int q = 0; q < 9; ++q) a.R[q] = r.R[q];
+        for (int q = 0; q < 3; ++q) a.T[q] = r.T[q];
+        // the colour camera in force for this frame (a distorting model: its rectified pinhole)
+        if (ctx->custom) {
+            const cvo_fe_camera_model &m = ctx->cam;
+            a.cam[0] = m.depth_scale; a.cam[1] = m.fx; a.cam[2] = m.fy; a.cam[3] = m.cx; a.cam[4] = m.cy;
+        } else cvo_fe_camera(dataset_seq, a.cam);   // (never fails here: an index outside the table means row 0)
+        hipLaunchKernelGGL(k_fe_depth_warp, dim3(blocks(a.dw * a.dh)), dim3(FE_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf, np, ctx->depth);
+    }
 
     const FeDims &d = ctx->d;
     hipLaunchKernelGGL(k_fe_level0, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->img, w, h, ctx->sdiv, ctx->hdiv,
@@ -1306,6 +1590,10 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_EDGES: src = ctx->edges; need = np; break;
     case CVO_FE_STAGE_RECT_BGR: src = ctx->img; need = np * 3; break;
     case CVO_FE_STAGE_RECT_DEPTH: src = ctx->depth; need = np * 2; break;
+    case CVO_FE_STAGE_RAW_DEPTH:
+        src = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : ctx->depth;
+        need = (size_t)ctx->dw * ctx->dh * 2;
+        break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");

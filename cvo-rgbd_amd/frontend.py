@@ -24,11 +24,13 @@ from . import capi
 
 FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
- STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH) = range(12)
+ STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH) = range(13)
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
-           "cvo_fe_camera", "cvo_fe_set_camera", "cvo_fe_get_camera", "cvo_fe_rectify_map")
+           "cvo_fe_camera", "cvo_fe_set_camera", "cvo_fe_get_camera", "cvo_fe_rectify_map",
+           "cvo_fe_set_depth_camera", "cvo_fe_get_depth_camera", "cvo_fe_depth_rays",
+           "cvo_fe_check_depth_camera")
 
 
 class Info(C.Structure):
@@ -57,6 +59,37 @@ class CameraModel(C.Structure):
 
     def __repr__(self):
         return "CameraModel(depth_scale=%r, fx=%r, fy=%r, cx=%r, cy=%r, dist=%r)" % self.astuple()
+
+
+class DepthCamera(C.Structure):
+    """cvo_fe_depth_camera: a depth camera of its own -- the size of its image, its pinhole and lens,
+    and where it sits: p_colour = R p_depth + T (R row-major, T in metres).  `min_range` / `max_range`
+    in metres along its axis; <= 0: no limit on that side."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth_scale", C.c_float), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 5),
+                ("R", C.c_float * 9), ("T", C.c_float * 3), ("min_range", C.c_float), ("max_range", C.c_float)]
+
+    def __init__(self, width=0, height=0, depth_scale=1000.0, fx=1.0, fy=1.0, cx=0.0, cy=0.0,
+                 dist=(0.0, 0.0, 0.0, 0.0, 0.0), R=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), T=(0.0, 0.0, 0.0),
+                 min_range=0.0, max_range=0.0):
+        R = [float(v) for v in np.asarray(R, np.float64).reshape(-1)]
+        if len(dist) != 5 or len(R) != 9 or len(T) != 3:
+            raise ValueError("dist holds k1, k2, p1, p2, k3; R is 3 x 3; T holds 3 numbers")
+        super().__init__(int(width), int(height), depth_scale, fx, fy, cx, cy, (C.c_float * 5)(*dist),
+                         (C.c_float * 9)(*R), (C.c_float * 3)(*T), min_range, max_range)
+
+    def astuple(self):
+        return (self.width, self.height, self.depth_scale, self.fx, self.fy, self.cx, self.cy, tuple(self.dist),
+                tuple(self.R), tuple(self.T), self.min_range, self.max_range)
+
+    def __eq__(self, other):
+        return isinstance(other, DepthCamera) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return ("DepthCamera(width=%r, height=%r, depth_scale=%r, fx=%r, fy=%r, cx=%r, cy=%r, dist=%r, R=%r, T=%r, "
+                "min_range=%r, max_range=%r)" % self.astuple())
 
 
 # The published calibrations of the TUM RGB-D sequences (fx fy cx cy, d0..d4; depth 5000 per metre).
@@ -99,6 +132,10 @@ def lib():
         L.cvo_fe_get_camera.argtypes = [vp, C.POINTER(CameraModel), C.POINTER(C.c_int)]
         L.cvo_fe_rectify_map.argtypes = [C.POINTER(CameraModel), C.c_int, C.c_int, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32)]
+        L.cvo_fe_set_depth_camera.argtypes = [vp, C.POINTER(DepthCamera)]
+        L.cvo_fe_get_depth_camera.argtypes = [vp, C.POINTER(DepthCamera), C.POINTER(C.c_int)]
+        L.cvo_fe_depth_rays.argtypes = [C.POINTER(DepthCamera), fp, fp]
+        L.cvo_fe_check_depth_camera.argtypes = [C.POINTER(DepthCamera)]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -133,6 +170,22 @@ def rectify_map(model, width, height):
     return qu, qv
 
 
+def depth_rays(rig):
+    """The ray table of the registration contract (include/cvo_frontend.h) for a DepthCamera:
+    (xn, yn), float32 (height+1) x (width+1), the rays through the corners of the depth pixels; NaN where
+    the lens cannot be inverted.  Host only."""
+    xn = np.empty((int(rig.height) + 1, int(rig.width) + 1), np.float32)
+    yn = np.empty_like(xn)
+    fp = C.POINTER(C.c_float)
+    capi.check(lib().cvo_fe_depth_rays(C.byref(rig), xn.ctypes.data_as(fp), yn.ctypes.data_as(fp)), what="depth_rays")
+    return xn, yn
+
+
+def check_depth_camera(rig):
+    """True for a DepthCamera set_depth_camera() accepts (cvo_fe_check_depth_camera).  Host only."""
+    return lib().cvo_fe_check_depth_camera(C.byref(rig)) == 0
+
+
 class PcdGenerator:
     """ref include/pcd_generator.hpp:30-108; one object per image size."""
 
@@ -146,6 +199,7 @@ class PcdGenerator:
         self.num_want = int(num_want)
         self._chk(lib().cvo_fe_set_num_want(self._h, self.num_want), "set_num_want")
         self.capacity = self.width * self.height   # (upper bound of any selection)
+        self._dshape = (self.height, self.width)   # of the depth image: the depth camera's, if one is set
         self._pos = np.empty((self.capacity, 3), np.float32)
         self._feat = np.empty((self.capacity, 5), np.float32)
 
@@ -160,13 +214,13 @@ class PcdGenerator:
         (positions n x 3, features n x 5 row-major), points in image scan order."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
         depth = np.ascontiguousarray(depth, np.uint16)
-        if bgr.shape != (self.height, self.width, 3) or depth.shape != (self.height, self.width):
+        if bgr.shape != (self.height, self.width, 3) or depth.shape != self._dshape:
             raise ValueError("expected a %dx%dx3 uint8 image and a %dx%d uint16 depth map"
-                             % (self.height, self.width, self.height, self.width))
+                             % ((self.height, self.width) + self._dshape))
         n = C.c_int(0)
         st = lib().cvo_fe_create_pointcloud(
             self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3,
-            depth.ctypes.data_as(C.POINTER(C.c_uint16)), self.width * 2, int(dataset_seq), int(feature_type),
+            depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2, int(dataset_seq), int(feature_type),
             self._pos.ctypes.data_as(C.POINTER(C.c_float)), self._feat.ctypes.data_as(C.POINTER(C.c_float)),
             self.capacity, C.byref(n))
         self._chk(st, "create_pointcloud")
@@ -176,11 +230,11 @@ class PcdGenerator:
         """First half of create_pointcloud: stage the images, enqueue everything, return."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
         depth = np.ascontiguousarray(depth, np.uint16)
-        if bgr.shape != (self.height, self.width, 3) or depth.shape != (self.height, self.width):
+        if bgr.shape != (self.height, self.width, 3) or depth.shape != self._dshape:
             raise ValueError("expected a %dx%dx3 uint8 image and a %dx%d uint16 depth map"
-                             % (self.height, self.width, self.height, self.width))
+                             % ((self.height, self.width) + self._dshape))
         self._chk(lib().cvo_fe_submit(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3,
-                                      depth.ctypes.data_as(C.POINTER(C.c_uint16)), self.width * 2,
+                                      depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2,
                                       int(dataset_seq), int(feature_type)), "submit")
 
     def collect(self):
@@ -200,11 +254,12 @@ class PcdGenerator:
 
     def host_buffers(self):
         """numpy views of the context's pinned staging images (h x w x 3 uint8, h x w uint16): fill
-        them in place and pass them to submit() / create_pointcloud() to save a copy."""
+        them in place and pass them to submit() / create_pointcloud() to save a copy.  The depth view is
+        of the depth camera's size while one is set and valid until the next set_depth_camera()."""
         pi, pd = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint16)()
         self._chk(lib().cvo_fe_host_buffers(self._h, C.byref(pi), C.byref(pd)), "host_buffers")
         img = np.ctypeslib.as_array(pi, shape=(self.height, self.width, 3))
-        dep = np.ctypeslib.as_array(pd, shape=(self.height, self.width))
+        dep = np.ctypeslib.as_array(pd, shape=self._dshape)
         return img, dep
 
     def set_device_output(self, on=True):
@@ -225,6 +280,21 @@ class PcdGenerator:
 
     rectify_map = staticmethod(rectify_map)
 
+    def set_depth_camera(self, rig):
+        """A DepthCamera for every following frame: their `depth` is then rig.height x rig.width and is
+        registered into the colour camera's frame on the device (the registration contract of
+        include/cvo_frontend.h); None: depth is registered to colour already, as for a new object."""
+        self._chk(lib().cvo_fe_set_depth_camera(self._h, None if rig is None else C.byref(rig)), "set_depth_camera")
+        self._dshape = (self.height, self.width) if rig is None else (int(rig.height), int(rig.width))
+
+    def depth_camera(self):
+        """The DepthCamera set, or None."""
+        out, isset = DepthCamera(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_depth_camera(self._h, C.byref(out), C.byref(isset)), "get_depth_camera")
+        return out if isset.value else None
+
+    depth_rays = staticmethod(depth_rays)
+
     def info(self):
         out = Info()
         self._chk(lib().cvo_fe_get_info(self._h, C.byref(out)), "get_info")
@@ -237,7 +307,8 @@ class PcdGenerator:
                   STAGE_AG0: ((h, w), np.float32), STAGE_AG1: ((h // 2, w // 2), np.float32),
                   STAGE_AG2: ((h // 4, w // 4), np.float32), STAGE_THS: ((h // 32, w // 32), np.float32),
                   STAGE_DX0: ((h, w), np.float32), STAGE_DY0: ((h, w), np.float32), STAGE_EDGES: ((h, w), np.uint8),
-                  STAGE_RECT_BGR: ((h, w, 3), np.uint8), STAGE_RECT_DEPTH: ((h, w), np.uint16)}
+                  STAGE_RECT_BGR: ((h, w, 3), np.uint8), STAGE_RECT_DEPTH: ((h, w), np.uint16),
+                  STAGE_RAW_DEPTH: (self._dshape, np.uint16)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -283,10 +354,12 @@ def load_img(rgb_path, depth_path):
 
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
-               camera=None):
+               camera=None, depth_camera=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
+    `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
+    are registered to colour on the device; None leaves the generator as it is.
     `device`: the cloud goes from the front end to the registration in device memory
     (cvo_fe_collect_device -> cvo_hip_set_*_device) instead of through host arrays.
     `prefetch`: frame k+1 is in the front end (its own, low-priority stream) while frame k
@@ -304,6 +377,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen = PcdGenerator(cur[1].shape[1], cur[1].shape[0])
     if camera is not None:
         gen.set_camera(camera)
+    if depth_camera is not None:
+        gen.set_depth_camera(depth_camera)
     gen.set_device_output(device)
     gen.submit(cur[1], cur[2], dataset_seq, ftype)
     while cur is not None:
@@ -332,12 +407,13 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
-                  generator=None, camera=None):
+                  generator=None, camera=None, depth_camera=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
     features, acvo the HSV ones (ref src/cvo.cpp:329, src/adaptive_cvo.cpp:451).  `camera`: as in
-    run_frames, e.g. TUM_CAMERAS["fr1"] for a freiburg1 sequence with its lens distortion removed."""
+    run_frames, e.g. TUM_CAMERAS["fr1"] for a freiburg1 sequence with its lens distortion removed.
+    `depth_camera`: as in run_frames, for a recording whose depth images are not registered to colour."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -347,4 +423,5 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
             bgr, depth = load_img(os.path.join(folder, r), os.path.join(folder, d))
             yield name, bgr, depth
 
-    return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera)
+    return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
+                      depth_camera=depth_camera)

@@ -109,6 +109,12 @@ class registration {
     // before the first image; throws for a model the front end refuses.  clear_camera(): back to the table.
     void set_camera(const cvo_fe_camera_model &model);
     void clear_camera();
+    // A depth camera of its own for the image form of set_pcd() / run_cvo(): cvo_fe_set_depth_camera.  The depth
+    // image_view of every following frame is then rig.height x rig.width and is registered into the colour
+    // camera's frame on the device (the contract: cvo_frontend.h).  May be called before the first image; throws
+    // for a rig the front end refuses.  clear_depth_camera(): depth is registered to colour again.
+    void set_depth_camera(const cvo_fe_depth_camera &rig);
+    void clear_depth_camera();
     int num_points_last_frame() const { return fe_points_; }
     // Batched mode: align() of `count` objects (each with its moving cloud set) in
     // one call, their kernel launches shared (cvo_hip_align_many).  The result of
@@ -130,6 +136,8 @@ class registration {
     int device_;
     cvo_fe_camera_model camera_;   // what set_camera() gave, for the front end created with the first image
     bool have_camera_;
+    cvo_fe_depth_camera depth_camera_;   // what set_depth_camera() gave, likewise
+    bool have_depth_camera_;
     void check(int status, const char *what);
     void publish();
     void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep);

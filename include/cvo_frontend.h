@@ -21,7 +21,11 @@
  * six-row table, with the lens distortion removed on the device as the first
  * stage of a frame.  The reference treats every camera as an ideal pinhole; its
  * own run script's sequence (TUM fr1) is not one.  The rectification contract is
- * stated at cvo_fe_camera_model below.
+ * stated at cvo_fe_camera_model below.  And a depth camera of its own
+ * (cvo_fe_set_depth_camera): another size, pinhole and lens, mounted beside the
+ * colour camera; every frame then registers the depth image into the colour
+ * camera's frame on the device.  The registration contract is stated at
+ * cvo_fe_depth_camera below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -52,8 +56,11 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_DX0 = 7, CVO_FE_STAGE_DY0 = 8,   /* level-0 gradients: w*h float */
        CVO_FE_STAGE_EDGES = 9,    /* Canny edges of the last top-up: w*h uint8 (0 / 255) */
        CVO_FE_STAGE_RECT_BGR = 10,    /* the colour image every later stage read: w*h*3 uint8 */
-       CVO_FE_STAGE_RECT_DEPTH = 11 };/* ... and the depth image: w*h uint16.  Without a distorting
-                                         camera model these two are the input images. */
+       CVO_FE_STAGE_RECT_DEPTH = 11,  /* ... and the depth image: w*h uint16.  Without a distorting
+                                         camera model these two are the input images.  With a depth
+                                         camera this one is the registered depth (colour size). */
+       CVO_FE_STAGE_RAW_DEPTH = 12 }; /* the depth image as uploaded: the depth camera's width*height
+                                         uint16, or w*h without a depth camera */
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
@@ -97,6 +104,61 @@ typedef struct cvo_fe_camera_model {
     float dist[5];                       /* k1 k2 p1 p2 k3; all 0: ideal pinhole, no rectification pass */
 } cvo_fe_camera_model;
 
+/* A depth camera of its own: the depth image has its own size, pinhole and lens and is taken
+ * from another place than the colour image (7-Scenes, raw NYUv2, ScanNet, Azure Kinect and
+ * RealSense recordings).  Without one the library assumes what the reference assumes: depth
+ * pixel (u, v) is colour pixel (u, v).
+ *
+ * THE REGISTRATION CONTRACT.  While a depth camera is set every frame of the context starts
+ * with a forward warp of the depth image into the frame of the colour camera in force for that
+ * frame -- the cvo_fe_set_camera model if one is set (its rectified pinhole if it distorts),
+ * otherwise the table row of dataset_seq -- and every later stage reads the registered image,
+ * unchanged.  k_fe_rectify then resamples colour only: the raw depth reaches the rectified
+ * frame in one resampling, not two.  The results are defined by the arithmetic below, not by
+ * the device.  It is this library's own definition -- the footprint idea of the common SDKs'
+ * depth-to-colour alignment, nearest surface wins -- and it is NOT pinned against any of them.
+ *
+ * The ray table, once per rig, on the host in float64 on the rig's floats widened exactly, no
+ * operation contracted, in this order; for the corner (i, j), i = 0..width, j = 0..height, at
+ * image position (i - 0.5, j - 0.5):
+ *     xd = ((i - 0.5) - cx) / fx;  yd = ((j - 0.5) - cy) / fy;  x = xd;  y = yd;
+ *     if dist is not all zero, 20 times:
+ *         r2 = x*x + y*y;  rad = 1 + r2*(k1 + r2*(k2 + r2*k3));
+ *         dx = (2*p1)*x*y + p2*(r2 + (2*x)*x);  dy = p1*(r2 + (2*y)*y) + (2*p2)*x*y;
+ *         x = (xd - dx) / rad;  y = (yd - dy) / rad;
+ *       then (x, y) is distorted forward with the formulae of the rectification contract to
+ *       (us, vs); unless |us - (i - 0.5)| <= 1/32 and |vs - (j - 0.5)| <= 1/32 (a value that is
+ *       not a number fails) the ray is invalid: x = y = NaN.  (A lens the fixed point cannot
+ *       invert gives such pixels no depth rather than a wrong one.)
+ *     xn[j][i] = (float)x;  yn[j][i] = (float)y.
+ * Per depth pixel (u, v) with d = depth[v][u], every frame, in float32, every operation
+ * explicit in this order, division correctly rounded, no FMA; c marks the colour camera, w x h
+ * its image:
+ *     skip if d == 0;  z = (float)d / depth_scale;
+ *     skip if (min_range > 0 and z < min_range) or (max_range > 0 and z > max_range);
+ *     for the corners a = (u, v) and b = (u+1, v+1) of the table:
+ *         X = xn*z;  Y = yn*z;  Q.k = ((R[k][0]*X + R[k][1]*Y) + R[k][2]*z) + T[k],  k = 0, 1, 2;
+ *     skip unless Qa.z > 0 and Qb.z > 0 (an invalid ray fails this);
+ *     ua = fxc*(Qa.x/Qa.z) + cxc;  va = fyc*(Qa.y/Qa.z) + cyc;  ub, vb likewise;
+ *     skip if any of the four is not finite;
+ *     q = rintf((0.5f*(Qa.z + Qb.z)) * depth_scale_c);  skip unless 1 <= q <= 65535;
+ *     x0 = (int)ceilf(clamp(fminf(ua, ub), -1, w + 1));  x1 = (int)ceilf(clamp(fmaxf(ua, ub), -1, w + 1));
+ *     x1 = min(x1, x0 + 8);  y0, y1 likewise with h;
+ *     for every colour pixel (x, y), max(x0, 0) <= x < min(x1, w), max(y0, 0) <= y < min(y1, h):
+ *         Z[y][x] = min(Z[y][x], q).
+ * The registered pixel is Z where something was written and 0 (no point) otherwise.  The
+ * footprint is the set of pixel centres inside the projected cell, half-open, capped at 8 x 8 so
+ * that a pixel's work is bounded; a rig that is the colour camera itself (same size and pinhole,
+ * R = I, T = 0) returns the depth image byte for byte; the result does not depend on the order
+ * of the writes.  Holes a forward warp leaves are not filled. */
+typedef struct cvo_fe_depth_camera {
+    int32_t width, height;               /* of the DEPTH image; may differ from the context's (colour) size */
+    float depth_scale, fx, fy, cx, cy;   /* units per metre of the depth image's values; the depth camera's pinhole */
+    float dist[5];                       /* k1 k2 p1 p2 k3 of the depth camera's lens; all 0: none */
+    float R[9], T[3];                    /* p_colour = R p_depth + T, R row-major, T in metres */
+    float min_range, max_range;          /* metres along the depth camera's axis; <= 0: no limit on that side */
+} cvo_fe_depth_camera;
+
 /* One context per image size, device and stream.  `stream` as in cvo_hip_create
  * (NULL: a stream of its own).  Images must be at least 64 x 64. */
 int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **out);
@@ -110,7 +172,9 @@ int cvo_fe_set_num_want(cvo_fe_ctx *ctx, int num_want);
  *   img:   height rows of width*3 bytes, `img_stride` bytes apart, channel order as
  *          decoded from the file by cv::imread (B, G, R) -- the reference hands that
  *          to its RGB conversions unchanged, and so does this.
- *   depth: height rows of width uint16, `depth_stride` BYTES apart.
+ *   depth: height rows of width uint16, `depth_stride` BYTES apart; while a depth camera is
+ *          set (cvo_fe_set_depth_camera): rig.height rows of rig.width uint16, and
+ *          depth_stride >= rig.width * 2.
  *   dataset_seq: camera table index (ref src/pcd_generator.cpp:241-295); 1 = TUM fr1.
  *          Ignored while the context has a camera model of its own (cvo_fe_set_camera).
  *   positions: capacity*3 floats (x y z per point); features: capacity*5 floats,
@@ -125,7 +189,8 @@ int cvo_fe_create_pointcloud(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_str
  * depth row, no padding): a decoder that writes straight into them -- e.g. a cv::Mat header
  * over the pointer handed to cv::imdecode -- saves the copy that submit() / create_pointcloud()
  * otherwise make; pass these same pointers (and the dense strides) to them.  They may be
- * refilled once the frame has been collected. */
+ * refilled once the frame has been collected.  While a depth camera is set the depth image is
+ * of its size; the depth pointer is valid until the next cvo_fe_set_depth_camera(). */
 int cvo_fe_host_buffers(cvo_fe_ctx *ctx, uint8_t **img, uint16_t **depth);
 
 /* The same in two halves, for callers that have other work while the GPU is busy (the
@@ -157,6 +222,18 @@ int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model);
  * dataset_seq with zero distortion.  `custom` may be NULL. */
 int cvo_fe_get_camera(const cvo_fe_ctx *ctx, cvo_fe_camera_model *out, int *custom);
 
+/* While a rig is set the depth image of every frame is the depth camera's (see the
+ * registration contract at cvo_fe_depth_camera); rig == NULL: depth is registered again (the
+ * state of a new context).  CVO_HIP_ERR_INVALID, the context keeping what it had: a null
+ * context; a frame submitted and not collected; width or height outside [8, 8192]; a
+ * non-finite member; fx, fy or depth_scale <= 0; max_range > 0 && max_range <= min_range; R
+ * further than 1e-3 (largest absolute entry of R R^T - I) from orthonormal or with a
+ * non-positive determinant.  The raw depth, the ray table and the z-buffer take device memory
+ * only once a rig has been set. */
+int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig);
+/* *set = 1 and the rig, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_depth_camera(const cvo_fe_ctx *ctx, cvo_fe_depth_camera *out, int *set);
+
 /* what the last create_pointcloud / collect did */
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out);
 /* copy an intermediate image of the last create_pointcloud to host memory */
@@ -172,6 +249,14 @@ int cvo_fe_camera(int dataset_seq, float cam[5]);
  * qu and qv, width*height int32 each, row-major.  Host only.  CVO_HIP_ERR_INVALID for a null
  * pointer, width or height < 1 and a model cvo_fe_set_camera() would refuse. */
 int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, int32_t *qu, int32_t *qv);
+
+/* The ray table of the registration contract (see cvo_fe_depth_camera): xn and yn,
+ * (height+1) x (width+1) floats each, row-major.  Host only.  CVO_HIP_ERR_INVALID for a null
+ * pointer and a rig cvo_fe_set_depth_camera() would refuse. */
+int cvo_fe_depth_rays(const cvo_fe_depth_camera *rig, float *xn, float *yn);
+/* CVO_HIP_OK for a rig cvo_fe_set_depth_camera() would accept on an idle context, CVO_HIP_ERR_INVALID
+ * otherwise (and for NULL): the one statement of what a rig must satisfy.  Host only. */
+int cvo_fe_check_depth_camera(const cvo_fe_depth_camera *rig);
 
 #ifdef __cplusplus
 }
