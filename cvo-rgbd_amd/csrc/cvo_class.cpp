@@ -58,7 +58,8 @@ void Affine3f::quaternion(float q[4]) const
 
 registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
-      fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false)
+      fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
+      depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -98,6 +99,22 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
             cvo_fe_destroy(fe_);
             fe_ = nullptr;
             throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" + why + ")");
+        }
+        if (have_depth_gate_ && (rc = cvo_fe_set_depth_gate(fe_, &depth_gate_)) != CVO_HIP_OK) {
+            const std::string why = cvo_fe_last_error(fe_);
+            cvo_fe_destroy(fe_);
+            fe_ = nullptr;
+            throw std::runtime_error(std::string("cvo_fe_set_depth_gate: ") + cvo_hip_error_string(rc) + " (" + why + ")");
+        }
+        if (have_mask_) {
+            const bool fits = mask_rows_ == rgb.rows && mask_cols_ == rgb.cols;
+            rc = fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID;
+            if (rc != CVO_HIP_OK) {
+                const std::string why = fits ? cvo_fe_last_error(fe_) : "the mask must have the colour image's size";
+                cvo_fe_destroy(fe_);
+                fe_ = nullptr;
+                throw std::runtime_error(std::string("cvo_fe_set_mask: ") + cvo_hip_error_string(rc) + " (" + why + ")");
+            }
         }
     }
     if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
@@ -177,6 +194,74 @@ void registration::clear_depth_camera()
                                      cvo_fe_last_error(fe_) + ")");
     }
     have_depth_camera_ = false;
+}
+
+void registration::set_depth_gate(const cvo_fe_depth_gate &gate)
+{
+    if (fe_) {
+        const int rc = cvo_fe_set_depth_gate(fe_, &gate);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_depth_gate: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    } else {
+        // (the host-only entry refuses what cvo_fe_set_depth_gate refuses: the answer does not wait for the first image)
+        if (cvo_fe_check_depth_gate(&gate) != CVO_HIP_OK)
+            throw std::runtime_error("set_depth_gate(): finite members, jump_rel >= 0, max_range above min_range, "
+                                     "grow in [0, 3], hole_border 0 or 1, pad_ 0");
+    }
+    depth_gate_ = gate;
+    have_depth_gate_ = true;
+}
+
+void registration::clear_depth_gate()
+{
+    if (fe_) {
+        const int rc = cvo_fe_set_depth_gate(fe_, nullptr);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_depth_gate: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    }
+    have_depth_gate_ = false;
+}
+
+void registration::set_mask(const image_view &mask)
+{
+    if (!mask.data || mask.rows < 1 || mask.cols < 1 || mask.step < (size_t)mask.cols)
+        throw std::runtime_error("set_mask(): a mask of rows x cols bytes, step >= cols");
+    if (fe_) {
+        if (mask.rows != fe_h_ || mask.cols != fe_w_)
+            throw std::runtime_error("set_mask(): the mask must have the colour image's size");
+        const int rc = cvo_fe_set_mask(fe_, (const uint8_t *)mask.data, mask.step);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_mask: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+        have_mask_ = true;   // (the front end holds the bytes: no second copy here)
+        return;
+    }
+    mask_.resize((size_t)mask.rows * mask.cols);
+    for (int y = 0; y < mask.rows; ++y)
+        std::memcpy(mask_.data() + (size_t)y * mask.cols, (const uint8_t *)mask.data + (size_t)y * mask.step, (size_t)mask.cols);
+    mask_rows_ = mask.rows;
+    mask_cols_ = mask.cols;
+    have_mask_ = true;
+}
+
+void registration::set_mask(const uint8_t *mask, size_t stride)
+{
+    if (!fe_) throw std::runtime_error("set_mask(): no image yet, so no size: use the image_view form");
+    set_mask(image_view{mask, fe_h_, fe_w_, stride});
+}
+
+void registration::clear_mask()
+{
+    if (fe_) {
+        const int rc = cvo_fe_set_mask(fe_, nullptr, 0);
+        if (rc != CVO_HIP_OK)
+            throw std::runtime_error(std::string("cvo_fe_set_mask: ") + cvo_hip_error_string(rc) + " (" +
+                                     cvo_fe_last_error(fe_) + ")");
+    }
+    have_mask_ = false;
+    mask_.clear();
 }
 
 void registration::set_pcd(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,

@@ -248,6 +248,178 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_depth_final(uint32_t *z, int np
     }
 }
 
+// The last stage in front of level 0 while a gate or a mask is set (the gate contract of
+// include/cvo_frontend.h, at cvo_fe_depth_gate): the depth plane U that k_fe_rectify, k_fe_depth_final or
+// the upload left becomes the plane every later stage reads, with 0 where a pixel is out of range, on or
+// within `grow` of a depth jump, or masked; the reasons go to a plane of flags.
+// A workgroup owns a tile of 64 x 16 pixels; a thread owns four consecutive pixels of one tile row, so
+// 16 threads cover a row and FE_BLOCK threads the tile, and the depth goes out as one 8-byte store and the
+// flags as one dword per thread, as in the sibling kernels.  The tile is wide and flat because the halo
+// costs per row and per column alike while only the rows are contiguous in memory: 64 x 16 with the
+// largest halo reads 72 x 24 = 1.69 cells per pixel in lines of 144 bytes; 32 x 32 would read 1.56 in
+// lines of 80.
+//   phase 1: U of the tile and a halo of grow + 1 into LDS, row by row (consecutive lanes, consecutive
+//            uint16: a wave reads whole lines).  Every address is tested against the image; a cell outside
+//            holds 0 and is told from a hole by its coordinates in phase 2, never by its value.
+//   phase 2: J of the tile and a halo of grow into LDS bytes, from the eight neighbours in LDS.
+//   phase 3: each thread ORs J over the (2 grow + 1)^2 windows of its four pixels -- the window rows read as
+//            dwords and folded into one bit row first, then four shifts -- applies range and mask, writes.
+// U is read from memory once per cell of tile + halo; the mask and, under a distorting model, qu / qv
+// once per pixel.  LDS: 24 x 72 uint16 + 22 x 72 bytes = 5 KiB per workgroup, no limit on occupancy.  The
+// U rows are 36 dwords apart and the J rows 18: a lane's neighbours above and below sit 4 (18) banks to
+// the side, not on its own bank, and consecutive lanes walk consecutive banks, two (four) cells to a
+// dword.  A group of four that is cut by the right border, or whose first pixel is no multiple of four in
+// the plane (a width that is none), goes pixel by pixel.
+constexpr int FG_TW = 64, FG_TH = 16;            // the tile; FG_TW / 4 * FG_TH == FE_BLOCK
+constexpr int FG_HALO = 4;                       // the largest grow + 1
+constexpr int FG_UW = FG_TW + 2 * FG_HALO, FG_UH = FG_TH + 2 * FG_HALO;               // 72 x 24 cells of U
+constexpr int FG_JW = FG_TW + 2 * (FG_HALO - 1), FG_JH = FG_TH + 2 * (FG_HALO - 1);   // 70 x 22 cells of J
+constexpr int FG_JS = 72;                        // ... in rows of this many bytes
+static_assert((FG_TW / 4) * FG_TH == FE_BLOCK, "one thread per four pixels of the tile");
+
+struct GateArgs {
+    const uint16_t *u;       // w * h: the plane the gate reads
+    uint16_t *depth;         // w * h: the plane every later stage reads
+    uint8_t *flags;          // w * h: CVO_FE_GATE_*
+    const uint8_t *mask;     // w * h on the grid of the image as uploaded, or null: no mask
+    const int32_t *qu, *qv;  // the rectification map if the mask goes through it, or null
+    int w, h;
+    float scale, min_range, max_range, jump_rel;
+    int grow, hole_border;
+};
+
+__device__ __forceinline__ bool fe_gate_masked(const GateArgs &a, size_t i, int qu, int qv)
+{
+    if (!a.qu) return a.mask[i] != 0;
+    const int xn = (qu + 16) >> 5, yn = (qv + 16) >> 5;
+    if (xn < 0 || xn >= a.w || yn < 0 || yn >= a.h) return true;
+    return a.mask[(size_t)yn * a.w + xn] != 0;
+}
+
+__device__ __forceinline__ uint32_t fe_gate_flags(const GateArgs &a, uint32_t u, bool near, bool masked)
+{
+    if (u == 0) return 0u;
+    const float z = (float)u / a.scale;
+    const bool range = (a.min_range > 0.0f && z < a.min_range) || (a.max_range > 0.0f && z > a.max_range);
+    return (masked ? (uint32_t)CVO_FE_GATE_MASKED : 0u) | (range ? (uint32_t)CVO_FE_GATE_RANGE : 0u) |
+           (near ? (uint32_t)CVO_FE_GATE_JUMP : 0u);
+}
+
+// (G is grow, 0..3, a template argument: every loop below has constant bounds and is unrolled, so that a thread's
+// loads from memory and from LDS are in flight together instead of one latency after the other)
+template <int G>
+__global__ void __launch_bounds__(FE_BLOCK) k_fe_depth_gate(const GateArgs a)
+{
+    __shared__ __align__(8) uint16_t s_u[FG_UH * FG_UW];             // (phase 3 reads a thread's four cells at once)
+    __shared__ uint32_t s_jw[FG_JH * FG_JS / 4];                     // bytes, read as dwords in phase 3
+    uint8_t *s_j = reinterpret_cast<uint8_t *>(s_jw);
+    const int tx0 = blockIdx.x * FG_TW, ty0 = blockIdx.y * FG_TH;
+    constexpr int g = G;
+    const bool jumps = a.jump_rel > 0.0f || a.hole_border != 0;      // (else J is 0 everywhere)
+    // phase 1: LDS cell (r, c) is pixel (tx0 - FG_HALO + c, ty0 - FG_HALO + r); the rows the halo of grow + 1 needs
+    {
+        constexpr int r0 = FG_HALO - (g + 1), n = (FG_TH + 2 * (g + 1)) * FG_UW;
+#pragma unroll
+        for (int k = 0; k < (n + FE_BLOCK - 1) / FE_BLOCK; ++k) {
+            const int idx = k * FE_BLOCK + (int)threadIdx.x;
+            if (idx < n) {
+                const int r = r0 + idx / FG_UW, c = idx % FG_UW;
+                const int x = tx0 - FG_HALO + c, y = ty0 - FG_HALO + r;
+                uint16_t v = 0;
+                if (x >= 0 && x < a.w && y >= 0 && y < a.h) v = a.u[(size_t)y * a.w + x];
+                s_u[r * FG_UW + c] = v;
+            }
+        }
+    }
+    __syncthreads();
+    // phase 2: J cell (r, c) is pixel (tx0 - 3 + c, ty0 - 3 + r), i.e. U cell (r + 1, c + 1); the nine cells are
+    // read first (all of them lie in the LDS image, whatever the pixel), then judged
+    if (jumps) {
+        constexpr int r0 = FG_HALO - 1 - g, n = (FG_TH + 2 * g) * FG_JW;
+#pragma unroll
+        for (int k = 0; k < (n + FE_BLOCK - 1) / FE_BLOCK; ++k) {
+            const int idx = k * FE_BLOCK + (int)threadIdx.x;
+            if (idx < n) {
+                const int r = r0 + idx / FG_JW, c = idx % FG_JW;
+                const int x = tx0 - (FG_HALO - 1) + c, y = ty0 - (FG_HALO - 1) + r;
+                uint32_t u9[9];
+#pragma unroll
+                for (int q = 0; q < 9; ++q) u9[q] = s_u[(r + q / 3) * FG_UW + c + q % 3];
+                const uint32_t up = u9[4];
+                bool mark = false;
+#pragma unroll
+                for (int q = 0; q < 9; ++q) {
+                    if (q == 4) continue;
+                    const int xq = x + q % 3 - 1, yq = y + q / 3 - 1;
+                    const bool inside = xq >= 0 && xq < a.w && yq >= 0 && yq < a.h;
+                    const uint32_t uq = u9[q], m = min(up, uq), D = max(up, uq) - m;
+                    const bool by = uq == 0 ? a.hole_border != 0 : (a.jump_rel > 0.0f && (float)D > a.jump_rel * (float)m);
+                    mark = mark || (inside && by);
+                }
+                // (a pixel outside the image marks nobody, and neither does one without depth)
+                mark = mark && up != 0 && x >= 0 && x < a.w && y >= 0 && y < a.h;
+                s_j[r * FG_JS + c] = mark ? 1 : 0;
+            }
+        }
+    }
+    __syncthreads();
+    // phase 3
+    const int ry = threadIdx.x / (FG_TW / 4), cx = 4 * (threadIdx.x % (FG_TW / 4));
+    const int x0 = tx0 + cx, y = ty0 + ry;
+    if (x0 >= a.w || y >= a.h) return;
+    // the window rows of the four pixels ORed as three dwords -- J columns cx .. cx + 11, of which the windows
+    // reach cx + 3 - g .. cx + 6 + g -- and their bytes (0 / 1) gathered into bits: bit j of `cols` is column cx + j
+    uint32_t cols = 0;
+    if (jumps) {
+        uint32_t c0 = 0, c1 = 0, c2 = 0;
+#pragma unroll
+        for (int dy = -g; dy <= g; ++dy) {
+            const uint32_t *row = s_jw + ((ry + FG_HALO - 1 + dy) * FG_JS + cx) / 4;
+            c0 |= row[0]; c1 |= row[1];
+            if (g >= 2) c2 |= row[2];
+        }
+        auto bits = [](uint32_t v) { return (v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u); };
+        cols = (bits(c0) | (bits(c1) << 4) | (bits(c2) << 8)) >> (FG_HALO - 1 - g);   // bit j: column cx + 3 - g + j
+    }
+    const uint32_t win = (1u << (2 * g + 1)) - 1u;
+    const uint2 own2 = *reinterpret_cast<const uint2 *>(s_u + (ry + FG_HALO) * FG_UW + cx + FG_HALO);   // (8-byte aligned)
+    const uint32_t own[4] = {own2.x & 0xFFFFu, own2.x >> 16, own2.y & 0xFFFFu, own2.y >> 16};
+    const size_t i0 = (size_t)y * a.w + x0;
+    if (x0 + 4 <= a.w && (i0 & 3) == 0) {
+        bool masked[4] = {false, false, false, false};
+        if (a.mask) {
+            if (a.qu) {
+                const int4 u4 = *reinterpret_cast<const int4 *>(a.qu + i0), v4 = *reinterpret_cast<const int4 *>(a.qv + i0);
+                masked[0] = fe_gate_masked(a, i0, u4.x, v4.x); masked[1] = fe_gate_masked(a, i0 + 1, u4.y, v4.y);
+                masked[2] = fe_gate_masked(a, i0 + 2, u4.z, v4.z); masked[3] = fe_gate_masked(a, i0 + 3, u4.w, v4.w);
+            } else {
+                const uint32_t m4 = *reinterpret_cast<const uint32_t *>(a.mask + i0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) masked[k] = ((m4 >> (8 * k)) & 255u) != 0;
+            }
+        }
+        uint32_t d[4], f[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t u = own[k];
+            f[k] = fe_gate_flags(a, u, ((cols >> k) & win) != 0, masked[k]);
+            d[k] = f[k] ? 0u : u;
+        }
+        *reinterpret_cast<uint2 *>(a.depth + i0) = make_uint2(d[0] | (d[1] << 16), d[2] | (d[3] << 16));
+        *reinterpret_cast<uint32_t *>(a.flags + i0) = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
+    } else {
+        const int n = min(4, a.w - x0);
+        for (int k = 0; k < n; ++k) {
+            const size_t i = i0 + k;
+            const uint32_t u = own[k];
+            const bool masked = a.mask && fe_gate_masked(a, i, a.qu ? a.qu[i] : 0, a.qu ? a.qv[i] : 0);
+            const uint32_t f = fe_gate_flags(a, u, ((cols >> k) & win) != 0, masked);
+            a.depth[i] = f ? (uint16_t)0 : (uint16_t)u;
+            a.flags[i] = (uint8_t)f;
+        }
+    }
+}
+
 // Level 0 in one pass.  load_image: cv::cvtColor RGB2GRAY and RGB2HSV on 8-bit data,
 // channel 0 taken as R (ref src/pcd_generator.cpp:389-390), OpenCV's fixed-point
 // definitions; the grey image as float is level 0 of the pyramid (ref :53-61); its
@@ -843,6 +1015,15 @@ struct cvo_fe_ctx {
     uint16_t *rig_depth = nullptr;
     float2 *rays = nullptr;        // (dh + 1) * (dw + 1)
     uint32_t *zbuf = nullptr;      // rect_plane(np) entries, FE_Z_EMPTY between frames
+    // the caller's gate and mask (cvo_fe_set_depth_gate, cvo_fe_set_mask); with either, frames pass k_fe_depth_gate
+    cvo_fe_depth_gate gate{};
+    bool has_gate = false, has_mask = false;
+    bool mask_dirty = false;       // h_mask holds bytes the device has not seen yet: the next submit() uploads them
+    // with the first gate or mask: the plane the stages in front of the gate write, and the flags
+    uint16_t *ungated = nullptr;   // rect_plane(np) entries
+    uint8_t *gate_flags = nullptr;
+    // with the first mask: its device plane and its pinned staging image
+    uint8_t *d_mask = nullptr, *h_mask = nullptr;
     std::string err;
 };
 
@@ -900,6 +1081,50 @@ bool rig_ok(const cvo_fe_depth_camera &r)
     const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) +
                        R[2] * (R[3] * R[7] - R[4] * R[6]);
     return det > 0.0;
+}
+
+// what cvo_fe_set_depth_gate accepts
+bool gate_ok(const cvo_fe_depth_gate &g)
+{
+    static_assert(sizeof(cvo_fe_depth_gate) == 3 * sizeof(float) + 3 * sizeof(int32_t), "24 bytes, no padding");
+    if (!std::isfinite(g.min_range) || !std::isfinite(g.max_range) || !std::isfinite(g.jump_rel)) return false;
+    if (g.jump_rel < 0.0f) return false;
+    if (g.max_range > 0.0f && g.max_range <= g.min_range) return false;
+    if (g.grow < 0 || g.grow > FG_HALO - 1) return false;
+    return (g.hole_border == 0 || g.hole_border == 1) && g.pad_ == 0;
+}
+
+inline bool gate_active(const cvo_fe_ctx *ctx) { return ctx->has_gate || ctx->has_mask; }
+
+// the depth plane the stages in front of level 0 write: the gate's input while it runs
+inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? ctx->ungated : ctx->depth; }
+
+// after a change of what a frame's sequence is: the graphs captured before hold the old buffers and numbers
+void drop_graphs(cvo_fe_ctx *ctx)
+{
+    ctx->cam_gen++;
+    for (auto &g : ctx->graphs) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    ctx->graphs.clear();
+}
+
+// the ungated plane and the flags, with the first gate or mask; both or neither
+int gate_buffers(cvo_fe_ctx *ctx)
+{
+    if (ctx->ungated) return CVO_HIP_OK;
+    uint16_t *u = nullptr;
+    uint8_t *f = nullptr;
+    const size_t n = rect_plane(ctx->np);
+    if (dev_alloc(&u, n) != hipSuccess || dev_alloc(&f, n) != hipSuccess) {
+        if (u) (void)hipFree(u);
+        (void)hipGetLastError();
+        return fail(ctx, CVO_HIP_ERR_NOMEM, "device memory for the ungated depth and the gate's flags");
+    }
+    ctx->ungated = u;
+    ctx->gate_flags = f;
+    return CVO_HIP_OK;
 }
 
 // the Canny path of a frame whose selection came out short (host loop: rare)
@@ -1139,6 +1364,83 @@ int cvo_fe_get_depth_camera(const cvo_fe_ctx *ctx, cvo_fe_depth_camera *out, int
     return CVO_HIP_OK;
 }
 
+int cvo_fe_check_depth_gate(const cvo_fe_depth_gate *gate)
+{
+    return gate && gate_ok(*gate) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID;
+}
+
+int cvo_fe_set_depth_gate(cvo_fe_ctx *ctx, const cvo_fe_depth_gate *gate)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_gate: a frame is in flight");
+    if (gate && !gate_ok(*gate))
+        return fail(ctx, CVO_HIP_ERR_INVALID,
+                    "set_depth_gate: finite members, jump_rel >= 0, max_range above min_range, grow in [0, 3], "
+                    "hole_border 0 or 1, pad_ 0");
+    if (!gate && !ctx->has_gate) return CVO_HIP_OK;
+    if (gate && ctx->has_gate && std::memcmp(gate, &ctx->gate, sizeof(*gate)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    if (gate) {
+        const int rc = gate_buffers(ctx);
+        if (rc) return rc;
+    }
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->has_gate = gate != nullptr;
+    ctx->gate = gate ? *gate : cvo_fe_depth_gate{};
+    drop_graphs(ctx);   // (the gate's numbers and the planes of a frame are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_depth_gate(const cvo_fe_ctx *ctx, cvo_fe_depth_gate *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_gate ? ctx->gate : cvo_fe_depth_gate{};
+    if (set) *set = ctx->has_gate ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_mask: a frame is in flight");
+    const int w = ctx->d.w, h = ctx->d.h;
+    if (mask && stride < (size_t)w) return fail(ctx, CVO_HIP_ERR_INVALID, "set_mask: stride below the width");
+    if (!mask && !ctx->has_mask) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    if (mask) {
+        const int rc = gate_buffers(ctx);
+        if (rc) return rc;
+        if (!ctx->d_mask) {   // (the two come and go together)
+            uint8_t *dm = nullptr, *hm = nullptr;
+            if (dev_alloc(&dm, rect_plane(ctx->np)) != hipSuccess || pin_alloc(&hm, (size_t)ctx->np) != hipSuccess) {
+                if (dm) (void)hipFree(dm);
+                (void)hipGetLastError();
+                return fail(ctx, CVO_HIP_ERR_NOMEM, "set_mask: device and pinned memory for the mask");
+            }
+            ctx->d_mask = dm;
+            ctx->h_mask = hm;
+        }
+    }
+    // (no frame is in flight: once the stream is idle no upload reads the staging image any more)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    if (mask) {
+        if (stride == (size_t)w) std::memcpy(ctx->h_mask, mask, (size_t)ctx->np);
+        else
+            for (int y = 0; y < h; ++y) std::memcpy(ctx->h_mask + (size_t)y * w, mask + (size_t)y * stride, (size_t)w);
+        ctx->mask_dirty = true;
+    }
+    // new contents go to the same address: only a mask that appears or disappears changes a frame's sequence
+    if ((mask != nullptr) != ctx->has_mask) {
+        ctx->has_mask = mask != nullptr;
+        drop_graphs(ctx);
+    }
+    return CVO_HIP_OK;
+}
+
 int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
 {
     cvo_lock::Api api_guard;
@@ -1229,14 +1531,14 @@ int cvo_fe_destroy(cvo_fe_ctx *ctx)
                    ctx->I[0], ctx->I[1], ctx->I[2], ctx->ag[0], ctx->ag[1], ctx->ag[2], ctx->dx0, ctx->dy0,
                    ctx->map, ctx->ths, ctx->ths_s, ctx->pos, ctx->feat, ctx->sdiv, ctx->hdiv, ctx->cnt,
                    ctx->mag, ctx->grad, ctx->ctrl, ctx->blk_cnt, ctx->raw_img, ctx->raw_depth, ctx->rect_map,
-                   ctx->rig_depth, ctx->rays, ctx->zbuf};
+                   ctx->rig_depth, ctx->rays, ctx->zbuf, ctx->ungated, ctx->gate_flags, ctx->d_mask};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (auto &g : ctx->graphs) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
         if (g.graph) (void)hipGraphDestroy(g.graph);
     }
-    void *pin[] = {ctx->h_img, ctx->h_depth, ctx->h_ctrl, ctx->h_pos, ctx->h_feat};
+    void *pin[] = {ctx->h_img, ctx->h_depth, ctx->h_ctrl, ctx->h_pos, ctx->h_feat, ctx->h_mask};
     for (void *p : pin)
         if (p) (void)hipHostFree(p);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1377,6 +1679,11 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
     *ctx->h_ctrl = c0;
+    // a mask set since the last frame: in front of the frame, outside the captured graph (its address is the graph's)
+    if (ctx->has_mask && ctx->mask_dirty) {
+        FE_HIP(hipMemcpyAsync(ctx->d_mask, ctx->h_mask, (size_t)np, hipMemcpyHostToDevice, s));
+        ctx->mask_dirty = false;
+    }
     // Everything from here to the copies back is the same sequence for every frame (fixed
     // buffers, fixed pinned staging): captured once per (camera, feature type, num_want,
     // output mode) and launched as one hipGraph -- 3 copies in, 11 kernels, the copies out.
@@ -1430,13 +1737,15 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
     FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img : ctx->img, ctx->h_img, (size_t)np * 3, hipMemcpyHostToDevice, s));
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
-    uint16_t *depth_in = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : ctx->depth;
+    // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
+    uint16_t *plane = depth_plane(ctx);
+    uint16_t *depth_in = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : plane;
     FE_HIP(hipMemcpyAsync(depth_in, ctx->h_depth, (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl, ctx->h_ctrl, sizeof(FeCtrl), hipMemcpyHostToDevice, s));
     if (ctx->rectify)
         hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img,
                            ctx->has_rig ? (const uint16_t *)nullptr : ctx->raw_depth, ctx->rect_map,
-                           ctx->rect_map + rect_plane(np), w, h, ctx->img, ctx->depth);
+                           ctx->rect_map + rect_plane(np), w, h, ctx->img, plane);
     if (ctx->has_rig) {
         const cvo_fe_depth_camera &r = ctx->rig;
         DepthWarpArgs a{};
@@ -1451,7 +1760,33 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
             a.cam[0] = m.depth_scale; a.cam[1] = m.fx; a.cam[2] = m.fy; a.cam[3] = m.cx; a.cam[4] = m.cy;
         } else cvo_fe_camera(dataset_seq, a.cam);   // (never fails here: an index outside the table means row 0)
         hipLaunchKernelGGL(k_fe_depth_warp, dim3(blocks(a.dw * a.dh)), dim3(FE_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf, np, ctx->depth);
+        hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf, np, plane);
+    }
+    if (gate_active(ctx)) {
+        GateArgs g{};
+        g.u = ctx->ungated; g.depth = ctx->depth; g.flags = ctx->gate_flags;
+        g.mask = ctx->has_mask ? ctx->d_mask : nullptr;
+        // the mask lies on the grid of the image as uploaded: under a distorting model it follows the map
+        g.qu = ctx->has_mask && ctx->rectify ? ctx->rect_map : nullptr;
+        g.qv = g.qu ? ctx->rect_map + rect_plane(np) : nullptr;
+        g.w = w; g.h = h;
+        if (ctx->custom) g.scale = ctx->cam.depth_scale;
+        else {
+            float cam[5];
+            cvo_fe_camera(dataset_seq, cam);
+            g.scale = cam[0];
+        }
+        if (ctx->has_gate) {
+            g.min_range = ctx->gate.min_range; g.max_range = ctx->gate.max_range; g.jump_rel = ctx->gate.jump_rel;
+            g.grow = ctx->gate.grow; g.hole_border = ctx->gate.hole_border;
+        }
+        const dim3 tiles((w + FG_TW - 1) / FG_TW, (h + FG_TH - 1) / FG_TH);
+        switch (g.grow) {   // (0..3: cvo_fe_check_depth_gate)
+        case 0: hipLaunchKernelGGL(k_fe_depth_gate<0>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        case 1: hipLaunchKernelGGL(k_fe_depth_gate<1>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        case 2: hipLaunchKernelGGL(k_fe_depth_gate<2>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        default: hipLaunchKernelGGL(k_fe_depth_gate<3>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        }
     }
 
     const FeDims &d = ctx->d;
@@ -1591,14 +1926,20 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_RECT_BGR: src = ctx->img; need = np * 3; break;
     case CVO_FE_STAGE_RECT_DEPTH: src = ctx->depth; need = np * 2; break;
     case CVO_FE_STAGE_RAW_DEPTH:
-        src = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : ctx->depth;
+        src = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : depth_plane(ctx);
         need = (size_t)ctx->dw * ctx->dh * 2;
         break;
+    case CVO_FE_STAGE_UNGATED_DEPTH: src = depth_plane(ctx); need = np * 2; break;
+    case CVO_FE_STAGE_GATE: src = gate_active(ctx) ? ctx->gate_flags : nullptr; need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");
     FE_HIP(hipSetDevice(ctx->device));
     FE_HIP(hipStreamSynchronize(ctx->stream));
+    if (!src) {   // (the flags of a context without gate and mask: there is no such plane, and nothing is flagged)
+        std::memset(out, 0, need);
+        return CVO_HIP_OK;
+    }
     if (stage == CVO_FE_STAGE_HSV) {   // packed words on the device, 3 bytes per pixel for the caller
         uint32_t *tmp = new (std::nothrow) uint32_t[np];
         if (!tmp) return fail(ctx, CVO_HIP_ERR_NOMEM, "read_stage");

@@ -24,13 +24,15 @@ from . import capi
 
 FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
- STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH) = range(13)
+ STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE) = range(15)
+GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
            "cvo_fe_camera", "cvo_fe_set_camera", "cvo_fe_get_camera", "cvo_fe_rectify_map",
            "cvo_fe_set_depth_camera", "cvo_fe_get_depth_camera", "cvo_fe_depth_rays",
-           "cvo_fe_check_depth_camera")
+           "cvo_fe_check_depth_camera", "cvo_fe_set_depth_gate", "cvo_fe_get_depth_gate", "cvo_fe_check_depth_gate",
+           "cvo_fe_set_mask")
 
 
 class Info(C.Structure):
@@ -92,6 +94,30 @@ class DepthCamera(C.Structure):
                 "min_range=%r, max_range=%r)" % self.astuple())
 
 
+class DepthGate(C.Structure):
+    """cvo_fe_depth_gate: which pixels with a depth keep it (the gate contract of include/cvo_frontend.h).
+    `min_range` / `max_range` in metres along the colour camera's axis, <= 0: no limit on that side;
+    `jump_rel`: the relative depth jump between neighbours that marks a discontinuity, 0: no jump test;
+    `grow` 0..3: the pixels around a marked one that go with it; `hole_border` 1: a pixel beside one
+    without depth is marked too."""
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("jump_rel", C.c_float), ("grow", C.c_int32),
+                ("hole_border", C.c_int32), ("pad_", C.c_int32)]
+
+    def __init__(self, min_range=0.0, max_range=0.0, jump_rel=0.0, grow=0, hole_border=0, pad_=0):
+        super().__init__(min_range, max_range, jump_rel, int(grow), int(hole_border), int(pad_))
+
+    def astuple(self):
+        return (self.min_range, self.max_range, self.jump_rel, self.grow, self.hole_border)
+
+    def __eq__(self, other):
+        return isinstance(other, DepthGate) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "DepthGate(min_range=%r, max_range=%r, jump_rel=%r, grow=%r, hole_border=%r)" % self.astuple()
+
+
 # The published calibrations of the TUM RGB-D sequences (fx fy cx cy, d0..d4; depth 5000 per metre).
 # The reference's table (camera(1..3)) holds the same intrinsics without the distortion.  The entries are
 # shared by every user of the module: read them, hand them to set_camera() (which copies), and make a model of
@@ -136,6 +162,10 @@ def lib():
         L.cvo_fe_get_depth_camera.argtypes = [vp, C.POINTER(DepthCamera), C.POINTER(C.c_int)]
         L.cvo_fe_depth_rays.argtypes = [C.POINTER(DepthCamera), fp, fp]
         L.cvo_fe_check_depth_camera.argtypes = [C.POINTER(DepthCamera)]
+        L.cvo_fe_set_depth_gate.argtypes = [vp, C.POINTER(DepthGate)]
+        L.cvo_fe_get_depth_gate.argtypes = [vp, C.POINTER(DepthGate), C.POINTER(C.c_int)]
+        L.cvo_fe_check_depth_gate.argtypes = [C.POINTER(DepthGate)]
+        L.cvo_fe_set_mask.argtypes = [vp, u8p, C.c_size_t]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -184,6 +214,11 @@ def depth_rays(rig):
 def check_depth_camera(rig):
     """True for a DepthCamera set_depth_camera() accepts (cvo_fe_check_depth_camera).  Host only."""
     return lib().cvo_fe_check_depth_camera(C.byref(rig)) == 0
+
+
+def check_depth_gate(gate):
+    """True for a DepthGate set_depth_gate() accepts (cvo_fe_check_depth_gate).  Host only."""
+    return lib().cvo_fe_check_depth_gate(C.byref(gate)) == 0
 
 
 class PcdGenerator:
@@ -295,6 +330,34 @@ class PcdGenerator:
 
     depth_rays = staticmethod(depth_rays)
 
+    def set_depth_gate(self, gate):
+        """A DepthGate for every following frame: pixels out of range or on / within `grow` of a depth
+        discontinuity give no point (the gate contract of include/cvo_frontend.h); None: no gate, as for a
+        new object."""
+        self._chk(lib().cvo_fe_set_depth_gate(self._h, None if gate is None else C.byref(gate)), "set_depth_gate")
+
+    def depth_gate(self):
+        """The DepthGate set, or None."""
+        out, isset = DepthGate(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_depth_gate(self._h, C.byref(out), C.byref(isset)), "get_depth_gate")
+        return out if isset.value else None
+
+    def set_mask(self, mask):
+        """A mask for every following frame: h x w uint8 or bool on the grid of the colour image as uploaded
+        (any row stride), non-zero = no point from this pixel; None: no mask.  The bytes are copied; the mask
+        stays until it is replaced or cleared."""
+        if mask is None:
+            self._chk(lib().cvo_fe_set_mask(self._h, None, 0), "set_mask")
+            return
+        mask = np.asarray(mask)
+        if mask.dtype == np.bool_:
+            mask = mask.view(np.uint8)
+        if mask.dtype != np.uint8 or mask.shape != (self.height, self.width):
+            raise ValueError("expected a %dx%d uint8 or bool mask" % (self.height, self.width))
+        if mask.strides[1] != 1 or mask.strides[0] < self.width:
+            mask = np.ascontiguousarray(mask)
+        self._chk(lib().cvo_fe_set_mask(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.strides[0]), "set_mask")
+
     def info(self):
         out = Info()
         self._chk(lib().cvo_fe_get_info(self._h, C.byref(out)), "get_info")
@@ -308,7 +371,8 @@ class PcdGenerator:
                   STAGE_AG2: ((h // 4, w // 4), np.float32), STAGE_THS: ((h // 32, w // 32), np.float32),
                   STAGE_DX0: ((h, w), np.float32), STAGE_DY0: ((h, w), np.float32), STAGE_EDGES: ((h, w), np.uint8),
                   STAGE_RECT_BGR: ((h, w, 3), np.uint8), STAGE_RECT_DEPTH: ((h, w), np.uint16),
-                  STAGE_RAW_DEPTH: (self._dshape, np.uint16)}
+                  STAGE_RAW_DEPTH: (self._dshape, np.uint16), STAGE_UNGATED_DEPTH: ((h, w), np.uint16),
+                  STAGE_GATE: ((h, w), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -354,12 +418,14 @@ def load_img(rgb_path, depth_path):
 
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
-               camera=None, depth_camera=None):
+               camera=None, depth_camera=None, depth_gate=None, mask=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
     are registered to colour on the device; None leaves the generator as it is.
+    `depth_gate`: a DepthGate for the generator; `mask`: an h x w mask for it, one for all frames (a caller with
+    a mask per frame drives the generator itself); None leaves the generator as it is.
     `device`: the cloud goes from the front end to the registration in device memory
     (cvo_fe_collect_device -> cvo_hip_set_*_device) instead of through host arrays.
     `prefetch`: frame k+1 is in the front end (its own, low-priority stream) while frame k
@@ -379,6 +445,10 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_camera(camera)
     if depth_camera is not None:
         gen.set_depth_camera(depth_camera)
+    if depth_gate is not None:
+        gen.set_depth_gate(depth_gate)
+    if mask is not None:
+        gen.set_mask(mask)
     gen.set_device_output(device)
     gen.submit(cur[1], cur[2], dataset_seq, ftype)
     while cur is not None:
@@ -407,13 +477,14 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
-                  generator=None, camera=None, depth_camera=None):
+                  generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
     features, acvo the HSV ones (ref src/cvo.cpp:329, src/adaptive_cvo.cpp:451).  `camera`: as in
     run_frames, e.g. TUM_CAMERAS["fr1"] for a freiburg1 sequence with its lens distortion removed.
-    `depth_camera`: as in run_frames, for a recording whose depth images are not registered to colour."""
+    `depth_camera`: as in run_frames, for a recording whose depth images are not registered to colour.
+    `depth_gate`, `mask`: as in run_frames, e.g. DepthGate(0.8, 4.0, 0.05, 1) for a Kinect-class sensor."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -424,4 +495,4 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
             yield name, bgr, depth
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
-                      depth_camera=depth_camera)
+                      depth_camera=depth_camera, depth_gate=depth_gate, mask=mask)

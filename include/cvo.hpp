@@ -18,6 +18,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "cvo_frontend.h"
 #include "cvo_hip.h"
@@ -115,6 +116,19 @@ class registration {
     // for a rig the front end refuses.  clear_depth_camera(): depth is registered to colour again.
     void set_depth_camera(const cvo_fe_depth_camera &rig);
     void clear_depth_camera();
+    // A gate on the depth values for the image form of set_pcd() / run_cvo(): cvo_fe_set_depth_gate.  Pixels out
+    // of range or on / beside a depth discontinuity give no point (the contract: cvo_frontend.h).  May be called
+    // before the first image; throws for a gate the front end refuses.  clear_depth_gate(): no gate.
+    void set_depth_gate(const cvo_fe_depth_gate &gate);
+    void clear_depth_gate();
+    // A mask for every following frame: rows x cols bytes of the colour image's size, `step` bytes apart,
+    // non-zero = no point from this pixel (cvo_fe_set_mask).  The bytes are copied.  May be called before the
+    // first image: the copy is handed to the front end when it is created, and a mask of another size than that
+    // image throws then.  The form without a size takes the size of the images seen so far, so it throws
+    // before the first one.  clear_mask(): no mask.
+    void set_mask(const image_view &mask);
+    void set_mask(const uint8_t *mask, size_t stride);
+    void clear_mask();
     int num_points_last_frame() const { return fe_points_; }
     // Batched mode: align() of `count` objects (each with its moving cloud set) in
     // one call, their kernel launches shared (cvo_hip_align_many).  The result of
@@ -138,6 +152,11 @@ class registration {
     bool have_camera_;
     cvo_fe_depth_camera depth_camera_;   // what set_depth_camera() gave, likewise
     bool have_depth_camera_;
+    cvo_fe_depth_gate depth_gate_;       // what set_depth_gate() gave, likewise
+    bool have_depth_gate_;
+    std::vector<uint8_t> mask_;          // what set_mask() gave (dense rows), likewise
+    int mask_rows_, mask_cols_;
+    bool have_mask_;
     void check(int status, const char *what);
     void publish();
     void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep);

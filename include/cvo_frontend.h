@@ -25,7 +25,10 @@
  * (cvo_fe_set_depth_camera): another size, pinhole and lens, mounted beside the
  * colour camera; every frame then registers the depth image into the colour
  * camera's frame on the device.  The registration contract is stated at
- * cvo_fe_depth_camera below.
+ * cvo_fe_depth_camera below.  And a gate on the depth values themselves
+ * (cvo_fe_set_depth_gate, cvo_fe_set_mask): pixels out of range, on or beside a depth
+ * discontinuity, or under a caller's mask lose their depth before any later stage reads it.
+ * The gate contract is stated at cvo_fe_depth_gate below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -59,8 +62,16 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_RECT_DEPTH = 11,  /* ... and the depth image: w*h uint16.  Without a distorting
                                          camera model these two are the input images.  With a depth
                                          camera this one is the registered depth (colour size). */
-       CVO_FE_STAGE_RAW_DEPTH = 12 }; /* the depth image as uploaded: the depth camera's width*height
+       CVO_FE_STAGE_RAW_DEPTH = 12,   /* the depth image as uploaded: the depth camera's width*height
                                          uint16, or w*h without a depth camera */
+       CVO_FE_STAGE_UNGATED_DEPTH = 13,   /* the depth plane the gate read: w*h uint16.  Without a gate
+                                             or mask it equals RECT_DEPTH (which, with one, is the gated
+                                             plane: still "the depth image every later stage read") */
+       CVO_FE_STAGE_GATE = 14 };      /* the gate's flags: w*h uint8, an OR of CVO_FE_GATE_*; all zero
+                                         without a gate or mask */
+
+/* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
+enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
@@ -159,6 +170,50 @@ typedef struct cvo_fe_depth_camera {
     float min_range, max_range;          /* metres along the depth camera's axis; <= 0: no limit on that side */
 } cvo_fe_depth_camera;
 
+/* A gate on the depth values: which pixels with a depth keep it.
+ *
+ * THE GATE CONTRACT.  While a gate or a mask (cvo_fe_set_mask) is set every frame of the context
+ * passes its depth plane -- as it stands after the rectification or the registration above, w x h
+ * uint16, called U here -- through one more stage before anything else reads it; level 0, the
+ * selector, the Canny top-up and the back-projection then run unchanged on the gated plane.  The
+ * results are defined by the arithmetic below, not by the device.  It is this library's own
+ * definition and is NOT pinned against any SDK's filter.
+ *
+ * `scale` is depth_scale of the colour camera in force for the frame (the cvo_fe_set_camera model,
+ * else the table row of dataset_seq).  For a pixel p with U(p) != 0:
+ *   range (CVO_FE_GATE_RANGE): z = (float)U(p) / scale in float32, correctly rounded; flagged if
+ *     (min_range > 0 && z < min_range) || (max_range > 0 && z > max_range) -- the rule and the
+ *     arithmetic of the rig's min_range / max_range.  (At scale 5000 and min_range 0.8f a pixel of
+ *     4000 is kept and one of 3999 is dropped.)
+ *   jump mark J(p): for each of the eight neighbours q inside the image,
+ *     U(q) != 0: m = min(U(p), U(q)), D = max(U(p), U(q)) - m; q marks p iff jump_rel > 0 and
+ *       (float)D > jump_rel * (float)m  (float32: one multiplication, one comparison; both integers
+ *       are exact in float32 and nothing can be contracted);
+ *     U(q) == 0: q marks p iff hole_border.
+ *     Neighbours outside the image never mark; J(p) = 0 where U(p) == 0.  Both sides of a step are
+ *     marked: that is intended.  The threshold is relative because that bounds the slope of a
+ *     surface against its ray whatever the range: two neighbouring rays 1/f apart see a depth step
+ *     of z tan(theta) / f on a surface inclined by theta, so D/m > jump_rel means
+ *     tan(theta) > about f * jump_rel at 1 m as at 4 m; an absolute threshold would not.
+ *   near a jump (CVO_FE_GATE_JUMP): flagged if some q inside the image with
+ *     max(|dx|, |dy|) <= grow has J(q) = 1.  Marks are computed on U: range and mask do not
+ *     change them.
+ *   masked (CVO_FE_GATE_MASKED): the mask is height rows of width bytes on the grid of the colour
+ *     image as uploaded, non-zero = drop.  Without a distorting model: flagged if mask[p] != 0.
+ *     With one the mask goes through the rectification map by the depth rule of the rectification
+ *     contract: (xn, yn) = (floor((qu+16)/32), floor((qv+16)/32)); masked if that lies outside the
+ *     image, else if mask[yn][xn] != 0.
+ * GATE(p) is the OR of the flags, and 0 where U(p) == 0; RECT_DEPTH(p) = GATE(p) ? 0 : U(p).
+ * Selection is untouched: a gated pixel is a selected pixel without depth, so num_selected does
+ * not move and num_points drops. */
+typedef struct cvo_fe_depth_gate {
+    float   min_range, max_range;  /* metres along the colour camera's axis; <= 0: no limit on that side */
+    float   jump_rel;              /* relative depth jump that marks a discontinuity; 0: no jump test */
+    int32_t grow;                  /* 0..3: pixels around a marked pixel that go with it (Chebyshev) */
+    int32_t hole_border;           /* 1: a valid pixel beside a pixel without depth is marked too */
+    int32_t pad_;                  /* must be 0 */
+} cvo_fe_depth_gate;               /* 24 bytes, no padding */
+
 /* One context per image size, device and stream.  `stream` as in cvo_hip_create
  * (NULL: a stream of its own).  Images must be at least 64 x 64. */
 int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **out);
@@ -234,6 +289,25 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig);
 /* *set = 1 and the rig, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_depth_camera(const cvo_fe_ctx *ctx, cvo_fe_depth_camera *out, int *set);
 
+/* While a gate is set every frame passes its depth through the gate contract at cvo_fe_depth_gate;
+ * gate == NULL: no gate (the state of a new context).  CVO_HIP_ERR_INVALID, the context keeping
+ * what it had: a null context; a frame submitted and not collected; whatever
+ * cvo_fe_check_depth_gate refuses.  A gate whose tests are all off (min_range <= 0, max_range <= 0,
+ * jump_rel == 0, hole_border == 0) is accepted and gates nothing.  The ungated plane and the flags
+ * take device memory only once a gate or a mask has been set. */
+int cvo_fe_set_depth_gate(cvo_fe_ctx *ctx, const cvo_fe_depth_gate *gate);
+/* *set = 1 and the gate, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_depth_gate(const cvo_fe_ctx *ctx, cvo_fe_depth_gate *out, int *set);
+/* A mask for every following frame: height rows of width bytes, `stride` bytes apart, non-zero =
+ * this pixel gives no point; mask == NULL: no mask (the state of a new context).  The bytes are
+ * copied into a pinned image of the context before the call returns; the next submit() uploads
+ * them in front of its frame.  The mask stays until it is replaced or cleared: a caller with a mask
+ * per frame calls this before every submit().  Mask and gate are independent: either alone makes
+ * the gate stage run.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a
+ * frame submitted and not collected; stride < width.  The device and the pinned mask take memory
+ * only once a mask has been set. */
+int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride);
+
 /* what the last create_pointcloud / collect did */
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out);
 /* copy an intermediate image of the last create_pointcloud to host memory */
@@ -257,6 +331,10 @@ int cvo_fe_depth_rays(const cvo_fe_depth_camera *rig, float *xn, float *yn);
 /* CVO_HIP_OK for a rig cvo_fe_set_depth_camera() would accept on an idle context, CVO_HIP_ERR_INVALID
  * otherwise (and for NULL): the one statement of what a rig must satisfy.  Host only. */
 int cvo_fe_check_depth_camera(const cvo_fe_depth_camera *rig);
+/* CVO_HIP_OK for a gate cvo_fe_set_depth_gate() would accept on an idle context, CVO_HIP_ERR_INVALID
+ * otherwise: NULL; a non-finite float; jump_rel < 0; max_range > 0 && max_range <= min_range; grow
+ * outside [0, 3]; hole_border not 0 or 1; pad_ != 0.  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_depth_gate(const cvo_fe_depth_gate *gate);
 
 #ifdef __cplusplus
 }
