@@ -72,6 +72,34 @@ registration::~registration()
     cvo_hip_destroy(ctx_);
 }
 
+// a call of the front end that did not succeed: what it was, the status, and why (`why` null: the front end's own text)
+void registration::fe_check(int rc, const char *what, const char *why)
+{
+    if (rc == CVO_HIP_OK) return;
+    throw std::runtime_error(std::string(what) + ": " + cvo_hip_error_string(rc) + " (" + (why ? why : cvo_fe_last_error(fe_)) +
+                             ")");
+}
+
+// what the setters stored before the first image, for the front end that image created
+void registration::apply_stored_settings()
+{
+    try {
+        if (have_camera_) fe_check(cvo_fe_set_camera(fe_, &camera_), "cvo_fe_set_camera");
+        if (have_depth_camera_) fe_check(cvo_fe_set_depth_camera(fe_, &depth_camera_), "cvo_fe_set_depth_camera");
+        if (have_depth_gate_) fe_check(cvo_fe_set_depth_gate(fe_, &depth_gate_), "cvo_fe_set_depth_gate");
+        if (have_mask_) {
+            const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
+            fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
+                     fits ? nullptr : "the mask must have the colour image's size");
+        }
+    } catch (...) {
+        // (no front end without its settings: the next image tries again instead of falling back to the table)
+        cvo_fe_destroy(fe_);
+        fe_ = nullptr;
+        throw;
+    }
+}
+
 // pcd_generator::load_image + create_pointcloud (ref src/cvo.cpp:321-341): cvo asks for
 // the raw colour features (type 1), acvo for the HSV ones (type 0, ref
 // src/adaptive_cvo.cpp:451,462).  The cloud never leaves the device: the front end's
@@ -83,39 +111,11 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
     if (have_depth_camera_ && (dep.rows != depth_camera_.height || dep.cols != depth_camera_.width))
         throw std::runtime_error("set_pcd(): the depth image must have the depth camera's size");
     if (!fe_) {
-        int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
+        const int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
         if (rc != CVO_HIP_OK) throw std::runtime_error(std::string("cvo_fe_create: ") + cvo_hip_error_string(rc));
         fe_w_ = rgb.cols; fe_h_ = rgb.rows;
         cvo_fe_set_device_output(fe_, 1);
-        if (have_camera_ && (rc = cvo_fe_set_camera(fe_, &camera_)) != CVO_HIP_OK) {
-            // (no front end without its model: the next image tries again instead of falling back to the table)
-            const std::string why = cvo_fe_last_error(fe_);
-            cvo_fe_destroy(fe_);
-            fe_ = nullptr;
-            throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" + why + ")");
-        }
-        if (have_depth_camera_ && (rc = cvo_fe_set_depth_camera(fe_, &depth_camera_)) != CVO_HIP_OK) {
-            const std::string why = cvo_fe_last_error(fe_);
-            cvo_fe_destroy(fe_);
-            fe_ = nullptr;
-            throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" + why + ")");
-        }
-        if (have_depth_gate_ && (rc = cvo_fe_set_depth_gate(fe_, &depth_gate_)) != CVO_HIP_OK) {
-            const std::string why = cvo_fe_last_error(fe_);
-            cvo_fe_destroy(fe_);
-            fe_ = nullptr;
-            throw std::runtime_error(std::string("cvo_fe_set_depth_gate: ") + cvo_hip_error_string(rc) + " (" + why + ")");
-        }
-        if (have_mask_) {
-            const bool fits = mask_rows_ == rgb.rows && mask_cols_ == rgb.cols;
-            rc = fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID;
-            if (rc != CVO_HIP_OK) {
-                const std::string why = fits ? cvo_fe_last_error(fe_) : "the mask must have the colour image's size";
-                cvo_fe_destroy(fe_);
-                fe_ = nullptr;
-                throw std::runtime_error(std::string("cvo_fe_set_mask: ") + cvo_hip_error_string(rc) + " (" + why + ")");
-            }
-        }
+        apply_stored_settings();
     }
     if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
         throw std::runtime_error("set_pcd(): the image size changed within a sequence");
@@ -124,9 +124,7 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
                            dataset_seq, ftype);
     const float *d_pos = nullptr, *d_feat = nullptr;
     if (rc == CVO_HIP_OK) rc = cvo_fe_collect_device(fe_, &d_pos, &d_feat, &fe_points_);
-    if (rc != CVO_HIP_OK)
-        throw std::runtime_error(std::string("front end: ") + cvo_hip_error_string(rc) + " (" +
-                                 cvo_fe_last_error(fe_) + ")");
+    fe_check(rc, "front end");
     if (init == false) {   // ref src/cvo.cpp:325-334
         std::cout << "initializing cvo..." << std::endl;
         check(cvo_hip_set_fixed_device(ctx_, d_pos, d_feat, fe_points_, CVO_HIP_FEAT_ROWMAJOR),
@@ -141,109 +139,80 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
     std::cout << "num moving: " << fe_points_ << std::endl;   // ref src/cvo.cpp:343-347
 }
 
+// A setting given (`value`) or cleared (null): to the front end at once if there is one, and kept for the one the
+// first image creates.  A refusal by the front end throws and leaves what was kept as it was.
+template <class S>
+void registration::store(int (*set)(cvo_fe_ctx *, const S *), const char *what, const S *value, S &kept, bool &have)
+{
+    if (fe_) fe_check(set(fe_, value), what);
+    if (value) kept = *value;
+    have = value != nullptr;
+}
+
+// (Without a front end yet, the host-only checks below refuse what its setters refuse: the answer does not wait
+// for the first image.)
 void registration::set_camera(const cvo_fe_camera_model &model)
 {
-    // (the host-only entry refuses what cvo_fe_set_camera refuses: the answer does not wait for the first image)
     int32_t qu = 0, qv = 0;
     if (cvo_fe_rectify_map(&model, 1, 1, &qu, &qv) != CVO_HIP_OK)
         throw std::runtime_error("set_camera(): members must be finite and fx, fy, depth_scale positive");
-    if (fe_) {
-        const int rc = cvo_fe_set_camera(fe_, &model);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-    }
-    camera_ = model;
-    have_camera_ = true;
+    store<cvo_fe_camera_model>(cvo_fe_set_camera, "cvo_fe_set_camera", &model, camera_, have_camera_);
 }
 
 void registration::clear_camera()
 {
-    if (fe_) {
-        const int rc = cvo_fe_set_camera(fe_, nullptr);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_camera: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-    }
-    have_camera_ = false;
+    store<cvo_fe_camera_model>(cvo_fe_set_camera, "cvo_fe_set_camera", nullptr, camera_, have_camera_);
 }
 
 void registration::set_depth_camera(const cvo_fe_depth_camera &rig)
 {
-    if (fe_) {
-        const int rc = cvo_fe_set_depth_camera(fe_, &rig);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-    } else {
-        // (the host-only entry refuses what cvo_fe_set_depth_camera refuses: the answer does not wait for the first image)
-        if (cvo_fe_check_depth_camera(&rig) != CVO_HIP_OK)
-            throw std::runtime_error("set_depth_camera(): size in [8, 8192], finite members, fx, fy, depth_scale "
-                                     "positive, max_range above min_range, R a rotation");
-    }
-    depth_camera_ = rig;
-    have_depth_camera_ = true;
+    if (!fe_ && cvo_fe_check_depth_camera(&rig) != CVO_HIP_OK)
+        throw std::runtime_error("set_depth_camera(): size in [8, 8192], finite members, fx, fy, depth_scale "
+                                 "positive, max_range above min_range, R a rotation");
+    store<cvo_fe_depth_camera>(cvo_fe_set_depth_camera, "cvo_fe_set_depth_camera", &rig, depth_camera_, have_depth_camera_);
 }
 
 void registration::clear_depth_camera()
 {
-    if (fe_) {
-        const int rc = cvo_fe_set_depth_camera(fe_, nullptr);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_depth_camera: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-    }
-    have_depth_camera_ = false;
+    store<cvo_fe_depth_camera>(cvo_fe_set_depth_camera, "cvo_fe_set_depth_camera", nullptr, depth_camera_, have_depth_camera_);
 }
 
 void registration::set_depth_gate(const cvo_fe_depth_gate &gate)
 {
-    if (fe_) {
-        const int rc = cvo_fe_set_depth_gate(fe_, &gate);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_depth_gate: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-    } else {
-        // (the host-only entry refuses what cvo_fe_set_depth_gate refuses: the answer does not wait for the first image)
-        if (cvo_fe_check_depth_gate(&gate) != CVO_HIP_OK)
-            throw std::runtime_error("set_depth_gate(): finite members, jump_rel >= 0, max_range above min_range, "
-                                     "grow in [0, 3], hole_border 0 or 1, pad_ 0");
-    }
-    depth_gate_ = gate;
-    have_depth_gate_ = true;
+    if (!fe_ && cvo_fe_check_depth_gate(&gate) != CVO_HIP_OK)
+        throw std::runtime_error("set_depth_gate(): finite members, jump_rel >= 0, max_range above min_range, "
+                                 "grow in [0, 3], hole_border 0 or 1, pad_ 0");
+    store<cvo_fe_depth_gate>(cvo_fe_set_depth_gate, "cvo_fe_set_depth_gate", &gate, depth_gate_, have_depth_gate_);
 }
 
 void registration::clear_depth_gate()
 {
-    if (fe_) {
-        const int rc = cvo_fe_set_depth_gate(fe_, nullptr);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_depth_gate: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
+    store<cvo_fe_depth_gate>(cvo_fe_set_depth_gate, "cvo_fe_set_depth_gate", nullptr, depth_gate_, have_depth_gate_);
+}
+
+// the mask given or cleared (null); with a front end that one holds the bytes, and no second copy is kept here
+void registration::store_mask(const image_view *mask)
+{
+    if (fe_) fe_check(cvo_fe_set_mask(fe_, mask ? (const uint8_t *)mask->data : nullptr, mask ? mask->step : 0), "cvo_fe_set_mask");
+    mask_.clear();
+    if (mask && !fe_) {
+        mask_.resize((size_t)mask->rows * mask->cols);
+        for (int y = 0; y < mask->rows; ++y)
+            std::memcpy(mask_.data() + (size_t)y * mask->cols, (const uint8_t *)mask->data + (size_t)y * mask->step,
+                        (size_t)mask->cols);
+        mask_rows_ = mask->rows;
+        mask_cols_ = mask->cols;
     }
-    have_depth_gate_ = false;
+    have_mask_ = mask != nullptr;
 }
 
 void registration::set_mask(const image_view &mask)
 {
     if (!mask.data || mask.rows < 1 || mask.cols < 1 || mask.step < (size_t)mask.cols)
         throw std::runtime_error("set_mask(): a mask of rows x cols bytes, step >= cols");
-    if (fe_) {
-        if (mask.rows != fe_h_ || mask.cols != fe_w_)
-            throw std::runtime_error("set_mask(): the mask must have the colour image's size");
-        const int rc = cvo_fe_set_mask(fe_, (const uint8_t *)mask.data, mask.step);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_mask: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-        have_mask_ = true;   // (the front end holds the bytes: no second copy here)
-        return;
-    }
-    mask_.resize((size_t)mask.rows * mask.cols);
-    for (int y = 0; y < mask.rows; ++y)
-        std::memcpy(mask_.data() + (size_t)y * mask.cols, (const uint8_t *)mask.data + (size_t)y * mask.step, (size_t)mask.cols);
-    mask_rows_ = mask.rows;
-    mask_cols_ = mask.cols;
-    have_mask_ = true;
+    if (fe_ && (mask.rows != fe_h_ || mask.cols != fe_w_))
+        throw std::runtime_error("set_mask(): the mask must have the colour image's size");
+    store_mask(&mask);
 }
 
 void registration::set_mask(const uint8_t *mask, size_t stride)
@@ -252,17 +221,8 @@ void registration::set_mask(const uint8_t *mask, size_t stride)
     set_mask(image_view{mask, fe_h_, fe_w_, stride});
 }
 
-void registration::clear_mask()
-{
-    if (fe_) {
-        const int rc = cvo_fe_set_mask(fe_, nullptr, 0);
-        if (rc != CVO_HIP_OK)
-            throw std::runtime_error(std::string("cvo_fe_set_mask: ") + cvo_hip_error_string(rc) + " (" +
-                                     cvo_fe_last_error(fe_) + ")");
-    }
-    have_mask_ = false;
-    mask_.clear();
-}
+void registration::clear_mask() { store_mask(nullptr); }
+
 
 void registration::set_pcd(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,
                            const std::string &, const std::string &)

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -970,6 +971,13 @@ struct FeGraph {
     hipGraphExec_t exec = nullptr;
 };
 
+// A buffer and its release.  Every buffer of the context is held by one of these, and so is every buffer a
+// setter builds: whatever is not handed on frees itself.  Launch sites take the raw pointer (get()).
+struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
+struct PinFree { void operator()(void *p) const { (void)hipHostFree(p); } };
+template <class T> using Dev = std::unique_ptr<T, DevFree>;   // device memory
+template <class T> using Pin = std::unique_ptr<T, PinFree>;   // pinned host memory
+
 struct cvo_fe_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -979,19 +987,19 @@ struct cvo_fe_ctx {
     int num_want = 3000;
     int cap = 0;
     // device
-    uint8_t *img = nullptr, *gray = nullptr, *pattern = nullptr, *tmp8 = nullptr, *st8 = nullptr, *edges = nullptr;
-    uint16_t *depth = nullptr;
-    uint32_t *hsv = nullptr;
-    float *I[FE_LEVELS] = {}, *ag[FE_LEVELS] = {}, *dx0 = nullptr, *dy0 = nullptr, *map = nullptr;
-    float *ths = nullptr, *ths_s = nullptr, *pos = nullptr, *feat = nullptr;
-    int *sdiv = nullptr, *hdiv = nullptr, *cnt = nullptr, *mag = nullptr, *blk_cnt = nullptr;
-    short2 *grad = nullptr;
-    FeCtrl *ctrl = nullptr;
+    Dev<uint8_t> img, gray, pattern, tmp8, st8, edges;
+    Dev<uint16_t> depth;
+    Dev<uint32_t> hsv;
+    Dev<float> I[FE_LEVELS], ag[FE_LEVELS], dx0, dy0, map;
+    Dev<float> ths, ths_s, pos, feat;
+    Dev<int> sdiv, hdiv, cnt, mag, blk_cnt;
+    Dev<short2> grad;
+    Dev<FeCtrl> ctrl;
     // pinned host
-    uint8_t *h_img = nullptr;
-    uint16_t *h_depth = nullptr;
-    FeCtrl *h_ctrl = nullptr;
-    float *h_pos = nullptr, *h_feat = nullptr;
+    Pin<uint8_t> h_img;
+    Pin<uint16_t> h_depth;
+    Pin<FeCtrl> h_ctrl;
+    Pin<float> h_pos, h_feat;
     cvo_fe_info info{};
     std::vector<FeGraph> graphs;   // one frame's device work, captured per (camera, features, ...)
     int copied = 0;            // points of the cloud already on their way to h_pos / h_feat
@@ -1004,26 +1012,27 @@ struct cvo_fe_ctx {
     bool rectify = false;      // ... and its dist is not all zero: frames start with k_fe_rectify
     uint64_t cam_gen = 0;      // counts the changes of camera: part of a captured graph's key
     // with the first distorting model: the upload targets of such frames and the map (qu, then qv)
-    uint8_t *raw_img = nullptr;
-    uint16_t *raw_depth = nullptr;
-    int32_t *rect_map = nullptr;   // 2 planes of rect_plane(np) entries
+    Dev<uint8_t> raw_img;
+    Dev<uint16_t> raw_depth;
+    Dev<int32_t> rect_map;     // 2 planes of rect_plane(np) entries
     // the caller's depth camera (cvo_fe_set_depth_camera); without one depth is registered to colour
     cvo_fe_depth_camera rig{};
     bool has_rig = false;      // frames start with k_fe_depth_warp / k_fe_depth_final
     int dw = 0, dh = 0;        // the size of the depth image a frame takes: the rig's, or the context's
     // with the first rig: the upload target of the depth image, the ray table and the z-buffer
-    uint16_t *rig_depth = nullptr;
-    float2 *rays = nullptr;        // (dh + 1) * (dw + 1)
-    uint32_t *zbuf = nullptr;      // rect_plane(np) entries, FE_Z_EMPTY between frames
+    Dev<uint16_t> rig_depth;
+    Dev<float2> rays;          // (dh + 1) * (dw + 1)
+    Dev<uint32_t> zbuf;        // rect_plane(np) entries, FE_Z_EMPTY between frames
     // the caller's gate and mask (cvo_fe_set_depth_gate, cvo_fe_set_mask); with either, frames pass k_fe_depth_gate
     cvo_fe_depth_gate gate{};
     bool has_gate = false, has_mask = false;
     bool mask_dirty = false;       // h_mask holds bytes the device has not seen yet: the next submit() uploads them
     // with the first gate or mask: the plane the stages in front of the gate write, and the flags
-    uint16_t *ungated = nullptr;   // rect_plane(np) entries
-    uint8_t *gate_flags = nullptr;
+    Dev<uint16_t> ungated;     // rect_plane(np) entries
+    Dev<uint8_t> gate_flags;
     // with the first mask: its device plane and its pinned staging image
-    uint8_t *d_mask = nullptr, *h_mask = nullptr;
+    Dev<uint8_t> d_mask;
+    Pin<uint8_t> h_mask;
     std::string err;
 };
 
@@ -1044,8 +1053,35 @@ int fail(cvo_fe_ctx *c, int code, const char *what, hipError_t e = hipSuccess)
         if (e_ != hipSuccess) return fail(ctx, CVO_HIP_ERR_HIP, #call, e_);     \
     } while (0)
 
-template <class T> hipError_t dev_alloc(T **p, size_t n) { return hipMalloc((void **)p, n * sizeof(T)); }
-template <class T> hipError_t pin_alloc(T **p, size_t n) { return hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocDefault); }
+template <class T> bool dev_alloc(Dev<T> &b, size_t n)
+{
+    T *p = nullptr;
+    if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) return false;
+    b.reset(p);
+    return true;
+}
+
+template <class T> bool pin_alloc(Pin<T> &b, size_t n)
+{
+    T *p = nullptr;
+    if (hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) return false;
+    b.reset(p);
+    return true;
+}
+
+// a setter whose allocation failed: the runtime's error is taken, so that the next frame does not find it
+int no_memory(cvo_fe_ctx *ctx, const char *what)
+{
+    (void)hipGetLastError();
+    return fail(ctx, CVO_HIP_ERR_NOMEM, what);
+}
+
+// The setters replace only when whole: they build what they need in locals, and after the last step that can
+// fail the context takes what was built.  A local left empty (the context has that buffer already) changes nothing.
+template <class B> void hand_over(B &to, B &built)
+{
+    if (built) to = std::move(built);
+}
 
 inline int blocks(int n) { return (n + FE_BLOCK - 1) / FE_BLOCK; }
 
@@ -1094,12 +1130,86 @@ bool gate_ok(const cvo_fe_depth_gate &g)
     return (g.hole_border == 0 || g.hole_border == 1) && g.pad_ == 0;
 }
 
+// The lens model of include/cvo_frontend.h for a colour or a depth camera, operation by operation (float64,
+// nothing contracted).  The tables made from it are held to their numpy restatements by bytes, so every
+// parenthesis here is part of the contract.
+struct Lens {
+    double fx, fy, cx, cy, k1, k2, p1, p2, k3;
+    template <class M>
+    explicit Lens(const M &m)
+        : fx(m.fx), fy(m.fy), cx(m.cx), cy(m.cy), k1(m.dist[0]), k2(m.dist[1]), p1(m.dist[2]), p2(m.dist[3]), k3(m.dist[4])
+    {
+    }
+    // the radial factor and the tangential shift at the ideal point (x, y)
+    void terms(double x, double y, double &rad, double &dx, double &dy) const
+    {
+        const double r2 = x * x + y * y;
+        rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+        dx = (2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x);
+        dy = p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y;
+    }
+    // the pixel at which the camera sees the ideal point (x, y)
+    void project(double x, double y, double &us, double &vs) const
+    {
+        double rad, dx, dy;
+        terms(x, y, rad, dx, dy);
+        const double xd = x * rad + dx, yd = y * rad + dy;
+        us = fx * xd + cx;
+        vs = fy * yd + cy;
+    }
+};
+
+inline bool distorts(const float dist[5])
+{
+    bool any = false;
+    for (int q = 0; q < 5; ++q) any = any || dist[q] != 0.0f;
+    return any;
+}
+
+// `rows` rows of `row` bytes from an image of any stride into a dense one; in one call when the stride is dense
+void copy_rows(void *dst, const void *src, size_t stride, size_t row, int rows)
+{
+    if (stride == row) {
+        std::memcpy(dst, src, row * (size_t)rows);
+        return;
+    }
+    for (int y = 0; y < rows; ++y) std::memcpy((uint8_t *)dst + (size_t)y * row, (const uint8_t *)src + (size_t)y * stride, row);
+}
+
 inline bool gate_active(const cvo_fe_ctx *ctx) { return ctx->has_gate || ctx->has_mask; }
 
 // the depth plane the stages in front of level 0 write: the gate's input while it runs
-inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? ctx->ungated : ctx->depth; }
+inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? ctx->ungated.get() : ctx->depth.get(); }
 
-// after a change of what a frame's sequence is: the graphs captured before hold the old buffers and numbers
+// where the uploaded depth image lands: the raw buffer of a depth camera's size, else the raw depth that
+// k_fe_rectify resamples, else the depth plane itself
+inline uint16_t *depth_upload(const cvo_fe_ctx *ctx)
+{
+    return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : depth_plane(ctx);
+}
+
+// the points of the cloud that follow the control block to the host before their number is known: enough for
+// any normal frame (none when the consumer takes the cloud from device memory: cvo_fe_set_device_output)
+inline int optimistic_copy(const cvo_fe_ctx *ctx)
+{
+    return ctx->device_output ? 0 : std::min(ctx->cap, std::max(4096, 2 * ctx->num_want));
+}
+
+// the colour camera in force for a frame: the caller's model (a distorting one: its rectified pinhole), else
+// the table row of dataset_seq (never fails: an index outside the table means row 0)
+void camera_in_force(const cvo_fe_ctx *ctx, int dataset_seq, float cam[5])
+{
+    if (ctx->custom) {
+        const cvo_fe_camera_model &m = ctx->cam;
+        cam[0] = m.depth_scale; cam[1] = m.fx; cam[2] = m.fy; cam[3] = m.cx; cam[4] = m.cy;
+    } else cvo_fe_camera(dataset_seq, cam);
+}
+
+// After a change of what a frame's sequence is -- and the only place that destroys a graph.  A graph captured
+// before the change holds the old numbers, the old buffers (the map's address too) and the old first node.
+// Dropping those graphs here is what keeps them from being launched again -- and what keeps the cache of 8
+// from filling with dead entries; the generation in the key is the guard behind it, should a graph ever
+// outlive such a change.
 void drop_graphs(cvo_fe_ctx *ctx)
 {
     ctx->cam_gen++;
@@ -1110,21 +1220,12 @@ void drop_graphs(cvo_fe_ctx *ctx)
     ctx->graphs.clear();
 }
 
-// the ungated plane and the flags, with the first gate or mask; both or neither
-int gate_buffers(cvo_fe_ctx *ctx)
+// the ungated plane and the flags, with the first gate or mask; both or neither (left empty for a context that has them)
+int gate_buffers(cvo_fe_ctx *ctx, Dev<uint16_t> &ungated, Dev<uint8_t> &flags)
 {
-    if (ctx->ungated) return CVO_HIP_OK;
-    uint16_t *u = nullptr;
-    uint8_t *f = nullptr;
     const size_t n = rect_plane(ctx->np);
-    if (dev_alloc(&u, n) != hipSuccess || dev_alloc(&f, n) != hipSuccess) {
-        if (u) (void)hipFree(u);
-        (void)hipGetLastError();
-        return fail(ctx, CVO_HIP_ERR_NOMEM, "device memory for the ungated depth and the gate's flags");
-    }
-    ctx->ungated = u;
-    ctx->gate_flags = f;
-    return CVO_HIP_OK;
+    if (ctx->ungated || (dev_alloc(ungated, n) && dev_alloc(flags, n))) return CVO_HIP_OK;
+    return no_memory(ctx, "device memory for the ungated depth and the gate's flags");
 }
 
 // the Canny path of a frame whose selection came out short (host loop: rare)
@@ -1132,20 +1233,22 @@ int run_canny(cvo_fe_ctx *ctx)
 {
     const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
     hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(k_fe_blur, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->gray, w, h, ctx->tmp8);
-    hipLaunchKernelGGL(k_fe_sobel, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->tmp8, w, h, ctx->grad, ctx->mag);
-    hipLaunchKernelGGL(k_fe_nms, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->grad, ctx->mag, w, h, 0, 25, ctx->st8);
+    uint8_t *st8 = ctx->st8.get();
+    hipLaunchKernelGGL(k_fe_blur, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->gray.get(), w, h, ctx->tmp8.get());
+    hipLaunchKernelGGL(k_fe_sobel, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->tmp8.get(), w, h, ctx->grad.get(),
+                       ctx->mag.get());
+    hipLaunchKernelGGL(k_fe_nms, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->grad.get(), ctx->mag.get(), w, h, 0, 25, st8);
     const int tiles_x = (w + 31) / 32, tiles_y = (h + 31) / 32;
     for (int sweep = 0; sweep < w + h; ++sweep) {
         FE_HIP(hipMemsetAsync(&ctx->ctrl->changed, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_fe_hyst, dim3(tiles_x * tiles_y), dim3(FE_BLOCK), 0, s, ctx->st8, w, h, tiles_x, ctx->ctrl);
-        FE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->ctrl, sizeof(FeCtrl), hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_fe_hyst, dim3(tiles_x * tiles_y), dim3(FE_BLOCK), 0, s, st8, w, h, tiles_x, ctx->ctrl.get());
+        FE_HIP(hipMemcpyAsync(ctx->h_ctrl.get(), ctx->ctrl.get(), sizeof(FeCtrl), hipMemcpyDeviceToHost, s));
         FE_HIP(hipStreamSynchronize(s));
         if (!ctx->h_ctrl->changed) break;
     }
-    hipLaunchKernelGGL(k_fe_edges, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->st8, np, ctx->edges);
-    hipLaunchKernelGGL(k_fe_topup, dim3(blocks(((w + 7) / 8) * ((h + 7) / 8))), dim3(FE_BLOCK), 0, s, ctx->st8, w, h,
-                       ctx->map);
+    hipLaunchKernelGGL(k_fe_edges, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, st8, np, ctx->edges.get());
+    hipLaunchKernelGGL(k_fe_topup, dim3(blocks(((w + 7) / 8) * ((h + 7) / 8))), dim3(FE_BLOCK), 0, s, st8, w, h,
+                       ctx->map.get());
     FE_HIP(hipGetLastError());
     return CVO_HIP_OK;
 }
@@ -1153,25 +1256,145 @@ int run_canny(cvo_fe_ctx *ctx)
 int run_emit(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
 {
     hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(k_fe_count<1>, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, ctx->map, ctx->depth, ctx->np, ctx->ctrl,
-                       ctx->cnt);
+    hipLaunchKernelGGL(k_fe_count<1>, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, ctx->map.get(), ctx->depth.get(), ctx->np,
+                       ctx->ctrl.get(), ctx->cnt.get());
     EmitArgs e{};
-    e.map = ctx->map; e.depth = ctx->depth; e.img = ctx->img; e.hsv = ctx->hsv; e.dx0 = ctx->dx0; e.dy0 = ctx->dy0;
-    e.cnt = ctx->cnt; e.ctrl = ctx->ctrl; e.pos = ctx->pos; e.feat = ctx->feat;
+    e.map = ctx->map.get(); e.depth = ctx->depth.get(); e.img = ctx->img.get(); e.hsv = ctx->hsv.get();
+    e.dx0 = ctx->dx0.get(); e.dy0 = ctx->dy0.get();
+    e.cnt = ctx->cnt.get(); e.ctrl = ctx->ctrl.get(); e.pos = ctx->pos.get(); e.feat = ctx->feat.get();
     e.np = ctx->np; e.w = ctx->d.w; e.cap = ctx->cap; e.feature_type = feature_type; e.nblocks = ctx->nchunks;
-    if (ctx->custom) {
-        const cvo_fe_camera_model &m = ctx->cam;
-        e.cam[0] = m.depth_scale; e.cam[1] = m.fx; e.cam[2] = m.fy; e.cam[3] = m.cx; e.cam[4] = m.cy;
-    } else cvo_fe_camera(dataset_seq, e.cam);
+    camera_in_force(ctx, dataset_seq, e.cam);
     hipLaunchKernelGGL(k_fe_emit, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, e);
-    FE_HIP(hipMemcpyAsync(ctx->h_ctrl, ctx->ctrl, sizeof(FeCtrl), hipMemcpyDeviceToHost, s));
-    // the cloud follows optimistically (its size is not known yet): enough for any normal frame
-    // (not when the consumer takes it from device memory: cvo_fe_set_device_output)
-    ctx->copied = 0;
-    if (ctx->device_output) return CVO_HIP_OK;
-    ctx->copied = std::min(ctx->cap, std::max(4096, 2 * ctx->num_want));
-    FE_HIP(hipMemcpyAsync(ctx->h_pos, ctx->pos, (size_t)ctx->copied * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    FE_HIP(hipMemcpyAsync(ctx->h_feat, ctx->feat, (size_t)ctx->copied * 5 * sizeof(float), hipMemcpyDeviceToHost, s));
+    FE_HIP(hipMemcpyAsync(ctx->h_ctrl.get(), ctx->ctrl.get(), sizeof(FeCtrl), hipMemcpyDeviceToHost, s));
+    // the cloud follows optimistically (its size is not known yet)
+    ctx->copied = optimistic_copy(ctx);
+    if (!ctx->copied) return CVO_HIP_OK;
+    FE_HIP(hipMemcpyAsync(ctx->h_pos.get(), ctx->pos.get(), (size_t)ctx->copied * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+    FE_HIP(hipMemcpyAsync(ctx->h_feat.get(), ctx->feat.get(), (size_t)ctx->copied * 5 * sizeof(float), hipMemcpyDeviceToHost, s));
+    return CVO_HIP_OK;
+}
+
+// one frame's device work, in stream order (also what a captured graph holds)
+int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
+{
+    const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
+    hipStream_t s = ctx->stream;
+    uint8_t *img = ctx->img.get();
+    const int32_t *qu = ctx->rect_map.get(), *qv = qu ? qu + rect_plane(np) : nullptr;   // (read under a distorting model)
+    // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
+    FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img.get() : img, ctx->h_img.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
+    // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
+    // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
+    uint16_t *plane = depth_plane(ctx);
+    FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
+    FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
+    if (ctx->rectify)
+        hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img.get(),
+                           ctx->has_rig ? (const uint16_t *)nullptr : ctx->raw_depth.get(), qu, qv, w, h, img, plane);
+    if (ctx->has_rig) {
+        const cvo_fe_depth_camera &r = ctx->rig;
+        DepthWarpArgs a{};
+        a.depth = ctx->rig_depth.get(); a.rays = ctx->rays.get(); a.z = ctx->zbuf.get();
+        a.dw = r.width; a.dh = r.height; a.w = w; a.h = h;
+        a.scale = r.depth_scale; a.min_range = r.min_range; a.max_range = r.max_range;
+        for (int q = 0; q < 9; ++q) a.R[q] = r.R[q];
+        for (int q = 0; q < 3; ++q) a.T[q] = r.T[q];
+        camera_in_force(ctx, dataset_seq, a.cam);
+        hipLaunchKernelGGL(k_fe_depth_warp, dim3(blocks(a.dw * a.dh)), dim3(FE_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf.get(), np, plane);
+    }
+    if (gate_active(ctx)) {
+        GateArgs g{};
+        g.u = ctx->ungated.get(); g.depth = ctx->depth.get(); g.flags = ctx->gate_flags.get();
+        g.mask = ctx->has_mask ? ctx->d_mask.get() : nullptr;
+        // the mask lies on the grid of the image as uploaded: under a distorting model it follows the map
+        g.qu = ctx->has_mask && ctx->rectify ? qu : nullptr;
+        g.qv = g.qu ? qv : nullptr;
+        g.w = w; g.h = h;
+        float cam[5];
+        camera_in_force(ctx, dataset_seq, cam);
+        g.scale = cam[0];
+        if (ctx->has_gate) {
+            g.min_range = ctx->gate.min_range; g.max_range = ctx->gate.max_range; g.jump_rel = ctx->gate.jump_rel;
+            g.grow = ctx->gate.grow; g.hole_border = ctx->gate.hole_border;
+        }
+        const dim3 tiles((w + FG_TW - 1) / FG_TW, (h + FG_TH - 1) / FG_TH);
+        switch (g.grow) {   // (0..3: cvo_fe_check_depth_gate)
+        case 0: hipLaunchKernelGGL(k_fe_depth_gate<0>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        case 1: hipLaunchKernelGGL(k_fe_depth_gate<1>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        case 2: hipLaunchKernelGGL(k_fe_depth_gate<2>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        default: hipLaunchKernelGGL(k_fe_depth_gate<3>, tiles, dim3(FE_BLOCK), 0, s, g); break;
+        }
+    }
+
+    const FeDims &d = ctx->d;
+    hipLaunchKernelGGL(k_fe_level0, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, img, w, h, ctx->sdiv.get(), ctx->hdiv.get(),
+                       ctx->gray.get(), ctx->hsv.get(), ctx->I[0].get(), ctx->ag[0].get(), ctx->dx0.get(), ctx->dy0.get());
+    for (int l = 1; l < FE_LEVELS; ++l)
+        hipLaunchKernelGGL(k_fe_level, dim3(blocks(d.wl[l] * d.hl[l])), dim3(FE_BLOCK), 0, s, ctx->I[l - 1].get(),
+                           2 * d.wl[l] /* the reference's row stride of the level above, also when
+                                           that level is one pixel wider (ref src/pcd_generator.cpp:82) */,
+                           ctx->I[l].get(), d.wl[l], d.hl[l], ctx->ag[l].get());
+    const int ncell = d.w32 * d.h32;
+    float *map = ctx->map.get();
+    FeCtrl *ctrl = ctx->ctrl.get();
+    int *blk_cnt = ctx->blk_cnt.get(), *cnt = ctx->cnt.get();
+    hipLaunchKernelGGL(k_fe_hist, dim3(ncell), dim3(FE_BLOCK), 0, s, ctx->ag[0].get(), w, h, d.w32, ctx->ths.get());
+    hipLaunchKernelGGL(k_fe_smooth, dim3(blocks(ncell)), dim3(FE_BLOCK), 0, s, ctx->ths.get(), d.w32, d.h32, ctx->ths_s.get());
+    SelectArgs sa{ctx->ag[0].get(), ctx->ag[1].get(), ctx->ag[2].get(), ctx->ths_s.get(), map, ctrl, blk_cnt, w, h, d.w32, ncell, 0};
+    const int nb0 = (((w + 11) / 12) * ((h + 11) / 12) + 3) / 4;   // potential 3: one wave per 12 x 12 block
+    hipLaunchKernelGGL(k_fe_select, dim3(nb0), dim3(FE_BLOCK), 0, s, sa);
+    hipLaunchKernelGGL(k_fe_decide, dim3(1), dim3(FE_BLOCK), 0, s, ctrl, blk_cnt, nb0, 0, (float)ctx->num_want);
+    sa.pass = 1;
+    const int nb1 = (((w + 3) / 4) * ((h + 3) / 4) + 3) / 4;       // any potential >= 1
+    hipLaunchKernelGGL(k_fe_select, dim3(nb1), dim3(FE_BLOCK), 0, s, sa);
+    hipLaunchKernelGGL(k_fe_decide, dim3(1), dim3(FE_BLOCK), 0, s, ctrl, blk_cnt, nb1, 1, (float)ctx->num_want);
+    hipLaunchKernelGGL(k_fe_count<0>, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, map, ctx->depth.get(), np, ctrl, cnt);
+    hipLaunchKernelGGL(k_fe_subsample, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, map, np, ctx->pattern.get(), cnt, ctrl);
+    FE_HIP(hipGetLastError());
+    // the cloud is emitted at once; a frame that needs the edge top-up (rare: a nearly
+    // texture-free image) is noticed at collect(), when the control block has arrived, and
+    // emitted again
+    return run_emit(ctx, dataset_seq, feature_type);
+}
+
+int collect_impl(cvo_fe_ctx *ctx, float *positions, float *features, int capacity, int *num_points, bool to_host)
+{
+    if (!ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "collect: no frame was submitted");
+    ctx->pending = false;
+    FE_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    FE_HIP(hipStreamSynchronize(s));
+    int rc = CVO_HIP_OK;
+    // ref src/pcd_generator.cpp:141-144: fewer than a third of what was asked for?
+    const int num_selected = ctx->h_ctrl->in_map;   // (before any top-up: that is what the reference tests)
+    const bool canny = num_selected < ctx->num_want / 3;
+    if (canny) {
+        rc = run_canny(ctx);
+        if (!rc) rc = run_emit(ctx, ctx->p_seq, ctx->p_ftype);
+        if (rc) return rc;
+        FE_HIP(hipStreamSynchronize(s));
+    }
+    const FeCtrl &c = *ctx->h_ctrl;
+    ctx->info.num_selected = num_selected;
+    ctx->info.reselected = c.redo;
+    ctx->info.pot_used = c.pot[c.redo ? 1 : 0];
+    ctx->info.canny_used = canny ? 1 : 0;
+    ctx->info.num_points = c.num_points;
+    *num_points = c.num_points;
+    const int ncopy = std::min(std::min(c.num_points, capacity), ctx->cap);
+    float *h_pos = ctx->h_pos.get(), *h_feat = ctx->h_feat.get();
+    if (to_host && ncopy > ctx->copied) {   // an unusually large cloud: fetch the rest
+        const size_t from = (size_t)ctx->copied, more = (size_t)(ncopy - ctx->copied);
+        FE_HIP(hipMemcpyAsync(h_pos + from * 3, ctx->pos.get() + from * 3, more * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        FE_HIP(hipMemcpyAsync(h_feat + from * 5, ctx->feat.get() + from * 5, more * 5 * sizeof(float), hipMemcpyDeviceToHost, s));
+        FE_HIP(hipStreamSynchronize(s));
+    }
+    if (to_host && ncopy > 0) {
+        std::memcpy(positions, h_pos, (size_t)ncopy * 3 * sizeof(float));
+        std::memcpy(features, h_feat, (size_t)ncopy * 5 * sizeof(float));
+    }
+    if (c.num_points > ncopy) return fail(ctx, CVO_HIP_ERR_INVALID, "create_pointcloud: more points than capacity");
     return CVO_HIP_OK;
 }
 
@@ -1198,19 +1421,14 @@ int cvo_fe_camera(int dataset_seq, float cam[5])
 int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, int32_t *qu, int32_t *qv)
 {
     if (!model || !qu || !qv || width < 1 || height < 1 || !model_ok(*model)) return CVO_HIP_ERR_INVALID;
-    // the contract of include/cvo_frontend.h, operation by operation (float64, nothing contracted)
-    const double fx = model->fx, fy = model->fy, cx = model->cx, cy = model->cy;
-    const double k1 = model->dist[0], k2 = model->dist[1], p1 = model->dist[2], p2 = model->dist[3], k3 = model->dist[4];
+    const Lens lens(*model);
     const double wmax = (double)width, hmax = (double)height;
     for (int v = 0; v < height; ++v) {
-        const double y = ((double)v - cy) / fy;
+        const double y = ((double)v - lens.cy) / lens.fy;
         for (int u = 0; u < width; ++u) {
-            const double x = ((double)u - cx) / fx;
-            const double r2 = x * x + y * y;
-            const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-            const double xd = x * rad + ((2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x));
-            const double yd = y * rad + (p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y);
-            double us = fx * xd + cx, vs = fy * yd + cy;
+            const double x = ((double)u - lens.cx) / lens.fx;
+            double us, vs;
+            lens.project(x, y, us, vs);
             if (!(us >= -1.0)) us = -1.0;   // (also what is not a number)
             if (us > wmax) us = wmax;
             if (!(vs >= -1.0)) vs = -1.0;
@@ -1231,31 +1449,23 @@ int cvo_fe_check_depth_camera(const cvo_fe_depth_camera *rig)
 int cvo_fe_depth_rays(const cvo_fe_depth_camera *rig, float *xn, float *yn)
 {
     if (!rig || !xn || !yn || !rig_ok(*rig)) return CVO_HIP_ERR_INVALID;
-    // the contract of include/cvo_frontend.h, operation by operation (float64, nothing contracted)
-    const double fx = rig->fx, fy = rig->fy, cx = rig->cx, cy = rig->cy;
-    const double k1 = rig->dist[0], k2 = rig->dist[1], p1 = rig->dist[2], p2 = rig->dist[3], k3 = rig->dist[4];
-    bool distorts = false;
-    for (int q = 0; q < 5; ++q) distorts = distorts || rig->dist[q] != 0.0f;
+    const Lens lens(*rig);
+    const bool bent = distorts(rig->dist);
     const double nan = std::nan("");
     for (int j = 0; j <= rig->height; ++j) {
-        const double py = (double)j - 0.5, yd = (py - cy) / fy;
+        const double py = (double)j - 0.5, yd = (py - lens.cy) / lens.fy;
         for (int i = 0; i <= rig->width; ++i) {
-            const double px = (double)i - 0.5, xd = (px - cx) / fx;
+            const double px = (double)i - 0.5, xd = (px - lens.cx) / lens.fx;
             double x = xd, y = yd;
-            if (distorts) {
-                for (int it = 0; it < 20; ++it) {
-                    const double r2 = x * x + y * y;
-                    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-                    const double dx = (2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x);
-                    const double dy = p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y;
+            if (bent) {
+                for (int it = 0; it < 20; ++it) {   // the fixed-point step
+                    double rad, dx, dy;
+                    lens.terms(x, y, rad, dx, dy);
                     x = (xd - dx) / rad;
                     y = (yd - dy) / rad;
                 }
-                const double r2 = x * x + y * y;
-                const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-                const double xf = x * rad + ((2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x));
-                const double yf = y * rad + (p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y);
-                const double us = fx * xf + cx, vs = fy * yf + cy;
+                double us, vs;   // the forward check
+                lens.project(x, y, us, vs);
                 if (!(std::fabs(us - px) <= 1.0 / 32.0 && std::fabs(vs - py) <= 1.0 / 32.0)) x = y = nan;
             }
             const size_t c = (size_t)j * ((size_t)rig->width + 1) + i;
@@ -1280,78 +1490,48 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
     FE_HIP(hipSetDevice(ctx->device));
     const int dw = rig ? rig->width : ctx->d.w, dh = rig ? rig->height : ctx->d.h;
     const size_t dnp = (size_t)dw * dh;
-    // Everything new goes into buffers of its own and replaces what the context has only once it is
-    // whole: after any failure here the context still has the rig, the buffers and the graphs it had.
-    uint16_t *new_depth = nullptr, *new_host = nullptr;
-    float2 *new_rays = nullptr;
-    uint32_t *new_z = nullptr;
-    auto undo = [&]() {
-        if (new_depth) (void)hipFree(new_depth);
-        if (new_rays) (void)hipFree(new_rays);
-        if (new_z) (void)hipFree(new_z);
-        if (new_host) (void)hipHostFree(new_host);
-        (void)hipGetLastError();
-    };
+    Dev<uint16_t> new_depth;
+    Pin<uint16_t> new_host;
+    Dev<float2> new_rays;
+    Dev<uint32_t> new_z;
     const bool resize = dw != ctx->dw || dh != ctx->dh;   // the pinned staging image follows the depth size
-    if (resize && pin_alloc(&new_host, dnp) != hipSuccess) {
-        undo();
-        return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera: pinned memory for the depth image");
-    }
+    if (resize && !pin_alloc(new_host, dnp)) return no_memory(ctx, "set_depth_camera: pinned memory for the depth image");
     if (rig) {
         const size_t nr = (size_t)(dw + 1) * (dh + 1), nz = rect_plane(ctx->np);
         std::vector<float> t;
         std::vector<float2> inter;
         try { t.resize(2 * nr); inter.resize(nr); } catch (const std::bad_alloc &) {
-            undo();
             return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera");
         }
-        if (cvo_fe_depth_rays(rig, t.data(), t.data() + nr) != CVO_HIP_OK) {
-            undo();
+        if (cvo_fe_depth_rays(rig, t.data(), t.data() + nr) != CVO_HIP_OK)
             return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: depth_rays");
-        }
         for (size_t q = 0; q < nr; ++q) inter[q] = make_float2(t[q], t[nr + q]);
-        if (dev_alloc(&new_depth, dnp) != hipSuccess || dev_alloc(&new_rays, nr) != hipSuccess ||
-            (!ctx->zbuf && dev_alloc(&new_z, nz) != hipSuccess)) {
-            undo();
-            return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera: device memory for the raw depth, the rays and the z-buffer");
-        }
+        if (!dev_alloc(new_depth, dnp) || !dev_alloc(new_rays, nr) || (!ctx->zbuf && !dev_alloc(new_z, nz)))
+            return no_memory(ctx, "set_depth_camera: device memory for the raw depth, the rays and the z-buffer");
         // (no frame is in flight: once the stream is idle nothing reads the old buffers any more)
         hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(new_rays, inter.data(), nr * sizeof(float2), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(new_rays.get(), inter.data(), nr * sizeof(float2), hipMemcpyHostToDevice);
         // the z-buffer is armed here and by every frame's k_fe_depth_final after it
-        if (e == hipSuccess) e = hipMemset(new_z ? new_z : ctx->zbuf, 0xFF, nz * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(new_z ? new_z.get() : ctx->zbuf.get(), 0xFF, nz * sizeof(uint32_t));
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) {
-            undo();
+            (void)hipGetLastError();
             return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera: upload of the rays", e);
         }
     } else {
         const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            undo();
-            return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera", e);
-        }
+        if (e != hipSuccess) return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera", e);
     }
-    if (ctx->rig_depth) (void)hipFree(ctx->rig_depth);
-    if (ctx->rays) (void)hipFree(ctx->rays);
-    ctx->rig_depth = new_depth;
-    ctx->rays = new_rays;
-    if (new_z) ctx->zbuf = new_z;
-    if (new_host) {
-        (void)hipHostFree(ctx->h_depth);
-        ctx->h_depth = new_host;
-    }
+    // whole: the old raw depth and rays go, with or without new ones
+    ctx->rig_depth = std::move(new_depth);
+    ctx->rays = std::move(new_rays);
+    hand_over(ctx->zbuf, new_z);
+    hand_over(ctx->h_depth, new_host);
     ctx->has_rig = rig != nullptr;
     ctx->rig = rig ? *rig : cvo_fe_depth_camera{};
     ctx->dw = dw;
     ctx->dh = dh;
-    // as after a change of camera: the graphs captured before hold the old buffers and numbers
-    ctx->cam_gen++;
-    for (auto &g : ctx->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    ctx->graphs.clear();
+    drop_graphs(ctx);
     return CVO_HIP_OK;
 }
 
@@ -1381,12 +1561,16 @@ int cvo_fe_set_depth_gate(cvo_fe_ctx *ctx, const cvo_fe_depth_gate *gate)
     if (!gate && !ctx->has_gate) return CVO_HIP_OK;
     if (gate && ctx->has_gate && std::memcmp(gate, &ctx->gate, sizeof(*gate)) == 0) return CVO_HIP_OK;
     FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint16_t> ungated;
+    Dev<uint8_t> flags;
     if (gate) {
-        const int rc = gate_buffers(ctx);
+        const int rc = gate_buffers(ctx, ungated, flags);
         if (rc) return rc;
     }
     // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
     FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->ungated, ungated);
+    hand_over(ctx->gate_flags, flags);
     ctx->has_gate = gate != nullptr;
     ctx->gate = gate ? *gate : cvo_fe_depth_gate{};
     drop_graphs(ctx);   // (the gate's numbers and the planes of a frame are part of a captured graph)
@@ -1411,26 +1595,24 @@ int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride)
     if (mask && stride < (size_t)w) return fail(ctx, CVO_HIP_ERR_INVALID, "set_mask: stride below the width");
     if (!mask && !ctx->has_mask) return CVO_HIP_OK;
     FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint16_t> ungated;
+    Dev<uint8_t> flags, d_mask;
+    Pin<uint8_t> h_mask;
     if (mask) {
-        const int rc = gate_buffers(ctx);
+        const int rc = gate_buffers(ctx, ungated, flags);
         if (rc) return rc;
-        if (!ctx->d_mask) {   // (the two come and go together)
-            uint8_t *dm = nullptr, *hm = nullptr;
-            if (dev_alloc(&dm, rect_plane(ctx->np)) != hipSuccess || pin_alloc(&hm, (size_t)ctx->np) != hipSuccess) {
-                if (dm) (void)hipFree(dm);
-                (void)hipGetLastError();
-                return fail(ctx, CVO_HIP_ERR_NOMEM, "set_mask: device and pinned memory for the mask");
-            }
-            ctx->d_mask = dm;
-            ctx->h_mask = hm;
-        }
+        // (the mask's device plane and its staging image come and go together)
+        if (!ctx->d_mask && !(dev_alloc(d_mask, rect_plane(ctx->np)) && pin_alloc(h_mask, (size_t)ctx->np)))
+            return no_memory(ctx, "set_mask: device and pinned memory for the mask");
     }
     // (no frame is in flight: once the stream is idle no upload reads the staging image any more)
     FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->ungated, ungated);
+    hand_over(ctx->gate_flags, flags);
+    hand_over(ctx->d_mask, d_mask);
+    hand_over(ctx->h_mask, h_mask);
     if (mask) {
-        if (stride == (size_t)w) std::memcpy(ctx->h_mask, mask, (size_t)ctx->np);
-        else
-            for (int y = 0; y < h; ++y) std::memcpy(ctx->h_mask + (size_t)y * w, mask + (size_t)y * stride, (size_t)w);
+        copy_rows(ctx->h_mask.get(), mask, stride, (size_t)w, h);
         ctx->mask_dirty = true;
     }
     // new contents go to the same address: only a mask that appears or disappears changes a frame's sequence
@@ -1450,58 +1632,32 @@ int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
         return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: members must be finite and fx, fy, depth_scale positive");
     if (!model && !ctx->custom) return CVO_HIP_OK;
     if (model && ctx->custom && std::memcmp(model, &ctx->cam, sizeof(*model)) == 0) return CVO_HIP_OK;
-    bool distorts = false;
-    if (model)
-        for (int q = 0; q < 5; ++q) distorts = distorts || model->dist[q] != 0.0f;
-    if (distorts) {
+    const bool bent = model && distorts(model->dist);
+    if (bent) {
         const size_t np = (size_t)ctx->np, plane = rect_plane(ctx->np);
         std::vector<int32_t> map;
         try { map.resize(2 * plane); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "set_camera"); }
         if (cvo_fe_rectify_map(model, ctx->d.w, ctx->d.h, map.data(), map.data() + plane) != CVO_HIP_OK)
             return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: rectify_map");
         FE_HIP(hipSetDevice(ctx->device));
-        // the new map goes into a buffer of its own and replaces the old one only once it is whole:
-        // after any failure here the context still has the camera, the map and the graphs it had
-        int32_t *new_map = nullptr;
+        Dev<uint8_t> raw_img;
+        Dev<uint16_t> raw_depth;
+        Dev<int32_t> new_map;
         const bool first = !ctx->raw_img;   // (the two raw buffers come and go together)
-        auto undo = [&]() {
-            if (new_map) (void)hipFree(new_map);
-            if (first) {
-                if (ctx->raw_img) (void)hipFree(ctx->raw_img);
-                if (ctx->raw_depth) (void)hipFree(ctx->raw_depth);
-                ctx->raw_img = nullptr;
-                ctx->raw_depth = nullptr;
-            }
-        };
-        if ((first && (dev_alloc(&ctx->raw_img, np * 3) != hipSuccess || dev_alloc(&ctx->raw_depth, np) != hipSuccess)) ||
-            dev_alloc(&new_map, 2 * plane) != hipSuccess) {
-            (void)hipGetLastError();
-            undo();
-            return fail(ctx, CVO_HIP_ERR_NOMEM, "set_camera: device memory for the raw images and the map");
-        }
-        hipError_t e = hipMemcpy(new_map, map.data(), 2 * plane * sizeof(int32_t), hipMemcpyHostToDevice);
+        if ((first && !(dev_alloc(raw_img, np * 3) && dev_alloc(raw_depth, np))) || !dev_alloc(new_map, 2 * plane))
+            return no_memory(ctx, "set_camera: device memory for the raw images and the map");
+        hipError_t e = hipMemcpy(new_map.get(), map.data(), 2 * plane * sizeof(int32_t), hipMemcpyHostToDevice);
         // (no frame is in flight: once the stream is idle nothing reads the old map any more)
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            undo();
-            return fail(ctx, CVO_HIP_ERR_HIP, "set_camera: upload of the map", e);
-        }
-        if (ctx->rect_map) (void)hipFree(ctx->rect_map);
-        ctx->rect_map = new_map;
+        if (e != hipSuccess) return fail(ctx, CVO_HIP_ERR_HIP, "set_camera: upload of the map", e);
+        hand_over(ctx->raw_img, raw_img);
+        hand_over(ctx->raw_depth, raw_depth);
+        ctx->rect_map = std::move(new_map);
     }
     ctx->custom = model != nullptr;
     ctx->cam = model ? *model : cvo_fe_camera_model{};
-    ctx->rectify = distorts;
-    // A graph captured for the camera before holds its numbers, its buffers (the map's address too) and
-    // its first node.  Dropping those graphs here is what keeps them from being launched again -- and what
-    // keeps the cache of 8 from filling with dead entries; the generation in the key is the guard
-    // behind it, should a graph ever outlive a change of camera.
-    ctx->cam_gen++;
-    for (auto &g : ctx->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    ctx->graphs.clear();
+    ctx->rectify = bent;
+    drop_graphs(ctx);
     return CVO_HIP_OK;
 }
 
@@ -1509,12 +1665,10 @@ int cvo_fe_get_camera(const cvo_fe_ctx *ctx, cvo_fe_camera_model *out, int *cust
 {
     cvo_lock::Api api_guard;
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    if (ctx->custom) *out = ctx->cam;
-    else {
-        float cam[5];
-        cvo_fe_camera(ctx->p_seq, cam);
-        *out = cvo_fe_camera_model{cam[0], cam[1], cam[2], cam[3], cam[4], {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
-    }
+    float cam[5];
+    camera_in_force(ctx, ctx->p_seq, cam);
+    const float *dist = ctx->cam.dist;   // (all zero without a caller's model)
+    *out = cvo_fe_camera_model{cam[0], cam[1], cam[2], cam[3], cam[4], {dist[0], dist[1], dist[2], dist[3], dist[4]}};
     if (custom) *custom = ctx->custom ? 1 : 0;
     return CVO_HIP_OK;
 }
@@ -1527,22 +1681,10 @@ int cvo_fe_destroy(cvo_fe_ctx *ctx)
     if (!ctx) return CVO_HIP_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    void *dev[] = {ctx->img, ctx->gray, ctx->pattern, ctx->tmp8, ctx->st8, ctx->edges, ctx->depth, ctx->hsv,
-                   ctx->I[0], ctx->I[1], ctx->I[2], ctx->ag[0], ctx->ag[1], ctx->ag[2], ctx->dx0, ctx->dy0,
-                   ctx->map, ctx->ths, ctx->ths_s, ctx->pos, ctx->feat, ctx->sdiv, ctx->hdiv, ctx->cnt,
-                   ctx->mag, ctx->grad, ctx->ctrl, ctx->blk_cnt, ctx->raw_img, ctx->raw_depth, ctx->rect_map,
-                   ctx->rig_depth, ctx->rays, ctx->zbuf, ctx->ungated, ctx->gate_flags, ctx->d_mask};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    for (auto &g : ctx->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    void *pin[] = {ctx->h_img, ctx->h_depth, ctx->h_ctrl, ctx->h_pos, ctx->h_feat, ctx->h_mask};
-    for (void *p : pin)
-        if (p) (void)hipHostFree(p);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    drop_graphs(ctx);
+    const hipStream_t own = ctx->own_stream ? ctx->stream : nullptr;
+    delete ctx;   // (every buffer goes with its owner)
+    if (own) (void)hipStreamDestroy(own);
     return CVO_HIP_OK;
 }
 
@@ -1581,29 +1723,22 @@ int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **
     ctx->np = (int)np;
     ctx->nchunks = (int)((np + FE_CHUNK - 1) / FE_CHUNK);
     ctx->cap = (int)np;   // (a selection can never hold more points than the image has pixels)
-    bool ok = true;
-    ok = ok && dev_alloc(&ctx->img, np * 3) == hipSuccess && dev_alloc(&ctx->gray, np) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->pattern, np) == hipSuccess && dev_alloc(&ctx->tmp8, np) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->st8, np) == hipSuccess && dev_alloc(&ctx->edges, np) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->depth, np) == hipSuccess && dev_alloc(&ctx->hsv, np) == hipSuccess;
+    const size_t cap = np, ncell = (size_t)d.w32 * d.h32 + 1;
+    bool ok = dev_alloc(ctx->img, np * 3) && dev_alloc(ctx->gray, np) && dev_alloc(ctx->pattern, np) &&
+              dev_alloc(ctx->tmp8, np) && dev_alloc(ctx->st8, np) && dev_alloc(ctx->edges, np) &&
+              dev_alloc(ctx->depth, np) && dev_alloc(ctx->hsv, np);
     for (int l = 0; l < FE_LEVELS; ++l) {
         const size_t nl = (size_t)d.wl[l] * d.hl[l] + 8;
-        ok = ok && dev_alloc(&ctx->I[l], nl) == hipSuccess && dev_alloc(&ctx->ag[l], nl) == hipSuccess;
+        ok = ok && dev_alloc(ctx->I[l], nl) && dev_alloc(ctx->ag[l], nl);
     }
-    ok = ok && dev_alloc(&ctx->dx0, np) == hipSuccess && dev_alloc(&ctx->dy0, np) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->map, np) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->ths, (size_t)d.w32 * d.h32 + 1) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->ths_s, (size_t)d.w32 * d.h32 + 1) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->pos, (size_t)ctx->cap * 3) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->feat, (size_t)ctx->cap * 5) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->sdiv, 256) == hipSuccess && dev_alloc(&ctx->hdiv, 256) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->cnt, 2 * (size_t)ctx->nchunks) == hipSuccess && dev_alloc(&ctx->mag, np) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->grad, np) == hipSuccess && dev_alloc(&ctx->ctrl, 1) == hipSuccess;
-    ok = ok && dev_alloc(&ctx->blk_cnt, 3 * ((size_t)((width + 3) / 4) * ((height + 3) / 4) / 4 + 2)) == hipSuccess;
-    ok = ok && pin_alloc(&ctx->h_img, np * 3) == hipSuccess && pin_alloc(&ctx->h_depth, np) == hipSuccess;
-    ok = ok && pin_alloc(&ctx->h_ctrl, 1) == hipSuccess;
-    ok = ok && pin_alloc(&ctx->h_pos, (size_t)ctx->cap * 3) == hipSuccess;
-    ok = ok && pin_alloc(&ctx->h_feat, (size_t)ctx->cap * 5) == hipSuccess;
+    ok = ok && dev_alloc(ctx->dx0, np) && dev_alloc(ctx->dy0, np) && dev_alloc(ctx->map, np) &&
+         dev_alloc(ctx->ths, ncell) && dev_alloc(ctx->ths_s, ncell) && dev_alloc(ctx->pos, cap * 3) &&
+         dev_alloc(ctx->feat, cap * 5) && dev_alloc(ctx->sdiv, 256) && dev_alloc(ctx->hdiv, 256) &&
+         dev_alloc(ctx->cnt, 2 * (size_t)ctx->nchunks) && dev_alloc(ctx->mag, np) && dev_alloc(ctx->grad, np) &&
+         dev_alloc(ctx->ctrl, 1) &&
+         dev_alloc(ctx->blk_cnt, 3 * ((size_t)((width + 3) / 4) * ((height + 3) / 4) / 4 + 2)) &&
+         pin_alloc(ctx->h_img, np * 3) && pin_alloc(ctx->h_depth, np) && pin_alloc(ctx->h_ctrl, 1) &&
+         pin_alloc(ctx->h_pos, cap * 3) && pin_alloc(ctx->h_feat, cap * 5);
     if (!ok) return bail(CVO_HIP_ERR_NOMEM);
     // OpenCV's reciprocal tables of the 8-bit HSV conversion (12-bit fixed point)
     int sdiv[256], hdiv[256];
@@ -1614,11 +1749,11 @@ int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **
     }
     // the selector's pattern does not depend on the frame: made once (the reference
     // re-seeds and redraws it for every frame, ref thirdparty/PixelSelector2.cpp:33-37)
-    cvo_fe_random_pattern((int)np, ctx->h_img);
-    if (hipMemcpy(ctx->pattern, ctx->h_img, np, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ctx->sdiv, sdiv, sizeof(sdiv), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ctx->hdiv, hdiv, sizeof(hdiv), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(ctx->edges, 0, np) != hipSuccess || hipMemset(ctx->map, 0, np * sizeof(float)) != hipSuccess)
+    cvo_fe_random_pattern((int)np, ctx->h_img.get());
+    if (hipMemcpy(ctx->pattern.get(), ctx->h_img.get(), np, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ctx->sdiv.get(), sdiv, sizeof(sdiv), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ctx->hdiv.get(), hdiv, sizeof(hdiv), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(ctx->edges.get(), 0, np) != hipSuccess || hipMemset(ctx->map.get(), 0, np * sizeof(float)) != hipSuccess)
         return bail(CVO_HIP_ERR_HIP);
     *out = ctx;
     return CVO_HIP_OK;
@@ -1627,8 +1762,8 @@ int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **
 int cvo_fe_host_buffers(cvo_fe_ctx *ctx, uint8_t **img, uint16_t **depth)
 {
     if (!ctx || !img || !depth) return CVO_HIP_ERR_INVALID;
-    *img = ctx->h_img;
-    *depth = ctx->h_depth;
+    *img = ctx->h_img.get();
+    *depth = ctx->h_depth.get();
     return CVO_HIP_OK;
 }
 
@@ -1647,10 +1782,6 @@ int cvo_fe_set_num_want(cvo_fe_ctx *ctx, int num_want)
     return CVO_HIP_OK;
 }
 
-namespace {
-int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type);
-}
-
 int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const uint16_t *depth,
                   size_t depth_stride, int dataset_seq, int feature_type)
 {
@@ -1664,24 +1795,16 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the previous frame was not collected");
     FE_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // pinned staging; the depth rows are staged while the colour image is on its way
-    if (img == ctx->h_img && img_stride == (size_t)w * 3) {
-        // (the caller decoded into the staging image itself: cvo_fe_host_buffers)
-    } else if (img_stride == (size_t)w * 3) std::memcpy(ctx->h_img, img, (size_t)np * 3);
-    else
-        for (int y = 0; y < h; ++y)
-            std::memcpy(ctx->h_img + (size_t)y * w * 3, img + (size_t)y * img_stride, (size_t)w * 3);
-    if (depth == ctx->h_depth && depth_stride == (size_t)dw * 2) {
-    } else if (depth_stride == (size_t)dw * 2) std::memcpy(ctx->h_depth, depth, (size_t)dw * dh * 2);
-    else
-        for (int y = 0; y < dh; ++y)
-            std::memcpy(ctx->h_depth + (size_t)y * dw, (const uint8_t *)depth + (size_t)y * depth_stride, (size_t)dw * 2);
+    // pinned staging (not when the caller decoded into the staging image itself: cvo_fe_host_buffers)
+    if (!(img == ctx->h_img.get() && img_stride == (size_t)w * 3)) copy_rows(ctx->h_img.get(), img, img_stride, (size_t)w * 3, h);
+    if (!(depth == ctx->h_depth.get() && depth_stride == (size_t)dw * 2))
+        copy_rows(ctx->h_depth.get(), depth, depth_stride, (size_t)dw * 2, dh);
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
     *ctx->h_ctrl = c0;
     // a mask set since the last frame: in front of the frame, outside the captured graph (its address is the graph's)
     if (ctx->has_mask && ctx->mask_dirty) {
-        FE_HIP(hipMemcpyAsync(ctx->d_mask, ctx->h_mask, (size_t)np, hipMemcpyHostToDevice, s));
+        FE_HIP(hipMemcpyAsync(ctx->d_mask.get(), ctx->h_mask.get(), (size_t)np, hipMemcpyHostToDevice, s));
         ctx->mask_dirty = false;
     }
     // Everything from here to the copies back is the same sequence for every frame (fixed
@@ -1715,7 +1838,7 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
             }
         }
     }
-    ctx->copied = ctx->device_output ? 0 : std::min(ctx->cap, std::max(4096, 2 * ctx->num_want));
+    ctx->copied = optimistic_copy(ctx);   // (a launched graph does not pass run_emit)
     if (g) {
         FE_HIP(hipGraphLaunch(g->exec, s));
     } else {
@@ -1726,100 +1849,6 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     ctx->p_seq = seq_given;
     ctx->p_ftype = feature_type;
     return CVO_HIP_OK;
-}
-
-namespace {
-// one frame's device work, in stream order (also what a captured graph holds)
-int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
-{
-    const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
-    hipStream_t s = ctx->stream;
-    // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
-    FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img : ctx->img, ctx->h_img, (size_t)np * 3, hipMemcpyHostToDevice, s));
-    // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
-    // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
-    uint16_t *plane = depth_plane(ctx);
-    uint16_t *depth_in = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : plane;
-    FE_HIP(hipMemcpyAsync(depth_in, ctx->h_depth, (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
-    FE_HIP(hipMemcpyAsync(ctx->ctrl, ctx->h_ctrl, sizeof(FeCtrl), hipMemcpyHostToDevice, s));
-    if (ctx->rectify)
-        hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img,
-                           ctx->has_rig ? (const uint16_t *)nullptr : ctx->raw_depth, ctx->rect_map,
-                           ctx->rect_map + rect_plane(np), w, h, ctx->img, plane);
-    if (ctx->has_rig) {
-        const cvo_fe_depth_camera &r = ctx->rig;
-        DepthWarpArgs a{};
-        a.depth = ctx->rig_depth; a.rays = ctx->rays; a.z = ctx->zbuf;
-        a.dw = r.width; a.dh = r.height; a.w = w; a.h = h;
-        a.scale = r.depth_scale; a.min_range = r.min_range; a.max_range = r.max_range;
-        for (int q = 0; q < 9; ++q) a.R[q] = r.R[q];
-        for (int q = 0; q < 3; ++q) a.T[q] = r.T[q];
-        // the colour camera in force for this frame (a distorting model: its rectified pinhole)
-        if (ctx->custom) {
-            const cvo_fe_camera_model &m = ctx->cam;
-            a.cam[0] = m.depth_scale; a.cam[1] = m.fx; a.cam[2] = m.fy; a.cam[3] = m.cx; a.cam[4] = m.cy;
-        } else cvo_fe_camera(dataset_seq, a.cam);   // (never fails here: an index outside the table means row 0)
-        hipLaunchKernelGGL(k_fe_depth_warp, dim3(blocks(a.dw * a.dh)), dim3(FE_BLOCK), 0, s, a);
-        hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf, np, plane);
-    }
-    if (gate_active(ctx)) {
-        GateArgs g{};
-        g.u = ctx->ungated; g.depth = ctx->depth; g.flags = ctx->gate_flags;
-        g.mask = ctx->has_mask ? ctx->d_mask : nullptr;
-        // the mask lies on the grid of the image as uploaded: under a distorting model it follows the map
-        g.qu = ctx->has_mask && ctx->rectify ? ctx->rect_map : nullptr;
-        g.qv = g.qu ? ctx->rect_map + rect_plane(np) : nullptr;
-        g.w = w; g.h = h;
-        if (ctx->custom) g.scale = ctx->cam.depth_scale;
-        else {
-            float cam[5];
-            cvo_fe_camera(dataset_seq, cam);
-            g.scale = cam[0];
-        }
-        if (ctx->has_gate) {
-            g.min_range = ctx->gate.min_range; g.max_range = ctx->gate.max_range; g.jump_rel = ctx->gate.jump_rel;
-            g.grow = ctx->gate.grow; g.hole_border = ctx->gate.hole_border;
-        }
-        const dim3 tiles((w + FG_TW - 1) / FG_TW, (h + FG_TH - 1) / FG_TH);
-        switch (g.grow) {   // (0..3: cvo_fe_check_depth_gate)
-        case 0: hipLaunchKernelGGL(k_fe_depth_gate<0>, tiles, dim3(FE_BLOCK), 0, s, g); break;
-        case 1: hipLaunchKernelGGL(k_fe_depth_gate<1>, tiles, dim3(FE_BLOCK), 0, s, g); break;
-        case 2: hipLaunchKernelGGL(k_fe_depth_gate<2>, tiles, dim3(FE_BLOCK), 0, s, g); break;
-        default: hipLaunchKernelGGL(k_fe_depth_gate<3>, tiles, dim3(FE_BLOCK), 0, s, g); break;
-        }
-    }
-
-    const FeDims &d = ctx->d;
-    hipLaunchKernelGGL(k_fe_level0, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, ctx->img, w, h, ctx->sdiv, ctx->hdiv,
-                       ctx->gray, ctx->hsv, ctx->I[0], ctx->ag[0], ctx->dx0, ctx->dy0);
-    for (int l = 1; l < FE_LEVELS; ++l)
-        hipLaunchKernelGGL(k_fe_level, dim3(blocks(d.wl[l] * d.hl[l])), dim3(FE_BLOCK), 0, s, ctx->I[l - 1],
-                           2 * d.wl[l] /* the reference's row stride of the level above, also when
-                                           that level is one pixel wider (ref src/pcd_generator.cpp:82) */,
-                           ctx->I[l], d.wl[l], d.hl[l], ctx->ag[l]);
-    const int ncell = d.w32 * d.h32;
-    hipLaunchKernelGGL(k_fe_hist, dim3(ncell), dim3(FE_BLOCK), 0, s, ctx->ag[0], w, h, d.w32, ctx->ths);
-    hipLaunchKernelGGL(k_fe_smooth, dim3(blocks(ncell)), dim3(FE_BLOCK), 0, s, ctx->ths, d.w32, d.h32, ctx->ths_s);
-    SelectArgs sa{ctx->ag[0], ctx->ag[1], ctx->ag[2], ctx->ths_s, ctx->map, ctx->ctrl, ctx->blk_cnt, w, h, d.w32, ncell, 0};
-    const int nb0 = (((w + 11) / 12) * ((h + 11) / 12) + 3) / 4;   // potential 3: one wave per 12 x 12 block
-    hipLaunchKernelGGL(k_fe_select, dim3(nb0), dim3(FE_BLOCK), 0, s, sa);
-    hipLaunchKernelGGL(k_fe_decide, dim3(1), dim3(FE_BLOCK), 0, s, ctx->ctrl, ctx->blk_cnt, nb0, 0, (float)ctx->num_want);
-    sa.pass = 1;
-    const int nb1 = (((w + 3) / 4) * ((h + 3) / 4) + 3) / 4;       // any potential >= 1
-    hipLaunchKernelGGL(k_fe_select, dim3(nb1), dim3(FE_BLOCK), 0, s, sa);
-    hipLaunchKernelGGL(k_fe_decide, dim3(1), dim3(FE_BLOCK), 0, s, ctx->ctrl, ctx->blk_cnt, nb1, 1, (float)ctx->num_want);
-    hipLaunchKernelGGL(k_fe_count<0>, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, ctx->map, ctx->depth, np, ctx->ctrl,
-                       ctx->cnt);
-    hipLaunchKernelGGL(k_fe_subsample, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, ctx->map, np, ctx->pattern, ctx->cnt,
-                       ctx->ctrl);
-    FE_HIP(hipGetLastError());
-    // the cloud is emitted at once; a frame that needs the edge top-up (rare: a nearly
-    // texture-free image) is noticed at collect(), when the control block has arrived, and
-    // emitted again
-    return run_emit(ctx, dataset_seq, feature_type);
-}
-
-int collect_impl(cvo_fe_ctx *ctx, float *positions, float *features, int capacity, int *num_points, bool to_host);
 }
 
 int cvo_fe_collect(cvo_fe_ctx *ctx, float *positions, float *features, int capacity, int *num_points)
@@ -1837,52 +1866,10 @@ int cvo_fe_collect_device(cvo_fe_ctx *ctx, const float **d_positions, const floa
     if (!ctx) return CVO_HIP_ERR_INVALID;
     if (!d_positions || !d_features || !num_points) return fail(ctx, CVO_HIP_ERR_INVALID, "collect_device: bad argument");
     const int rc = collect_impl(ctx, nullptr, nullptr, ctx->cap, num_points, false);
-    *d_positions = ctx->pos;
-    *d_features = ctx->feat;
+    *d_positions = ctx->pos.get();
+    *d_features = ctx->feat.get();
     return rc;
 }
-
-namespace {
-int collect_impl(cvo_fe_ctx *ctx, float *positions, float *features, int capacity, int *num_points, bool to_host)
-{
-    if (!ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "collect: no frame was submitted");
-    ctx->pending = false;
-    FE_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    FE_HIP(hipStreamSynchronize(s));
-    int rc = CVO_HIP_OK;
-    // ref src/pcd_generator.cpp:141-144: fewer than a third of what was asked for?
-    const int num_selected = ctx->h_ctrl->in_map;   // (before any top-up: that is what the reference tests)
-    const bool canny = num_selected < ctx->num_want / 3;
-    if (canny) {
-        rc = run_canny(ctx);
-        if (!rc) rc = run_emit(ctx, ctx->p_seq, ctx->p_ftype);
-        if (rc) return rc;
-        FE_HIP(hipStreamSynchronize(s));
-    }
-    const FeCtrl &c = *ctx->h_ctrl;
-    ctx->info.num_selected = num_selected;
-    ctx->info.reselected = c.redo;
-    ctx->info.pot_used = c.pot[c.redo ? 1 : 0];
-    ctx->info.canny_used = canny ? 1 : 0;
-    ctx->info.num_points = c.num_points;
-    *num_points = c.num_points;
-    const int ncopy = std::min(std::min(c.num_points, capacity), ctx->cap);
-    if (to_host && ncopy > ctx->copied) {   // an unusually large cloud: fetch the rest
-        const size_t from = (size_t)ctx->copied, more = (size_t)(ncopy - ctx->copied);
-        FE_HIP(hipMemcpyAsync(ctx->h_pos + from * 3, ctx->pos + from * 3, more * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        FE_HIP(hipMemcpyAsync(ctx->h_feat + from * 5, ctx->feat + from * 5, more * 5 * sizeof(float), hipMemcpyDeviceToHost, s));
-        FE_HIP(hipStreamSynchronize(s));
-    }
-    if (to_host && ncopy > 0) {
-        std::memcpy(positions, ctx->h_pos, (size_t)ncopy * 3 * sizeof(float));
-        std::memcpy(features, ctx->h_feat, (size_t)ncopy * 5 * sizeof(float));
-    }
-    if (c.num_points > ncopy) return fail(ctx, CVO_HIP_ERR_INVALID, "create_pointcloud: more points than capacity");
-    return CVO_HIP_OK;
-}
-
-}   // namespace
 
 int cvo_fe_create_pointcloud(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const uint16_t *depth,
                              size_t depth_stride, int dataset_seq, int feature_type, float *positions,
@@ -1913,24 +1900,21 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     const void *src = nullptr;
     size_t need = 0;
     switch (stage) {
-    case CVO_FE_STAGE_GRAY: src = ctx->gray; need = np; break;
-    case CVO_FE_STAGE_HSV: src = ctx->hsv; need = np * 3; break;
-    case CVO_FE_STAGE_MAP: src = ctx->map; need = np * 4; break;
-    case CVO_FE_STAGE_AG0: src = ctx->ag[0]; need = np * 4; break;
-    case CVO_FE_STAGE_AG1: src = ctx->ag[1]; need = (size_t)d.wl[1] * d.hl[1] * 4; break;
-    case CVO_FE_STAGE_AG2: src = ctx->ag[2]; need = (size_t)d.wl[2] * d.hl[2] * 4; break;
-    case CVO_FE_STAGE_THS: src = ctx->ths_s; need = (size_t)d.w32 * d.h32 * 4; break;
-    case CVO_FE_STAGE_DX0: src = ctx->dx0; need = np * 4; break;
-    case CVO_FE_STAGE_DY0: src = ctx->dy0; need = np * 4; break;
-    case CVO_FE_STAGE_EDGES: src = ctx->edges; need = np; break;
-    case CVO_FE_STAGE_RECT_BGR: src = ctx->img; need = np * 3; break;
-    case CVO_FE_STAGE_RECT_DEPTH: src = ctx->depth; need = np * 2; break;
-    case CVO_FE_STAGE_RAW_DEPTH:
-        src = ctx->has_rig ? ctx->rig_depth : ctx->rectify ? ctx->raw_depth : depth_plane(ctx);
-        need = (size_t)ctx->dw * ctx->dh * 2;
-        break;
+    case CVO_FE_STAGE_GRAY: src = ctx->gray.get(); need = np; break;
+    case CVO_FE_STAGE_HSV: src = ctx->hsv.get(); need = np * 3; break;
+    case CVO_FE_STAGE_MAP: src = ctx->map.get(); need = np * 4; break;
+    case CVO_FE_STAGE_AG0: src = ctx->ag[0].get(); need = np * 4; break;
+    case CVO_FE_STAGE_AG1: src = ctx->ag[1].get(); need = (size_t)d.wl[1] * d.hl[1] * 4; break;
+    case CVO_FE_STAGE_AG2: src = ctx->ag[2].get(); need = (size_t)d.wl[2] * d.hl[2] * 4; break;
+    case CVO_FE_STAGE_THS: src = ctx->ths_s.get(); need = (size_t)d.w32 * d.h32 * 4; break;
+    case CVO_FE_STAGE_DX0: src = ctx->dx0.get(); need = np * 4; break;
+    case CVO_FE_STAGE_DY0: src = ctx->dy0.get(); need = np * 4; break;
+    case CVO_FE_STAGE_EDGES: src = ctx->edges.get(); need = np; break;
+    case CVO_FE_STAGE_RECT_BGR: src = ctx->img.get(); need = np * 3; break;
+    case CVO_FE_STAGE_RECT_DEPTH: src = ctx->depth.get(); need = np * 2; break;
+    case CVO_FE_STAGE_RAW_DEPTH: src = depth_upload(ctx); need = (size_t)ctx->dw * ctx->dh * 2; break;
     case CVO_FE_STAGE_UNGATED_DEPTH: src = depth_plane(ctx); need = np * 2; break;
-    case CVO_FE_STAGE_GATE: src = gate_active(ctx) ? ctx->gate_flags : nullptr; need = np; break;
+    case CVO_FE_STAGE_GATE: src = gate_active(ctx) ? ctx->gate_flags.get() : nullptr; need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");

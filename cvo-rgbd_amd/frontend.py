@@ -40,7 +40,24 @@ class Info(C.Structure):
                 ("canny_used", C.c_int32), ("num_points", C.c_int32), ("pad_", C.c_int32)]
 
 
-class CameraModel(C.Structure):
+class _Settings(C.Structure):
+    """What the structures a caller hands to a setter share, derived from `_fields_`; a `pad_` is shown nowhere."""
+
+    def astuple(self):
+        vals = (getattr(self, name) for name, _ in self._fields_ if name != "pad_")
+        return tuple(tuple(v) if isinstance(v, C.Array) else v for v in vals)
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        names = (name for name, _ in self._fields_ if name != "pad_")
+        return "%s(%s)" % (type(self).__name__, ", ".join("%s=%r" % nv for nv in zip(names, self.astuple())))
+
+
+class CameraModel(_Settings):
     """cvo_fe_camera_model: a caller's camera in place of the table row of `dataset_seq`.
     `dist` is (k1, k2, p1, p2, k3) in OpenCV's / TUM's order; all zero: an ideal pinhole."""
     _fields_ = [("depth_scale", C.c_float), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
@@ -51,19 +68,8 @@ class CameraModel(C.Structure):
             raise ValueError("dist holds k1, k2, p1, p2, k3")
         super().__init__(depth_scale, fx, fy, cx, cy, (C.c_float * 5)(*dist))
 
-    def astuple(self):
-        return (self.depth_scale, self.fx, self.fy, self.cx, self.cy, tuple(self.dist))
 
-    def __eq__(self, other):
-        return isinstance(other, CameraModel) and bytes(self) == bytes(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        return "CameraModel(depth_scale=%r, fx=%r, fy=%r, cx=%r, cy=%r, dist=%r)" % self.astuple()
-
-
-class DepthCamera(C.Structure):
+class DepthCamera(_Settings):
     """cvo_fe_depth_camera: a depth camera of its own -- the size of its image, its pinhole and lens,
     and where it sits: p_colour = R p_depth + T (R row-major, T in metres).  `min_range` / `max_range`
     in metres along its axis; <= 0: no limit on that side."""
@@ -80,21 +86,8 @@ class DepthCamera(C.Structure):
         super().__init__(int(width), int(height), depth_scale, fx, fy, cx, cy, (C.c_float * 5)(*dist),
                          (C.c_float * 9)(*R), (C.c_float * 3)(*T), min_range, max_range)
 
-    def astuple(self):
-        return (self.width, self.height, self.depth_scale, self.fx, self.fy, self.cx, self.cy, tuple(self.dist),
-                tuple(self.R), tuple(self.T), self.min_range, self.max_range)
 
-    def __eq__(self, other):
-        return isinstance(other, DepthCamera) and bytes(self) == bytes(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        return ("DepthCamera(width=%r, height=%r, depth_scale=%r, fx=%r, fy=%r, cx=%r, cy=%r, dist=%r, R=%r, T=%r, "
-                "min_range=%r, max_range=%r)" % self.astuple())
-
-
-class DepthGate(C.Structure):
+class DepthGate(_Settings):
     """cvo_fe_depth_gate: which pixels with a depth keep it (the gate contract of include/cvo_frontend.h).
     `min_range` / `max_range` in metres along the colour camera's axis, <= 0: no limit on that side;
     `jump_rel`: the relative depth jump between neighbours that marks a discontinuity, 0: no jump test;
@@ -105,17 +98,6 @@ class DepthGate(C.Structure):
 
     def __init__(self, min_range=0.0, max_range=0.0, jump_rel=0.0, grow=0, hole_border=0, pad_=0):
         super().__init__(min_range, max_range, jump_rel, int(grow), int(hole_border), int(pad_))
-
-    def astuple(self):
-        return (self.min_range, self.max_range, self.jump_rel, self.grow, self.hole_border)
-
-    def __eq__(self, other):
-        return isinstance(other, DepthGate) and bytes(self) == bytes(other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        return "DepthGate(min_range=%r, max_range=%r, jump_rel=%r, grow=%r, hole_border=%r)" % self.astuple()
 
 
 # The published calibrations of the TUM RGB-D sequences (fx fy cx cy, d0..d4; depth 5000 per metre).
@@ -244,14 +226,19 @@ class PcdGenerator:
             raise capi.CvoHipError("%s: %s (%s)" % (what, capi.lib().cvo_hip_error_string(st).decode(),
                                                      msg.decode() if msg else ""))
 
-    def create_pointcloud(self, bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB):
-        """load_image + create_pointcloud (ref src/pcd_generator.cpp:387-420): returns
-        (positions n x 3, features n x 5 row-major), points in image scan order."""
+    def _images(self, bgr, depth):
+        """The two images of a frame as dense arrays of the sizes the context takes."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
         depth = np.ascontiguousarray(depth, np.uint16)
         if bgr.shape != (self.height, self.width, 3) or depth.shape != self._dshape:
             raise ValueError("expected a %dx%dx3 uint8 image and a %dx%d uint16 depth map"
                              % ((self.height, self.width) + self._dshape))
+        return bgr, depth
+
+    def create_pointcloud(self, bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB):
+        """load_image + create_pointcloud (ref src/pcd_generator.cpp:387-420): returns
+        (positions n x 3, features n x 5 row-major), points in image scan order."""
+        bgr, depth = self._images(bgr, depth)
         n = C.c_int(0)
         st = lib().cvo_fe_create_pointcloud(
             self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3,
@@ -263,11 +250,7 @@ class PcdGenerator:
 
     def submit(self, bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB):
         """First half of create_pointcloud: stage the images, enqueue everything, return."""
-        bgr = np.ascontiguousarray(bgr, np.uint8)
-        depth = np.ascontiguousarray(depth, np.uint16)
-        if bgr.shape != (self.height, self.width, 3) or depth.shape != self._dshape:
-            raise ValueError("expected a %dx%dx3 uint8 image and a %dx%d uint16 depth map"
-                             % ((self.height, self.width) + self._dshape))
+        bgr, depth = self._images(bgr, depth)
         self._chk(lib().cvo_fe_submit(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3,
                                       depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2,
                                       int(dataset_seq), int(feature_type)), "submit")

@@ -158,6 +158,11 @@ class registration {
     int mask_rows_, mask_cols_;
     bool have_mask_;
     void check(int status, const char *what);
+    void fe_check(int status, const char *what, const char *why = nullptr);
+    void apply_stored_settings();
+    template <class S>
+    void store(int (*set)(cvo_fe_ctx *, const S *), const char *what, const S *value, S &kept, bool &have);
+    void store_mask(const image_view *mask);
     void publish();
     void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep);
 };

@@ -9,38 +9,9 @@
 // Per frame one line "cloud <name> <points> <digest of positions> <digest of features>" of the
 // cloud the registration holds for that frame (cvo_hip_get_device_cloud, live rows) and, once
 // initialised, the pose line of the reference's drivers.
-// Input: int32 n_frames, width, height; cvo_fe_depth_camera; per frame 32 bytes of name,
-// height*width*3 bytes (B,G,R), int32 depth width, depth height, and that many uint16 of depth.
+// Input (fe_demo_common.hpp): behind the header the cvo_fe_depth_camera; every depth image behind its size.
 // Build: g++ -std=c++17 -I include cvo_depth_camera_demo.cpp -L cvo-rgbd_amd/csrc -lcvo_hip
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <iostream>
-#include <memory>
-#include <sstream>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-#include "cvo.hpp"
-
-// digest of `rows` rows of `k` 32-bit words, modulo 2^64, whatever the order of the rows:
-// h(row) = sum of word j * (j + 1); digest = sum of h * h
-static uint64_t digest(const float *p, size_t rows, size_t k)
-{
-    uint64_t acc = 0;
-    for (size_t i = 0; i < rows; ++i) {
-        uint64_t h = 0;
-        for (size_t j = 0; j < k; ++j) {
-            uint32_t u;
-            std::memcpy(&u, p + i * k + j, 4);
-            h += (uint64_t)u * (uint64_t)(j + 1);
-        }
-        acc += h * h;
-    }
-    return acc;
-}
+#include "fe_demo_common.hpp"
 
 static void try_reflection(cvo_hip::registration &reg, cvo_fe_depth_camera rig, std::ostream &lines)
 {
@@ -55,65 +26,21 @@ static void try_reflection(cvo_hip::registration &reg, cvo_fe_depth_camera rig, 
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: demo frames.bin cvo|acvo\n"); return 2; }
-    std::ifstream in(argv[1], std::ios::binary);
-    int32_t hdr[3] = {0, 0, 0};
-    in.read(reinterpret_cast<char *>(hdr), 12);
-    cvo_fe_depth_camera rig;
-    in.read(reinterpret_cast<char *>(&rig), sizeof(rig));
-    const int nf = hdr[0], w = hdr[1], h = hdr[2];
-    const bool adaptive = std::string(argv[2]) == "acvo";
-    std::ostringstream lines, quiet;
-    std::streambuf *old = std::cout.rdbuf(quiet.rdbuf());   // run_cvo prints like the reference does
-    try {
-        std::unique_ptr<cvo_hip::registration> reg;
-        if (adaptive) reg.reset(new acvo::acvo());
-        else reg.reset(new cvo::cvo());
-        try_reflection(*reg, rig, lines);
-        reg->set_depth_camera(rig);
-        std::vector<uint8_t> rgb((size_t)w * h * 3);
-        std::vector<uint16_t> dep;
-        std::vector<float> pos4, feat8;
-        for (int i = 0; i < nf; ++i) {
-            char name[33] = {0};
-            int32_t dsz[2] = {0, 0};
-            in.read(name, 32);
-            in.read(reinterpret_cast<char *>(rgb.data()), (std::streamsize)rgb.size());
-            in.read(reinterpret_cast<char *>(dsz), 8);
-            if (!in || dsz[0] < 1 || dsz[1] < 1 || dsz[0] > 8192 || dsz[1] > 8192) { std::fprintf(stderr, "short read\n"); return 2; }
-            dep.resize((size_t)dsz[0] * dsz[1]);
-            in.read(reinterpret_cast<char *>(dep.data()), (std::streamsize)dep.size() * 2);
-            if (!in) { std::fprintf(stderr, "short read\n"); return 2; }
-            if (i == 2) reg->clear_depth_camera();
+    return fe_demo::run(argc, argv, 3, "demo frames.bin cvo|acvo", [](fe_demo::Demo &d) {
+        cvo_fe_depth_camera rig;
+        d.read(&rig, 1);
+        try_reflection(*d.reg, rig, d.lines);
+        d.reg->set_depth_camera(rig);
+        for (int i = 0; i < d.nf; ++i) {
+            d.next_frame(/*depth_sizes*/ true);
+            if (i == 2) d.reg->clear_depth_camera();
             if (i == 3) {
-                try_reflection(*reg, rig, lines);
-                reg->set_depth_camera(rig);
+                try_reflection(*d.reg, rig, d.lines);
+                d.reg->set_depth_camera(rig);
             }
-            const cvo_hip::image_view RGB_img{rgb.data(), h, w, (size_t)w * 3};
-            const cvo_hip::image_view dep_img{dep.data(), dsz[1], dsz[0], (size_t)dsz[0] * 2};
-            reg->run_cvo(/*dataset_seq*/ 1, RGB_img, dep_img);
-            // the frame's cloud is the fixed one now (first frame: handed over as fixed; later: swapped after align)
-            int rows = 0, points = 0;
-            if (cvo_hip_get_device_cloud(reg->context(), 0, nullptr, nullptr, nullptr, &rows, &points) != CVO_HIP_OK)
-                throw std::runtime_error("cvo_hip_get_device_cloud");
-            pos4.assign((size_t)rows * 4, 0.0f);
-            feat8.assign((size_t)rows * 8, 0.0f);
-            if (cvo_hip_get_device_cloud(reg->context(), 0, pos4.data(), feat8.data(), nullptr, &rows, &points) != CVO_HIP_OK)
-                throw std::runtime_error("cvo_hip_get_device_cloud");
-            lines << "cloud " << name << " " << points << " " << digest(pos4.data(), (size_t)points, 4) << " "
-                  << digest(feat8.data(), (size_t)points, 8) << "\n";
-            float q[4];
-            reg->accum_transform.quaternion(q);
-            lines << name << " " << reg->accum_transform.matrix()(0, 3) << " " << reg->accum_transform.matrix()(1, 3) << " "
-                  << reg->accum_transform.matrix()(2, 3) << " " << q[0] << " " << q[1] << " " << q[2] << " " << q[3] << "\n";
+            d.reg->run_cvo(/*dataset_seq*/ 1, d.rgb_view(), d.dep_view());
+            d.cloud_line();
+            d.pose_line();
         }
-        std::cout.rdbuf(old);
-        std::cout << lines.str();
-        std::cout << "points_last_frame " << reg->num_points_last_frame() << " iterations " << reg->num_iterations() << "\n";
-    } catch (const std::exception &e) {
-        std::cout.rdbuf(old);
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+    });
 }

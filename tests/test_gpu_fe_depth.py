@@ -6,9 +6,6 @@ depth: every cloud bit for bit.  The rectified colour frame as the target, the u
 without a rig, the captured graphs across changes of rig and camera, the Python and C++
 layers above, and the refusals."""
 import io
-import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +13,7 @@ import pytest
 import fe_depth_ref as D
 import fe_rectify_ref as R
 from conftest import low_texture_frame
+from fe_gpu_common import _demo_lines, _device_path_lines, _four_frames, _pose_line_f32, _same_cloud
 from oracle import pyoracle_fe as fo
 
 pytestmark = pytest.mark.gpu
@@ -31,15 +29,6 @@ def _reg(key, rig, cam, w, h, dep):
         out.setflags(write=False)
         _REG[key] = out
     return _REG[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same_cloud(got, want):
-    return (got[0].shape == want[0].shape and np.array_equal(_bits(got[0]), _bits(want[0])) and
-            np.array_equal(_bits(got[1]), _bits(want[1])))
 
 
 def _generator(pkg, name):
@@ -256,19 +245,15 @@ def test_twenty_repeats_give_the_same_bytes(pkg):
 
 # ---- 4. the layers above --------------------------------------------------------------------
 
-def _four_frames(pkg):
-    out = []
-    for k in range(4):
-        bgr, dep = pkg.data.synthetic_rgbd_frame(seed=75, texture=1.0, motion=(1.2 * k, -0.6 * k))
-        out.append(("1305031453.%06d" % (359684 + 33333 * k), bgr, np.ascontiguousarray(dep // 5)))
-    return out
+def _frames(pkg):
+    return _four_frames(pkg, 75, lambda k, dep: np.ascontiguousarray(dep // 5))
 
 
 def test_run_frames_with_a_depth_camera(pkg):
     """run_frames(depth_camera=rig) on the raw frames = run_frames without a rig on the reference-registered
     frames: the same poses"""
     F = pkg.frontend
-    frames = _four_frames(pkg)
+    frames = _frames(pkg)
     reg_frames = [(name, bgr, _reg(("seq", k), D.VGA_RIG, D.VGA_COLOUR, 640, 480, dep))
                   for k, (name, bgr, dep) in enumerate(frames)]
     poses = []
@@ -282,109 +267,41 @@ def test_run_frames_with_a_depth_camera(pkg):
     assert np.array_equal(poses[0][1], poses[1][1]) and poses[0][2] == poses[1][2] > 0
 
 
-def _digest(a):
-    """cvo_depth_camera_demo.cpp's digest of an array of rows: modulo 2^64, whatever the order of the rows"""
-    w = np.ascontiguousarray(a).view(np.uint32).astype(np.uint64)
-    h = (w * np.arange(1, w.shape[1] + 1, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
-    return int((h * h).sum(dtype=np.uint64))
-
-
-def _pose_line_f32(name, M):
-    """The pose line as the C++ object prints it: the translation and Affine3f::quaternion of cvo_class.cpp (Eigen's
-    quaternion-from-matrix, every operation in float32, in that order) of the float32 matrix, each as a default
-    std::ostream prints a float (%g).  data.pose_line forms the quaternion in float64 from the same matrix, so its sixth
-    digit may differ; this restatement is what the demo's text is compared with, character for character."""
-    f = np.float32
-    m = np.asarray(M)
-    assert m.dtype == np.float32 and m.shape == (4, 4)
-    m = m.reshape(16)
-    t = (m[0] + m[5]) + m[10]
-    if t > f(0.0):
-        t = np.sqrt(t + f(1.0))
-        w = f(0.5) * t
-        t = f(0.5) / t
-        x, y, z = (m[9] - m[6]) * t, (m[2] - m[8]) * t, (m[4] - m[1]) * t
-    else:
-        i = 0
-        if m[5] > m[0]:
-            i = 1
-        if m[10] > m[5 * i]:
-            i = 2
-        j = (i + 1) % 3
-        k = (j + 1) % 3
-        t = np.sqrt(((m[5 * i] - m[5 * j]) - m[5 * k]) + f(1.0))
-        q = [f(0.0)] * 3
-        q[i] = f(0.5) * t
-        t = f(0.5) / t
-        w = (m[4 * k + j] - m[4 * j + k]) * t
-        q[j] = (m[4 * j + i] + m[4 * i + j]) * t
-        q[k] = (m[4 * k + i] + m[4 * i + k]) * t
-        x, y, z = q
-    vals = [m[3], m[7], m[11], x, y, z, w]
-    assert all(type(v) is np.float32 for v in vals)
-    return "%s %s" % (name, " ".join("%g" % float(v) for v in vals))
-
-
 @pytest.mark.parametrize("mode_name", ["cvo", "acvo"])
 def test_cpp_objects_take_a_depth_camera(pkg, tmp_path, mode_name):
     """include/cvo.hpp registration::set_depth_camera / clear_depth_camera (tests/cpp/cvo_depth_camera_demo.cpp):
     the clouds the C++ object registers and its pose lines equal the Python path's"""
     F = pkg.frontend
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "cvo_depth_camera_demo")
-    lib = os.path.join(root, "cvo-rgbd_amd", "csrc")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                    os.path.join(root, "tests", "cpp", "cvo_depth_camera_demo.cpp"), "-L", lib, "-lcvo_hip",
-                    "-Wl,-rpath," + lib, "-o", exe], check=True, timeout=120)
     w, h = 640, 480
     # frame 2 goes without a rig: a depth image of the colour size, registered already; the others come from a
     # depth camera of half the size
     frames = [(name, bgr, np.ascontiguousarray(dep * 5 if k == 2 else dep[::2, ::2]))
-              for k, (name, bgr, dep) in enumerate(_four_frames(pkg))]
+              for k, (name, bgr, dep) in enumerate(_frames(pkg))]
     small = dict(D.VGA_RIG, width=320, height=240, fx=290.0, fy=290.0, cx=156.75, cy=125.75)
     rig = D.to_struct(F, small)
-    path = str(tmp_path / "frames.bin")
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<iii", len(frames), w, h))
-        fh.write(bytes(rig))
-        for name, bgr, dep in frames:
-            fh.write(name.encode().ljust(32, b"\0"))
-            fh.write(bgr.tobytes())
-            fh.write(struct.pack("<ii", dep.shape[1], dep.shape[0]))
-            fh.write(dep.tobytes())
-    out = subprocess.run([exe, path, mode_name], check=True, capture_output=True, text=True, timeout=120).stdout
-    got = out.strip().split("\n")
-    acvo = mode_name == "acvo"
-    reg = (pkg.Acvo if acvo else pkg.Cvo)()
+    got = _demo_lines(tmp_path, "cvo_depth_camera_demo", frames, w, h, bytes(rig), [mode_name], depth_sizes=True)
     gen = F.PcdGenerator(w, h)
-    gen.set_device_output(True)
-    ftype = F.FEATURES_HSV if acvo else F.FEATURES_RGB
-    want = ["refused a reflection"]
-    sizes = []
-    for k, (name, bgr, dep) in enumerate(frames):
+
+    def prepare(k):
         gen.set_depth_camera(None if k == 2 else rig)
-        if k == 3:
-            want.append("refused a reflection")
-        gen.submit(bgr, dep, 1, ftype)                   # (the hand-over the C++ object uses: device memory)
-        dp, df, n = gen.collect_device()
-        sizes.append(n)
-        reg.run_cvo_device(dp, df, n)
-        d = reg.ctx.device_cloud(0)
-        assert d["points"] == n
-        want.append("cloud %s %d %d %d" % (name, n, _digest(d["pos"][:n]), _digest(d["feat"][:n])))
-        want.append(_pose_line_f32(name, reg.accum_transform))
-        # ... which is the Python writer's line up to the float64 of its quaternion
+        return ["refused a reflection"] if k == 3 else []
+
+    want, sizes, poses = _device_path_lines(pkg, mode_name, gen, frames, prepare)
+    assert got == ["refused a reflection"] + want
+    # ... whose pose lines are the Python writer's up to the float64 of its quaternion
+    for name, M in poses:
+        line = _pose_line_f32(name, M)
+        assert line in want
         buf = io.StringIO()
-        pkg.trajectory.TrajectoryWriter(buf).append(name, reg.accum_transform)
-        assert buf.getvalue().split()[:4] == want[-1].split()[:4]
-        assert np.allclose([float(v) for v in buf.getvalue().split()[4:]], [float(v) for v in want[-1].split()[4:]],
+        pkg.trajectory.TrajectoryWriter(buf).append(name, M)
+        assert buf.getvalue().split()[:4] == line.split()[:4]
+        assert np.allclose([float(v) for v in buf.getvalue().split()[4:]], [float(v) for v in line.split()[4:]],
                            rtol=1e-5, atol=0)
-    want.append("points_last_frame %d iterations %d" % (sizes[-1], reg.num_iterations))
-    assert got == want
+    ftype = F.FEATURES_HSV if mode_name == "acvo" else F.FEATURES_RGB
     # the clouds of the rig's frames are the oracle's on the reference-registered depth (half-size depth: 2 x 2 footprints)
     rd = D.register(small, D.VGA_COLOUR, w, h, frames[0][2])
     assert sizes[0] == len(fo.create_pointcloud(frames[0][1], rd, 1, ftype)["positions"]) > 100
-    reg.close(); gen.close()
+    gen.close()
 
 
 # ---- 5. refusals ----------------------------------------------------------------------------

@@ -5,15 +5,13 @@ k_fe_rectify against the numpy restatement of the rectification contract
 cloud bit for bit.  Custom intrinsics, the unchanged table path, the captured graphs across
 changes of camera, the Python and C++ layers above, and the refusals."""
 import io
-import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import fe_rectify_ref as R
 from conftest import low_texture_frame
+from fe_gpu_common import _bits, _demo_lines, _digest, _four_frames, _same_cloud
 from oracle import pyoracle_fe as fo
 
 pytestmark = pytest.mark.gpu
@@ -29,15 +27,6 @@ def _rect(key, model, bgr, dep):
         rb.setflags(write=False); rd.setflags(write=False)
         _RECT[key] = (rb, rd)
     return _RECT[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same_cloud(got, want):
-    return (got[0].shape == want[0].shape and np.array_equal(_bits(got[0]), _bits(want[0])) and
-            np.array_equal(_bits(got[1]), _bits(want[1])))
 
 
 def _check_stages(pkg, gen, model, bgr, dep, key):
@@ -241,16 +230,11 @@ def test_changes_of_camera_on_one_context(pkg):
 
 # ---- 6. the layers above ----------------------------------------------------------------
 
-def _four_frames(pkg):
-    return [("1305031453.%06d" % (359684 + 33333 * k),) +
-            pkg.data.synthetic_rgbd_frame(seed=68, texture=1.0, motion=(1.2 * k, -0.6 * k)) for k in range(4)]
-
-
 def test_run_frames_with_a_camera(pkg):
     """run_frames(camera=fr1) on the raw frames = run_frames(camera=fr1 without the lens) on the
     reference-rectified frames: the same poses"""
     F = pkg.frontend
-    frames = _four_frames(pkg)
+    frames = _four_frames(pkg, 68)
     rect = [(name,) + _rect(("seq", k), R.FR1, bgr, dep) for k, (name, bgr, dep) in enumerate(frames)]
     pinhole = F.CameraModel(*(R.FR1[:5] + (ZERO,)))
     poses = []
@@ -269,36 +253,15 @@ def test_run_frames_with_a_camera(pkg):
     reg.close()
 
 
-def _digest(a):
-    """cvo_camera_demo.cpp's digest of an array of rows: modulo 2^64, whatever the order of the rows"""
-    w = np.ascontiguousarray(a).view(np.uint32).astype(np.uint64)
-    h = (w * np.arange(1, w.shape[1] + 1, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
-    return int((h * h).sum(dtype=np.uint64))
-
-
 @pytest.mark.parametrize("mode_name", ["cvo", "acvo"])
 def test_cpp_objects_take_a_camera(pkg, tmp_path, mode_name):
     """include/cvo.hpp registration::set_camera / clear_camera (tests/cpp/cvo_camera_demo.cpp): the
     clouds the C++ object registers and its pose lines equal the Python path's"""
     F = pkg.frontend
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "cvo_camera_demo")
-    lib = os.path.join(root, "cvo-rgbd_amd", "csrc")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
-                    os.path.join(root, "tests", "cpp", "cvo_camera_demo.cpp"), "-L", lib, "-lcvo_hip",
-                    "-Wl,-rpath," + lib, "-o", exe], check=True)
     w, h = 640, 480
-    frames = _four_frames(pkg)
+    frames = _four_frames(pkg, 68)
     model = F.TUM_CAMERAS["fr1"]
-    path = str(tmp_path / "frames.bin")
-    with open(path, "wb") as fh:
-        fh.write(struct.pack("<iii", len(frames), w, h))
-        fh.write(bytes(model))
-        for name, bgr, dep in frames:
-            fh.write(name.encode().ljust(32, b"\0"))
-            fh.write(bgr.tobytes()); fh.write(dep.tobytes())
-    out = subprocess.run([exe, path, mode_name], check=True, capture_output=True, text=True).stdout
-    got = out.strip().split("\n")
+    got = _demo_lines(tmp_path, "cvo_camera_demo", frames, w, h, bytes(model), [mode_name])
     acvo = mode_name == "acvo"
     reg = (pkg.Acvo if acvo else pkg.Cvo)()
     gen = F.PcdGenerator(w, h)
