@@ -59,7 +59,7 @@ void Affine3f::quaternion(float q[4]) const
 registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
-      depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false)
+      depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -87,6 +87,7 @@ void registration::apply_stored_settings()
         if (have_camera_) fe_check(cvo_fe_set_camera(fe_, &camera_), "cvo_fe_set_camera");
         if (have_depth_camera_) fe_check(cvo_fe_set_depth_camera(fe_, &depth_camera_), "cvo_fe_set_depth_camera");
         if (have_depth_gate_) fe_check(cvo_fe_set_depth_gate(fe_, &depth_gate_), "cvo_fe_set_depth_gate");
+        if (have_stereo_) fe_check(cvo_fe_set_stereo(fe_, &stereo_), "cvo_fe_set_stereo");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -104,11 +105,17 @@ void registration::apply_stored_settings()
 // the raw colour features (type 1), acvo for the HSV ones (type 0, ref
 // src/adaptive_cvo.cpp:451,462).  The cloud never leaves the device: the front end's
 // output arrays go straight into cvo_hip_set_*_device.
-void registration::cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep)
+// `stereo`: `dep` is the right colour image of a rectified pair (cvo_fe_submit_stereo) and `rgb` the left one.
+void registration::cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo)
 {
-    if (!rgb.data || !dep.data || (!have_depth_camera_ && (rgb.rows != dep.rows || rgb.cols != dep.cols)))
-        throw std::runtime_error("set_pcd(): colour and depth image must have the same size");
-    if (have_depth_camera_ && (dep.rows != depth_camera_.height || dep.cols != depth_camera_.width))
+    if (stereo && !have_stereo_) throw std::runtime_error("set_pcd_stereo(): no stereo settings: set_stereo() first");
+    if (!stereo && have_stereo_)
+        throw std::runtime_error("set_pcd(): stereo is set, a frame is a pair of colour images: set_pcd_stereo()");
+    const bool own_size = !stereo && have_depth_camera_;
+    if (!rgb.data || !dep.data || (!own_size && (rgb.rows != dep.rows || rgb.cols != dep.cols)))
+        throw std::runtime_error(stereo ? "set_pcd_stereo(): the two colour images must have the same size"
+                                        : "set_pcd(): colour and depth image must have the same size");
+    if (own_size && (dep.rows != depth_camera_.height || dep.cols != depth_camera_.width))
         throw std::runtime_error("set_pcd(): the depth image must have the depth camera's size");
     if (!fe_) {
         const int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
@@ -120,8 +127,10 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
     if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
         throw std::runtime_error("set_pcd(): the image size changed within a sequence");
     const int ftype = params_.mode == CVO_HIP_MODE_ACVO ? CVO_FE_FEATURES_HSV : CVO_FE_FEATURES_RGB;
-    int rc = cvo_fe_submit(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint16_t *)dep.data, dep.step,
-                           dataset_seq, ftype);
+    int rc = stereo ? cvo_fe_submit_stereo(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint8_t *)dep.data, dep.step,
+                                           dataset_seq, ftype)
+                    : cvo_fe_submit(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint16_t *)dep.data, dep.step,
+                                    dataset_seq, ftype);
     const float *d_pos = nullptr, *d_feat = nullptr;
     if (rc == CVO_HIP_OK) rc = cvo_fe_collect_device(fe_, &d_pos, &d_feat, &fe_points_);
     fe_check(rc, "front end");
@@ -190,6 +199,19 @@ void registration::clear_depth_gate()
     store<cvo_fe_depth_gate>(cvo_fe_set_depth_gate, "cvo_fe_set_depth_gate", nullptr, depth_gate_, have_depth_gate_);
 }
 
+void registration::set_stereo(const cvo_fe_stereo &stereo)
+{
+    if (!fe_ && cvo_fe_check_stereo(&stereo) != CVO_HIP_OK)
+        throw std::runtime_error("set_stereo(): baseline positive and finite, max_disp a multiple of 8 in [8, 128], "
+                                 "min_disp >= 1, 1 <= p1 <= p2 <= 255, uniqueness in [0, 99], lr_max in [-1, 8], pad_ 0");
+    store<cvo_fe_stereo>(cvo_fe_set_stereo, "cvo_fe_set_stereo", &stereo, stereo_, have_stereo_);
+}
+
+void registration::clear_stereo()
+{
+    store<cvo_fe_stereo>(cvo_fe_set_stereo, "cvo_fe_set_stereo", nullptr, stereo_, have_stereo_);
+}
+
 // the mask given or cleared (null); with a front end that one holds the bytes, and no second copy is kept here
 void registration::store_mask(const image_view *mask)
 {
@@ -227,14 +249,29 @@ void registration::clear_mask() { store_mask(nullptr); }
 void registration::set_pcd(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,
                            const std::string &, const std::string &)
 {
-    cloud_from_images(dataset_seq, RGB_img, dep_img);
+    cloud_from_images(dataset_seq, RGB_img, dep_img, false);
+}
+
+void registration::set_pcd_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img)
+{
+    cloud_from_images(dataset_seq, left_img, right_img, true);
 }
 
 void registration::run_cvo(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,
                            const std::string &, const std::string &)
+{
+    run_images(dataset_seq, RGB_img, dep_img, false);
+}
+
+void registration::run_cvo_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img)
+{
+    run_images(dataset_seq, left_img, right_img, true);
+}
+
+void registration::run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo)
 {   // ref src/cvo.cpp:422-435
     const bool first = !init;
-    cloud_from_images(dataset_seq, RGB_img, dep_img);
+    cloud_from_images(dataset_seq, rgb, second, stereo);
     if (first) return;
     align();
     std::cout << "Total iterations: " << iter << std::endl;

@@ -21,6 +21,7 @@
 
 #include "cvo_frontend.h"
 #include "cvo_lock.h"
+#include "cvo_stereo.h"
 
 namespace {
 
@@ -434,11 +435,9 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_level0(const uint8_t *img, int 
     const int i = blockIdx.x * FE_BLOCK + threadIdx.x;
     const int np = w * h;
     if (i >= np) return;
-    auto grey = [&](int j) {
-        return (img[3 * j] * 4899 + img[3 * j + 1] * 9617 + img[3 * j + 2] * 1868 + (1 << 13)) >> 14;
-    };
+    auto grey = [&](int j) { return fe_grey(img[3 * j], img[3 * j + 1], img[3 * j + 2]); };
     const int r = img[3 * i], g = img[3 * i + 1], b = img[3 * i + 2];
-    const int gr = (r * 4899 + g * 9617 + b * 1868 + (1 << 13)) >> 14;
+    const int gr = fe_grey(r, g, b);
     gray[i] = (uint8_t)gr;
     I0[i] = (float)gr;
     int v = max(b, max(g, r)), vmin = min(b, min(g, r));
@@ -1033,6 +1032,20 @@ struct cvo_fe_ctx {
     // with the first mask: its device plane and its pinned staging image
     Dev<uint8_t> d_mask;
     Pin<uint8_t> h_mask;
+    // the caller's stereo settings (cvo_fe_set_stereo); with them a frame is a stereo pair and the matcher of
+    // cvo_stereo.hip fills the depth plane
+    cvo_fe_stereo stereo{};
+    bool has_stereo = false;
+    // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
+    // table U(q) with its staging copy; the cost sums follow max_disp
+    Dev<uint8_t> right_img, right_gray, stereo_flags;
+    Pin<uint8_t> h_right;
+    Dev<uint64_t> census;      // 2 planes of np entries: left, right
+    Dev<uint16_t> sgm_sum;     // np * stereo.max_disp
+    Dev<uint32_t> stereo_win;
+    Dev<uint16_t> disparity, depth_table;
+    Pin<uint16_t> h_depth_table;
+    float table_fx = 0.0f, table_scale = 0.0f;   // the camera the device's table was made for; 0: none yet
     std::string err;
 };
 
@@ -1128,6 +1141,18 @@ bool gate_ok(const cvo_fe_depth_gate &g)
     if (g.max_range > 0.0f && g.max_range <= g.min_range) return false;
     if (g.grow < 0 || g.grow > FG_HALO - 1) return false;
     return (g.hole_border == 0 || g.hole_border == 1) && g.pad_ == 0;
+}
+
+// what cvo_fe_set_stereo accepts
+bool stereo_ok(const cvo_fe_stereo &s)
+{
+    static_assert(sizeof(cvo_fe_stereo) == sizeof(float) + 7 * sizeof(int32_t), "32 bytes, no padding");
+    if (!std::isfinite(s.baseline) || !(s.baseline > 0.0f)) return false;
+    if (s.max_disp < 8 || s.max_disp > 128 || s.max_disp % 8 != 0) return false;
+    if (s.min_disp < 1) return false;
+    if (!(1 <= s.p1 && s.p1 <= s.p2 && s.p2 <= 255)) return false;
+    if (s.uniqueness < 0 || s.uniqueness > 99) return false;
+    return s.lr_max >= -1 && s.lr_max <= 8 && s.pad_ == 0;
 }
 
 // The lens model of include/cvo_frontend.h for a colour or a depth camera, operation by operation (float64,
@@ -1285,9 +1310,26 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img.get() : img, ctx->h_img.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
+    // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
     uint16_t *plane = depth_plane(ctx);
-    FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
+    if (ctx->has_stereo)
+        FE_HIP(hipMemcpyAsync(ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
+    else
+        FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
+    if (ctx->has_stereo) {   // (neither a distorting model nor a depth camera beside it: cvo_fe_set_stereo)
+        const cvo_fe_stereo &st = ctx->stereo;
+        FeStereoArgs a{};
+        a.left = img; a.right = ctx->right_img.get();
+        a.gray_l = ctx->gray.get();   // (k_fe_level0 writes the same bytes again)
+        a.gray_r = ctx->right_gray.get();
+        a.census_l = ctx->census.get(); a.census_r = ctx->census.get() + np;
+        a.sum = ctx->sgm_sum.get(); a.win = ctx->stereo_win.get(); a.table = ctx->depth_table.get();
+        a.disparity = ctx->disparity.get(); a.flags = ctx->stereo_flags.get(); a.depth = plane;
+        a.w = w; a.h = h; a.D = st.max_disp;
+        a.min_disp = st.min_disp; a.p1 = st.p1; a.p2 = st.p2; a.uniqueness = st.uniqueness; a.lr_max = st.lr_max;
+        fe_stereo_enqueue(a, s);
+    }
     if (ctx->rectify)
         hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img.get(),
                            ctx->has_rig ? (const uint16_t *)nullptr : ctx->raw_depth.get(), qu, qv, w, h, img, plane);
@@ -1485,6 +1527,8 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
         return fail(ctx, CVO_HIP_ERR_INVALID,
                     "set_depth_camera: size in [8, 8192], finite members, fx, fy, depth_scale positive, "
                     "max_range above min_range, R a rotation");
+    if (rig && ctx->has_stereo)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: stereo is set, there is no depth image");
     if (!rig && !ctx->has_rig) return CVO_HIP_OK;
     if (rig && ctx->has_rig && std::memcmp(rig, &ctx->rig, sizeof(*rig)) == 0) return CVO_HIP_OK;
     FE_HIP(hipSetDevice(ctx->device));
@@ -1586,6 +1630,85 @@ int cvo_fe_get_depth_gate(const cvo_fe_ctx *ctx, cvo_fe_depth_gate *out, int *se
     return CVO_HIP_OK;
 }
 
+int cvo_fe_check_stereo(const cvo_fe_stereo *st) { return st && stereo_ok(*st) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
+
+int cvo_fe_stereo_depth_table(const cvo_fe_stereo *st, float fx, float depth_scale, uint16_t *out)
+{
+    if (!st || !out || !stereo_ok(*st) || !std::isfinite(fx) || !std::isfinite(depth_scale) || !(fx > 0.0f) ||
+        !(depth_scale > 0.0f))
+        return CVO_HIP_ERR_INVALID;
+    // contract 9, operation by operation in float64 (nothing can be contracted: there is no addition)
+    const double num = (((double)fx * (double)st->baseline) * (double)depth_scale) * 16.0;
+    const int n = 16 * st->max_disp, q0 = 16 * st->min_disp;
+    for (int q = 0; q < n; ++q) {
+        double u = 0.0;
+        if (q >= q0) u = std::nearbyint(num / (double)q);   // (ties to even: the default rounding mode)
+        out[q] = (u >= 1.0 && u <= 65535.0) ? (uint16_t)u : (uint16_t)0;
+    }
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a frame is in flight");
+    if (st && !stereo_ok(*st))
+        return fail(ctx, CVO_HIP_ERR_INVALID,
+                    "set_stereo: baseline positive and finite, max_disp a multiple of 8 in [8, 128], min_disp >= 1, "
+                    "1 <= p1 <= p2 <= 255, uniqueness in [0, 99], lr_max in [-1, 8], pad_ 0");
+    if (st && ctx->has_rig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a depth camera is set");
+    if (st && ctx->rectify)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: the camera model has a lens distortion; the pair must be rectified");
+    if (!st && !ctx->has_stereo) return CVO_HIP_OK;
+    if (st && ctx->has_stereo && std::memcmp(st, &ctx->stereo, sizeof(*st)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    const size_t np = (size_t)ctx->np;
+    Dev<uint8_t> right_img, right_gray, flags;
+    Pin<uint8_t> h_right;
+    Dev<uint64_t> census;
+    Dev<uint16_t> sum, disparity, table;
+    Dev<uint32_t> win;
+    Pin<uint16_t> h_table;
+    if (st) {
+        // (all but the cost sums come with the first settings and stay; the table has room for the largest max_disp)
+        if (!ctx->right_img &&
+            !(dev_alloc(right_img, np * 3) && dev_alloc(right_gray, np) && dev_alloc(flags, np) && pin_alloc(h_right, np * 3) &&
+              dev_alloc(census, 2 * np) && dev_alloc(disparity, np) && dev_alloc(win, np) && dev_alloc(table, 16 * 128) &&
+              pin_alloc(h_table, 16 * 128)))
+            return no_memory(ctx, "set_stereo: device and pinned memory for the right image and the matcher's planes");
+        if ((!ctx->sgm_sum || !ctx->has_stereo || st->max_disp != ctx->stereo.max_disp) && !dev_alloc(sum, np * (size_t)st->max_disp))
+            return no_memory(ctx, "set_stereo: device memory for the cost sums");
+    }
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->right_img, right_img);
+    hand_over(ctx->right_gray, right_gray);
+    hand_over(ctx->stereo_flags, flags);
+    hand_over(ctx->h_right, h_right);
+    hand_over(ctx->census, census);
+    hand_over(ctx->disparity, disparity);
+    hand_over(ctx->stereo_win, win);
+    hand_over(ctx->depth_table, table);
+    hand_over(ctx->h_depth_table, h_table);
+    hand_over(ctx->sgm_sum, sum);
+    if (!st) ctx->sgm_sum.reset();   // (the one large buffer: a context back on depth images does not keep it)
+    ctx->has_stereo = st != nullptr;
+    ctx->stereo = st ? *st : cvo_fe_stereo{};
+    ctx->table_fx = ctx->table_scale = 0.0f;   // (the table depends on baseline, min_disp and max_disp: made again)
+    drop_graphs(ctx);   // (the settings and the planes of a frame are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_stereo(const cvo_fe_ctx *ctx, cvo_fe_stereo *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_stereo ? ctx->stereo : cvo_fe_stereo{};
+    if (set) *set = ctx->has_stereo ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
 int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride)
 {
     cvo_lock::Api api_guard;
@@ -1633,6 +1756,8 @@ int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
     if (!model && !ctx->custom) return CVO_HIP_OK;
     if (model && ctx->custom && std::memcmp(model, &ctx->cam, sizeof(*model)) == 0) return CVO_HIP_OK;
     const bool bent = model && distorts(model->dist);
+    if (bent && ctx->has_stereo)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: stereo is set and takes a rectified pair: dist must be zero");
     if (bent) {
         const size_t np = (size_t)ctx->np, plane = rect_plane(ctx->np);
         std::vector<int32_t> map;
@@ -1782,14 +1907,21 @@ int cvo_fe_set_num_want(cvo_fe_ctx *ctx, int num_want)
     return CVO_HIP_OK;
 }
 
-int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const uint16_t *depth,
-                  size_t depth_stride, int dataset_seq, int feature_type)
+}   // extern "C"
+
+namespace {
+
+// submit() of either kind of frame: `second` is the depth image (uint16 rows) of a depth frame and the right colour
+// image of a stereo frame (`stereo`); the kind must be the one the context is set up for
+int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *second, size_t second_stride,
+                 int dataset_seq, int feature_type, bool stereo)
 {
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
     const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
     const int dw = ctx->dw, dh = ctx->dh;   // (the depth camera's image, if the context has one)
-    if (!img || !depth || img_stride < (size_t)w * 3 || depth_stride < (size_t)dw * 2 ||
+    if (stereo != ctx->has_stereo)
+        return fail(ctx, CVO_HIP_ERR_INVALID, stereo ? "submit_stereo: no stereo settings (cvo_fe_set_stereo)"
+                                                     : "submit: stereo is set, a frame is a stereo pair (cvo_fe_submit_stereo)");
+    if (!img || !second || img_stride < (size_t)w * 3 || second_stride < (stereo ? (size_t)w * 3 : (size_t)dw * 2) ||
         (feature_type != CVO_FE_FEATURES_HSV && feature_type != CVO_FE_FEATURES_RGB))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit: bad argument");
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the previous frame was not collected");
@@ -1797,8 +1929,22 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     hipStream_t s = ctx->stream;
     // pinned staging (not when the caller decoded into the staging image itself: cvo_fe_host_buffers)
     if (!(img == ctx->h_img.get() && img_stride == (size_t)w * 3)) copy_rows(ctx->h_img.get(), img, img_stride, (size_t)w * 3, h);
-    if (!(depth == ctx->h_depth.get() && depth_stride == (size_t)dw * 2))
-        copy_rows(ctx->h_depth.get(), depth, depth_stride, (size_t)dw * 2, dh);
+    if (stereo) {
+        copy_rows(ctx->h_right.get(), second, second_stride, (size_t)w * 3, h);
+        // the table U(q) of the camera in force, if the device holds another's: in front of the frame, outside the
+        // captured graph (its address is the graph's), as the mask below
+        float cam[5];
+        camera_in_force(ctx, dataset_seq, cam);
+        if (cam[1] != ctx->table_fx || cam[0] != ctx->table_scale) {
+            if (cvo_fe_stereo_depth_table(&ctx->stereo, cam[1], cam[0], ctx->h_depth_table.get()) != CVO_HIP_OK)
+                return fail(ctx, CVO_HIP_ERR_INVALID, "submit_stereo: depth table");
+            FE_HIP(hipMemcpyAsync(ctx->depth_table.get(), ctx->h_depth_table.get(), (size_t)16 * ctx->stereo.max_disp * 2,
+                                  hipMemcpyHostToDevice, s));
+            ctx->table_fx = cam[1];
+            ctx->table_scale = cam[0];
+        }
+    } else if (!(second == ctx->h_depth.get() && second_stride == (size_t)dw * 2))
+        copy_rows(ctx->h_depth.get(), second, second_stride, (size_t)dw * 2, dh);
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
     *ctx->h_ctrl = c0;
@@ -1851,6 +1997,26 @@ int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const 
     return CVO_HIP_OK;
 }
 
+}   // namespace
+
+extern "C" {
+
+int cvo_fe_submit(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const uint16_t *depth,
+                  size_t depth_stride, int dataset_seq, int feature_type)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    return submit_frame(ctx, img, img_stride, depth, depth_stride, dataset_seq, feature_type, false);
+}
+
+int cvo_fe_submit_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_stride, const uint8_t *right,
+                         size_t right_stride, int dataset_seq, int feature_type)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    return submit_frame(ctx, left, left_stride, right, right_stride, dataset_seq, feature_type, true);
+}
+
 int cvo_fe_collect(cvo_fe_ctx *ctx, float *positions, float *features, int capacity, int *num_points)
 {
     cvo_lock::Api api_guard;
@@ -1880,6 +2046,19 @@ int cvo_fe_create_pointcloud(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_str
     if (!num_points || capacity < 0 || (capacity > 0 && (!positions || !features)))
         return fail(ctx, CVO_HIP_ERR_INVALID, "create_pointcloud: bad argument");
     const int rc = cvo_fe_submit(ctx, img, img_stride, depth, depth_stride, dataset_seq, feature_type);
+    if (rc) return rc;
+    return cvo_fe_collect(ctx, positions, features, capacity, num_points);
+}
+
+int cvo_fe_create_pointcloud_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_stride, const uint8_t *right,
+                                    size_t right_stride, int dataset_seq, int feature_type, float *positions,
+                                    float *features, int capacity, int *num_points)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (!num_points || capacity < 0 || (capacity > 0 && (!positions || !features)))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "create_pointcloud_stereo: bad argument");
+    const int rc = cvo_fe_submit_stereo(ctx, left, left_stride, right, right_stride, dataset_seq, feature_type);
     if (rc) return rc;
     return cvo_fe_collect(ctx, positions, features, capacity, num_points);
 }
@@ -1915,8 +2094,16 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_RAW_DEPTH: src = depth_upload(ctx); need = (size_t)ctx->dw * ctx->dh * 2; break;
     case CVO_FE_STAGE_UNGATED_DEPTH: src = depth_plane(ctx); need = np * 2; break;
     case CVO_FE_STAGE_GATE: src = gate_active(ctx) ? ctx->gate_flags.get() : nullptr; need = np; break;
+    case CVO_FE_STAGE_RIGHT_GRAY: src = ctx->right_gray.get(); need = np; break;
+    case CVO_FE_STAGE_CENSUS_L: src = ctx->census.get(); need = np * 8; break;
+    case CVO_FE_STAGE_CENSUS_R: src = ctx->census ? ctx->census.get() + np : nullptr; need = np * 8; break;
+    case CVO_FE_STAGE_SGM_SUM: src = ctx->sgm_sum.get(); need = np * (size_t)ctx->stereo.max_disp * 2; break;
+    case CVO_FE_STAGE_DISPARITY: src = ctx->disparity.get(); need = np * 2; break;
+    case CVO_FE_STAGE_STEREO: src = ctx->stereo_flags.get(); need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
+    if (stage >= CVO_FE_STAGE_RIGHT_GRAY && !ctx->has_stereo)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a stage of a stereo frame, and stereo is not set");
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");
     FE_HIP(hipSetDevice(ctx->device));
     FE_HIP(hipStreamSynchronize(ctx->stream));

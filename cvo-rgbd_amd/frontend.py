@@ -7,6 +7,12 @@ device raises).
     gen = PcdGenerator(width=640, height=480)
     xyz, feat = gen.create_pointcloud(bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB)
 
+A rectified stereo pair in place of the depth image (the stereo contract of include/cvo_frontend.h):
+
+    gen = PcdGenerator(width=1241, height=376)
+    gen.set_stereo(Stereo(baseline=0.54, max_disp=128))
+    xyz, feat = gen.create_pointcloud_stereo(left, right, dataset_seq=4)
+
 `bgr` is the h x w x 3 uint8 array an image decoder returns in OpenCV's channel
 order (cv::imread: B, G, R) -- the reference passes exactly that to its "RGB"
 conversions (ref src/pcd_generator.cpp:389-390), so channel 0 plays the role of R
@@ -24,15 +30,18 @@ from . import capi
 
 FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
- STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE) = range(15)
+ STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
+ STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO) = range(21)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
+STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH = 1, 2, 4, 8   # the flags of STAGE_STEREO
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
            "cvo_fe_camera", "cvo_fe_set_camera", "cvo_fe_get_camera", "cvo_fe_rectify_map",
            "cvo_fe_set_depth_camera", "cvo_fe_get_depth_camera", "cvo_fe_depth_rays",
            "cvo_fe_check_depth_camera", "cvo_fe_set_depth_gate", "cvo_fe_get_depth_gate", "cvo_fe_check_depth_gate",
-           "cvo_fe_set_mask")
+           "cvo_fe_set_mask", "cvo_fe_check_stereo", "cvo_fe_set_stereo", "cvo_fe_get_stereo", "cvo_fe_submit_stereo",
+           "cvo_fe_create_pointcloud_stereo", "cvo_fe_stereo_depth_table")
 
 
 class Info(C.Structure):
@@ -100,6 +109,19 @@ class DepthGate(_Settings):
         super().__init__(min_range, max_range, jump_rel, int(grow), int(hole_border), int(pad_))
 
 
+class Stereo(_Settings):
+    """cvo_fe_stereo: a rectified stereo pair in place of the depth image (the stereo contract of
+    include/cvo_frontend.h).  `baseline` in metres; disparities 0 .. `max_disp` - 1 are searched (a multiple of 8
+    in [8, 128]); a pixel whose disparity is below `min_disp` gets no depth; `p1` <= `p2` <= 255: the penalties of
+    the semi-global paths; `uniqueness` 0..99 per cent, 0: no uniqueness test; `lr_max` 0..8: the largest
+    left-right difference kept, -1: no left-right test."""
+    _fields_ = [("baseline", C.c_float), ("max_disp", C.c_int32), ("min_disp", C.c_int32), ("p1", C.c_int32),
+                ("p2", C.c_int32), ("uniqueness", C.c_int32), ("lr_max", C.c_int32), ("pad_", C.c_int32)]
+
+    def __init__(self, baseline=0.54, max_disp=64, min_disp=1, p1=8, p2=32, uniqueness=10, lr_max=1, pad_=0):
+        super().__init__(baseline, int(max_disp), int(min_disp), int(p1), int(p2), int(uniqueness), int(lr_max), int(pad_))
+
+
 # The published calibrations of the TUM RGB-D sequences (fx fy cx cy, d0..d4; depth 5000 per metre).
 # The reference's table (camera(1..3)) holds the same intrinsics without the distortion.  The entries are
 # shared by every user of the module: read them, hand them to set_camera() (which copies), and make a model of
@@ -148,6 +170,13 @@ def lib():
         L.cvo_fe_get_depth_gate.argtypes = [vp, C.POINTER(DepthGate), C.POINTER(C.c_int)]
         L.cvo_fe_check_depth_gate.argtypes = [C.POINTER(DepthGate)]
         L.cvo_fe_set_mask.argtypes = [vp, u8p, C.c_size_t]
+        L.cvo_fe_check_stereo.argtypes = [C.POINTER(Stereo)]
+        L.cvo_fe_set_stereo.argtypes = [vp, C.POINTER(Stereo)]
+        L.cvo_fe_get_stereo.argtypes = [vp, C.POINTER(Stereo), C.POINTER(C.c_int)]
+        L.cvo_fe_submit_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int]
+        L.cvo_fe_create_pointcloud_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int, fp, fp,
+                                                      C.c_int, C.POINTER(C.c_int)]
+        L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -203,6 +232,20 @@ def check_depth_gate(gate):
     return lib().cvo_fe_check_depth_gate(C.byref(gate)) == 0
 
 
+def check_stereo(stereo):
+    """True for a Stereo set_stereo() accepts (cvo_fe_check_stereo).  Host only."""
+    return lib().cvo_fe_check_stereo(C.byref(stereo)) == 0
+
+
+def stereo_depth_table(stereo, fx, depth_scale):
+    """U(q) of the stereo contract (include/cvo_frontend.h) for q = 0 .. 16 * max_disp - 1: the depth value of a
+    disparity of q / 16 pixel under a camera of focal length `fx` and `depth_scale` units per metre; uint16.  Host only."""
+    out = np.empty(16 * int(stereo.max_disp), np.uint16)
+    capi.check(lib().cvo_fe_stereo_depth_table(C.byref(stereo), fx, depth_scale, out.ctypes.data_as(C.POINTER(C.c_uint16))),
+               what="stereo_depth_table")
+    return out
+
+
 class PcdGenerator:
     """ref include/pcd_generator.hpp:30-108; one object per image size."""
 
@@ -217,6 +260,7 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_set_num_want(self._h, self.num_want), "set_num_want")
         self.capacity = self.width * self.height   # (upper bound of any selection)
         self._dshape = (self.height, self.width)   # of the depth image: the depth camera's, if one is set
+        self._max_disp = 0                         # of the stereo settings, if some are set
         self._pos = np.empty((self.capacity, 3), np.float32)
         self._feat = np.empty((self.capacity, 5), np.float32)
 
@@ -341,6 +385,45 @@ class PcdGenerator:
             mask = np.ascontiguousarray(mask)
         self._chk(lib().cvo_fe_set_mask(self._h, mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.strides[0]), "set_mask")
 
+    def set_stereo(self, stereo):
+        """A Stereo for every following frame: a frame is then a rectified stereo pair (submit_stereo /
+        create_pointcloud_stereo) and a semi-global matcher on the device fills the depth plane (the stereo contract
+        of include/cvo_frontend.h); None: back to depth images, as for a new object."""
+        self._chk(lib().cvo_fe_set_stereo(self._h, None if stereo is None else C.byref(stereo)), "set_stereo")
+        self._max_disp = 0 if stereo is None else int(stereo.max_disp)
+
+    def stereo(self):
+        """The Stereo set, or None."""
+        out, isset = Stereo(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_stereo(self._h, C.byref(out), C.byref(isset)), "get_stereo")
+        return out if isset.value else None
+
+    def _pair(self, left, right):
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        if left.shape != (self.height, self.width, 3) or right.shape != left.shape:
+            raise ValueError("expected two %dx%dx3 uint8 images" % (self.height, self.width))
+        return left, right
+
+    def create_pointcloud_stereo(self, left, right, dataset_seq=4, feature_type=FEATURES_RGB):
+        """create_pointcloud() for a stereo pair: two h x w x 3 uint8 images (a grey right image is replicated by the
+        caller); the left one is the colour image of the frame."""
+        left, right = self._pair(left, right)
+        n = C.c_int(0)
+        u8p, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_float)
+        st = lib().cvo_fe_create_pointcloud_stereo(
+            self._h, left.ctypes.data_as(u8p), self.width * 3, right.ctypes.data_as(u8p), self.width * 3, int(dataset_seq),
+            int(feature_type), self._pos.ctypes.data_as(fp), self._feat.ctypes.data_as(fp), self.capacity, C.byref(n))
+        self._chk(st, "create_pointcloud_stereo")
+        return self._pos[:n.value].copy(), self._feat[:n.value].copy()
+
+    def submit_stereo(self, left, right, dataset_seq=4, feature_type=FEATURES_RGB):
+        """submit() for a stereo pair; collect() / collect_device() as for any other frame."""
+        left, right = self._pair(left, right)
+        u8p = C.POINTER(C.c_uint8)
+        self._chk(lib().cvo_fe_submit_stereo(self._h, left.ctypes.data_as(u8p), self.width * 3, right.ctypes.data_as(u8p),
+                                             self.width * 3, int(dataset_seq), int(feature_type)), "submit_stereo")
+
     def info(self):
         out = Info()
         self._chk(lib().cvo_fe_get_info(self._h, C.byref(out)), "get_info")
@@ -355,7 +438,10 @@ class PcdGenerator:
                   STAGE_DX0: ((h, w), np.float32), STAGE_DY0: ((h, w), np.float32), STAGE_EDGES: ((h, w), np.uint8),
                   STAGE_RECT_BGR: ((h, w, 3), np.uint8), STAGE_RECT_DEPTH: ((h, w), np.uint16),
                   STAGE_RAW_DEPTH: (self._dshape, np.uint16), STAGE_UNGATED_DEPTH: ((h, w), np.uint16),
-                  STAGE_GATE: ((h, w), np.uint8)}
+                  STAGE_GATE: ((h, w), np.uint8), STAGE_RIGHT_GRAY: ((h, w), np.uint8),
+                  STAGE_CENSUS_L: ((h, w), np.uint64), STAGE_CENSUS_R: ((h, w), np.uint64),
+                  STAGE_SGM_SUM: ((h, w, self._max_disp), np.uint16), STAGE_DISPARITY: ((h, w), np.uint16),
+                  STAGE_STEREO: ((h, w), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -401,8 +487,10 @@ def load_img(rgb_path, depth_path):
 
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
-               camera=None, depth_camera=None, depth_gate=None, mask=None):
+               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
+    pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -432,8 +520,11 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_depth_gate(depth_gate)
     if mask is not None:
         gen.set_mask(mask)
+    if stereo is not None:
+        gen.set_stereo(stereo)
+    submit = gen.submit_stereo if stereo is not None else gen.submit
     gen.set_device_output(device)
-    gen.submit(cur[1], cur[2], dataset_seq, ftype)
+    submit(cur[1], cur[2], dataset_seq, ftype)
     while cur is not None:
         if device:
             d_xyz, d_feat, npts = gen.collect_device()
@@ -441,19 +532,19 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
             first = not registration.init
             registration.set_pcd_device(d_xyz, d_feat, npts)   # (consumed: the next frame may overwrite it)
             if nxt is not None and prefetch:
-                gen.submit(nxt[1], nxt[2], dataset_seq, ftype)
+                submit(nxt[1], nxt[2], dataset_seq, ftype)
             if not first:
                 registration.align()
         else:
             xyz, feat = gen.collect()
             nxt = next(it, None)
             if nxt is not None and prefetch:
-                gen.submit(nxt[1], nxt[2], dataset_seq, ftype)
+                submit(nxt[1], nxt[2], dataset_seq, ftype)
             registration.run_cvo(xyz, feat)
         if writer is not None and registration.init:
             writer.append(cur[0], registration.accum_transform)
         if nxt is not None and not prefetch:
-            gen.submit(nxt[1], nxt[2], dataset_seq, ftype)
+            submit(nxt[1], nxt[2], dataset_seq, ftype)
         count += 1
         cur = nxt
     return count
@@ -479,3 +570,26 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_camera=depth_camera, depth_gate=depth_gate, mask=mask)
+
+
+def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
+                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None):
+    """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
+    name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
+    a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
+    `camera`, `depth_gate`, `mask`: as in run_frames."""
+    with open(os.path.join(folder, times)) as fh:
+        names = [line.strip() for line in fh if line.strip()]
+    if limit is not None:
+        names = names[:limit]
+
+    def colour(path):
+        from PIL import Image
+        return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), np.uint8)[:, :, ::-1])
+
+    def decoded():
+        for k, name in enumerate(names):
+            yield name, colour(os.path.join(folder, left, "%06d.png" % k)), colour(os.path.join(folder, right, "%06d.png" % k))
+
+    return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
+                      depth_gate=depth_gate, mask=mask, stereo=stereo)

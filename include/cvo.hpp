@@ -129,6 +129,15 @@ class registration {
     void set_mask(const image_view &mask);
     void set_mask(const uint8_t *mask, size_t stride);
     void clear_mask();
+    // A rectified stereo pair in place of the depth image: cvo_fe_set_stereo.  A frame is then two colour images of
+    // one size and goes in through set_pcd_stereo() / run_cvo_stereo() -- the image form of set_pcd() / run_cvo() for
+    // two colour views, the left one the frame's colour image; a semi-global matcher on the device fills the depth
+    // (the contract: cvo_frontend.h).  May be called before the first image; throws for settings the front end
+    // refuses, and beside a depth camera or a camera model with lens distortion.  clear_stereo(): depth images again.
+    void set_stereo(const cvo_fe_stereo &stereo);
+    void clear_stereo();
+    void set_pcd_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
+    void run_cvo_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
     int num_points_last_frame() const { return fe_points_; }
     // Batched mode: align() of `count` objects (each with its moving cloud set) in
     // one call, their kernel launches shared (cvo_hip_align_many).  The result of
@@ -157,6 +166,8 @@ class registration {
     std::vector<uint8_t> mask_;          // what set_mask() gave (dense rows), likewise
     int mask_rows_, mask_cols_;
     bool have_mask_;
+    cvo_fe_stereo stereo_;               // what set_stereo() gave, likewise
+    bool have_stereo_;
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();
@@ -164,7 +175,8 @@ class registration {
     void store(int (*set)(cvo_fe_ctx *, const S *), const char *what, const S *value, S &kept, bool &have);
     void store_mask(const image_view *mask);
     void publish();
-    void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep);
+    void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo);
+    void run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo);
 };
 
 }   // namespace cvo_hip

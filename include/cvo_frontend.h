@@ -28,7 +28,9 @@
  * cvo_fe_depth_camera below.  And a gate on the depth values themselves
  * (cvo_fe_set_depth_gate, cvo_fe_set_mask): pixels out of range, on or beside a depth
  * discontinuity, or under a caller's mask lose their depth before any later stage reads it.
- * The gate contract is stated at cvo_fe_depth_gate below.
+ * The gate contract is stated at cvo_fe_depth_gate below.  And a rectified stereo pair in place
+ * of the depth image (cvo_fe_set_stereo, cvo_fe_submit_stereo): a semi-global matcher on the device
+ * fills the depth plane.  The stereo contract is stated at cvo_fe_stereo below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -67,11 +69,21 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_UNGATED_DEPTH = 13,   /* the depth plane the gate read: w*h uint16.  Without a gate
                                              or mask it equals RECT_DEPTH (which, with one, is the gated
                                              plane: still "the depth image every later stage read") */
-       CVO_FE_STAGE_GATE = 14 };      /* the gate's flags: w*h uint8, an OR of CVO_FE_GATE_*; all zero
+       CVO_FE_STAGE_GATE = 14,        /* the gate's flags: w*h uint8, an OR of CVO_FE_GATE_*; all zero
                                          without a gate or mask */
+       /* of a stereo frame (cvo_fe_set_stereo; CVO_HIP_ERR_INVALID on a context without stereo).  Under
+          stereo RAW_DEPTH and UNGATED_DEPTH are the plane that stereo wrote, RECT_DEPTH that plane after
+          the gate, if a gate or mask is set. */
+       CVO_FE_STAGE_RIGHT_GRAY = 15,  /* w*h uint8 */
+       CVO_FE_STAGE_CENSUS_L = 16, CVO_FE_STAGE_CENSUS_R = 17,   /* w*h uint64 each */
+       CVO_FE_STAGE_SGM_SUM = 18,     /* S: w*h*max_disp uint16, index (y*w + x)*max_disp + d */
+       CVO_FE_STAGE_DISPARITY = 19,   /* w*h uint16: q in 1/16 pixel, 0 = none */
+       CVO_FE_STAGE_STEREO = 20 };    /* w*h uint8: an OR of CVO_FE_STEREO_* */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
+/* flags of CVO_FE_STAGE_STEREO (the stereo contract at cvo_fe_stereo) */
+enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CVO_FE_STEREO_DEPTH = 8 };
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
@@ -214,6 +226,54 @@ typedef struct cvo_fe_depth_gate {
     int32_t pad_;                  /* must be 0 */
 } cvo_fe_depth_gate;               /* 24 bytes, no padding */
 
+/* A rectified stereo pair in place of a depth image: rows 4 and 5 of cvo_fe_camera() ("kitti 15",
+ * "kitti 05") are the left colour camera of a stereo rig with no depth sensor behind it.
+ *
+ * THE STEREO CONTRACT.  While stereo is set a frame is a left and a right colour image of the
+ * context's size (cvo_fe_submit_stereo); the left one is the colour image of every later stage, and a
+ * semi-global matcher (census cost, four paths) fills the depth plane that an uploaded depth image
+ * fills otherwise -- the input of the gate, if one is set, and of level 0.  The pair must be rectified:
+ * a match for left pixel (x, y) is looked for at right pixel (x - d, y) only.  The results are defined by
+ * the integer arithmetic below, not by the device.  It is this library's own definition, NOT pinned
+ * against OpenCV's or libSGM's.  D is max_disp; p is a pixel (x, y) of the w x h image.
+ *   1. Grey.  Both images by the formula of STAGE_GRAY: (c0*4899 + c1*9617 + c2*1868 + 8192) >> 14.
+ *   2. Census.  A window 9 wide and 7 high: dy = -3..3 outer, dx = -4..4 inner, the centre skipped, the
+ *      neighbour's coordinates clamped to the image; each comparison appends one bit at the low end,
+ *      c = (c << 1) | (grey(n) < grey(centre)): 62 bits in a uint64.
+ *   3. Cost.  C(x, y, d) = popcount(cL(x, y) ^ cR(x - d, y)) for x - d >= 0, and 64 otherwise.
+ *   4. Paths.  Four directions r: left to right, right to left, top to bottom, bottom to top.  The first
+ *      pixel of a path has L_r = C.  After that
+ *          L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + p1, L_r(p-r, d+1) + p1, m + p2) - m,
+ *          m = min over k of L_r(p-r, k);
+ *      terms whose d-1 or d+1 lies outside [0, D) are left out.  S = sum over r of L_r; with p2 <= 255 it
+ *      is at most 4 * (64 + 255), so uint16 holds it, and being integer it does not depend on the order in
+ *      which the paths are added.
+ *   5. Winner.  d* = argmin over d of S(p, d), the smallest d on ties; S1 = S(p, d*).
+ *   6. Uniqueness.  S2 = min of S(p, d) over |d - d*| > 1.  UNIQUE iff such a d exists and
+ *      S2 * (100 - uniqueness) < S1 * 100.
+ *   7. Left-right.  dR(x, y) = argmin over d with x + d < w of S(x + d, y, d), the smallest d on ties.
+ *      LR iff lr_max >= 0 and (x - d* < 0 or |dR(x - d*, y) - d*| > lr_max).
+ *   8. Sub-pixel.  Sm = S(p, d* - 1), Sp = S(p, d* + 1).  If 0 < d* < D - 1 and den = Sm + Sp - 2*S1 > 0:
+ *      off = floor(((Sm - Sp)*16 + den) / (2*den)) -- floor division of signed integers; off lies in
+ *      [-8, 8] -- otherwise off = 0.  q = 16*d* + off.  MIN iff q < 16*min_disp.
+ *   9. Depth.  fx and depth_scale are those of the colour camera in force (the cvo_fe_set_camera model,
+ *      else the table row of dataset_seq).  A table, once per frame's camera, on the host in float64 on
+ *      the floats widened exactly: U(q) = rint((((fx*baseline)*depth_scale)*16) / q), ties to even;
+ *      U(q) = 0 for q < 16*min_disp and where the result lies outside [1, 65535].  The device only looks
+ *      U(q) up.  DEPTH iff the pixel has no other flag and U(q) == 0.
+ *  10. Output.  STEREO(p) is the OR of the flags; DISPARITY(p) = STEREO(p) ? 0 : q; the depth plane gets
+ *      STEREO(p) ? 0 : U(q).
+ * Rectifying a pair, diagonal paths, hole filling and a median filter are not part of it. */
+typedef struct cvo_fe_stereo {
+    float   baseline;      /* metres between the two cameras; > 0 */
+    int32_t max_disp;      /* D: disparities 0 .. D-1 are searched; a multiple of 8 in [8, 128] */
+    int32_t min_disp;      /* >= 1: a pixel whose disparity is below it gets no depth */
+    int32_t p1, p2;        /* SGM penalties, 1 <= p1 <= p2 <= 255 */
+    int32_t uniqueness;    /* 0..99, per cent; 0: no uniqueness test */
+    int32_t lr_max;        /* 0..8: largest |dL - dR| kept; -1: no left-right test */
+    int32_t pad_;          /* must be 0 */
+} cvo_fe_stereo;           /* 32 bytes */
+
 /* One context per image size, device and stream.  `stream` as in cvo_hip_create
  * (NULL: a stream of its own).  Images must be at least 64 x 64. */
 int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **out);
@@ -308,6 +368,27 @@ int cvo_fe_get_depth_gate(const cvo_fe_ctx *ctx, cvo_fe_depth_gate *out, int *se
  * only once a mask has been set. */
 int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride);
 
+/* While stereo is set a frame is a rectified stereo pair (the stereo contract at cvo_fe_stereo) and goes
+ * in through cvo_fe_submit_stereo / cvo_fe_create_pointcloud_stereo; st == NULL: back to depth images (the
+ * state of a new context).  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame
+ * submitted and not collected; whatever cvo_fe_check_stereo refuses; a depth camera is set; a camera model
+ * with a non-zero `dist` is set (the pair must be rectified already).  While stereo is set
+ * cvo_fe_set_depth_camera refuses a rig, cvo_fe_set_camera refuses a model with a non-zero `dist`, and
+ * cvo_fe_submit / cvo_fe_create_pointcloud refuse.  The right image, the census planes, the cost sums and
+ * the disparity maps take device and pinned memory only once stereo has been set. */
+int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st);
+/* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_stereo(const cvo_fe_ctx *ctx, cvo_fe_stereo *out, int *set);
+/* cvo_fe_submit / cvo_fe_create_pointcloud for a stereo pair: `left` and `right` are height rows of
+ * width*3 bytes each, as `img` there (a caller whose right image is grey replicates it); the left image
+ * is the colour image of the frame.  CVO_HIP_ERR_INVALID without stereo set.  collect, collect_device,
+ * get_info, set_device_output and set_num_want work on a stereo frame as on any other. */
+int cvo_fe_submit_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_stride, const uint8_t *right,
+                         size_t right_stride, int dataset_seq, int feature_type);
+int cvo_fe_create_pointcloud_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_stride, const uint8_t *right,
+                                    size_t right_stride, int dataset_seq, int feature_type, float *positions,
+                                    float *features, int capacity, int *num_points);
+
 /* what the last create_pointcloud / collect did */
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out);
 /* copy an intermediate image of the last create_pointcloud to host memory */
@@ -335,6 +416,14 @@ int cvo_fe_check_depth_camera(const cvo_fe_depth_camera *rig);
  * otherwise: NULL; a non-finite float; jump_rel < 0; max_range > 0 && max_range <= min_range; grow
  * outside [0, 3]; hole_border not 0 or 1; pad_ != 0.  The one statement of what is accepted.  Host only. */
 int cvo_fe_check_depth_gate(const cvo_fe_depth_gate *gate);
+/* CVO_HIP_OK for settings cvo_fe_set_stereo() would accept on an idle context without a depth camera and
+ * a distorting model, CVO_HIP_ERR_INVALID otherwise: NULL; baseline not finite or <= 0; max_disp no multiple
+ * of 8 in [8, 128]; min_disp < 1; not 1 <= p1 <= p2 <= 255; uniqueness outside [0, 99]; lr_max outside
+ * [-1, 8]; pad_ != 0.  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_stereo(const cvo_fe_stereo *st);
+/* U(q) of the stereo contract for q = 0 .. 16*max_disp - 1.  Host only.  CVO_HIP_ERR_INVALID for a null
+ * pointer, settings cvo_fe_check_stereo refuses, and fx or depth_scale not finite or <= 0. */
+int cvo_fe_stereo_depth_table(const cvo_fe_stereo *st, float fx, float depth_scale, uint16_t *out);
 
 #ifdef __cplusplus
 }
