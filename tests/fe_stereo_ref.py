@@ -4,7 +4,7 @@ arithmetic; the table is float64 on floats widened exactly.  The order of operat
 the kernels of csrc/cvo_stereo.hip repeat it.
 
 Settings here are a dict with the members of cvo_fe_stereo (without pad_).  Also here: the synthetic pairs and
-the cases the tests share."""
+the cases the tests share, CASES and EDGE_CASES."""
 import numpy as np
 
 UNIQUE, LR, MIN, DEPTH = 1, 2, 4, 8
@@ -181,6 +181,12 @@ def match(left, right, st, fx, depth_scale):
     gl, gr = grey(left), grey(right)
     cl, cr = census(gl), census(gr)
     S = path_sums(cost(cl, cr, D), st["p1"], st["p2"])
+    return dict(decide(S, st, fx, depth_scale), gray_l=gl, gray_r=gr, census_l=cl, census_r=cr)
+
+
+def decide(S, st, fx, depth_scale, winners=winners, not_unique=not_unique, right_map=right_map, subpixel=subpixel):
+    """5 to 10: the planes behind the cost sums.  (The keywords put another form of one stage in its place: the
+    mutants of tests/fe_stereo_mutants.py.)"""
     ds, S1 = winners(S)
     dR = right_map(S)
     q = subpixel(S, ds, S1)
@@ -191,7 +197,7 @@ def match(left, right, st, fx, depth_scale):
     flags |= np.where(q < 16 * st["min_disp"], MIN, 0)
     flags = np.where((flags == 0) & (U[q] == 0), DEPTH, flags).astype(np.uint8)
     keep = flags == 0
-    return dict(gray_l=gl, gray_r=gr, census_l=cl, census_r=cr, sum=S, dL=ds, dR=dR, q=q, table=U, flags=flags,
+    return dict(sum=S, dL=ds, dR=dR, q=q, table=U, flags=flags,
                 disparity=np.where(keep, q, 0).astype(np.uint16), depth=np.where(keep, U[q], 0).astype(np.uint16))
 
 
@@ -220,18 +226,18 @@ def disparity_map(w, h, box=15.0, back=6.0):
     return disp
 
 
-def pair(w, h, seed, box=15.0, back=6.0):
+def pair(w, h, seed, box=15.0, back=6.0, pad=PAD):
     """(left, right, disp): the right image is a window of the texture, the left one the right one resampled at
-    x - disp(x, y), bilinear and rounded"""
-    tex = texture(h, w + PAD, seed)
+    x - disp(x, y), bilinear and rounded; `pad` columns of texture lie to the left of the right image"""
+    tex = texture(h, w + pad, seed)
     disp = disparity_map(w, h, box, back)
-    assert disp.max() + 1 < PAD
-    xs = PAD + np.arange(w)[None, :] - disp
+    assert disp.max() + 1 < pad
+    xs = pad + np.arange(w)[None, :] - disp
     x0 = np.floor(xs).astype(np.int64)
     a = (xs - x0)[:, :, None]
     rows = np.arange(h)[:, None]
     left = (1.0 - a) * tex[rows, x0] + a * tex[rows, x0 + 1]
-    right = tex[:, PAD:PAD + w]
+    right = tex[:, pad:pad + w]
     as_bytes = lambda t: np.ascontiguousarray(np.clip(np.rint(t), 0, 255).astype(np.uint8))
     return as_bytes(left), as_bytes(right), disp
 
@@ -290,6 +296,96 @@ def case_planes(name):
             a.setflags(write=False)
         _DONE[name] = out
     return _DONE[name]
+
+
+# ---- the edge cases: the seam between the two disparities of a lane, the ends of D, settings at the edge of what
+# cvo_fe_check_stereo accepts, hostile images.  A table of its own beside CASES; what each one is for is asserted
+# in tests/test_fe_stereo_cpu.py ---------------------------------------------------------------------------------
+
+EDGE_PAD = 140         # room for a disparity of 127 and the ramp's reach
+EDGE_BASELINE = 0.54   # 388 m px at FX: every disparity from 12 pixels up has a depth at 2000 units per metre
+# uniqueness 0 and lr_max -1 switch both tests off: the disparity plane then shows q wherever there is a depth
+_OPEN = dict(baseline=EDGE_BASELINE, uniqueness=0, lr_max=-1)
+_LR0 = dict(baseline=EDGE_BASELINE, lr_max=0)
+# name: (width, height, settings, scene).  Scenes: ("pair", seed, box, back, pad) is pair(); ("noise", seed) two
+# independent planes of uniform random bytes; ("stripes",) vertical stripes of period 8, ("checker",) a one-pixel
+# checkerboard and ("same", seed) a texture, each the same in both images; ("saturated",) left all 255, right all 0;
+# ("tail", seed, k) is "same" with the last k columns of the left image replaced by uniform random bytes
+EDGE_CASES = {
+    "seam-128": (192, 64, make_stereo(max_disp=128, **_OPEN), ("pair", 81, 63.5, 6.0, EDGE_PAD)),
+    "seam-72": (192, 64, make_stereo(max_disp=72, **_OPEN), ("pair", 81, 64.5, 6.0, EDGE_PAD)),
+    "seam-back": (192, 64, make_stereo(max_disp=128, **_OPEN), ("pair", 81, 64.0, 62.0, EDGE_PAD)),
+    "full-64": (192, 64, make_stereo(max_disp=64, **_OPEN), ("pair", 81, 62.5, 6.0, EDGE_PAD)),
+    "top-128": (320, 64, make_stereo(max_disp=128, **_OPEN), ("pair", 81, 126.5, 120.0, EDGE_PAD)),
+    # (a background at 3 pixels has a depth below 0.137 m of baseline only)
+    "d8": (64, 64, make_stereo(max_disp=8, **dict(_OPEN, baseline=0.1)), ("pair", 81, 6.5, 3.0, EDGE_PAD)),
+    "d120": (288, 64, make_stereo(max_disp=120, **_OPEN), ("pair", 81, 100.5, 70.0, EDGE_PAD)),
+    "narrow": (64, 64, make_stereo(max_disp=128, **_OPEN), ("pair", 81, 15.0, 6.0, EDGE_PAD)),
+    "wide": (1241, 64, make_stereo(max_disp=128, **_OPEN), ("pair", 81, 70.0, 6.0, EDGE_PAD)),
+    # the seam scenes under the default uniqueness and lr_max 0: LR turns on the exact dR
+    "seam-128-lr0": (192, 64, make_stereo(max_disp=128, **_LR0), ("pair", 81, 63.5, 6.0, EDGE_PAD)),
+    "seam-72-lr0": (192, 64, make_stereo(max_disp=72, **_LR0), ("pair", 81, 64.5, 6.0, EDGE_PAD)),
+    "seam-back-lr0": (192, 64, make_stereo(max_disp=128, **_LR0), ("pair", 81, 64.0, 62.0, EDGE_PAD)),
+    # settings at the edge of what is accepted, on the pair of default-96x64-82
+    "p255": (96, 64, make_stereo(p1=255, p2=255), ("pair", 82, 15.0, 6.0, PAD)),
+    "p255-noise": (96, 64, make_stereo(p1=255, p2=255), ("noise", 85)),
+    "p1": (96, 64, make_stereo(p1=1, p2=1), ("pair", 82, 15.0, 6.0, PAD)),
+    "u99-lr8": (96, 64, make_stereo(uniqueness=99, lr_max=8), ("pair", 82, 15.0, 6.0, PAD)),
+    "lr0": (96, 64, make_stereo(lr_max=0), ("pair", 82, 15.0, 6.0, PAD)),
+    "min200": (96, 64, make_stereo(min_disp=200), ("pair", 82, 15.0, 6.0, PAD)),
+    # (FX * 1e-6 * SCALE * 16 = 23: the table is 1 up to q = 46 and 0 from there, so under min_disp 3 it is all zero)
+    "baseline1e-6": (96, 64, make_stereo(baseline=1e-6), ("pair", 82, 15.0, 6.0, PAD)),
+    "baseline1e-6-min3": (96, 64, make_stereo(baseline=1e-6, min_disp=3), ("pair", 82, 15.0, 6.0, PAD)),
+    # hostile images under the default settings
+    "noise": (96, 64, make_stereo(), ("noise", 85)),
+    "stripes": (96, 64, make_stereo(), ("stripes",)),
+    "checker": (96, 64, make_stereo(), ("checker",)),
+    "saturated": (96, 64, make_stereo(), ("saturated",)),
+    "same": (96, 64, make_stereo(), ("same", 82)),
+    # the right map's x + d < w: the last two columns of the left image match nothing, so right pixels there have
+    # only costly candidates inside the row, and the row below begins with cheap ones (see the CPU test)
+    "tail": (96, 64, make_stereo(p2=255, lr_max=0), ("tail", 82, 2)),
+}
+STRIPE = (40, 90, 200, 250, 160, 120, 60, 10)     # one period of the stripes, every channel
+
+
+def edge_inputs(name):
+    """(settings, left, right, disp or None) of an edge case"""
+    w, h, st, scene = EDGE_CASES[name]
+    kind = scene[0]
+    if kind == "pair":
+        left, right, disp = pair(w, h, *scene[1:4], pad=scene[4])
+        return st, left, right, disp
+    if kind == "noise":
+        rng = np.random.Generator(np.random.PCG64(3000 + scene[1]))
+        left, right = (rng.integers(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(2))
+    elif kind == "saturated":
+        left, right = np.full((h, w, 3), 255, np.uint8), np.zeros((h, w, 3), np.uint8)
+    else:
+        if kind == "stripes":
+            plane = np.broadcast_to(np.array(STRIPE)[np.arange(w) % 8][None, :, None], (h, w, 3))
+        elif kind == "checker":
+            plane = np.broadcast_to((255 * ((np.arange(w)[None, :] + np.arange(h)[:, None]) % 2))[:, :, None], (h, w, 3))
+        else:
+            plane = np.rint(texture(h, w, scene[1]))
+        left = np.ascontiguousarray(plane.astype(np.uint8))
+        right = left.copy()
+        if kind == "tail":
+            rng = np.random.Generator(np.random.PCG64(4000 + scene[1]))
+            left[:, w - scene[2]:] = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)[:, w - scene[2]:]
+    return st, left, right, None
+
+
+def edge_planes(name):
+    """match() of an edge case, computed once and left unchanged"""
+    key = ("edge", name)
+    if key not in _DONE:
+        st, left, right, _ = edge_inputs(name)
+        out = match(left, right, st, FX, SCALE)
+        for a in out.values():
+            a.setflags(write=False)
+        _DONE[key] = out
+    return _DONE[key]
 
 
 def bad_stereos():

@@ -1,8 +1,9 @@
 """CPU: the stereo contract of include/cvo_frontend.h (at cvo_fe_stereo).  The numpy restatement
 (tests/fe_stereo_ref.py) against answers written by hand and against a second, plain-loops form of the path
 recurrence; the library's host-only cvo_fe_check_stereo and cvo_fe_stereo_depth_table; the structure against its
-ctypes mirror; and the conditions the shared cases are there for, which the restatement alone must meet, so that the
-GPU tests cannot pass on nothing.  The contract is the library's own definition: PARITY UNPINNED against OpenCV's
+ctypes mirror; and the conditions the shared cases and the edge cases are there for, which the restatement alone must
+meet, so that the GPU tests cannot pass on nothing, with mutants of the restatement (tests/fe_stereo_mutants.py) that
+the edge cases must tell from it.  The contract is the library's own definition: PARITY UNPINNED against OpenCV's
 or libSGM's matchers."""
 import ctypes as C
 import os
@@ -11,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import fe_stereo_mutants as M
 import fe_stereo_ref as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -292,3 +294,246 @@ def test_ties_occur_in_the_textured_cases():
         for d in range(min(D, w)):
             SR[:, :w - d, d] = Sv[:, d:, d]
         assert np.count_nonzero((SR == SR.min(axis=2, keepdims=True)).sum(axis=2) > 1) >= 20
+
+
+# ---- the edge cases reach what they are for ------------------------------------------------
+
+def _edge(name):
+    """(planes, kept, d*, sub-pixel offset) of an edge case"""
+    P = S.edge_planes(name)
+    return P, P["flags"] == 0, P["dL"], P["q"] - 16 * P["dL"]
+
+
+def _kept_at(name, d):
+    """(kept pixels with d* = d, those of them with a non-zero offset)"""
+    P, kept, ds, off = _edge(name)
+    here = kept & (ds == d)
+    return int(here.sum()), int((here & (off != 0)).sum())
+
+
+def test_the_vector_form_equals_the_plain_loops_across_the_seam():
+    """the restatement itself across d = 63 | 64: a crop of 80 x 8 of seam-72's pair at D 72, so that d = 60 .. 71 have
+    pixels inside the image, and at penalties under which the neighbour terms decide"""
+    st, left, right, _ = S.edge_inputs("seam-72")
+    left, right = left[24:32, 60:140], right[24:32, 60:140]
+    for p1, p2 in ((8, 32), (1, 255)):
+        Cv = S.cost(S.census(S.grey(left)), S.census(S.grey(right)), 72)
+        assert (Cv[:, 72:, 60:] < 64).all()
+        a, b = S.path_sums(Cv, p1, p2), S.path_sums_loops(Cv, p1, p2)
+        assert a.dtype == b.dtype == np.uint16 and a.shape == (8, 80, 72) and np.array_equal(a, b)
+        assert len(np.unique(a[:, :, 62:66])) > 20
+
+
+def test_the_seam_cases_show_q_on_both_sides_of_the_seam():
+    """uniqueness 0 and lr_max -1: the disparity plane shows q wherever there is a depth.  Measured on the restatement
+    (kept pixels at that d*, those of them with a non-zero offset; the floor is 200 with an offset, 1000 kept for
+    seam-back): seam-128 d* 63: 979, 955; d* 64: 1046, 1020.  seam-72 d* 64: 1000, 974; d* 65: 1033, 1010, with all
+    2033 kept winners in the 8 live lanes of the upper register.  seam-back d* 62: 4949; d* 64: 2039."""
+    for name, d in (("seam-128", 63), ("seam-128", 64), ("seam-72", 64), ("seam-72", 65)):
+        n, with_offset = _kept_at(name, d)
+        print(name, d, n, with_offset)
+        assert with_offset >= 200, (name, d)
+    for d in (62, 64):
+        n, _ = _kept_at("seam-back", d)
+        print("seam-back", d, n)
+        assert n >= 1000, d
+    for name in ("seam-128", "seam-72", "seam-back"):
+        P, kept, ds, off = _edge(name)
+        assert not (P["flags"] & (S.UNIQUE | S.LR)).any()
+        assert np.array_equal(P["disparity"][kept], P["q"][kept]) and (P["disparity"][kept] != 0).all()
+    assert S.EDGE_CASES["seam-72"][2]["max_disp"] == 72
+
+
+def test_the_ends_of_D():
+    """d* = D - 1 has no upper neighbour and no offset; d* = D - 2 has both.  Measured (kept, with an offset; the floor
+    is 200, for d8 100): full-64 d* 62: 987, 957; d* 63: 1029, 0.  top-128 d* 126: 1471, 1424; d* 127: 1307, 0.  d8
+    d* 6: 470, 446; d* 7: 564, 0.  d120 (box 100.5 over a background at 70): d* 100: 1548, 1505; d* 101: 1380, 1342,
+    and 11722 kept winners from d = 64 up."""
+    for name, D, floor in (("full-64", 64, 200), ("top-128", 128, 200), ("d8", 8, 100)):
+        assert S.EDGE_CASES[name][2]["max_disp"] == D
+        n, with_offset = _kept_at(name, D - 2)
+        top, top_with_offset = _kept_at(name, D - 1)
+        print(name, n, with_offset, top, top_with_offset)
+        assert n >= floor and with_offset >= floor and top >= floor and top_with_offset == 0, name
+    for d in (100, 101):
+        assert _kept_at("d120", d)[1] >= 200
+    P, kept, ds, off = _edge("d120")
+    assert P["sum"].shape[2] == 120 and np.count_nonzero(kept & (ds >= 64)) >= 1000
+
+
+def test_narrow_and_wide():
+    """narrow: 64 pixels wide at D 128: x - d < 0 at 75 % of all (pixel, d), at half of the d for every pixel, and the
+    right map still finds disparities up to 35.  wide: 1241 steps along a row, no multiple of 8, the box at 70: 13236
+    pixels kept, every one with d* >= 64; beyond x = 1024 the background at 6 is found at 11714 of 13888 pixels."""
+    P, kept, ds, off = _edge("narrow")
+    Cv = S.cost(P["census_l"], P["census_r"], 128)
+    assert P["sum"].shape == (64, 64, 128) and (Cv[:, :, 64:] == 64).all() and (Cv == 64).mean() >= 0.7
+    assert kept.sum() >= 500 and ds.max() < 64 and P["dR"].max() < 64
+    P, kept, ds, off = _edge("wide")
+    assert P["sum"].shape == (64, 1241, 128) and 1241 % 8 != 0
+    assert np.count_nonzero(kept & (ds >= 64)) >= 5000
+    assert np.count_nonzero(ds[:, 1024:] == 6) >= 5000        # the background beyond step 1024 (no depth there: DEPTH)
+
+
+def test_the_left_right_test_turns_on_dR_at_the_seam():
+    """The seam scenes under uniqueness 10 and lr_max 0: a pixel is kept only where dR equals d* exactly.  Measured:
+    seam-128-lr0: dR = 62, 63, 64, 65 at 42, 226, 91, 12 pixels, 164 kept with d* in 63..65; seam-72-lr0: 24, 48, 197,
+    92 and 133.  The floors: 10 pixels for each value, 50 kept.  seam-back-lr0 has dR = 62, 63, 64 at 4886, 73, 2032
+    pixels (none at 65: nothing lies there) and 2032 kept with d* in 63..65."""
+    for name in ("seam-128-lr0", "seam-72-lr0"):
+        P, kept, ds, off = _edge(name)
+        assert S.EDGE_CASES[name][2]["lr_max"] == 0 and S.EDGE_CASES[name][2]["uniqueness"] == 10
+        counts = [int(np.count_nonzero(P["dR"] == v)) for v in (62, 63, 64, 65)]
+        n = int(np.count_nonzero(kept & (ds >= 63) & (ds <= 65)))
+        print(name, counts, n)
+        assert min(counts) >= 10 and n >= 50, name
+        assert np.count_nonzero(P["flags"] & S.LR) >= 1000 and np.count_nonzero(P["flags"] & S.UNIQUE) >= 10
+    P, kept, ds, off = _edge("seam-back-lr0")
+    assert min(np.count_nonzero(P["dR"] == v) for v in (62, 63, 64)) >= 10
+    assert np.count_nonzero(kept & (ds == 62)) >= 1000 and np.count_nonzero(kept & (ds == 64)) >= 1000
+
+
+def test_the_settings_cases():
+    """On the pair of default-96x64-82, measured (share kept; UNIQUE, LR, MIN, DEPTH): p255 84.6 %; 155, 677, 304, 73.
+    p1 83.1 %; 141, 740, 233, 248.  u99-lr8 56.4 %; 2623, 289, 220, 19.  lr0 84.1 %; 47, 769, 220, 192.  min200 0 %;
+    47, 604, 6144, 0.  baseline1e-6 0.1 %; 47, 604, 220, 5505: at the cases' camera 1e-6 m are 23 / q units, so the table
+    is 1 up to q = 46 and six pixels keep a depth of 1, the smallest there is.  baseline1e-6-min3 0 %; 47, 604, 294,
+    5505: the table begins at q = 48 and is all zero.  p255-noise 11.1 %; 2447, 2523, 2008, 793.
+    The bound under every uint16 sum, ST_INF and the winner's keys, S <= 4 (64 + p2), is reached at p2 = 255 on the
+    texture and on the noise: 1276.  At p1 = p2 = 1 it is 260 and reached too."""
+    base = S.case_planes("default-96x64-82")
+    for name in ("p255", "p255-noise"):
+        assert int(S.edge_planes(name)["sum"].max()) == 4 * (64 + 255) == 1276, name
+    assert int(S.edge_planes("p1")["sum"].max()) == 4 * (64 + 1)
+    for name in ("p255", "p1", "u99-lr8", "lr0"):
+        P, kept, ds, off = _edge(name)
+        assert np.array_equal(P["census_l"], base["census_l"]) and kept.mean() >= 0.5, name
+        assert not np.array_equal(P["flags"], base["flags"]), name
+    assert np.array_equal(S.edge_planes("u99-lr8")["sum"], base["sum"])
+    # uniqueness 99: S2 < 100 S1 flags all but a lone minimum of 0; lr_max 8 forgives what lr_max 1 does not
+    u = S.edge_planes("u99-lr8")["flags"]
+    assert np.count_nonzero(u & S.UNIQUE) >= 10 * np.count_nonzero(base["flags"] & S.UNIQUE) >= 10
+    assert 1 <= np.count_nonzero(u & S.LR) < np.count_nonzero(base["flags"] & S.LR)
+    assert np.count_nonzero(S.edge_planes("lr0")["flags"] & S.LR) > np.count_nonzero(base["flags"] & S.LR)
+    P, kept, ds, off = _edge("min200")
+    assert (P["flags"] & S.MIN).all() and not kept.any() and not P["depth"].any() and not P["table"].any()
+    P, kept, ds, off = _edge("baseline1e-6-min3")
+    assert not P["table"].any() and not kept.any()
+    clean = P["flags"]
+    assert np.count_nonzero(clean == S.DEPTH) >= 5000 and not (clean & S.DEPTH)[(clean & 7) != 0].any()
+    P, kept, ds, off = _edge("baseline1e-6")
+    assert int(P["table"].max()) == 1 and 1 <= kept.sum() <= 20 and (P["depth"][kept] == 1).all()
+    assert np.count_nonzero(P["flags"] == S.DEPTH) >= 5000
+
+
+def _tie_share(V):
+    """the share of pixels at which the minimum over d is attained more than once"""
+    return float(((V == V.min(axis=2, keepdims=True)).sum(axis=2) > 1).mean())
+
+
+def test_the_hostile_images():
+    """Measured on the restatement (share kept; UNIQUE, LR, MIN, DEPTH), 96 x 64 under the default settings:
+    noise      17.2 %; 2843, 3682, 538, 409.  d* and dR take every one of the 32 values.
+    stripes     0 %; 0, 0, 6144, 0.  The cost C(p, .) is 0 at every multiple of 8 inside the row; its minimum is
+                attained more than once at 89.6 % of the pixels.  The minimum of S(p, .) is attained more than once at
+                NO pixel (share 0): at x = 0 only d = 0 lies inside the image, and the path from the left carries that
+                along the row as min(p1 d, p2) for ever, as it does on a texture-free pair.  What ties is the second
+                minimum of the uniqueness test, over d outside d* - 1 .. d* + 1: it is attained more than once at
+                83.3 % of the pixels, and from x = 26 on it is S(8) = S(16) = S(24) (46 in the middle of the image).
+    checker     0 %; 0, 0, 6144, 0.  C ties at 93.8 % of the pixels (every even d), S at none, for the same reason.
+    saturated   0 %; 0, 0, 6144, 0.  No pixel has a darker neighbour in either image: both census planes are zero.
+    same        0 %; 0, 0, 6144, 0.  d* = dR = 0 at every pixel although the texture is there (C ties at 1 %).
+    tail        0 %; 28, 70, 6076, 4.  See test_the_mutants_are_told_apart.
+    What each is there for is asserted below; that all pixels are flagged where d* = 0 is the rule q < 16 min_disp."""
+    out = {}
+    for name in ("noise", "stripes", "checker", "saturated", "same", "tail"):
+        P, kept, ds, off = _edge(name)
+        Cv = S.cost(P["census_l"], P["census_r"], 32)
+        out[name] = (P, kept, _tie_share(Cv), _tie_share(P["sum"].astype(np.int64)))
+        print(name, kept.mean(), [int(np.count_nonzero(P["flags"] & k)) for k in (1, 2, 4, 8)], out[name][2:])
+    P, kept, c_ties, s_ties = out["noise"]
+    assert len(np.unique(P["dL"])) == 32 and len(np.unique(P["dR"])) == 32 and kept.sum() >= 500
+    assert all(np.count_nonzero(P["flags"] & k) >= 100 for k in (1, 2, 4, 8))
+    P, kept, c_ties, s_ties = out["stripes"]
+    Cv = S.cost(P["census_l"], P["census_r"], 32)
+    assert (Cv[:, 36:92, ::8] == 0).all() and c_ties >= 0.8 and s_ties == 0.0
+    Sv = P["sum"].astype(np.int64)
+    assert not Sv[:, :, 0].any() and Sv[:, :, 1:].min() >= 32                  # p2, from the path from the left
+    assert (Sv[:, 26:, 8] == Sv[:, 26:, 16]).all() and (Sv[:, 26:, 8] == Sv[:, 26:, 24]).all()
+    assert (Sv[:, 26:88, 8:9] == Sv[:, 26:88, 2:].min(axis=2, keepdims=True)).all() and _tie_share(Sv[:, :, 2:]) >= 0.8
+    assert (P["flags"] == S.MIN).all() and not P["dL"].any()
+    P, kept, c_ties, s_ties = out["checker"]
+    assert P["census_l"].any() and c_ties >= 0.9 and (P["flags"] == S.MIN).all() and not P["dL"].any()
+    P, kept, c_ties, s_ties = out["saturated"]
+    assert (P["gray_l"] == 255).all() and not P["gray_r"].any() and not P["census_l"].any() and not P["census_r"].any()
+    assert (P["flags"] == S.MIN).all() and not P["dL"].any()
+    P, kept, c_ties, s_ties = out["same"]
+    assert len(np.unique(P["census_l"])) > 5000 and np.array_equal(P["census_l"], P["census_r"])
+    assert not P["dL"].any() and not P["dR"].any() and (P["flags"] == S.MIN).all() and c_ties < 0.05
+    for name in ("stripes", "checker", "saturated", "same", "tail", "min200", "baseline1e-6-min3"):
+        P = S.edge_planes(name)
+        assert not P["depth"].any() and not P["disparity"].any(), name       # the GPU test expects an empty cloud
+
+
+# ---- ... and would catch the errors they are there for -------------------------------------
+
+def _differ(a, b):
+    return int(np.count_nonzero(np.asarray(a) != np.asarray(b)))
+
+
+def test_the_mutants_are_told_apart():
+    """Each mutant of tests/fe_stereo_mutants.py against the restatement, on the cases named for it (measured: the
+    number of elements that differ; the floor is one):
+    seam cut in the path        sum: seam-128 33502, seam-72 7619, seam-back 33265, top-128 11179
+    wrong register, sub-pixel   kept disparity: seam-128 2023, seam-72 806, seam-back 2062
+    wrap at the top             sum: full-64 694, top-128 4003, d8 476
+    right map without x + d < w flags: tail 7
+    band cut at the seam        flags: seam-128-lr0 354, seam-back-lr0 14
+    narrow keys                 p255-noise: d* 2414, flags 2098, disparity 117
+    The right map's bound is all but redundant under this contract: what the diagonal reads beyond the row are pixels
+    at the left end of the next row with x - d < 0, whose cost is 64 on every path, so their sum is above 256 and above
+    every sum inside the row that won at its own pixel with less.  On the textured, noise and seam cases with lr_max >= 0
+    the mutant changes dR at no more than 5 right pixels and no flag.  `tail` is made for it: under p2 = 255 the last two
+    columns of the left image (noise against an otherwise identical pair) win at d = 0 with sums above 256 (23 pixels
+    of the last column), the next row begins with d = 1 one step outside the image at 64 + p1 per path, and lr_max = 0
+    turns on dR = 0 against dR = 1: 7 flags."""
+    st = lambda name: S.EDGE_CASES[name][2]
+    for name in ("seam-128", "seam-72", "seam-back", "top-128"):
+        P = S.edge_planes(name)
+        n = _differ(M.sums(P, st(name), seam_cut=True), P["sum"])
+        print("seam cut", name, n)
+        assert n >= 1, name
+    for name in ("seam-128", "seam-72", "seam-back"):
+        P = S.edge_planes(name)
+        Q = M.planes(P, st(name), subpixel=M.subpixel_own_half)
+        kept = P["flags"] == 0
+        n = _differ(Q["disparity"][kept], P["disparity"][kept])
+        print("wrong register", name, n)
+        assert n >= 1, name
+    for name in ("full-64", "top-128", "d8"):
+        P = S.edge_planes(name)
+        n = _differ(M.sums(P, st(name), wrap=True), P["sum"])
+        print("wrap", name, n)
+        assert n >= 1, name
+    P = S.edge_planes("tail")
+    assert st("tail")["lr_max"] >= 0
+    n = _differ(M.planes(P, st("tail"), right_map=M.right_map_unbounded)["flags"], P["flags"])
+    print("right map", n)
+    assert n >= 1
+    for name in ("seam-128-lr0", "seam-back-lr0"):
+        P = S.edge_planes(name)
+        n = _differ(M.planes(P, st(name), not_unique=M.not_unique_own_half)["flags"], P["flags"])
+        print("band", name, n)
+        assert n >= 1, name
+    P = S.edge_planes("p255-noise")
+    Q = M.planes(P, st("p255-noise"), winners=M.winners_narrow_keys, subpixel=M.subpixel_unchecked)
+    print("narrow keys", [_differ(Q[k], P[k]) for k in ("dL", "flags", "disparity", "depth")])
+    assert _differ(Q["flags"], P["flags"]) >= 1 and _differ(Q["disparity"], P["disparity"]) >= 1
+    # the mutants are the restatement where their error cannot show: below the seam, and with every key in 10 bits
+    P = S.case_planes("default-64x64-81")
+    st0 = S.CASES["default-64x64-81"][3]
+    assert np.array_equal(M.sums(P, st0, seam_cut=True), P["sum"]) and np.array_equal(M.sums(P, st0), P["sum"])
+    for stage in (dict(subpixel=M.subpixel_own_half), dict(not_unique=M.not_unique_own_half),
+                  dict(winners=M.winners_narrow_keys, subpixel=M.subpixel_unchecked), dict(subpixel=M.subpixel_unchecked)):
+        Q = M.planes(P, st0, **stage)
+        assert all(np.array_equal(Q[k], P[k]) for k in Q), list(stage)

@@ -3,8 +3,9 @@ the kernels of csrc/cvo_stereo.hip against the numpy restatement of the stereo c
 bytes, stage by stage, and, downstream of them, the CPU restatement of the front end (oracle/frontend_oracle.c)
 applied to the left image and the reference's depth plane: every cloud bit for bit.  The gate behind the matcher, the
 captured graphs across changes of settings and camera, the unchanged path without stereo, the three ways of taking a
-cloud, the refusals, the memory, and run_frames, run_stereo_directory and the C++ objects above.  What the shared cases reach is asserted in
-tests/test_fe_stereo_cpu.py."""
+cloud, the refusals, the memory, and run_frames, run_stereo_directory and the C++ objects above; last, the edge cases: the seam
+between a lane's two disparities, the ends of D, extreme settings, hostile images.  What the shared cases and the edge
+cases reach is asserted in tests/test_fe_stereo_cpu.py."""
 import ctypes as C
 import io
 
@@ -472,3 +473,67 @@ def test_cpp_objects_take_a_stereo_pair(pkg, tmp_path, mode_name):
     depth = S.match(pairs[0][1], pairs[0][2], st, S.FX, S.SCALE)["depth"]
     assert sizes[0] == len(fo.create_pointcloud(pairs[0][1], depth, S.SEQ, ftype)["positions"]) > 100
     assert sizes[2] > sizes[1]                                # without the left-right test more pixels keep a depth
+
+
+# ---- 7. the seam between a lane's two disparities, the ends of D, extreme settings, hostile images ---------------
+
+def _edge_frame(gen, F, name, left, right, P, ftype):
+    """one frame of an edge case: every plane by bytes, the cloud against the front-end oracle by bits, and an empty
+    cloud where the reference keeps nothing"""
+    xyz, feat = gen.create_pointcloud_stereo(left, right, S.SEQ, ftype)
+    _stages_equal(gen, F, P, left)
+    info = gen.info()
+    ref = fo.create_pointcloud(left, P["depth"], S.SEQ, ftype, num_want=gen.num_want)
+    assert info["num_selected"] == ref["num_selected"] and info["num_points"] == len(ref["positions"]) == len(xyz)
+    assert np.array_equal(gen.read_stage(F.STAGE_MAP), ref["map"])
+    assert _same_cloud((xyz, feat), (ref["positions"], ref["features"]))
+    if not P["depth"].any():
+        assert len(xyz) == 0 and len(feat) == 0 and info["num_points"] == 0, name
+    else:
+        assert len(xyz) > 20 or np.count_nonzero(P["depth"]) <= 200, name
+
+
+@pytest.mark.parametrize("name", list(S.EDGE_CASES))
+def test_edge_cases_by_bytes_on_two_frames(pkg, name):
+    """Every case of EDGE_CASES (what each reaches, and which error of the device it would show, is asserted in
+    tests/test_fe_stereo_cpu.py) on two consecutive frames of one context -- the second replays the captured graph --
+    with the other feature type between them.  seam-128 also takes its left image with padded rows, and switches D on
+    the one context 128 -> 64 -> 72 -> 8 -> 128 with a frame after each: both kernel templates (one and two
+    disparities per lane) and the cost sums allocated anew across D = 64."""
+    F = pkg.frontend
+    w, h = S.EDGE_CASES[name][:2]
+    st, left, right, _ = S.edge_inputs(name)
+    P = S.edge_planes(name)
+    # (an eighth of the pixels wanted: the 133 and 164 pixels the lr0 seam scenes keep still give 17 and 24 points)
+    gen = pkg.frontend.PcdGenerator(w, h, num_want=w * h // 8)
+    gen.set_stereo(S.to_struct(F, st))
+    for ftype in (F.FEATURES_RGB, F.FEATURES_HSV, F.FEATURES_HSV):
+        _edge_frame(gen, F, name, left, right, P, ftype)
+    if name == "seam-128":
+        want = gen.create_pointcloud_stereo(left, right, S.SEQ, F.FEATURES_HSV)
+        padded = np.zeros((h, w + 5, 3), np.uint8)            # rows further apart than they are long
+        padded[:, :w] = left
+        padded[:, w:] = 255
+        u8p = C.POINTER(C.c_uint8)
+        for _ in range(2):
+            assert F.lib().cvo_fe_submit_stereo(gen._h, padded.ctypes.data_as(u8p), (w + 5) * 3, right.ctypes.data_as(u8p),
+                                                w * 3, S.SEQ, F.FEATURES_HSV) == 0
+            assert _same_cloud(gen.collect(), want) and len(want[0]) > 20
+            _stages_equal(gen, F, P, left)
+        # D 8 has no case of this size: full-64's pair under d8's settings
+        st8 = S.EDGE_CASES["d8"][2]
+        _, left8, right8, _ = S.edge_inputs("full-64")
+        P8 = S.match(left8, right8, st8, S.FX, S.SCALE)
+        assert np.count_nonzero(P8["depth"]) > 1000
+        for other in ("full-64", "seam-72", None, "seam-128"):
+            if other is None:
+                s, l, r, Q = st8, left8, right8, P8
+            else:
+                assert S.EDGE_CASES[other][:2] == (w, h)
+                s, l, r, _ = S.edge_inputs(other)
+                Q = S.edge_planes(other)
+            gen.set_stereo(S.to_struct(F, s))
+            assert gen.stereo() == S.to_struct(F, s)
+            for ftype in (F.FEATURES_RGB, F.FEATURES_RGB):
+                _edge_frame(gen, F, other or "d8 on full-64's pair", l, r, Q, ftype)
+    gen.close()
