@@ -3458,6 +3458,10 @@ __device__ __forceinline__ void run_body(const Slot *__restrict__ tab, const int
             }
         }
         if (tid == 0) { s_xx_ell = -1.0f; s_xx_keep[0] = 0.0; s_xx_keep[1] = 0.0; }   // (no Axx sums yet)
+        // (every wave reads s_xx_ell in the first slot's xx_fresh, in front of that pass's first barrier: without this one a wave ahead of
+        // thread 0 read what the last kernel on this compute unit had left there -- an earlier run's length scale, equal to this slot's when
+        // the same pair is registered again -- and left its xx candidates out of Axx: nnz_xx 482 ... 569 for 646, tests/test_gpu_loop_ref.py)
+        __syncthreads();
     }
     // the row of flags the entry head has read is cleared as the slot's step launch would (nothing is flagged in a run);
     // the counters of a build the entry head has named are zeroed as its flow launch would

@@ -156,9 +156,9 @@ def dense_members(p, margin):
     return rows, cols
 
 
-def roots_step(bcde, min_step=np.float32(0.2)):
-    """The step tests/test_host_math.py test_pick_step_matches_numpy_roots expects for float64 coefficients, or None where
-    that test skips (nearly a double root) -- and for a degenerate cubic, which that test's random draws never meet."""
+def cubic_roots(bcde):
+    """(positive real roots, nearly_double) of the cubic of cvo.cpp:291-296 as numpy.roots finds them on the monic form with
+    float32-rounded ratios, or None for a degenerate cubic (E == 0 as a float, or a coefficient that is not finite)."""
     c = np.array([4.0 * np.float32(bcde[3]), 3.0 * np.float32(bcde[2]), 2.0 * np.float32(bcde[1]), np.float32(bcde[0])],
                  np.float32).astype(np.float64)
     if c[0] == 0.0 or not np.all(np.isfinite(c)):
@@ -167,8 +167,16 @@ def roots_step(bcde, min_step=np.float32(0.2)):
     r = np.roots(mon)
     real = r[np.abs(r.imag) < 1e-9 * np.maximum(1.0, np.abs(r.real))].real
     cplx = r[np.abs(r.imag) >= 1e-9 * np.maximum(1.0, np.abs(r.real))]
-    if len(cplx) and np.min(np.abs(cplx.imag) / np.maximum(1.0, np.abs(cplx.real))) < 1e-5:
+    near = bool(len(cplx) and np.min(np.abs(cplx.imag) / np.maximum(1.0, np.abs(cplx.real))) < 1e-5)
+    return real[real > 0], near
+
+
+def roots_step(bcde, min_step=np.float32(0.2)):
+    """The step tests/test_host_math.py test_pick_step_matches_numpy_roots expects for float64 coefficients, or None where
+    that test skips (nearly a double root) -- and for a degenerate cubic, which that test's random draws never meet."""
+    found = cubic_roots(bcde)
+    if found is None or found[1]:
         return None
-    pos = real[real > 0]
+    pos = found[0]
     want = np.float32(pos.min()) if len(pos) else np.float32(min_step)
     return float(np.float32(0.8) if want > 0.8 else want)
