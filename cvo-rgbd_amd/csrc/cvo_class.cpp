@@ -59,7 +59,8 @@ void Affine3f::quaternion(float q[4]) const
 registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
-      depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false)
+      depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
+      stereo_rig_(), have_stereo_rig_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -88,6 +89,7 @@ void registration::apply_stored_settings()
         if (have_depth_camera_) fe_check(cvo_fe_set_depth_camera(fe_, &depth_camera_), "cvo_fe_set_depth_camera");
         if (have_depth_gate_) fe_check(cvo_fe_set_depth_gate(fe_, &depth_gate_), "cvo_fe_set_depth_gate");
         if (have_stereo_) fe_check(cvo_fe_set_stereo(fe_, &stereo_), "cvo_fe_set_stereo");
+        if (have_stereo_rig_) fe_check(cvo_fe_set_stereo_rig(fe_, &stereo_rig_), "cvo_fe_set_stereo_rig");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -165,6 +167,7 @@ void registration::set_camera(const cvo_fe_camera_model &model)
     int32_t qu = 0, qv = 0;
     if (cvo_fe_rectify_map(&model, 1, 1, &qu, &qv) != CVO_HIP_OK)
         throw std::runtime_error("set_camera(): members must be finite and fx, fy, depth_scale positive");
+    if (!fe_ && have_stereo_rig_) throw std::runtime_error("set_camera(): a stereo rig is set: clear the rig first");
     store<cvo_fe_camera_model>(cvo_fe_set_camera, "cvo_fe_set_camera", &model, camera_, have_camera_);
 }
 
@@ -209,7 +212,23 @@ void registration::set_stereo(const cvo_fe_stereo &stereo)
 
 void registration::clear_stereo()
 {
+    if (!fe_ && have_stereo_rig_) throw std::runtime_error("clear_stereo(): a stereo rig is set: clear the rig first");
     store<cvo_fe_stereo>(cvo_fe_set_stereo, "cvo_fe_set_stereo", nullptr, stereo_, have_stereo_);
+}
+
+void registration::set_stereo_rig(const cvo_fe_stereo_rig &rig)
+{
+    if (!fe_ && cvo_fe_check_stereo_rig(&rig) != CVO_HIP_OK)
+        throw std::runtime_error("set_stereo_rig(): finite members, every fx, fy, depth_scale and baseline positive, "
+                                 "R_left and R_right rotations");
+    if (!fe_ && (!have_stereo_ || have_camera_))
+        throw std::runtime_error("set_stereo_rig(): after set_stereo(), and without a camera model");
+    store<cvo_fe_stereo_rig>(cvo_fe_set_stereo_rig, "cvo_fe_set_stereo_rig", &rig, stereo_rig_, have_stereo_rig_);
+}
+
+void registration::clear_stereo_rig()
+{
+    store<cvo_fe_stereo_rig>(cvo_fe_set_stereo_rig, "cvo_fe_set_stereo_rig", nullptr, stereo_rig_, have_stereo_rig_);
 }
 
 // the mask given or cleared (null); with a front end that one holds the bytes, and no second copy is kept here

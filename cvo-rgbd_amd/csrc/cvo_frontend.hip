@@ -108,6 +108,14 @@ __device__ __forceinline__ int block_base(const int *cnt, int b)
 // pixel by pixel.  No tap leaves the images whatever the map holds: every coordinate is
 // clamped or tested here.  A null `dsrc` (a context with a depth camera: k_fe_depth_warp brings
 // the raw depth into the rectified frame itself) leaves the depth plane alone.
+// (the depth rule of the rectification contract: the nearest sample of a map entry, and whether it lies inside the image)
+__device__ __forceinline__ bool fe_nearest(int qu, int qv, int w, int h, int *xn, int *yn)
+{
+    *xn = (qu + 16) >> 5;
+    *yn = (qv + 16) >> 5;
+    return *xn >= 0 && *xn < w && *yn >= 0 && *yn < h;
+}
+
 __device__ __forceinline__ void fe_rectify_pixel(const uint8_t *src, const uint16_t *dsrc, int w, int h, int qu, int qv,
                                                  int out[3], uint16_t *dout)
 {
@@ -121,8 +129,9 @@ __device__ __forceinline__ void fe_rectify_pixel(const uint8_t *src, const uint1
 #pragma unroll
     for (int c = 0; c < 3; ++c)
         out[c] = (w00 * p00[c] + w01 * p01[c] + w10 * p10[c] + w11 * p11[c] + 512) >> 10;
-    const int xn = (qu + 16) >> 5, yn = (qv + 16) >> 5;
-    *dout = (dsrc && xn >= 0 && xn < w && yn >= 0 && yn < h) ? dsrc[(size_t)yn * w + xn] : (uint16_t)0;
+    int xn, yn;
+    const bool inside = fe_nearest(qu, qv, w, h, &xn, &yn);
+    *dout = (dsrc && inside) ? dsrc[(size_t)yn * w + xn] : (uint16_t)0;
 }
 
 __global__ void __launch_bounds__(FE_BLOCK) k_fe_rectify(const uint8_t *src, const uint16_t *dsrc, const int32_t *qu,
@@ -156,6 +165,74 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_rectify(const uint8_t *src, con
             fe_rectify_pixel(src, dsrc, w, h, qu[i], qv[i], c, &d);
             dst[3 * (size_t)i] = (uint8_t)c[0]; dst[3 * (size_t)i + 1] = (uint8_t)c[1]; dst[3 * (size_t)i + 2] = (uint8_t)c[2];
             if (dsrc) ddst[i] = d;
+        }
+    }
+}
+
+// The first stage of a frame under a stereo rig (the rig contract of include/cvo_frontend.h, at cvo_fe_stereo_rig):
+// both raw images resampled through their maps (cvo_fe_stereo_rig_map's, made on the host once per rig) in ONE
+// launch, blockIdx.y the image, and the validity plane written.  The shape is k_fe_rectify's: a thread owns four
+// consecutive output pixels of one image, loads its map entries as two 16-byte words, gathers the taps with
+// fe_rectify_pixel (the one copy of the tap arithmetic; without a depth source) and stores three packed dwords of
+// colour.  The validity byte of a pixel holds a bit of either camera, so one thread must write it: the left image's
+// threads read the right map's entries of their four pixels as well (two more 16-byte loads, no taps) and store the
+// four bytes as one dword.  No tap leaves the images whatever the maps hold (fe_rectify_pixel clamps every
+// coordinate), and validity only tests coordinates.
+struct StereoRectifyArgs {
+    const uint8_t *raw_l, *raw_r;    // w*h*3 each: the pair as uploaded
+    const int32_t *qu_l, *qv_l, *qu_r, *qv_r;   // w*h each, 16-byte aligned
+    uint8_t *dst_l, *dst_r;          // w*h*3 each: the rectified pair
+    uint8_t *valid;                  // w*h: bit 0 V_L, bit 1 V_R
+    int w, h;
+};
+
+__device__ __forceinline__ uint32_t fe_nearest_inside(int qu, int qv, int w, int h)
+{
+    int xn, yn;
+    return fe_nearest(qu, qv, w, h, &xn, &yn) ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(FE_BLOCK) k_fe_stereo_rectify(const StereoRectifyArgs a)
+{
+    const bool right = blockIdx.y != 0;
+    const uint8_t *src = right ? a.raw_r : a.raw_l;
+    const int32_t *qu = right ? a.qu_r : a.qu_l, *qv = right ? a.qv_r : a.qv_l;
+    uint8_t *dst = right ? a.dst_r : a.dst_l;
+    const int w = a.w, h = a.h, np = w * h;
+    const int i0 = 4 * (blockIdx.x * FE_BLOCK + threadIdx.x);
+    if (i0 >= np) return;
+    if (i0 + 4 <= np) {
+        const int4 u4 = *reinterpret_cast<const int4 *>(qu + i0), v4 = *reinterpret_cast<const int4 *>(qv + i0);
+        const int us[4] = {u4.x, u4.y, u4.z, u4.w}, vs[4] = {v4.x, v4.y, v4.z, v4.w};
+        uint32_t b[12];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int c[3];
+            uint16_t none;
+            fe_rectify_pixel(src, nullptr, w, h, us[q], vs[q], c, &none);
+            b[3 * q] = (uint32_t)c[0]; b[3 * q + 1] = (uint32_t)c[1]; b[3 * q + 2] = (uint32_t)c[2];
+        }
+        uint32_t *o = reinterpret_cast<uint32_t *>(dst + 3 * (size_t)i0);   // 12 * (i0 / 4): dword aligned
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o[k] = b[4 * k] | (b[4 * k + 1] << 8) | (b[4 * k + 2] << 16) | (b[4 * k + 3] << 24);
+        if (!right) {
+            const int4 ru = *reinterpret_cast<const int4 *>(a.qu_r + i0), rv = *reinterpret_cast<const int4 *>(a.qv_r + i0);
+            const int rus[4] = {ru.x, ru.y, ru.z, ru.w}, rvs[4] = {rv.x, rv.y, rv.z, rv.w};
+            uint32_t v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                v |= (fe_nearest_inside(us[q], vs[q], w, h) | (fe_nearest_inside(rus[q], rvs[q], w, h) << 1)) << (8 * q);
+            *reinterpret_cast<uint32_t *>(a.valid + i0) = v;
+        }
+    } else {
+        for (int i = i0; i < np; ++i) {
+            int c[3];
+            uint16_t none;
+            fe_rectify_pixel(src, nullptr, w, h, qu[i], qv[i], c, &none);
+            dst[3 * (size_t)i] = (uint8_t)c[0]; dst[3 * (size_t)i + 1] = (uint8_t)c[1]; dst[3 * (size_t)i + 2] = (uint8_t)c[2];
+            if (!right)
+                a.valid[i] = (uint8_t)(fe_nearest_inside(qu[i], qv[i], w, h) | (fe_nearest_inside(a.qu_r[i], a.qv_r[i], w, h) << 1));
         }
     }
 }
@@ -293,8 +370,8 @@ struct GateArgs {
 __device__ __forceinline__ bool fe_gate_masked(const GateArgs &a, size_t i, int qu, int qv)
 {
     if (!a.qu) return a.mask[i] != 0;
-    const int xn = (qu + 16) >> 5, yn = (qv + 16) >> 5;
-    if (xn < 0 || xn >= a.w || yn < 0 || yn >= a.h) return true;
+    int xn, yn;
+    if (!fe_nearest(qu, qv, a.w, a.h, &xn, &yn)) return true;
     return a.mask[(size_t)yn * a.w + xn] != 0;
 }
 
@@ -1046,6 +1123,13 @@ struct cvo_fe_ctx {
     Dev<uint16_t> disparity, depth_table;
     Pin<uint16_t> h_depth_table;
     float table_fx = 0.0f, table_scale = 0.0f;   // the camera the device's table was made for; 0: none yet
+    // the caller's stereo rig (cvo_fe_set_stereo_rig); with it a frame is a RAW pair and starts with k_fe_stereo_rectify
+    cvo_fe_stereo_rig srig{};
+    bool has_srig = false;
+    // with a rig, and gone with it: the upload targets of the raw pair, the four map planes (qu, qv of the left camera,
+    // qu, qv of the right one; rect_plane(np) entries each) and the validity plane (rect_plane(np) bytes)
+    Dev<uint8_t> srig_raw_l, srig_raw_r, srig_valid;
+    Dev<int32_t> srig_map;
     std::string err;
 };
 
@@ -1110,6 +1194,22 @@ bool model_ok(const cvo_fe_camera_model &m)
     return m.depth_scale > 0.0f && m.fx > 0.0f && m.fy > 0.0f;
 }
 
+// a rotation, as a depth camera's and a stereo rig's must be: within 1e-3 (largest absolute entry of R R^T - I) of
+// orthonormal, with a positive determinant
+bool rotation_ok(const float Rf[9])
+{
+    double R[9];
+    for (int q = 0; q < 9; ++q) R[q] = (double)Rf[q];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double e = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2];
+            if (!(std::fabs(e - (i == j ? 1.0 : 0.0)) <= 1e-3)) return false;
+        }
+    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) +
+                       R[2] * (R[3] * R[7] - R[4] * R[6]);
+    return det > 0.0;
+}
+
 // what cvo_fe_set_depth_camera accepts
 bool rig_ok(const cvo_fe_depth_camera &r)
 {
@@ -1120,16 +1220,21 @@ bool rig_ok(const cvo_fe_depth_camera &r)
         if (!std::isfinite(f[q])) return false;
     if (!(r.depth_scale > 0.0f && r.fx > 0.0f && r.fy > 0.0f)) return false;
     if (r.max_range > 0.0f && r.max_range <= r.min_range) return false;
-    double R[9];
-    for (int q = 0; q < 9; ++q) R[q] = (double)r.R[q];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const double e = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2];
-            if (!(std::fabs(e - (i == j ? 1.0 : 0.0)) <= 1e-3)) return false;
-        }
-    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) +
-                       R[2] * (R[3] * R[7] - R[4] * R[6]);
-    return det > 0.0;
+    return rotation_ok(r.R);
+}
+
+// what cvo_fe_set_stereo_rig accepts
+bool srig_ok(const cvo_fe_stereo_rig &r)
+{
+    static_assert(sizeof(cvo_fe_lens) == 9 * sizeof(float), "36 bytes, no padding");
+    static_assert(sizeof(cvo_fe_stereo_rig) == 42 * sizeof(float), "168 bytes, no padding");
+    const float *f = &r.left.fx;   // floats only
+    for (int q = 0; q < 42; ++q)
+        if (!std::isfinite(f[q])) return false;
+    if (!(r.left.fx > 0.0f && r.left.fy > 0.0f && r.right.fx > 0.0f && r.right.fy > 0.0f && r.fx > 0.0f && r.fy > 0.0f))
+        return false;
+    if (!(r.depth_scale > 0.0f && r.baseline > 0.0f)) return false;
+    return rotation_ok(r.R_left) && rotation_ok(r.R_right);
 }
 
 // what cvo_fe_set_depth_gate accepts
@@ -1184,6 +1289,17 @@ struct Lens {
     }
 };
 
+// a source position as the entry of a map: clamped to [-1, w] x [-1, h] and in 1/32 pixel (the rectification contract)
+inline void map_entry(double us, double vs, double wmax, double hmax, int32_t &qu, int32_t &qv)
+{
+    if (!(us >= -1.0)) us = -1.0;   // (also what is not a number)
+    if (us > wmax) us = wmax;
+    if (!(vs >= -1.0)) vs = -1.0;
+    if (vs > hmax) vs = hmax;
+    qu = (int32_t)std::nearbyint(32.0 * us);   // ties to even (the default rounding mode)
+    qv = (int32_t)std::nearbyint(32.0 * vs);
+}
+
 inline bool distorts(const float dist[5])
 {
     bool any = false;
@@ -1220,11 +1336,14 @@ inline int optimistic_copy(const cvo_fe_ctx *ctx)
     return ctx->device_output ? 0 : std::min(ctx->cap, std::max(4096, 2 * ctx->num_want));
 }
 
-// the colour camera in force for a frame: the caller's model (a distorting one: its rectified pinhole), else
-// the table row of dataset_seq (never fails: an index outside the table means row 0)
+// the colour camera in force for a frame: a stereo rig's rectified pinhole, else the caller's model (a distorting
+// one: its rectified pinhole), else the table row of dataset_seq (never fails: an index outside the table means row 0)
 void camera_in_force(const cvo_fe_ctx *ctx, int dataset_seq, float cam[5])
 {
-    if (ctx->custom) {
+    if (ctx->has_srig) {
+        const cvo_fe_stereo_rig &r = ctx->srig;
+        cam[0] = r.depth_scale; cam[1] = r.fx; cam[2] = r.fy; cam[3] = r.cx; cam[4] = r.cy;
+    } else if (ctx->custom) {
         const cvo_fe_camera_model &m = ctx->cam;
         cam[0] = m.depth_scale; cam[1] = m.fx; cam[2] = m.fy; cam[3] = m.cx; cam[4] = m.cy;
     } else cvo_fe_camera(dataset_seq, cam);
@@ -1307,19 +1426,33 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     uint8_t *img = ctx->img.get();
     const int32_t *qu = ctx->rect_map.get(), *qv = qu ? qu + rect_plane(np) : nullptr;   // (read under a distorting model)
     // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
-    FE_HIP(hipMemcpyAsync(ctx->rectify ? ctx->raw_img.get() : img, ctx->h_img.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
+    // (a stereo rig: the pair lands in the rig's raw buffers and k_fe_stereo_rectify fills img / right_img)
+    uint8_t *img_upload = ctx->has_srig ? ctx->srig_raw_l.get() : ctx->rectify ? ctx->raw_img.get() : img;
+    FE_HIP(hipMemcpyAsync(img_upload, ctx->h_img.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
     uint16_t *plane = depth_plane(ctx);
     if (ctx->has_stereo)
-        FE_HIP(hipMemcpyAsync(ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
+        FE_HIP(hipMemcpyAsync(ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3,
+                              hipMemcpyHostToDevice, s));
     else
         FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
+    const int32_t *srig_qu = ctx->srig_map.get();   // (read under a stereo rig: qu, qv left, qu, qv right)
+    if (ctx->has_srig) {
+        const size_t plane = rect_plane(np);
+        StereoRectifyArgs r{};
+        r.raw_l = ctx->srig_raw_l.get(); r.raw_r = ctx->srig_raw_r.get();
+        r.qu_l = srig_qu; r.qv_l = srig_qu + plane; r.qu_r = srig_qu + 2 * plane; r.qv_r = srig_qu + 3 * plane;
+        r.dst_l = img; r.dst_r = ctx->right_img.get(); r.valid = ctx->srig_valid.get();
+        r.w = w; r.h = h;
+        hipLaunchKernelGGL(k_fe_stereo_rectify, dim3(blocks((np + 3) / 4), 2), dim3(FE_BLOCK), 0, s, r);
+    }
     if (ctx->has_stereo) {   // (neither a distorting model nor a depth camera beside it: cvo_fe_set_stereo)
         const cvo_fe_stereo &st = ctx->stereo;
         FeStereoArgs a{};
+        a.valid = ctx->has_srig ? ctx->srig_valid.get() : nullptr;
         a.left = img; a.right = ctx->right_img.get();
         a.gray_l = ctx->gray.get();   // (k_fe_level0 writes the same bytes again)
         a.gray_r = ctx->right_gray.get();
@@ -1349,9 +1482,10 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         GateArgs g{};
         g.u = ctx->ungated.get(); g.depth = ctx->depth.get(); g.flags = ctx->gate_flags.get();
         g.mask = ctx->has_mask ? ctx->d_mask.get() : nullptr;
-        // the mask lies on the grid of the image as uploaded: under a distorting model it follows the map
-        g.qu = ctx->has_mask && ctx->rectify ? qu : nullptr;
-        g.qv = g.qu ? qv : nullptr;
+        // the mask lies on the grid of the image as uploaded: under a distorting model it follows the map, under a
+        // stereo rig the left camera's
+        g.qu = !ctx->has_mask ? nullptr : ctx->has_srig ? srig_qu : ctx->rectify ? qu : nullptr;
+        g.qv = !g.qu ? nullptr : ctx->has_srig ? srig_qu + rect_plane(np) : qv;
         g.w = w; g.h = h;
         float cam[5];
         camera_in_force(ctx, dataset_seq, cam);
@@ -1471,13 +1605,8 @@ int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, 
             const double x = ((double)u - lens.cx) / lens.fx;
             double us, vs;
             lens.project(x, y, us, vs);
-            if (!(us >= -1.0)) us = -1.0;   // (also what is not a number)
-            if (us > wmax) us = wmax;
-            if (!(vs >= -1.0)) vs = -1.0;
-            if (vs > hmax) vs = hmax;
             const size_t i = (size_t)v * width + u;
-            qu[i] = (int32_t)std::nearbyint(32.0 * us);   // ties to even (the default rounding mode)
-            qv[i] = (int32_t)std::nearbyint(32.0 * vs);
+            map_entry(us, vs, wmax, hmax, qu[i], qv[i]);
         }
     }
     return CVO_HIP_OK;
@@ -1660,6 +1789,7 @@ int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
     if (st && ctx->has_rig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a depth camera is set");
     if (st && ctx->rectify)
         return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: the camera model has a lens distortion; the pair must be rectified");
+    if (!st && ctx->has_srig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a stereo rig is set: clear the rig first");
     if (!st && !ctx->has_stereo) return CVO_HIP_OK;
     if (st && ctx->has_stereo && std::memcmp(st, &ctx->stereo, sizeof(*st)) == 0) return CVO_HIP_OK;
     FE_HIP(hipSetDevice(ctx->device));
@@ -1709,6 +1839,167 @@ int cvo_fe_get_stereo(const cvo_fe_ctx *ctx, cvo_fe_stereo *out, int *set)
     return CVO_HIP_OK;
 }
 
+int cvo_fe_check_stereo_rig(const cvo_fe_stereo_rig *rig) { return rig && srig_ok(*rig) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
+
+int cvo_fe_stereo_rectify(const cvo_fe_stereo_calib *calib, int width, int height, cvo_fe_stereo_rig *out, float depth_scale)
+{
+    static_assert(sizeof(cvo_fe_stereo_calib) == 30 * sizeof(float), "120 bytes, no padding");
+    if (!calib || !out || width < 1 || height < 1) return CVO_HIP_ERR_INVALID;
+    const float *cf = &calib->left.fx;   // floats only
+    for (int q = 0; q < 30; ++q)
+        if (!std::isfinite(cf[q])) return CVO_HIP_ERR_INVALID;
+    if (!std::isfinite(depth_scale) || !(depth_scale > 0.0f)) return CVO_HIP_ERR_INVALID;
+    if (!(calib->left.fx > 0.0f && calib->left.fy > 0.0f && calib->right.fx > 0.0f && calib->right.fy > 0.0f))
+        return CVO_HIP_ERR_INVALID;
+    if (!rotation_ok(calib->R)) return CVO_HIP_ERR_INVALID;
+    // the helper of the rig contract, step by step in float64
+    double R[9], T[3];
+    for (int q = 0; q < 9; ++q) R[q] = (double)calib->R[q];
+    for (int q = 0; q < 3; ++q) T[q] = (double)calib->T[q];
+    // 1: the axis-angle of R
+    const double c = (((R[0] + R[4]) + R[8]) - 1.0) / 2.0;
+    const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    const double n = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    const double angle = std::atan2(n / 2.0, c);
+    if (!(angle <= 0.5)) return CVO_HIP_ERR_INVALID;
+    double k[3] = {0.0, 0.0, 0.0};
+    if (n > 0.0)
+        for (int q = 0; q < 3; ++q) k[q] = v[q] / n;
+    // 2: half the way each, by Rodrigues' formula
+    const double K[9] = {0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0};
+    double KK[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) KK[3 * i + j] = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
+    double Rl0[9], Rr0[9];
+    const double sl = std::sin(angle / 2.0), cl = 1.0 - std::cos(angle / 2.0);
+    for (int q = 0; q < 9; ++q) {
+        const double eye = (q % 4 == 0) ? 1.0 : 0.0;
+        Rl0[q] = (eye + sl * K[q]) + cl * KK[q];
+        Rr0[q] = (eye - sl * K[q]) + cl * KK[q];
+    }
+    // 3: the direction from the left centre to the right one
+    double t[3];
+    for (int i = 0; i < 3; ++i) t[i] = (Rr0[3 * i] * T[0] + Rr0[3 * i + 1] * T[1]) + Rr0[3 * i + 2] * T[2];
+    const double b = std::sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+    if (!(b > 0.0)) return CVO_HIP_ERR_INVALID;
+    const double e1[3] = {-t[0] / b, -t[1] / b, -t[2] / b};
+    if (!(e1[0] > 0.0 && e1[0] >= std::fabs(e1[1]) && e1[0] >= std::fabs(e1[2]))) return CVO_HIP_ERR_INVALID;
+    // 4: (0, 0, 1) x e1 = (-e1.y, e1.x, 0)
+    const double n2 = std::sqrt(e1[1] * e1[1] + e1[0] * e1[0]);
+    const double e2[3] = {-e1[1] / n2, e1[0] / n2, 0.0};
+    const double e3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    const double W[9] = {e1[0], e1[1], e1[2], e2[0], e2[1], e2[2], e3[0], e3[1], e3[2]};
+    double Rk[2][9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            Rk[0][3 * i + j] = (W[3 * i] * Rl0[j] + W[3 * i + 1] * Rl0[3 + j]) + W[3 * i + 2] * Rl0[6 + j];
+            Rk[1][3 * i + j] = (W[3 * i] * Rr0[j] + W[3 * i + 1] * Rr0[3 + j]) + W[3 * i + 2] * Rr0[6 + j];
+        }
+    // 5, 6: one focal length, and the centre that puts the mean of the two optical axes in the middle of the image
+    const double f = ((double)calib->left.fy + (double)calib->right.fy) / 2.0;
+    const double mx = (f * Rk[0][2] / Rk[0][8] + f * Rk[1][2] / Rk[1][8]) / 2.0;
+    const double my = (f * Rk[0][5] / Rk[0][8] + f * Rk[1][5] / Rk[1][8]) / 2.0;
+    // 7
+    cvo_fe_stereo_rig r{};
+    r.left = calib->left;
+    r.right = calib->right;
+    for (int q = 0; q < 9; ++q) { r.R_left[q] = (float)Rk[0][q]; r.R_right[q] = (float)Rk[1][q]; }
+    r.fx = r.fy = (float)f;
+    r.cx = (float)(((double)width - 1.0) / 2.0 - mx);
+    r.cy = (float)(((double)height - 1.0) / 2.0 - my);
+    r.baseline = (float)b;
+    r.depth_scale = depth_scale;
+    if (!srig_ok(r)) return CVO_HIP_ERR_INVALID;   // (a baseline that rounds to 0, a centre that overflows)
+    *out = r;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_stereo_rig_map(const cvo_fe_stereo_rig *rig, int which, int width, int height, int32_t *qu, int32_t *qv)
+{
+    if (!rig || !qu || !qv || width < 1 || height < 1 || (which != 0 && which != 1) || !srig_ok(*rig)) return CVO_HIP_ERR_INVALID;
+    const Lens lens(which ? rig->right : rig->left);
+    double R[9];
+    for (int q = 0; q < 9; ++q) R[q] = (double)(which ? rig->R_right : rig->R_left)[q];
+    const double fx = (double)rig->fx, fy = (double)rig->fy, cx = (double)rig->cx, cy = (double)rig->cy;
+    const double wmax = (double)width, hmax = (double)height;
+    for (int v = 0; v < height; ++v) {
+        const double yr = ((double)v - cy) / fy;
+        for (int u = 0; u < width; ++u) {
+            const double xr = ((double)u - cx) / fx;
+            // R^T applied to (xr, yr, 1): from the rectified frame back into the camera's
+            const double X = (R[0] * xr + R[3] * yr) + R[6];
+            const double Y = (R[1] * xr + R[4] * yr) + R[7];
+            const double Z = (R[2] * xr + R[5] * yr) + R[8];
+            double us = -1.0, vs = -1.0;
+            if (Z > 0.0) lens.project(X / Z, Y / Z, us, vs);
+            const size_t i = (size_t)v * width + u;
+            map_entry(us, vs, wmax, hmax, qu[i], qv[i]);
+        }
+    }
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_stereo_rig(cvo_fe_ctx *ctx, const cvo_fe_stereo_rig *rig)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: a frame is in flight");
+    if (rig && !srig_ok(*rig))
+        return fail(ctx, CVO_HIP_ERR_INVALID,
+                    "set_stereo_rig: finite members, every fx, fy, depth_scale and baseline positive, R_left and R_right rotations");
+    if (rig && !ctx->has_stereo) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: stereo is not set (cvo_fe_set_stereo)");
+    if (rig && ctx->custom)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: a camera model is set; the rig is the camera: clear the model first");
+    if (!rig && !ctx->has_srig) return CVO_HIP_OK;
+    if (rig && ctx->has_srig && std::memcmp(rig, &ctx->srig, sizeof(*rig)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint8_t> raw_l, raw_r, valid;
+    Dev<int32_t> new_map;
+    if (rig) {
+        const size_t np = (size_t)ctx->np, plane = rect_plane(ctx->np);
+        std::vector<int32_t> map;
+        try { map.resize(4 * plane); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "set_stereo_rig"); }
+        for (int k = 0; k < 2; ++k)
+            if (cvo_fe_stereo_rig_map(rig, k, ctx->d.w, ctx->d.h, map.data() + 2 * k * plane, map.data() + (2 * k + 1) * plane) !=
+                CVO_HIP_OK)
+                return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: stereo_rig_map");
+        // (the raw images and the validity plane come with the first rig and stay until it is cleared; the map is new)
+        if ((!ctx->srig_raw_l && !(dev_alloc(raw_l, np * 3) && dev_alloc(raw_r, np * 3) && dev_alloc(valid, plane))) ||
+            !dev_alloc(new_map, 4 * plane))
+            return no_memory(ctx, "set_stereo_rig: device memory for the raw pair, the maps and the validity plane");
+        hipError_t e = hipMemcpy(new_map.get(), map.data(), 4 * plane * sizeof(int32_t), hipMemcpyHostToDevice);
+        // (no frame is in flight: once the stream is idle nothing reads the old maps any more)
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, CVO_HIP_ERR_HIP, "set_stereo_rig: upload of the maps", e);
+        }
+    } else FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->srig_raw_l, raw_l);
+    hand_over(ctx->srig_raw_r, raw_r);
+    hand_over(ctx->srig_valid, valid);
+    ctx->srig_map = std::move(new_map);
+    if (!rig) {   // (given back with the rig)
+        ctx->srig_raw_l.reset();
+        ctx->srig_raw_r.reset();
+        ctx->srig_valid.reset();
+    }
+    ctx->has_srig = rig != nullptr;
+    ctx->srig = rig ? *rig : cvo_fe_stereo_rig{};
+    ctx->table_fx = ctx->table_scale = 0.0f;   // (the table follows the rig's baseline: made again)
+    drop_graphs(ctx);   // (the rig's buffers and numbers are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_stereo_rig(const cvo_fe_ctx *ctx, cvo_fe_stereo_rig *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_srig ? ctx->srig : cvo_fe_stereo_rig{};
+    if (set) *set = ctx->has_srig ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
 int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride)
 {
     cvo_lock::Api api_guard;
@@ -1753,6 +2044,8 @@ int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: a frame is in flight");
     if (model && !model_ok(*model))
         return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: members must be finite and fx, fy, depth_scale positive");
+    if (model && ctx->has_srig)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: a stereo rig is set and is the camera: clear the rig first");
     if (!model && !ctx->custom) return CVO_HIP_OK;
     if (model && ctx->custom && std::memcmp(model, &ctx->cam, sizeof(*model)) == 0) return CVO_HIP_OK;
     const bool bent = model && distorts(model->dist);
@@ -1792,9 +2085,9 @@ int cvo_fe_get_camera(const cvo_fe_ctx *ctx, cvo_fe_camera_model *out, int *cust
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     float cam[5];
     camera_in_force(ctx, ctx->p_seq, cam);
-    const float *dist = ctx->cam.dist;   // (all zero without a caller's model)
+    const float *dist = ctx->cam.dist;   // (all zero without a caller's model, and under a stereo rig: it has none)
     *out = cvo_fe_camera_model{cam[0], cam[1], cam[2], cam[3], cam[4], {dist[0], dist[1], dist[2], dist[3], dist[4]}};
-    if (custom) *custom = ctx->custom ? 1 : 0;
+    if (custom) *custom = ctx->custom || ctx->has_srig ? 1 : 0;
     return CVO_HIP_OK;
 }
 
@@ -1936,7 +2229,9 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
         float cam[5];
         camera_in_force(ctx, dataset_seq, cam);
         if (cam[1] != ctx->table_fx || cam[0] != ctx->table_scale) {
-            if (cvo_fe_stereo_depth_table(&ctx->stereo, cam[1], cam[0], ctx->h_depth_table.get()) != CVO_HIP_OK)
+            cvo_fe_stereo st = ctx->stereo;
+            if (ctx->has_srig) st.baseline = ctx->srig.baseline;   // (the rig's: the settings' is not read under a rig)
+            if (cvo_fe_stereo_depth_table(&st, cam[1], cam[0], ctx->h_depth_table.get()) != CVO_HIP_OK)
                 return fail(ctx, CVO_HIP_ERR_INVALID, "submit_stereo: depth table");
             FE_HIP(hipMemcpyAsync(ctx->depth_table.get(), ctx->h_depth_table.get(), (size_t)16 * ctx->stereo.max_disp * 2,
                                   hipMemcpyHostToDevice, s));
@@ -1958,7 +2253,7 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
     // output mode) and launched as one hipGraph -- 3 copies in, 11 kernels, the copies out.
     static const bool no_graph = getenv("CVO_FE_NO_GRAPH") != nullptr;
     const int seq_given = dataset_seq;
-    if (ctx->custom) dataset_seq = 0;   // (ignored: one key whatever the caller passed)
+    if (ctx->custom || ctx->has_srig) dataset_seq = 0;   // (ignored: one key whatever the caller passed)
     const uint64_t key = ((uint64_t)(uint32_t)dataset_seq << 40) ^ ((uint64_t)feature_type << 36) ^
                          ((uint64_t)ctx->device_output << 32) ^ (uint64_t)(uint32_t)ctx->num_want;
     int rc = CVO_HIP_OK;
@@ -2100,10 +2395,14 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_SGM_SUM: src = ctx->sgm_sum.get(); need = np * (size_t)ctx->stereo.max_disp * 2; break;
     case CVO_FE_STAGE_DISPARITY: src = ctx->disparity.get(); need = np * 2; break;
     case CVO_FE_STAGE_STEREO: src = ctx->stereo_flags.get(); need = np; break;
+    case CVO_FE_STAGE_RIGHT_BGR: src = ctx->right_img.get(); need = np * 3; break;
+    case CVO_FE_STAGE_STEREO_VALID: src = ctx->srig_valid.get(); need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if (stage >= CVO_FE_STAGE_RIGHT_GRAY && !ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a stage of a stereo frame, and stereo is not set");
+    if (stage == CVO_FE_STAGE_STEREO_VALID && !ctx->has_srig)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the validity plane of a stereo rig, and no rig is set");
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");
     FE_HIP(hipSetDevice(ctx->device));
     FE_HIP(hipStreamSynchronize(ctx->stream));

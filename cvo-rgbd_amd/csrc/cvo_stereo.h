@@ -24,12 +24,14 @@ struct FeStereoArgs {
     uint16_t *disparity;            // w*h
     uint8_t *flags;                 // w*h: CVO_FE_STEREO_*
     uint16_t *depth;                // w*h: the depth plane the gate or level 0 reads
+    const uint8_t *valid;           // w*h: bit 0 V_L, bit 1 V_R of the rig contract (k_fe_stereo_rectify's), or null: no rig
     int w, h, D;
     int min_disp, p1, p2, uniqueness, lr_max;
 };
 
 // grey and census of both images, the four path passes, winner and right map, tests and lookup: eight launches
-// in stream order (capturable).  The caller has checked the settings (cvo_fe_check_stereo) and the sizes.
+// in stream order (capturable).  With `valid` the last kernel is the instance that also applies the rig contract's
+// OUTSIDE rule; without, the one that does not know of it.  The caller has checked the settings (cvo_fe_check_stereo) and the sizes.
 void fe_stereo_enqueue(const FeStereoArgs &a, hipStream_t s);
 
 #endif

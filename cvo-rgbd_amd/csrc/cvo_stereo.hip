@@ -9,7 +9,8 @@
 //                       direction, the cost of contract 3 recomputed from the census rows (no cost volume is
 //                       stored); the first launch stores S, the others add to it
 //   k_fe_sgm_winner     contracts 5, 6, 8 and the right map of 7, per pixel, into one packed word
-//   k_fe_stereo_final   contracts 7, 8 (MIN), 9, 10: the tests, the lookup, the three planes
+//   k_fe_stereo_final   contracts 7, 8 (MIN), 9, 10: the tests, the lookup, the three planes; under a stereo rig
+//                       (the rig contract, at cvo_fe_stereo_rig) the instance that ORs OUTSIDE in behind them
 // S lies as [y][x][d]: a step of either path direction and the winner read one contiguous vector over d.
 #include "cvo_stereo.h"
 
@@ -217,9 +218,12 @@ __global__ void __launch_bounds__(ST_BLOCK) k_fe_sgm_winner(const uint16_t *sum,
 }
 
 // ---- contracts 7 to 10 ----------------------------------------------------------------------------------
-__global__ void __launch_bounds__(ST_BLOCK) k_fe_stereo_final(const uint32_t *win, const uint16_t *table, int w, int np,
-                                                              int min_disp, int lr_max, uint16_t *disparity, uint8_t *flags,
-                                                              uint16_t *depth)
+// RIG: the frame came through k_fe_stereo_rectify and `valid` is its plane (bit 0 V_L, bit 1 V_R).  OUTSIDE is ORed in
+// behind the other flags, DEPTH's "no other flag" included; the instance without a rig never reads `valid`.
+template <bool RIG>
+__global__ void __launch_bounds__(ST_BLOCK) k_fe_stereo_final(const uint32_t *win, const uint16_t *table, const uint8_t *valid,
+                                                              int w, int np, int min_disp, int lr_max, uint16_t *disparity,
+                                                              uint8_t *flags, uint16_t *depth)
 {
     const int i = blockIdx.x * ST_BLOCK + threadIdx.x;
     if (i >= np) return;
@@ -238,6 +242,11 @@ __global__ void __launch_bounds__(ST_BLOCK) k_fe_stereo_final(const uint32_t *wi
     if (q < 16 * min_disp) f |= (uint32_t)CVO_FE_STEREO_MIN;
     const uint16_t u = table[q];   // (q < 16 * D: the table's length)
     if (f == 0 && u == 0) f = (uint32_t)CVO_FE_STEREO_DEPTH;
+    if (RIG) {
+        bool outside = (valid[i] & 1u) == 0;
+        if (x - ds >= 0) outside = outside || (valid[i - ds] & 2u) == 0;   // (i - ds: the same row, inside the plane)
+        if (outside) f |= (uint32_t)CVO_FE_STEREO_OUTSIDE;
+    }
     disparity[i] = f ? (uint16_t)0 : (uint16_t)q;
     flags[i] = (uint8_t)f;
     depth[i] = f ? (uint16_t)0 : u;
@@ -267,6 +276,10 @@ void fe_stereo_enqueue(const FeStereoArgs &a, hipStream_t s)
                        a.gray_l, a.gray_r, a.w, a.h, a.census_l, a.census_r);
     if (a.D <= 64) launch_paths<1>(a, s);
     else launch_paths<2>(a, s);
-    hipLaunchKernelGGL(k_fe_stereo_final, dim3(nb), dim3(ST_BLOCK), 0, s, a.win, a.table, a.w, np, a.min_disp, a.lr_max,
-                       a.disparity, a.flags, a.depth);
+    if (a.valid)
+        hipLaunchKernelGGL(k_fe_stereo_final<true>, dim3(nb), dim3(ST_BLOCK), 0, s, a.win, a.table, a.valid, a.w, np, a.min_disp,
+                           a.lr_max, a.disparity, a.flags, a.depth);
+    else
+        hipLaunchKernelGGL(k_fe_stereo_final<false>, dim3(nb), dim3(ST_BLOCK), 0, s, a.win, a.table, a.valid, a.w, np, a.min_disp,
+                           a.lr_max, a.disparity, a.flags, a.depth);
 }

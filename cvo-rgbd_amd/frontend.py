@@ -13,6 +13,13 @@ A rectified stereo pair in place of the depth image (the stereo contract of incl
     gen.set_stereo(Stereo(baseline=0.54, max_disp=128))
     xyz, feat = gen.create_pointcloud_stereo(left, right, dataset_seq=4)
 
+A RAW pair with its rig (the rig contract of include/cvo_frontend.h): both images are rectified on the device
+
+    rig = stereo_rectify(StereoCalib(left=Lens(...), right=Lens(...), R=R, T=T), 752, 480, depth_scale=1000.0)
+    gen.set_stereo(Stereo(max_disp=64))
+    gen.set_stereo_rig(rig)
+    xyz, feat = gen.create_pointcloud_stereo(raw_left, raw_right)
+
 `bgr` is the h x w x 3 uint8 array an image decoder returns in OpenCV's channel
 order (cv::imread: B, G, R) -- the reference passes exactly that to its "RGB"
 conversions (ref src/pcd_generator.cpp:389-390), so channel 0 plays the role of R
@@ -31,9 +38,10 @@ from . import capi
 FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
  STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
- STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO) = range(21)
+ STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
+ STAGE_STEREO_VALID) = range(23)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
-STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH = 1, 2, 4, 8   # the flags of STAGE_STEREO
+STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE = 1, 2, 4, 8, 16   # the flags of STAGE_STEREO
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
@@ -41,7 +49,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_set_depth_camera", "cvo_fe_get_depth_camera", "cvo_fe_depth_rays",
            "cvo_fe_check_depth_camera", "cvo_fe_set_depth_gate", "cvo_fe_get_depth_gate", "cvo_fe_check_depth_gate",
            "cvo_fe_set_mask", "cvo_fe_check_stereo", "cvo_fe_set_stereo", "cvo_fe_get_stereo", "cvo_fe_submit_stereo",
-           "cvo_fe_create_pointcloud_stereo", "cvo_fe_stereo_depth_table")
+           "cvo_fe_create_pointcloud_stereo", "cvo_fe_stereo_depth_table", "cvo_fe_set_stereo_rig", "cvo_fe_get_stereo_rig",
+           "cvo_fe_check_stereo_rig", "cvo_fe_stereo_rectify", "cvo_fe_stereo_rig_map")
 
 
 class Info(C.Structure):
@@ -122,6 +131,63 @@ class Stereo(_Settings):
         super().__init__(baseline, int(max_disp), int(min_disp), int(p1), int(p2), int(uniqueness), int(lr_max), int(pad_))
 
 
+class Lens(_Settings):
+    """cvo_fe_lens: one camera of a stereo rig, its pinhole and its lens (k1, k2, p1, p2, k3)."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 5)]
+
+    def __init__(self, fx=1.0, fy=1.0, cx=0.0, cy=0.0, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
+        if len(dist) != 5:
+            raise ValueError("dist holds k1, k2, p1, p2, k3")
+        super().__init__(fx, fy, cx, cy, (C.c_float * 5)(*dist))
+
+    def astuple(self):
+        return (self.fx, self.fy, self.cx, self.cy, tuple(self.dist))
+
+
+def _lens(v):
+    return v if isinstance(v, Lens) else Lens(*v)
+
+
+def _floats(v, n, what):
+    v = [float(x) for x in np.asarray(v, np.float64).reshape(-1)]
+    if len(v) != n:
+        raise ValueError(what)
+    return (C.c_float * n)(*v)
+
+
+_EYE = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)
+
+
+class StereoCalib(_Settings):
+    """cvo_fe_stereo_calib: what a stereo calibration tool gives -- the two cameras (Lens, or its tuple) and where
+    the right one sits: p_right = R p_left + T (R 3 x 3 row-major, T in metres).  stereo_rectify() makes the rig."""
+    _fields_ = [("left", Lens), ("right", Lens), ("R", C.c_float * 9), ("T", C.c_float * 3)]
+
+    def __init__(self, left=(), right=(), R=_EYE, T=(-0.1, 0.0, 0.0)):
+        super().__init__(_lens(left), _lens(right), _floats(R, 9, "R is 3 x 3"), _floats(T, 3, "T holds 3 numbers"))
+
+    def astuple(self):
+        return (self.left.astuple(), self.right.astuple(), tuple(self.R), tuple(self.T))
+
+
+class StereoRig(_Settings):
+    """cvo_fe_stereo_rig: a raw stereo pair's rig (the rig contract of include/cvo_frontend.h) -- the two cameras,
+    the rectifying rotations (p_rect = R_k p_k, row-major), the common rectified pinhole, the `baseline` in metres
+    and `depth_scale`, the units per metre of the depth plane.  From stereo_rectify(), or filled from published
+    rectification data (KITTI raw: R_rect_0x, P_rect_0x)."""
+    _fields_ = [("left", Lens), ("right", Lens), ("R_left", C.c_float * 9), ("R_right", C.c_float * 9), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("baseline", C.c_float), ("depth_scale", C.c_float)]
+
+    def __init__(self, left=(), right=(), R_left=_EYE, R_right=_EYE, fx=1.0, fy=1.0, cx=0.0, cy=0.0, baseline=0.1,
+                 depth_scale=1000.0):
+        super().__init__(_lens(left), _lens(right), _floats(R_left, 9, "R_left is 3 x 3"),
+                         _floats(R_right, 9, "R_right is 3 x 3"), fx, fy, cx, cy, baseline, depth_scale)
+
+    def astuple(self):
+        return (self.left.astuple(), self.right.astuple(), tuple(self.R_left), tuple(self.R_right), self.fx, self.fy,
+                self.cx, self.cy, self.baseline, self.depth_scale)
+
+
 # The published calibrations of the TUM RGB-D sequences (fx fy cx cy, d0..d4; depth 5000 per metre).
 # The reference's table (camera(1..3)) holds the same intrinsics without the distortion.  The entries are
 # shared by every user of the module: read them, hand them to set_camera() (which copies), and make a model of
@@ -177,6 +243,12 @@ def lib():
         L.cvo_fe_create_pointcloud_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int, fp, fp,
                                                       C.c_int, C.POINTER(C.c_int)]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
+        L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
+        L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
+        L.cvo_fe_check_stereo_rig.argtypes = [C.POINTER(StereoRig)]
+        L.cvo_fe_stereo_rectify.argtypes = [C.POINTER(StereoCalib), C.c_int, C.c_int, C.POINTER(StereoRig), C.c_float]
+        L.cvo_fe_stereo_rig_map.argtypes = [C.POINTER(StereoRig), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32)]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -244,6 +316,33 @@ def stereo_depth_table(stereo, fx, depth_scale):
     capi.check(lib().cvo_fe_stereo_depth_table(C.byref(stereo), fx, depth_scale, out.ctypes.data_as(C.POINTER(C.c_uint16))),
                what="stereo_depth_table")
     return out
+
+
+def check_stereo_rig(rig):
+    """True for a StereoRig set_stereo_rig() accepts (cvo_fe_check_stereo_rig).  Host only."""
+    return lib().cvo_fe_check_stereo_rig(C.byref(rig)) == 0
+
+
+def stereo_rectify(calib, width, height, depth_scale=1000.0):
+    """The StereoRig of a StereoCalib for width x height images (cvo_fe_stereo_rectify, the helper of the rig contract
+    of include/cvo_frontend.h); `depth_scale`: the units per metre the depth plane shall have.  Raises for a calibration
+    the helper refuses: cameras turned more than 0.5 rad against each other, a rig that is not horizontal with the
+    right camera on the right.  Host only."""
+    out = StereoRig()
+    capi.check(lib().cvo_fe_stereo_rectify(C.byref(calib), int(width), int(height), C.byref(out), depth_scale),
+               what="stereo_rectify")
+    return out
+
+
+def stereo_rig_map(rig, which, width, height):
+    """The map of the rig contract for camera `which` (0 left, 1 right): (qu, qv), int32 height x width, where each
+    pixel of the rectified image looks in the raw one, in 1/32 pixel.  Host only."""
+    qu = np.empty((int(height), int(width)), np.int32)
+    qv = np.empty_like(qu)
+    i32p = C.POINTER(C.c_int32)
+    capi.check(lib().cvo_fe_stereo_rig_map(C.byref(rig), int(which), int(width), int(height), qu.ctypes.data_as(i32p),
+                                           qv.ctypes.data_as(i32p)), what="stereo_rig_map")
+    return qu, qv
 
 
 class PcdGenerator:
@@ -398,6 +497,20 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_stereo(self._h, C.byref(out), C.byref(isset)), "get_stereo")
         return out if isset.value else None
 
+    def set_stereo_rig(self, rig):
+        """A StereoRig for every following frame: submit_stereo / create_pointcloud_stereo then take the RAW pair and
+        both images are rectified on the device in front of the matcher (the rig contract of include/cvo_frontend.h);
+        the rig is the camera of the frame.  Stereo must be set and no camera model; None: rectified pairs again."""
+        self._chk(lib().cvo_fe_set_stereo_rig(self._h, None if rig is None else C.byref(rig)), "set_stereo_rig")
+
+    def stereo_rig(self):
+        """The StereoRig set, or None."""
+        out, isset = StereoRig(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_stereo_rig(self._h, C.byref(out), C.byref(isset)), "get_stereo_rig")
+        return out if isset.value else None
+
+    stereo_rig_map = staticmethod(stereo_rig_map)
+
     def _pair(self, left, right):
         left = np.ascontiguousarray(left, np.uint8)
         right = np.ascontiguousarray(right, np.uint8)
@@ -441,7 +554,8 @@ class PcdGenerator:
                   STAGE_GATE: ((h, w), np.uint8), STAGE_RIGHT_GRAY: ((h, w), np.uint8),
                   STAGE_CENSUS_L: ((h, w), np.uint64), STAGE_CENSUS_R: ((h, w), np.uint64),
                   STAGE_SGM_SUM: ((h, w, self._max_disp), np.uint16), STAGE_DISPARITY: ((h, w), np.uint16),
-                  STAGE_STEREO: ((h, w), np.uint8)}
+                  STAGE_STEREO: ((h, w), np.uint8), STAGE_RIGHT_BGR: ((h, w, 3), np.uint8),
+                  STAGE_STEREO_VALID: ((h, w), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -487,10 +601,12 @@ def load_img(rgb_path, depth_path):
 
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
-               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None):
+               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
     pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
+    `stereo_rig`: a StereoRig for the generator, beside `stereo`: the pairs are then RAW and are rectified on the
+    device (`dataset_seq` is ignored: the rig is the camera); None leaves the generator as it is.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -522,6 +638,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_mask(mask)
     if stereo is not None:
         gen.set_stereo(stereo)
+    if stereo_rig is not None:
+        gen.set_stereo_rig(stereo_rig)
     submit = gen.submit_stereo if stereo is not None else gen.submit
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype)
@@ -573,11 +691,13 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
-                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None):
+                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
+                         stereo_rig=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
-    `camera`, `depth_gate`, `mask`: as in run_frames."""
+    `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
+    image_02 / image_03 with the rig of its calib_cam_to_cam.txt)."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -592,4 +712,4 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
             yield name, colour(os.path.join(folder, left, "%06d.png" % k)), colour(os.path.join(folder, right, "%06d.png" % k))
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
-                      depth_gate=depth_gate, mask=mask, stereo=stereo)
+                      depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig)

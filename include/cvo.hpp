@@ -136,6 +136,13 @@ class registration {
     // refuses, and beside a depth camera or a camera model with lens distortion.  clear_stereo(): depth images again.
     void set_stereo(const cvo_fe_stereo &stereo);
     void clear_stereo();
+    // The rig of a RAW stereo pair: cvo_fe_set_stereo_rig.  The pairs of set_pcd_stereo() / run_cvo_stereo() are then as
+    // the two cameras deliver them and both images are rectified on the device in front of the matcher; the rig is the
+    // camera of the frame (the contract: cvo_frontend.h; cvo_fe_stereo_rectify makes a rig from a calibration).  After
+    // set_stereo(); throws for a rig the front end refuses, without stereo settings and beside a camera model.  While
+    // a rig is set set_camera() and clear_stereo() throw.  clear_stereo_rig(): rectified pairs again.
+    void set_stereo_rig(const cvo_fe_stereo_rig &rig);
+    void clear_stereo_rig();
     void set_pcd_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
     void run_cvo_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
     int num_points_last_frame() const { return fe_points_; }
@@ -168,6 +175,8 @@ class registration {
     bool have_mask_;
     cvo_fe_stereo stereo_;               // what set_stereo() gave, likewise
     bool have_stereo_;
+    cvo_fe_stereo_rig stereo_rig_;       // what set_stereo_rig() gave, likewise
+    bool have_stereo_rig_;
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();

@@ -30,7 +30,10 @@
  * discontinuity, or under a caller's mask lose their depth before any later stage reads it.
  * The gate contract is stated at cvo_fe_depth_gate below.  And a rectified stereo pair in place
  * of the depth image (cvo_fe_set_stereo, cvo_fe_submit_stereo): a semi-global matcher on the device
- * fills the depth plane.  The stereo contract is stated at cvo_fe_stereo below.
+ * fills the depth plane.  The stereo contract is stated at cvo_fe_stereo below.  And the rig behind such a pair
+ * (cvo_fe_set_stereo_rig): two cameras with lenses of their own that are not parallel; every frame then takes
+ * the RAW pair and rectifies both images on the device in front of the matcher.  The rig contract is stated at
+ * cvo_fe_stereo_rig below; cvo_fe_stereo_rectify makes a rig from what a calibration tool gives.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -78,12 +81,17 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_CENSUS_L = 16, CVO_FE_STAGE_CENSUS_R = 17,   /* w*h uint64 each */
        CVO_FE_STAGE_SGM_SUM = 18,     /* S: w*h*max_disp uint16, index (y*w + x)*max_disp + d */
        CVO_FE_STAGE_DISPARITY = 19,   /* w*h uint16: q in 1/16 pixel, 0 = none */
-       CVO_FE_STAGE_STEREO = 20 };    /* w*h uint8: an OR of CVO_FE_STEREO_* */
+       CVO_FE_STAGE_STEREO = 20,      /* w*h uint8: an OR of CVO_FE_STEREO_* */
+       CVO_FE_STAGE_RIGHT_BGR = 21,   /* the right colour image the matcher read: w*h*3 uint8.  Without a stereo rig
+                                         the image as uploaded, with one the rectified one */
+       CVO_FE_STAGE_STEREO_VALID = 22 };  /* of a frame under a stereo rig (CVO_HIP_ERR_INVALID without one): w*h
+                                             uint8, bit 0 = V_L, bit 1 = V_R of the rig contract */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
 /* flags of CVO_FE_STAGE_STEREO (the stereo contract at cvo_fe_stereo) */
-enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CVO_FE_STEREO_DEPTH = 8 };
+enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CVO_FE_STEREO_DEPTH = 8,
+       CVO_FE_STEREO_OUTSIDE = 16 };   /* (only under a stereo rig: the rig contract at cvo_fe_stereo_rig) */
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
@@ -263,7 +271,8 @@ typedef struct cvo_fe_depth_gate {
  *      U(q) up.  DEPTH iff the pixel has no other flag and U(q) == 0.
  *  10. Output.  STEREO(p) is the OR of the flags; DISPARITY(p) = STEREO(p) ? 0 : q; the depth plane gets
  *      STEREO(p) ? 0 : U(q).
- * Rectifying a pair, diagonal paths, hole filling and a median filter are not part of it. */
+ * Diagonal paths, hole filling and a median filter are not part of it; a pair that is not rectified goes in
+ * with its rig (cvo_fe_set_stereo_rig, the rig contract below). */
 typedef struct cvo_fe_stereo {
     float   baseline;      /* metres between the two cameras; > 0 */
     int32_t max_disp;      /* D: disparities 0 .. D-1 are searched; a multiple of 8 in [8, 128] */
@@ -273,6 +282,86 @@ typedef struct cvo_fe_stereo {
     int32_t lr_max;        /* 0..8: largest |dL - dR| kept; -1: no left-right test */
     int32_t pad_;          /* must be 0 */
 } cvo_fe_stereo;           /* 32 bytes */
+
+/* One camera of a stereo rig: its pinhole and its lens (k1 k2 p1 p2 k3, as cvo_fe_camera_model's dist). */
+typedef struct cvo_fe_lens {
+    float fx, fy, cx, cy;
+    float dist[5];
+} cvo_fe_lens;                 /* 36 bytes, no padding */
+
+/* What a stereo calibration tool gives: the two cameras and where the right one sits. */
+typedef struct cvo_fe_stereo_calib {
+    cvo_fe_lens left, right;
+    float R[9], T[3];          /* p_right = R p_left + T, R row-major, T in metres */
+} cvo_fe_stereo_calib;         /* 120 bytes, no padding */
+
+/* A raw stereo pair, rectified on the device by its rig: two cameras with lenses of their own whose axes are not
+ * parallel (KITTI raw, EuRoC, a ZED or RealSense IR pair, any rig bolted together).  A caller with published
+ * rectification data fills the struct directly (KITTI raw: R_left / R_right = R_rect_0x, fx fy cx cy from
+ * P_rect_0x, baseline = -P_rect(0,3) / fx of the right camera); everybody else gets it from
+ * cvo_fe_stereo_rectify.
+ *
+ * THE RIG CONTRACT.  While a rig is set cvo_fe_submit_stereo / cvo_fe_create_pointcloud_stereo take the RAW pair,
+ * and every frame starts with the resampling of both images through the rig's two maps; the rectified left image
+ * is the colour image of every later stage (CVO_FE_STAGE_RECT_BGR), the matcher of the stereo contract reads the
+ * rectified pair (CVO_FE_STAGE_RIGHT_BGR is the right one), and its steps 1 to 10 are unchanged.  The results
+ * are defined by the arithmetic below, not by the device.
+ *
+ * The helper cvo_fe_stereo_rectify(calib, width, height, out, depth_scale), host only, float64 on the floats
+ * widened exactly.  It is this library's own definition, in the manner of Bouguet's method, and is NOT pinned
+ * against cv::stereoRectify.  In this order:
+ *   1. om = the axis-angle of R: c = (((R00 + R11) + R22) - 1) / 2, v = (R21 - R12, R02 - R20, R10 - R01),
+ *      n = |v|, angle = atan2(n / 2, c), axis k = v / n (angle 0 and no axis if n == 0).  Refused: an angle
+ *      above 0.5 rad.
+ *   2. Rl0 = exp(om / 2), Rr0 = exp(-om / 2) by Rodrigues' formula I + sin(a) K + (1 - cos(a)) K K with
+ *      a = +-angle / 2 and K the cross-product matrix of k: R = Rr0^T Rl0, each camera turns half the way.
+ *   3. t = Rr0 T, b = |t|, e1 = -t / b: the direction from the left centre to the right one.  Refused unless
+ *      b > 0, e1.x > 0, e1.x >= |e1.y| and e1.x >= |e1.z|: the rig must be horizontal, the right camera on
+ *      the right.
+ *   4. e2 = normalise((0, 0, 1) x e1), e3 = e1 x e2; W has the rows e1, e2, e3; R_left = W Rl0,
+ *      R_right = W Rr0.
+ *   5. f = (left.fy + right.fy) / 2; fx = fy = f.
+ *   6. a_k = R_k (0, 0, 1), the third column of R_k: camera k's optical axis lands at
+ *      (f a_k.x / a_k.z, f a_k.y / a_k.z); m = the mean of the two landing points;
+ *      cx = (width - 1) / 2 - m.x, cy = (height - 1) / 2 - m.y.  Both cameras get ONE cx: a point at infinity
+ *      has disparity 0.
+ *   7. baseline = b; every member is rounded to float32; the two cameras are copied through.
+ *
+ * The maps, one per camera, once per (rig, image size), on the host in float64 on the rig's floats widened
+ * exactly, no operation contracted, in this order, for output pixel (u, v) of camera k (R_k = R_left or
+ * R_right, R_k[i][j] = R_k[3*i + j]):
+ *     xr = (u - cx) / fx;  yr = (v - cy) / fy;                       (the rectified pinhole)
+ *     X = (R_k[0][0]*xr + R_k[1][0]*yr) + R_k[2][0];                 (R_k^T applied to (xr, yr, 1):
+ *     Y = (R_k[0][1]*xr + R_k[1][1]*yr) + R_k[2][1];                  p_rect = R_k p_k)
+ *     Z = (R_k[0][2]*xr + R_k[1][2]*yr) + R_k[2][2];
+ *     unless Z > 0: us = vs = -1;  else x = X / Z, y = Y / Z and (us, vs) is (x, y) distorted forward and
+ *     projected with camera k's own fx fy cx cy and dist by the formulae of the rectification contract (rad, xd,
+ *     yd, us, vs at cvo_fe_camera_model);
+ *   then that contract's clamp to [-1, w] x [-1, h] (a value that is not a number counts as -1) and
+ *   qu = rint(32*us), qv = rint(32*vs), ties to even.  cvo_fe_stereo_rig_map returns the map.
+ * Colour of both images: the integer bilinear tap of the rectification contract (5 fractional bits, replicated
+ * border, + 512 >> 10).
+ * Validity: V_k(p) = 1 iff the nearest sample (floor((qu + 16) / 32), floor((qv + 16) / 32)) of camera k's map
+ * at p lies inside the raw image -- the depth rule of the rectification contract.  CVO_FE_STAGE_STEREO_VALID
+ * holds V_L in bit 0 and V_R in bit 1.
+ * One more flag, CVO_FE_STEREO_OUTSIDE: set at p = (x, y) iff !V_L(x, y), or x - d* >= 0 && !V_R(x - d*, y),
+ * d* the winner of step 5.  The flags of steps 6 to 9 are computed exactly as without a rig (OUTSIDE is not
+ * "another flag" for DEPTH) and OUTSIDE is ORed in afterwards; a pixel with any flag gets no disparity and no
+ * depth, as in step 10.
+ * The camera in force for the frame is (depth_scale, fx, fy, cx, cy) of the rig: back-projection, the gate's
+ * `scale` and the depth table; dataset_seq is ignored.  The table of step 9 is made from the rig's fx, baseline
+ * and depth_scale; cvo_fe_stereo.baseline is not read while a rig is set.
+ * A mask (cvo_fe_set_mask) lies on the grid of the raw LEFT image and goes through the left map by the gate
+ * contract's rule for a distorting model.
+ * Not part of it: hole filling, keeping the smeared border (the replicated taps outside the raw images) out of
+ * the path costs -- OUTSIDE drops such pixels, their costs still reach their neighbours -- and vertical rigs. */
+typedef struct cvo_fe_stereo_rig {
+    cvo_fe_lens left, right;             /* the two cameras as they are */
+    float R_left[9], R_right[9];         /* the rectifying rotations, row-major: p_rect = R_k p_k */
+    float fx, fy, cx, cy;                /* the rectified pinhole, common to both */
+    float baseline;                      /* metres between the rectified cameras; > 0 */
+    float depth_scale;                   /* units per metre of the depth plane; > 0 */
+} cvo_fe_stereo_rig;                     /* 168 bytes, no padding */
 
 /* One context per image size, device and stream.  `stream` as in cvo_hip_create
  * (NULL: a stream of its own).  Images must be at least 64 x 64. */
@@ -372,7 +461,8 @@ int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride);
  * in through cvo_fe_submit_stereo / cvo_fe_create_pointcloud_stereo; st == NULL: back to depth images (the
  * state of a new context).  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame
  * submitted and not collected; whatever cvo_fe_check_stereo refuses; a depth camera is set; a camera model
- * with a non-zero `dist` is set (the pair must be rectified already).  While stereo is set
+ * with a non-zero `dist` is set (a pair that is not rectified goes in with its rig: cvo_fe_set_stereo_rig); st == NULL
+ * while a stereo rig is set ("clear the rig first").  While stereo is set
  * cvo_fe_set_depth_camera refuses a rig, cvo_fe_set_camera refuses a model with a non-zero `dist`, and
  * cvo_fe_submit / cvo_fe_create_pointcloud refuse.  The right image, the census planes, the cost sums and
  * the disparity maps take device and pinned memory only once stereo has been set. */
@@ -388,6 +478,18 @@ int cvo_fe_submit_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_strid
 int cvo_fe_create_pointcloud_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_stride, const uint8_t *right,
                                     size_t right_stride, int dataset_seq, int feature_type, float *positions,
                                     float *features, int capacity, int *num_points);
+
+/* While a rig is set a frame is a RAW stereo pair (the rig contract at cvo_fe_stereo_rig); rig == NULL: back to
+ * rectified pairs (the state after cvo_fe_set_stereo).  CVO_HIP_ERR_INVALID, the context keeping what it had: a
+ * null context; a frame submitted and not collected; stereo not set; a cvo_fe_set_camera model set (of any
+ * kind: the rig is the camera); whatever cvo_fe_check_stereo_rig refuses.  While a rig is set
+ * cvo_fe_set_camera(model) and cvo_fe_set_stereo(NULL) refuse ("clear the rig first"); other stereo settings are
+ * welcome; cvo_fe_get_camera returns the rectified pinhole with zero `dist` and *custom = 1.  The raw images,
+ * the four map planes and the validity plane take device memory only once a rig has been set and are given back
+ * when it is cleared. */
+int cvo_fe_set_stereo_rig(cvo_fe_ctx *ctx, const cvo_fe_stereo_rig *rig);
+/* *set = 1 and the rig, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_stereo_rig(const cvo_fe_ctx *ctx, cvo_fe_stereo_rig *out, int *set);
 
 /* what the last create_pointcloud / collect did */
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out);
@@ -424,6 +526,21 @@ int cvo_fe_check_stereo(const cvo_fe_stereo *st);
 /* U(q) of the stereo contract for q = 0 .. 16*max_disp - 1.  Host only.  CVO_HIP_ERR_INVALID for a null
  * pointer, settings cvo_fe_check_stereo refuses, and fx or depth_scale not finite or <= 0. */
 int cvo_fe_stereo_depth_table(const cvo_fe_stereo *st, float fx, float depth_scale, uint16_t *out);
+/* CVO_HIP_OK for a rig cvo_fe_set_stereo_rig() would accept on an idle context with stereo set and no camera model,
+ * CVO_HIP_ERR_INVALID otherwise: NULL; a member that is not finite; fx or fy of either camera or of the rectified
+ * pinhole, depth_scale or baseline <= 0; R_left or R_right further than 1e-3 (largest absolute entry of
+ * R R^T - I) from orthonormal or with a non-positive determinant (the depth camera's rule).  The one statement of
+ * what is accepted.  Host only. */
+int cvo_fe_check_stereo_rig(const cvo_fe_stereo_rig *rig);
+/* The rig of a calibration for width x height images (the helper of the rig contract).  Host only.
+ * CVO_HIP_ERR_INVALID, *out untouched: a null pointer; width or height < 1; a member of calib or depth_scale not
+ * finite; fx or fy of either camera or depth_scale <= 0; R no rotation (the rule above); what steps 1 and 3 refuse. */
+int cvo_fe_stereo_rectify(const cvo_fe_stereo_calib *calib, int width, int height, cvo_fe_stereo_rig *out,
+                          float depth_scale);
+/* The map of the rig contract for camera `which` (0 left, 1 right) and a width x height image: qu and qv,
+ * width*height int32 each, row-major.  Host only.  CVO_HIP_ERR_INVALID for a null pointer, width or height < 1,
+ * `which` not 0 or 1 and a rig cvo_fe_check_stereo_rig refuses. */
+int cvo_fe_stereo_rig_map(const cvo_fe_stereo_rig *rig, int which, int width, int height, int32_t *qu, int32_t *qv);
 
 #ifdef __cplusplus
 }
