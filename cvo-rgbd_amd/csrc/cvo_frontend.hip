@@ -1113,6 +1113,8 @@ struct cvo_fe_ctx {
     // cvo_stereo.hip fills the depth plane
     cvo_fe_stereo stereo{};
     bool has_stereo = false;
+    // the path mask (cvo_fe_set_stereo_paths): a setting of the context beside `stereo`, read by stereo frames only
+    uint32_t stereo_paths = CVO_FE_PATHS_4;
     // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
     // table U(q) with its staging copy; the cost sums follow max_disp
     Dev<uint8_t> right_img, right_gray, stereo_flags;
@@ -1461,6 +1463,7 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         a.disparity = ctx->disparity.get(); a.flags = ctx->stereo_flags.get(); a.depth = plane;
         a.w = w; a.h = h; a.D = st.max_disp;
         a.min_disp = st.min_disp; a.p1 = st.p1; a.p2 = st.p2; a.uniqueness = st.uniqueness; a.lr_max = st.lr_max;
+        a.paths = ctx->stereo_paths;
         fe_stereo_enqueue(a, s);
     }
     if (ctx->rectify)
@@ -1836,6 +1839,29 @@ int cvo_fe_get_stereo(const cvo_fe_ctx *ctx, cvo_fe_stereo *out, int *set)
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     *out = ctx->has_stereo ? ctx->stereo : cvo_fe_stereo{};
     if (set) *set = ctx->has_stereo ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_check_stereo_paths(uint32_t mask) { return mask >= 1u && mask <= (uint32_t)CVO_FE_PATHS_8 ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
+
+int cvo_fe_set_stereo_paths(cvo_fe_ctx *ctx, uint32_t mask)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_paths: a frame is in flight");
+    if (cvo_fe_check_stereo_paths(mask) != CVO_HIP_OK)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_paths: a non-empty subset of the eight bits, 1 <= mask <= 0xFF");
+    if (mask == ctx->stereo_paths) return CVO_HIP_OK;
+    ctx->stereo_paths = mask;
+    drop_graphs(ctx);   // (which path launches a frame has is part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !mask) return CVO_HIP_ERR_INVALID;
+    *mask = ctx->stereo_paths;
     return CVO_HIP_OK;
 }
 

@@ -27,11 +27,13 @@ struct FeStereoArgs {
     const uint8_t *valid;           // w*h: bit 0 V_L, bit 1 V_R of the rig contract (k_fe_stereo_rectify's), or null: no rig
     int w, h, D;
     int min_disp, p1, p2, uniqueness, lr_max;
+    uint32_t paths;                 // the path mask (cvo_fe_set_stereo_paths): bit b set, direction b of contract 4 is summed
 };
 
-// grey and census of both images, the four path passes, winner and right map, tests and lookup: eight launches
-// in stream order (capturable).  With `valid` the last kernel is the instance that also applies the rig contract's
-// OUTSIDE rule; without, the one that does not know of it.  The caller has checked the settings (cvo_fe_check_stereo) and the sizes.
+// grey and census of both images, one path pass per set bit of `paths` in bit order, winner and right map, tests and
+// lookup: four launches and one per path, in stream order (capturable).  With `valid` the last kernel is the instance that also applies the rig contract's
+// OUTSIDE rule; without, the one that does not know of it.  The caller has checked the settings (cvo_fe_check_stereo,
+// cvo_fe_check_stereo_paths) and the sizes.
 void fe_stereo_enqueue(const FeStereoArgs &a, hipStream_t s);
 
 #endif

@@ -2,12 +2,14 @@
 // stereo contract of include/cvo_frontend.h (at cvo_fe_stereo).  Everything here is integer arithmetic; the
 // numpy restatement tests/fe_stereo_ref.py holds every plane to it by bytes.
 //
-// Five kernels, eight launches per frame:
+// Five kernels, four launches and one per chosen path per frame (eight under the default mask of four paths,
+// twelve under all eight):
 //   k_fe_stereo_grey    both colour images -> grey (contract 1)
 //   k_fe_census         both grey images -> 62-bit census words (contract 2)
-//   k_fe_sgm_path x 4   one launch per direction: the recurrence of contract 4 along every line of that
-//                       direction, the cost of contract 3 recomputed from the census rows (no cost volume is
-//                       stored); the first launch stores S, the others add to it
+//   k_fe_sgm_path x n   one launch per set bit of the path mask: the recurrence of contract 4 along every line of
+//                       that direction (rows, columns, or wrapped diagonals), the cost of contract 3 recomputed
+//                       from the census rows (no cost volume is stored); the first launch stores S, the others
+//                       add to it
 //   k_fe_sgm_winner     contracts 5, 6, 8 and the right map of 7, per pixel, into one packed word
 //   k_fe_stereo_final   contracts 7, 8 (MIN), 9, 10: the tests, the lookup, the three planes; under a stereo rig
 //                       (the rig contract, at cvo_fe_stereo_rig) the instance that ORs OUTSIDE in behind them
@@ -98,34 +100,72 @@ __global__ void __launch_bounds__(ST_BLOCK) k_fe_census(const uint8_t *gray_l, c
 }
 
 // ---- contracts 3 and 4 ------------------------------------------------------------------------------------
-// One wave per line of the direction (dir 0: left to right, 1: right to left -- a line is a row; 2: top to
-// bottom, 3: bottom to top -- a line is a column), lanes over d, NV = 1 for D <= 64 and 2 for D <= 128 (lane l
-// holds d = l and d = l + 64).  A lane whose d >= D holds ST_INF throughout: its neighbour sees a term that never
-// wins, which is the contract's "left out", and so does lane 0's missing d - 1.  The recurrence is a chain of
-// dependent steps, each a wave minimum (six DPP moves) and two neighbour moves; what does not depend on it -- the
-// census words, hence the costs, and the sums to add to -- is loaded CH steps ahead of the chain.
-template <int NV, bool FIRST>
-__global__ void __launch_bounds__(64) k_fe_sgm_path(const uint64_t *census_l, const uint64_t *census_r, int w, int h, int D,
-                                                    int p1, int p2, int dir, uint16_t *sum)
+// One wave per line of the direction, lanes over d, NV = 1 for D <= 64 and 2 for D <= 128 (lane l holds d = l and
+// d = l + 64).  A lane whose d >= D holds ST_INF throughout: its neighbour sees a term that never wins, which is the
+// contract's "left out", and so does lane 0's missing d - 1.  The recurrence is a chain of dependent steps, each a
+// wave minimum (six DPP moves) and two neighbour moves; what does not depend on it -- the census words, hence the
+// costs, and the sums to add to -- is loaded CH steps ahead of the chain.
+//
+// Which pixel a line visits at step t, and whether its path begins there, is the Walk's; the chain does not know
+// the direction.  AxisWalk: bits 0 to 3 of the path mask (0: left to right, 1: right to left -- a line is a row of
+// w steps; 2: top to bottom, 3: bottom to top -- a line is a column of h steps); a path begins at step 0 only.
+// DiagWalk: bits 4 to 7, a WRAPPED line: h steps, one row each (downwards for ry = +1, upwards for ry = -1), the
+// column moving by rx per step and wrapping round the image: x = (line + rx * t) mod w.  The pixel before, p - r,
+// lies outside the image at step 0 (the row) and at the step after a wrap (the column: x == 0 for rx = +1,
+// x == w - 1 for rx = -1), and there the path begins anew with L = C.  Between two restarts a wrapped line is one
+// true diagonal from the border where it enters to the border where it leaves, and the w lines of a launch visit
+// every pixel once.  Every line has h steps, as a vertical one, and the restart is the same in every lane.
+struct StStep {
+    int x, y;
+    bool first;   // p - r lies outside the image: L = C
+};
+
+struct AxisWalk {
+    static constexpr bool RESTARTS = false;   // a path begins at step 0 and nowhere else
+    int w, h, dir;
+    __device__ int steps() const { return dir < 2 ? w : h; }
+    __device__ StStep at(int line, int t) const
+    {
+        const int tt = (dir & 1) ? steps() - 1 - t : t;
+        return dir < 2 ? StStep{tt, line, t == 0} : StStep{line, tt, t == 0};
+    }
+};
+
+struct DiagWalk {
+    static constexpr bool RESTARTS = true;
+    int w, h, rx, ry;
+    __device__ int steps() const { return h; }
+    __device__ StStep at(int line, int t) const
+    {
+        int x = (line + rx * t) % w;   // (|rx * t| < h: no overflow; % truncates towards zero, so x > -w)
+        if (x < 0) x += w;
+        return StStep{x, ry > 0 ? t : h - 1 - t, t == 0 || x == (rx > 0 ? 0 : w - 1)};
+    }
+};
+
+template <int NV, bool FIRST, class Walk>
+__global__ void __launch_bounds__(64) k_fe_sgm_path(const uint64_t *census_l, const uint64_t *census_r, int w, int D,
+                                                    int p1, int p2, const Walk walk, uint16_t *sum)
 {
     constexpr int CH = 8;
     const int line = blockIdx.x, lane = threadIdx.x;
-    const bool horizontal = dir < 2;
-    const int nsteps = horizontal ? w : h;
+    const int nsteps = walk.steps();
     int L[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) L[k] = ST_INF;
     for (int t0 = 0; t0 < nsteps; t0 += CH) {
         int cost[CH][NV], old[CH][NV];
         size_t at[CH];
+        bool first[CH];
 #pragma unroll
         for (int j = 0; j < CH; ++j) {
-            const int t = min(t0 + j, nsteps - 1);   // (a step past the end repeats the last one and is not run below)
-            const int tt = (dir & 1) ? nsteps - 1 - t : t;
-            const int x = horizontal ? tt : line, y = horizontal ? line : tt;
-            const size_t row = (size_t)y * w;
+            // (a step past the end repeats the last one and is not run below)
+            const StStep p = walk.at(line, min(t0 + j, nsteps - 1));
+            const int x = p.x;
+            const size_t row = (size_t)p.y * w;
             const uint64_t cl = census_l[row + x];
             at[j] = (row + x) * (size_t)D;
+            first[j] = p.first;
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
                 const int d = lane + 64 * k;
@@ -138,10 +178,19 @@ __global__ void __launch_bounds__(64) k_fe_sgm_path(const uint64_t *census_l, co
 #pragma unroll
         for (int j = 0; j < CH; ++j) {
             if (t0 + j >= nsteps) break;   // (the same in every lane)
-            if (t0 + j == 0) {
+            // A path that begins has no pixel before it: L = C.  A walk that begins at step 0 only (AxisWalk) says so at
+            // compile time and takes the branch below once per line.  A walk that restarts forgets L instead -- a select on
+            // a flag every lane shares -- and runs the step: from L = ST_INF in every lane m is ST_INF and so is every
+            // term of the minimum, and cost + ST_INF - ST_INF is the cost.  Either way the eight steps of a chunk stay one
+            // straight run of code; with a branch on first[j] per step a launch measured up to 20 % slower.
+            if (!Walk::RESTARTS && t0 + j == 0) {
 #pragma unroll
                 for (int k = 0; k < NV; ++k) L[k] = (lane + 64 * k < D) ? cost[j][k] : ST_INF;
             } else {
+                if (Walk::RESTARTS) {
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) L[k] = first[j] ? ST_INF : L[k];
+                }
                 int lo = L[0];
                 if (NV == 2) lo = min(lo, L[1]);
                 const int m = st_wave_min(lo, ST_INF);
@@ -169,6 +218,8 @@ __global__ void __launch_bounds__(64) k_fe_sgm_path(const uint64_t *census_l, co
 // One wave per pixel, lanes over d as above, PW pixels after one another per wave.  The minima are wave minima
 // of keys (value << 8 | d: the smallest value, the smallest d on ties); S(d* - 1) and S(d* + 1) come from the
 // lanes that hold them.  The right map reads the diagonal S(x + d, y, d): one gathered uint16 per lane.
+// With all eight paths S <= 8 * (64 + 255) = 2552 < 2^12: a key S << 8 | d stays below 2^20, and S2 * (100 -
+// uniqueness) and S1 * 100 below 255 200 < 2^18, so neither the keys nor the uniqueness test change with the mask.
 template <int NV>
 __global__ void __launch_bounds__(ST_BLOCK) k_fe_sgm_winner(const uint16_t *sum, int w, int np, int D, int uniqueness,
                                                             uint32_t *win)
@@ -252,15 +303,31 @@ __global__ void __launch_bounds__(ST_BLOCK) k_fe_stereo_final(const uint32_t *wi
     depth[i] = f ? (uint16_t)0 : u;
 }
 
+// One launch per set bit of the path mask, in bit order; the first one stores S, the others add to it (no memset).
+// Two launches never run in one: they read-modify-write the same S.
+template <int NV, bool FIRST> void launch_path(const FeStereoArgs &a, int bit, hipStream_t s)
+{
+    if (bit < 4) {
+        const AxisWalk walk{a.w, a.h, bit};
+        hipLaunchKernelGGL((k_fe_sgm_path<NV, FIRST, AxisWalk>), dim3(bit < 2 ? a.h : a.w), dim3(64), 0, s, a.census_l,
+                           a.census_r, a.w, a.D, a.p1, a.p2, walk, a.sum);
+    } else {
+        // bit 4: (+1, +1), 5: (-1, -1), 6: (-1, +1), 7: (+1, -1)
+        const DiagWalk walk{a.w, a.h, (bit == 4 || bit == 7) ? 1 : -1, (bit == 4 || bit == 6) ? 1 : -1};
+        hipLaunchKernelGGL((k_fe_sgm_path<NV, FIRST, DiagWalk>), dim3(a.w), dim3(64), 0, s, a.census_l, a.census_r, a.w, a.D,
+                           a.p1, a.p2, walk, a.sum);
+    }
+}
+
 template <int NV> void launch_paths(const FeStereoArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL((k_fe_sgm_path<NV, true>), dim3(a.h), dim3(64), 0, s, a.census_l, a.census_r, a.w, a.h, a.D, a.p1, a.p2,
-                       0, a.sum);
-    hipLaunchKernelGGL((k_fe_sgm_path<NV, false>), dim3(a.h), dim3(64), 0, s, a.census_l, a.census_r, a.w, a.h, a.D, a.p1,
-                       a.p2, 1, a.sum);
-    for (int dir = 2; dir < 4; ++dir)
-        hipLaunchKernelGGL((k_fe_sgm_path<NV, false>), dim3(a.w), dim3(64), 0, s, a.census_l, a.census_r, a.w, a.h, a.D, a.p1,
-                           a.p2, dir, a.sum);
+    bool first = true;
+    for (int bit = 0; bit < 8; ++bit) {
+        if (!(a.paths >> bit & 1u)) continue;
+        if (first) launch_path<NV, true>(a, bit, s);
+        else launch_path<NV, false>(a, bit, s);
+        first = false;
+    }
     const int np = a.w * a.h, per_block = (ST_BLOCK / 64) * 4;   // (PW of k_fe_sgm_winner)
     hipLaunchKernelGGL(k_fe_sgm_winner<NV>, dim3((np + per_block - 1) / per_block), dim3(ST_BLOCK), 0, s, a.sum, a.w, np, a.D,
                        a.uniqueness, a.win);

@@ -11,6 +11,7 @@ A rectified stereo pair in place of the depth image (the stereo contract of incl
 
     gen = PcdGenerator(width=1241, height=376)
     gen.set_stereo(Stereo(baseline=0.54, max_disp=128))
+    gen.set_stereo_paths(PATHS_8)       # optional: the four diagonal paths beside rows and columns (PATHS_4 otherwise)
     xyz, feat = gen.create_pointcloud_stereo(left, right, dataset_seq=4)
 
 A RAW pair with its rig (the rig contract of include/cvo_frontend.h): both images are rectified on the device
@@ -42,6 +43,8 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
  STAGE_STEREO_VALID) = range(23)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE = 1, 2, 4, 8, 16   # the flags of STAGE_STEREO
+# path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
+PATHS_4, PATHS_8 = 0x0F, 0xFF
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
@@ -50,7 +53,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_check_depth_camera", "cvo_fe_set_depth_gate", "cvo_fe_get_depth_gate", "cvo_fe_check_depth_gate",
            "cvo_fe_set_mask", "cvo_fe_check_stereo", "cvo_fe_set_stereo", "cvo_fe_get_stereo", "cvo_fe_submit_stereo",
            "cvo_fe_create_pointcloud_stereo", "cvo_fe_stereo_depth_table", "cvo_fe_set_stereo_rig", "cvo_fe_get_stereo_rig",
-           "cvo_fe_check_stereo_rig", "cvo_fe_stereo_rectify", "cvo_fe_stereo_rig_map")
+           "cvo_fe_check_stereo_rig", "cvo_fe_stereo_rectify", "cvo_fe_stereo_rig_map", "cvo_fe_check_stereo_paths",
+           "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths")
 
 
 class Info(C.Structure):
@@ -242,6 +246,9 @@ def lib():
         L.cvo_fe_submit_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int]
         L.cvo_fe_create_pointcloud_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int, fp, fp,
                                                       C.c_int, C.POINTER(C.c_int)]
+        L.cvo_fe_check_stereo_paths.argtypes = [C.c_uint32]
+        L.cvo_fe_set_stereo_paths.argtypes = [vp, C.c_uint32]
+        L.cvo_fe_get_stereo_paths.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
         L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
         L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
@@ -307,6 +314,12 @@ def check_depth_gate(gate):
 def check_stereo(stereo):
     """True for a Stereo set_stereo() accepts (cvo_fe_check_stereo).  Host only."""
     return lib().cvo_fe_check_stereo(C.byref(stereo)) == 0
+
+
+def check_stereo_paths(mask):
+    """True for a path mask set_stereo_paths() accepts (cvo_fe_check_stereo_paths): 1 <= mask <= 0xFF.  Host only."""
+    mask = int(mask)
+    return 0 <= mask <= 0xFFFFFFFF and lib().cvo_fe_check_stereo_paths(mask) == 0
 
 
 def stereo_depth_table(stereo, fx, depth_scale):
@@ -497,6 +510,21 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_stereo(self._h, C.byref(out), C.byref(isset)), "get_stereo")
         return out if isset.value else None
 
+    def set_stereo_paths(self, mask):
+        """The path mask of the matcher for every following stereo frame (step 4 of the stereo contract): PATHS_4 (a new
+        object's), PATHS_8, or any non-empty subset of the eight bits; one launch per path.  A setting of its own: it
+        may be made with or without stereo set and survives set_stereo()."""
+        mask = int(mask)
+        if not 0 <= mask <= 0xFFFFFFFF:
+            raise capi.CvoHipError("set_stereo_paths: a mask of 32 bits at the most")
+        self._chk(lib().cvo_fe_set_stereo_paths(self._h, mask), "set_stereo_paths")
+
+    def stereo_paths(self):
+        """The path mask in force."""
+        out = C.c_uint32(0)
+        self._chk(lib().cvo_fe_get_stereo_paths(self._h, C.byref(out)), "get_stereo_paths")
+        return int(out.value)
+
     def set_stereo_rig(self, rig):
         """A StereoRig for every following frame: submit_stereo / create_pointcloud_stereo then take the RAW pair and
         both images are rectified on the device in front of the matcher (the rig contract of include/cvo_frontend.h);
@@ -601,12 +629,13 @@ def load_img(rgb_path, depth_path):
 
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
-               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None):
+               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
     pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
     `stereo_rig`: a StereoRig for the generator, beside `stereo`: the pairs are then RAW and are rectified on the
     device (`dataset_seq` is ignored: the rig is the camera); None leaves the generator as it is.
+    `stereo_paths`: a path mask for the generator's matcher (PATHS_4, PATHS_8, ...); None leaves the generator as it is.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -640,6 +669,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_stereo(stereo)
     if stereo_rig is not None:
         gen.set_stereo_rig(stereo_rig)
+    if stereo_paths is not None:
+        gen.set_stereo_paths(stereo_paths)
     submit = gen.submit_stereo if stereo is not None else gen.submit
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype)
@@ -692,12 +723,12 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                         stereo_rig=None):
+                         stereo_rig=None, stereo_paths=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
-    image_02 / image_03 with the rig of its calib_cam_to_cam.txt)."""
+    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`: as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -712,4 +743,5 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
             yield name, colour(os.path.join(folder, left, "%06d.png" % k)), colour(os.path.join(folder, right, "%06d.png" % k))
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
-                      depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig)
+                      depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
+                      stereo_paths=stereo_paths)

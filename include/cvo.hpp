@@ -141,6 +141,10 @@ class registration {
     // camera of the frame (the contract: cvo_frontend.h; cvo_fe_stereo_rectify makes a rig from a calibration).  After
     // set_stereo(); throws for a rig the front end refuses, without stereo settings and beside a camera model.  While
     // a rig is set set_camera() and clear_stereo() throw.  clear_stereo_rig(): rectified pairs again.
+    // The matcher's path mask: cvo_fe_set_stereo_paths (CVO_FE_PATHS_4, a new object's; CVO_FE_PATHS_8; any non-empty
+    // subset of the eight bits; one launch per path).  A setting of its own beside set_stereo(): with or without
+    // stereo settings, before or after the first image; throws for a mask the front end refuses.
+    void set_stereo_paths(unsigned mask);
     void set_stereo_rig(const cvo_fe_stereo_rig &rig);
     void clear_stereo_rig();
     void set_pcd_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
@@ -177,6 +181,7 @@ class registration {
     bool have_stereo_;
     cvo_fe_stereo_rig stereo_rig_;       // what set_stereo_rig() gave, likewise
     bool have_stereo_rig_;
+    uint32_t stereo_paths_;              // what set_stereo_paths() gave, likewise (CVO_FE_PATHS_4 without a call)
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();

@@ -239,7 +239,7 @@ typedef struct cvo_fe_depth_gate {
  *
  * THE STEREO CONTRACT.  While stereo is set a frame is a left and a right colour image of the
  * context's size (cvo_fe_submit_stereo); the left one is the colour image of every later stage, and a
- * semi-global matcher (census cost, four paths) fills the depth plane that an uploaded depth image
+ * semi-global matcher (census cost, four to eight paths) fills the depth plane that an uploaded depth image
  * fills otherwise -- the input of the gate, if one is set, and of level 0.  The pair must be rectified:
  * a match for left pixel (x, y) is looked for at right pixel (x - d, y) only.  The results are defined by
  * the integer arithmetic below, not by the device.  It is this library's own definition, NOT pinned
@@ -249,13 +249,20 @@ typedef struct cvo_fe_depth_gate {
  *      neighbour's coordinates clamped to the image; each comparison appends one bit at the low end,
  *      c = (c << 1) | (grey(n) < grey(centre)): 62 bits in a uint64.
  *   3. Cost.  C(x, y, d) = popcount(cL(x, y) ^ cR(x - d, y)) for x - d >= 0, and 64 otherwise.
- *   4. Paths.  Four directions r: left to right, right to left, top to bottom, bottom to top.  The first
- *      pixel of a path has L_r = C.  After that
+ *   4. Paths.  Eight directions r = (rx, ry), numbered as the bits of a path mask (cvo_fe_set_stereo_paths;
+ *      CVO_FE_PATHS_4 = 0x0F, bits 0 to 3, unless the caller chooses another):
+ *          bit 0 (+1, 0) left to right      bit 4 (+1, +1) towards lower right
+ *          bit 1 (-1, 0) right to left      bit 5 (-1, -1) towards upper left
+ *          bit 2 (0, +1) top to bottom      bit 6 (-1, +1) towards lower left
+ *          bit 3 (0, -1) bottom to top      bit 7 (+1, -1) towards upper right
+ *      A pixel p whose p - r = (x - rx, y - ry) lies outside the image is the first pixel of its path and has
+ *      L_r = C; for a diagonal that happens on two borders (x = 0 or y = 0 for bit 4).  After that
  *          L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + p1, L_r(p-r, d+1) + p1, m + p2) - m,
  *          m = min over k of L_r(p-r, k);
- *      terms whose d-1 or d+1 lies outside [0, D) are left out.  S = sum over r of L_r; with p2 <= 255 it
- *      is at most 4 * (64 + 255), so uint16 holds it, and being integer it does not depend on the order in
- *      which the paths are added.
+ *      terms whose d-1 or d+1 lies outside [0, D) are left out.  S = sum of L_r over the directions whose bit is
+ *      set; with n bits set and p2 <= 255 it is at most n * (64 + 255) <= 8 * 319 = 2552, so uint16 holds it, and
+ *      being integer it does not depend on the order in which the paths are added.  Under a mask of one bit S is
+ *      that direction's L_r.
  *   5. Winner.  d* = argmin over d of S(p, d), the smallest d on ties; S1 = S(p, d*).
  *   6. Uniqueness.  S2 = min of S(p, d) over |d - d*| > 1.  UNIQUE iff such a d exists and
  *      S2 * (100 - uniqueness) < S1 * 100.
@@ -271,7 +278,8 @@ typedef struct cvo_fe_depth_gate {
  *      U(q) up.  DEPTH iff the pixel has no other flag and U(q) == 0.
  *  10. Output.  STEREO(p) is the OR of the flags; DISPARITY(p) = STEREO(p) ? 0 : q; the depth plane gets
  *      STEREO(p) ? 0 : U(q).
- * Diagonal paths, hole filling and a median filter are not part of it; a pair that is not rectified goes in
+ * Diagonal paths are part of it where the path mask names them; hole filling and a median filter are not; what the
+ * diagonals are worth in accuracy on real pairs is not measured.  A pair that is not rectified goes in
  * with its rig (cvo_fe_set_stereo_rig, the rig contract below). */
 typedef struct cvo_fe_stereo {
     float   baseline;      /* metres between the two cameras; > 0 */
@@ -469,6 +477,16 @@ int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride);
 int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st);
 /* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_stereo(const cvo_fe_ctx *ctx, cvo_fe_stereo *out, int *set);
+/* The path mask of step 4 of the stereo contract: bit b set, direction b is summed into S.  Any non-empty subset
+ * of the eight bits is accepted: a caller pays one launch per path and may want a subset, and under a mask of one
+ * bit CVO_FE_STAGE_SGM_SUM is that direction's L_r alone. */
+enum { CVO_FE_PATHS_4 = 0x0F, CVO_FE_PATHS_8 = 0xFF };
+/* The mask is a setting of the context, like num_want: a new context has CVO_FE_PATHS_4; it may be set with or
+ * without stereo set, survives cvo_fe_set_stereo (settings or NULL) and changes of the rig, is read by stereo frames
+ * only and takes no memory.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame
+ * submitted and not collected; a mask cvo_fe_check_stereo_paths refuses. */
+int cvo_fe_set_stereo_paths(cvo_fe_ctx *ctx, uint32_t mask);
+int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask);
 /* cvo_fe_submit / cvo_fe_create_pointcloud for a stereo pair: `left` and `right` are height rows of
  * width*3 bytes each, as `img` there (a caller whose right image is grey replicates it); the left image
  * is the colour image of the frame.  CVO_HIP_ERR_INVALID without stereo set.  collect, collect_device,
@@ -523,6 +541,8 @@ int cvo_fe_check_depth_gate(const cvo_fe_depth_gate *gate);
  * of 8 in [8, 128]; min_disp < 1; not 1 <= p1 <= p2 <= 255; uniqueness outside [0, 99]; lr_max outside
  * [-1, 8]; pad_ != 0.  The one statement of what is accepted.  Host only. */
 int cvo_fe_check_stereo(const cvo_fe_stereo *st);
+/* CVO_HIP_OK for a path mask cvo_fe_set_stereo_paths() would accept on an idle context: 1 <= mask <= 0xFF.  Host only. */
+int cvo_fe_check_stereo_paths(uint32_t mask);
 /* U(q) of the stereo contract for q = 0 .. 16*max_disp - 1.  Host only.  CVO_HIP_ERR_INVALID for a null
  * pointer, settings cvo_fe_check_stereo refuses, and fx or depth_scale not finite or <= 0. */
 int cvo_fe_stereo_depth_table(const cvo_fe_stereo *st, float fx, float depth_scale, uint16_t *out);
