@@ -13,6 +13,14 @@
  * as called from cvo::set_pcd (ref src/cvo.cpp:318-341, feature type 1) and
  * acvo::set_pcd (ref src/adaptive_cvo.cpp:440-463, feature type 0).
  *
+ * The selector is held to the reference's own code: thirdparty/PixelSelector2.cpp,
+ * compiled as it lies, gives the thresholds, the map, the count, the potential and the
+ * re-selection of this library bit for bit, for budgets from 1 to 10^6
+ * (tests/test_gpu_selector_ref.py).  One read of the reference is undefined and is
+ * defined here: a pixel whose threshold cell (x>>5) + (y>>5)*(w/32) lies past the
+ * (w/32)*(h/32) cells that exist (any w % 32 > 5 or h % 32 > 3, 1280x720 among them)
+ * takes the last cell's threshold; the reference reads memory it never wrote.
+ *
  * Every stage runs as HIP kernels on the context's stream; the images are
  * copied in, the cloud is copied out.  There is no CPU path: without a gfx950
  * device cvo_fe_create() fails with CVO_HIP_ERR_NODEVICE.

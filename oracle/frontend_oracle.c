@@ -4,9 +4,15 @@
  * TEST INFRASTRUCTURE ONLY.  Nothing in the product path may call this; it is the
  * checker the HIP front end (cvo-rgbd_amd/csrc/cvo_frontend.hip) is compared with.
  *
- * PARITY UNPINNED: the reference has no tests or vectors for this path, its build
- * needs OpenCV / Eigen / PCL (absent here), and no RGB-D frame ships with it.  The
- * parts the reference writes itself are restated line by line:
+ * PARITY UNPINNED for the image stages: the reference has no tests or vectors for this
+ * path, its build needs OpenCV / Eigen / PCL (absent here), and no RGB-D frame ships
+ * with it.  PINNED: the pixel selector (fe_cell_thresholds, fe_select, fe_make_maps).
+ * The reference's own thirdparty/PixelSelector2.cpp compiles against a few stand-in
+ * headers (ref_shim/, ref_selector_harness.cpp, `make ref`), and these functions equal
+ * it bit for bit -- thresholds, map, count, potential, re-selection -- on the cases of
+ * tests/selector_ref_cases.py (tests/test_selector_ref_cpu.py; recorded results in
+ * tests/golden/selector_ref.json for a checkout without the reference).
+ * The parts the reference writes itself are restated line by line:
  *   pyramid + gradients      ref cpp/rkhs_registration/src/pcd_generator.cpp:33-129
  *   selection + Canny top-up ref src/pcd_generator.cpp:131-176
  *   back-projection          ref src/pcd_generator.cpp:233-327
@@ -20,7 +26,12 @@
  *
  * Where the reference reads memory it never wrote (gradients of the first / last
  * image row, `new[]` without a fill, ref src/pcd_generator.cpp:43-44,96) this
- * restatement reads zeros.
+ * restatement reads zeros.  One more such read is the selector's: a pixel with
+ * (xf>>5) == w/32 or (yf>>5) == h/32 indexes thsSmoothed past the (w/32)*(h/32) cells
+ * makeHists wrote, into the never-written slack of its new[] (any w % 32 > 5 or
+ * h % 32 > 3: 1280x720, not 640x480).  There the reference's result is indeterminate;
+ * this restatement and the kernels read the LAST cell (fe_select), and with its slack
+ * filled that way the reference gives the same map.
  */
 #include <math.h>
 #include <stdint.h>
@@ -131,11 +142,10 @@ static int fe_hist_quantile(const int *hist, float below)
 }
 
 /* ref thirdparty/PixelSelector2.cpp:70-136: per 32x32 cell the median gradient
- * magnitude + 7, then the squared 3x3 mean.  ths_smoothed: (w/32)*(h/32) floats. */
-void fe_thresholds(const float *ag0, int w, int h, float *ths_smoothed)
+ * magnitude + 7 (ths), then the squared 3x3 mean (ths_smoothed); (w/32)*(h/32) floats each. */
+void fe_cell_thresholds(const float *ag0, int w, int h, float *ths, float *ths_smoothed)
 {
     const int w32 = w / 32, h32 = h / 32;
-    float *ths = (float *)calloc((size_t)w32 * h32 + 1, sizeof(float));
     for (int y = 0; y < h32; ++y)
         for (int x = 0; x < w32; ++x) {
             int hist[50];
@@ -169,6 +179,12 @@ void fe_thresholds(const float *ag0, int w, int h, float *ths_smoothed)
             num++; sum += ths[x + y * w32];
             ths_smoothed[x + y * w32] = (sum / num) * (sum / num);
         }
+}
+
+void fe_thresholds(const float *ag0, int w, int h, float *ths_smoothed)
+{
+    float *ths = (float *)calloc((size_t)(w / 32) * (h / 32) + 1, sizeof(float));
+    fe_cell_thresholds(ag0, w, h, ths, ths_smoothed);
     free(ths);
 }
 
@@ -237,9 +253,9 @@ static void fe_select(const float *ag0, const float *ag1, const float *ag2, cons
 /* ref thirdparty/PixelSelector2.cpp:137-236 (one recursion allowed, thFactor 1,
  * a selector starts every frame at potential 3, ref :39 and pcd_generator.cpp:140).
  * Returns the number of pixels left in the map; *pot_used the potential of the
- * pass that produced it. */
+ * pass that produced it, *num_have_out what that pass kept before the sub-sampling. */
 int fe_make_maps(const float *ag0, const float *ag1, const float *ag2, const float *ths, const uint8_t *pattern,
-                 int w, int h, float density, float *map_out, int *pot_used)
+                 int w, int h, float density, float *map_out, int *pot_used, int *num_have_out)
 {
     int pot = 3, recursions = 1;
     float numHave, quotia;
@@ -266,6 +282,7 @@ int fe_make_maps(const float *ag0, const float *ag1, const float *ag2, const flo
     }
     if (pot_used) *pot_used = pot;
     int numHaveSub = (int)numHave;
+    if (num_have_out) *num_have_out = numHaveSub;
     if ((double)quotia < 0.95) {
         const unsigned char charTH = (unsigned char)(255 * quotia);
         int rn = 0;
@@ -427,7 +444,7 @@ int fe_create_pointcloud(const uint8_t *img, const uint16_t *depth, int w, int h
     fe_thresholds(ag[0], w, h, ths);
     fe_random_pattern((int)np, pattern);
     int pot = 0;
-    const int num_selected = fe_make_maps(ag[0], ag[1], ag[2], ths, pattern, w, h, (float)num_want, map, &pot);
+    const int num_selected = fe_make_maps(ag[0], ag[1], ag[2], ths, pattern, w, h, (float)num_want, map, &pot, NULL);
     if (num_selected < num_want / 3) fe_canny_topup(gray, w, h, map);
     float cam[5];
     fe_camera(dataset_seq, cam);

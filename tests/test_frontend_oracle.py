@@ -2,7 +2,9 @@
 known answers of the definitions it restates, the host-only entry points of
 include/cvo_frontend.h, and the file side of the drivers.  PARITY UNPINNED for the
 image stages (no OpenCV, no frames in the reference tree); the random pattern IS
-pinned: the product's restated generator against the C library's rand()."""
+pinned: the product's restated generator against the C library's rand().  So is the
+pixel selector, in a file of its own: tests/test_selector_ref_cpu.py holds the oracle's
+thresholds and maps to the reference's own PixelSelector2.cpp, compiled where it lies."""
 import ctypes
 import os
 import re

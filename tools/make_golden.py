@@ -12,6 +12,11 @@ only: needs /root/reference; the outputs are DATA and are committed).
                          relative poses (groundtruth.txt) -- soft references
   oracle_traces.json     per-iteration traces of the oracle itself (regression
                          pins; NOT reference-derived)
+  selector_ref.json      (`--selector` writes this file alone) what the REFERENCE'S
+                         OWN pixel selector (oracle/_ref/libselector_ref.so) gives on
+                         every case and budget of tests/selector_ref_cases.py:
+                         SHA-256 of ths, thsSmoothed and the map, the count, the
+                         potential used and the re-selection flag
 """
 import hashlib
 import io
@@ -145,11 +150,38 @@ def oracle_traces(cl):
         json.dump(out, fh)
 
 
+def selector_ref():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import selector_ref_cases as sc
+    import test_selector_ref_cpu as t
+    from oracle import pyoracle_fe as fo
+    if fo.ref_selector_lib() is None:
+        raise SystemExit("oracle/_ref not built (make -C oracle ref)")
+    pkg = ge.load_package()
+    runs, shas = {}, {}
+    for c in sc.CASES:
+        planes = t.planes_of(pkg, c)
+        shas[c.name] = digest(*planes)
+        for b in c.budgets:
+            runs["%s/%d" % (c.name, b)] = t.record(fo.ref_make_maps(*planes, b, sc.define_unwritten(c)))
+    with open(os.path.join(OUT, "selector_ref.json"), "w") as fh:
+        json.dump(dict(note="per case/num_want: the reference's thirdparty/PixelSelector2.cpp (makeHists + makeMaps on a "
+                            "fresh selector) on the oracle's squared-gradient planes of the case's frame, through "
+                            "oracle/ref_selector_harness.cpp (planes: SHA-256 of the three planes in turn); cases not of the raw group with the threshold cells the "
+                            "reference never wrote defined as the last cell",
+                       planes=shas, runs=runs), fh, indent=0, sort_keys=True)
+    print("selector_ref.json: %d runs" % len(runs))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
+    if "--selector" in sys.argv:
+        selector_ref()
+        sys.exit(0)
     cl = clouds()
     if "--skip-sets" not in sys.argv:
         nanoflann_sets(cl)
     matlab_and_mocap()
     oracle_traces(cl)
+    selector_ref()
     print("golden fixtures written to", OUT)
