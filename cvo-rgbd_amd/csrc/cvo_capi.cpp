@@ -916,6 +916,9 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     else if (is("async_builds_named")) *value = (double)ctx->async_stats[0];
     else if (is("async_stalls")) *value = (double)ctx->async_stats[1];
     else if (is("run_aborts")) *value = (double)ctx->run_aborts;
+    else if (is("engine_begins")) *value = (double)ctx->engine_begins;
+    else if (is("engine_final_mirrored")) *value = (double)ctx->engine_final_mirrored;
+    else if (is("engine_final_copied")) *value = (double)ctx->engine_final_copied;
     else if (is("no_run_backoff")) *value = ctx->no_run_backoff;
     else return CVO_HIP_ERR_INVALID;
     return CVO_HIP_OK;

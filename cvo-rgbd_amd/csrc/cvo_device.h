@@ -944,6 +944,14 @@ struct PrepareInit {
     int32_t iter, n_fixed, done;
     float center[3], xmax, y0max;
 };
+// One registration of a batched prepare (an engine's registrations of one pump: block b of k_prepare_many prepares entry b); they travel
+// by value in groups of MAXG, as the argument blocks of the post kernels do
+struct PrepareEntry {
+    DevState *st;
+    DevParams prm;
+    PrepareInit init;
+};
+static_assert(sizeof(Grp<PrepareEntry>) + 16 <= 4096, "a group of prepare entries and the masks' address must fit the kernel arguments");
 // A kept list as a PROC_FLOW pass recorded it, for the passes that stream it back outside the loop (the pose queries): the
 // fields of the recording pass's ProcessArgs, filled by kept_view (cvo_plan.cpp), read through kept_slice / kept_entry below.
 struct KeptView {
@@ -1244,6 +1252,9 @@ struct ScanArgs {
 void launch_pose_scan(const ScanArgs &a, int weight, hipStream_t s);
 
 void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t *build_masks = nullptr, const PrepareInit *init = nullptr);
+// n registrations that begin (or resume) in one table: ceil(n / MAXG) launches, a block per registration; the first block of
+// every launch sets the table's build masks
+void launch_prepare_many(const PrepareEntry *e, int n, hipStream_t s, uint32_t *build_masks);
 void launch_filter(const FilterArgs &a, dim3 grid, hipStream_t s, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);
 void launch_process(int mode, const ProcessArgs &a, hipStream_t s, hipEvent_t ev_start = nullptr,

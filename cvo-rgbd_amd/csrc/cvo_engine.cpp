@@ -91,6 +91,7 @@ struct Engine {
     struct Retire { hipEvent_t ev = nullptr; std::vector<AlignJob *> jobs; };
     std::vector<Retire> retiring;          // their final state is on its way to the host
     hipEvent_t ev[4] = {};
+    std::vector<PrepareEntry> prep;        // registrations that took a slot in this pump: prepared by ONE launch (flush_prepare)
     long long launched = 0, checked = 0;   // batches
     int zdim = 0;
     bool crowded = true, use_graph = true, dirty = true, failed = false;
@@ -103,7 +104,7 @@ struct Engine {
     struct FlowEv { hipEvent_t a, b; int live; };
     std::vector<FlowEv> flow_ev;           // engine profiling: one pair per flow-pass launch
     // diagnostics (CVO_HIP_ENGINE_DEBUG)
-    long long n_batches[5] = {}, n_replans = 0, n_inserts = 0, n_sends = 0;
+    long long n_batches[5] = {}, n_replans = 0, n_inserts = 0, n_sends = 0, n_prepares = 0, n_mirrored = 0, n_copied = 0;
     double t_replan = 0, t_insert = 0, t_launch = 0, t_finish = 0, t_wait = 0, t_collect = 0, t_idle_at = 0;
     static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -155,13 +156,32 @@ struct Engine {
         retiring.clear();
         for (AlignJob *j : pending) { j->rc = fail(j->ctx, CVO_HIP_ERR_HIP, msg); j->phase = 2; }
         pending.clear();
+        prep.clear();
         for (int z = 0; z < ENGINE_SLOTS; ++z) slot[z].active = 0;
         (void)tab.sync(slot, s, 0);
         (void)hipStreamSynchronize(s);
         launched = checked = 0;
     }
 
-    // a job takes slot z: its align() begins (or resumes after its lists grew) on this stream
+    // The registrations that took a slot since the last flush are prepared: one launch (per MAXG of them), a block each, in stream
+    // order behind whatever their insert queued (a resuming registration's `done` word) and in front of the next batch.
+    // THE TABLE'S BUILD MASKS (every bit up = every slot may have every list to build) are set by whichever of two things happens:
+    //   * a registration begins or resumes in the table: the first block of this launch sets them -- this also covers the slot whose
+    //     image did not change (the same context with the same buffers takes the slot it had: tab.sync finds nothing to send and
+    //     returns without arming);
+    //   * the table changes without anybody beginning (a member left, slots moved down, the plan's arguments changed): tab.sync
+    //     sends a copy and arms behind it.
+    // Both are ordered on this stream in front of the batch that reads the masks.
+    int flush_prepare()
+    {
+        if (prep.empty()) return CVO_HIP_OK;
+        launch_prepare_many(prep.data(), (int)prep.size(), s, tab.masks());
+        n_prepares += ((long long)prep.size() + MAXG - 1) / MAXG;
+        prep.clear();
+        return hipGetLastError() == hipSuccess ? CVO_HIP_OK : CVO_HIP_ERR_HIP;
+    }
+
+    // a job takes slot z: its align() begins (or resumes after its lists grew) on this stream; its prepare waits in `prep`
     int insert(AlignJob *j, int z)
     {
         cvo_hip_ctx *c = j->ctx;
@@ -177,15 +197,24 @@ struct Engine {
                                sizeof(zero), hipMemcpyHostToDevice, s) != hipSuccess)
                 rc = fail(c, CVO_HIP_ERR_HIP, "resume failed");
             *c->done_mirror = 0;
-            launch_prepare(c->st, loop_params(c), s, tab.masks());   // (the lists are built anew: the build masks' bits up)
+            PrepareEntry e{};   // (init.on = 0: the state is in place; the lists are built anew)
+            e.st = c->st;
+            e.prm = loop_params(c);
+            if (!rc) prep.push_back(e);
             j->phase = 0;
         } else {
-            rc = job_begin(*j);
+            PrepareEntry e{};
+            rc = job_begin(*j, &e);
+            if (!rc) prep.push_back(e);
         }
         if (rc) { finish_job(j, rc); return rc; }
-        if (j->phase != 0) {   // max_iter <= 0: nothing to run; the state copy is already queued
+        ++c->engine_begins;
+        if (j->phase != 0) {   // max_iter <= 0: nothing to run; its state comes back by a copy behind its prepare
             Retire r;
-            if (hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(r.ev, s) != hipSuccess) {
+            if (flush_prepare() != CVO_HIP_OK ||
+                hipMemcpyAsync(&c->st_host[0], c->st, sizeof(DevState), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(r.ev, s) != hipSuccess) {
+                if (r.ev) (void)hipEventDestroy(r.ev);
                 finish_job(j, fail(c, CVO_HIP_ERR_HIP, "event failed"));
                 return CVO_HIP_ERR_HIP;
             }
@@ -195,8 +224,7 @@ struct Engine {
         }
         member[z] = j;
         ops[z].clear();
-        dirty = true;
-        (void)tab.arm(s);   // (a registration begins: everything is built; the replan that follows arms again with its copy)
+        dirty = true;   // (the build masks: flush_prepare)
         return CVO_HIP_OK;
     }
 
@@ -252,16 +280,31 @@ struct Engine {
         return CVO_HIP_OK;
     }
 
-    // members whose loop has stopped leave their slots; their final state starts for the host
+    // Members whose loop has stopped leave their slots.  With a verdict the final head is in the context's pinned copy already, written
+    // by the post-step kernel in front of the `done` word (PostStepArgs::final_mirror, as for a registration on its own: job_pump): the
+    // registration is handed back at once, with no copy and no event behind the batches that are queued.  A loop that parked because a
+    // list overflowed (NEED_BIGGER_LIST: finish_arrived needs the counters of the state's tail), one that ended without a verdict,
+    // and a pinned copy that does not check out start the whole state for the host as ever.
     void collect_stopped()
     {
         Retire r;
         for (int z = 0; z < ENGINE_SLOTS; ++z) {
             AlignJob *j = member[z];
-            if (!j || *(volatile int32_t *)j->ctx->done_mirror == RUNNING) continue;
-            if (hipMemcpyAsync(&j->ctx->st_host[0], j->ctx->st, sizeof(DevState), hipMemcpyDeviceToHost, s) != hipSuccess) {
+            if (!j) continue;
+            cvo_hip_ctx *c = j->ctx;
+            const int32_t verdict = *(volatile int32_t *)c->done_mirror;
+            if (verdict == RUNNING) continue;
+            const bool mirrored = (verdict == DONE_BREAK_A || verdict == DONE_BREAK_B || verdict == DONE_MAX_ITER) && c->final_mirror &&
+                                  !c->opt.no_final_mirror && !multi_rank(c);   // (what enqueue_step goes by)
+            if (mirrored && take_final_mirror(c, verdict)) {
+                ++n_mirrored;
+                ++c->engine_final_mirrored;
+                finish_job(j, job_finish(*j));
+            } else if (hipMemcpyAsync(&j->ctx->st_host[0], j->ctx->st, sizeof(DevState), hipMemcpyDeviceToHost, s) != hipSuccess) {
                 finish_job(j, fail(j->ctx, CVO_HIP_ERR_HIP, "state copy failed"));
             } else {
+                ++n_copied;
+                ++c->engine_final_copied;
                 r.jobs.push_back(j);
             }
             member[z] = nullptr;
@@ -360,14 +403,22 @@ struct Engine {
             moved = true;
         }
         { const double t0 = now_ms(); if (finish_arrived(pending, false)) moved = true; t_finish += now_ms() - t0; }
-        // free slots take the next registrations
-        while (!pending.empty() && live() < std::min(want, (int)ENGINE_SLOTS)) {
+        // free slots take the next registrations -- not in the call's tail: a registration that comes back then (phase 3: a list of it
+        // overflowed) would get a `done` word and a prepare queued on this stream and be handed to job_continue_alone by release_members
+        // at once, with nothing that orders the two; the caller routes it to the leavers instead (cvo_hip_align_many)
+        while (!wind_down && !pending.empty() && live() < std::min(want, (int)ENGINE_SLOTS)) {
             AlignJob *j = pending.front();
             pending.pop_front();
             int z = 0;
             while (member[z]) ++z;
             { const double t0 = now_ms(); insert(j, z); t_insert += now_ms() - t0; }
             moved = true;
+        }
+        {
+            const double t0 = now_ms();
+            const int rc = flush_prepare();
+            t_insert += now_ms() - t0;
+            if (rc) { fail_all("prepare launch failed", pending); return true; }
         }
         // batches kept queued per engine (the other engines fill the gap between two batches of this one)
         constexpr long long depth = 2;   // (one batch queued per engine instead of two: -17 %, profiles/r02_ab.txt)
@@ -482,13 +533,13 @@ void engine_release(Engine *e)
     std::lock_guard<std::mutex> lock(*engine_mutex());
     if (engine_debug_on())
         fprintf(stderr, "[cvo_hip] engine %p: batches at zdim 1/2/4/8/16: %lld %lld %lld %lld %lld, replans %lld, "
-                "graph captures %lld hits %lld; host ms: insert %.2f replan %.2f launch %.2f collect %.2f finish %.2f wait %.2f\n",
+                "prepare launches %lld, final states mirrored %lld copied %lld, graph captures %lld hits %lld; host ms: insert %.2f replan %.2f launch %.2f collect %.2f finish %.2f wait %.2f\n",
                 (void *)e, e->n_batches[0], e->n_batches[1], e->n_batches[2],
-                e->n_batches[3], e->n_batches[4], e->n_replans, e->plans.captures, e->plans.hits,
+                e->n_batches[3], e->n_batches[4], e->n_replans, e->n_prepares, e->n_mirrored, e->n_copied, e->plans.captures, e->plans.hits,
                 e->t_insert, e->t_replan, e->t_launch, e->t_collect, e->t_finish, e->t_wait);
     e->t_insert = e->t_replan = e->t_launch = e->t_collect = e->t_finish = e->t_wait = 0;
     for (long long &v : e->n_batches) v = 0;
-    e->n_replans = 0;
+    e->n_replans = e->n_prepares = e->n_mirrored = e->n_copied = 0;
     e->launched = e->checked = 0;
     e->in_use = false;
 }
@@ -630,6 +681,13 @@ int cvo_hip_align_many(cvo_hip_ctx **ctxs, cvo_hip_state **states, int *n_iters,
                         if (leavers.size() != before) {
                             moved = true;
                             if (dbg_many) fprintf(stderr, "[cvo_hip]   tail: %zu registrations leave engine %p after %.2f ms\n", leavers.size() - before, (void *)e, Engine::now_ms() - t_many0);
+                        }
+                        // (the queue was empty when the tail began: whatever is in it now came back from an engine with a list to
+                        // grow -- finish_arrived, phase 3.  No engine takes it any more; it goes on alone with the others.)
+                        while (!pending.empty()) {
+                            leavers.push_back(pending.front());
+                            pending.pop_front();
+                            moved = true;
                         }
                     }
                     if (e->pump(pending, share)) moved = true;

@@ -291,6 +291,9 @@ struct cvo_hip_ctx {
     int no_run_backoff = 0;              // registrations to go without resident runs (one of them timed out, job_pump)
     long long side_builds_launched = 0;  // side builds launched by this context ("side_builds_launched")
     long long tail_handovers = 0;        // times this context's registration left an engine for runs of its own ("tail_handovers")
+    long long engine_begins = 0;         // registrations of this context that began or resumed in an engine's slot ("engine_begins")
+    long long engine_final_mirrored = 0; // ... and that an engine handed back from the pinned final head / after a copy of the whole
+    long long engine_final_copied = 0;   // state in stream order ("engine_final_mirrored", "engine_final_copied")
     long long run_aborts = 0;            // resident runs of this context that gave up at their entry hand-shake ("run_aborts")
     int list_stats[3] = {0, 0, 0};       // the last registration's all-pairs xy builds, narrowings, re-expansions (cvo_hip_get_list_stats)
     int async_stats[2] = {0, 0};         // ... and the asynchronous plans' xy builds named and stall slots (cvo_hip_get_option "async_builds_named", "async_stalls")
@@ -495,7 +498,8 @@ int fetch_red(cvo_hip_ctx *ctx, int off, int count, double *out);
 // ---- cvo_job.cpp
 void decide_scheme(cvo_hip_ctx *ctx);
 std::atomic<long long> &mirror_retries();
-int job_begin(AlignJob &j);
+int job_begin(AlignJob &j, PrepareEntry *defer = nullptr);
+bool take_final_mirror(cvo_hip_ctx *ctx, int32_t verdict);
 int job_finish(AlignJob &j);
 int job_continue_alone(AlignJob &j);
 int job_pump(AlignJob &j, bool block);

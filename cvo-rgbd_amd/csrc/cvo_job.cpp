@@ -52,7 +52,33 @@ std::atomic<long long> &mirror_retries()
     return n;
 }
 
-int job_begin(AlignJob &j)
+// The final head of a loop that stopped with `verdict`, from the pinned copy the post-step kernel wrote in front of the `done` word
+// (PostStepArgs::final_mirror) into st_host[0]: everything job_finish reads.  False: the copy did not check out within ~50 us -- the
+// caller fetches the state by a copy in stream order.
+bool take_final_mirror(cvo_hip_ctx *ctx, int32_t verdict)
+{
+    // (the check word: a piece of the copy that has not landed yet -- seen on this platform although the device fences
+    // at system scope between the copy and the `done` word -- is a retry)
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        std::atomic_thread_fence(std::memory_order_acquire);
+        std::memcpy(&ctx->st_host[0], ctx->final_mirror, sizeof(DevHead));
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(&ctx->st_host[0]);
+        constexpr int pieces = (int)(sizeof(DevHead) / 16);
+        uint32_t sum = 0;
+        for (int q = 0; q < pieces; ++q)
+            sum += head_check_mix(w[4 * q], q == pieces - 1 ? 0u : w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], (unsigned)q);
+        if (ctx->st_host[0].done == verdict && sum == (uint32_t)ctx->st_host[0].head_check_) return true;
+        mirror_retries().fetch_add(1, std::memory_order_relaxed);
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(50)) return false;
+        __builtin_ia32_pause();
+    }
+}
+
+// `defer` (a member of an engine, cvo_engine.cpp): the host half only -- the mirrors, the trace buffer, the filter's geometry, the scheme,
+// the buffers and the job's counters.  What the prepare kernel needs goes to *defer: the engine prepares the registrations of one pump
+// in one launch, and a registration with nothing to run (max_iter <= 0, phase 1) gets its state copy from the engine, behind that launch.
+int job_begin(AlignJob &j, PrepareEntry *defer)
 {
     cvo_hip_ctx *ctx = j.ctx;
     cvo_hip_state *s = j.s;
@@ -104,10 +130,16 @@ int job_begin(AlignJob &j)
         in.done = p.max_iter <= 0 ? DONE_MAX_ITER : RUNNING;
     }
     decide_scheme(ctx);
-    // (a member of a fused group: the group's table, armed by its insert; on its own: this context's table, whose build masks the
-    // prepare kernel sets -- it exists from the first align() on, and its first use arms it anyway)
-    launch_prepare(ctx->st, loop_params(ctx), loop_stream(ctx), (!j.in_group && ctx->table.raw) ? ctx->table.masks() : nullptr, &in);
-    HIP_TRY(ctx, hipGetLastError());
+    // (a member of a fused group: the group's table, whose build masks the engine's batched prepare sets; on its own: this context's
+    // table, whose build masks the prepare kernel sets -- it exists from the first align() on, and its first use arms it anyway)
+    if (defer) {
+        defer->st = ctx->st;
+        defer->prm = loop_params(ctx);
+        defer->init = in;
+    } else {
+        launch_prepare(ctx->st, loop_params(ctx), loop_stream(ctx), (!j.in_group && ctx->table.raw) ? ctx->table.masks() : nullptr, &in);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     ctx->have_tf = true;
     const int prc = prepare_buffers(ctx);
     if (prc) return prc;
@@ -137,7 +169,7 @@ int job_begin(AlignJob &j)
     if (ctx->big_run_backoff > 0) --ctx->big_run_backoff;
     if (ctx->opt.run_cand > 0) ctx->run_nnz_max = ctx->opt.run_cand;   // (tuning switch "run_candidates_max")
     j.phase = p.max_iter <= 0 ? 1 : 0;
-    if (j.phase == 1) {
+    if (j.phase == 1 && !defer) {
         HIP_TRY(ctx, hipMemcpyAsync(&ctx->st_host[0], ctx->st, sizeof(DevState), hipMemcpyDeviceToHost,
                                     loop_stream(ctx)));
         HIP_TRY(ctx, hipEventRecord(ctx->poll_ev[0], loop_stream(ctx)));
@@ -167,6 +199,15 @@ int job_continue_alone(AlignJob &j)
     if (ctx->final_mirror) ctx->final_mirror->done = RUNNING;
     decide_scheme(ctx);
     hipStream_t s = loop_stream(ctx);
+    if (j.phase == 3) {
+        // (a list of it overflowed while the engines wound down: it left them parked with NEED_BIGGER_LIST, its lists have grown since --
+        // the engine's finish_arrived -- and its loop goes on from the iteration it parked at.  The engine's copy of its state has
+        // arrived, so nothing of the engine's stream touches the state any more.)
+        int32_t zero = 0;
+        std::memcpy(&ctx->st_host[kPollSlots].done, &zero, sizeof(zero));
+        HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<char *>(ctx->st) + offsetof(DevState, done), &ctx->st_host[kPollSlots].done, sizeof(zero),
+                                    hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(ctx, hipMemsetAsync(reinterpret_cast<char *>(ctx->st) + offsetof(DevState, n_slots), 0, sizeof(int32_t), s));
     HIP_TRY(ctx, hipMemsetAsync(reinterpret_cast<char *>(ctx->st) + offsetof(DevState, run_count), 0, 4 * sizeof(int32_t), s));
     HIP_TRY(ctx, hipMemsetAsync(reinterpret_cast<char *>(ctx->st) + offsetof(DevState, run_last_entered), 0, 2 * sizeof(int32_t), s));
@@ -396,24 +437,7 @@ int job_pump(AlignJob &j, bool block)
             const int32_t verdict = *(volatile int32_t *)ctx->done_mirror;
             const bool mirrored = (verdict == DONE_BREAK_A || verdict == DONE_BREAK_B || verdict == DONE_MAX_ITER) && ctx->final_mirror &&
                                   ctx->table.image.size() == 1 && ctx->plan_has_final_mirror;
-            if (mirrored) {
-                // (the check word: a piece of the copy that has not landed yet -- seen on this platform although the device fences
-                // at system scope between the copy and the `done` word -- is a retry; after ~50 us the copy in stream order below)
-                const auto t0 = std::chrono::steady_clock::now();
-                for (;;) {
-                    std::atomic_thread_fence(std::memory_order_acquire);
-                    std::memcpy(&ctx->st_host[0], ctx->final_mirror, sizeof(DevHead));
-                    const uint32_t *w = reinterpret_cast<const uint32_t *>(&ctx->st_host[0]);
-                    constexpr int pieces = (int)(sizeof(DevHead) / 16);
-                    uint32_t sum = 0;
-                    for (int q = 0; q < pieces; ++q)
-                        sum += head_check_mix(w[4 * q], q == pieces - 1 ? 0u : w[4 * q + 1], w[4 * q + 2], w[4 * q + 3], (unsigned)q);
-                    if (ctx->st_host[0].done == verdict && sum == (uint32_t)ctx->st_host[0].head_check_) return finish_with(job_finish(j));
-                    mirror_retries().fetch_add(1, std::memory_order_relaxed);
-                    if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(50)) break;
-                    __builtin_ia32_pause();
-                }
-            }
+            if (mirrored && take_final_mirror(ctx, verdict)) return finish_with(job_finish(j));
         }
         if (hipMemcpyAsync(&ctx->st_host[0], ctx->st, sizeof(DevState), hipMemcpyDeviceToHost,
                            ctx->stream) != hipSuccess ||

@@ -2195,7 +2195,7 @@ __global__ void __launch_bounds__(BLOCK) k_post_step(const Grp<PostStepArgs> grp
 
 // First iteration of an align() (or of its resumption after a list grew): no
 // list is valid, everything is rebuilt.
-__global__ void k_prepare(DevState *st, const DevParams prm, uint32_t *build_masks, const PrepareInit init)
+__device__ __forceinline__ void prepare_body(DevState *st, const DevParams &prm, uint32_t *build_masks, const PrepareInit &init)
 {
     if (init.on) {   // a registration begins: zeros but for what the caller carries (everything in front of the mailbox sequence number)
         static_assert(DEVSTATE_INIT_BYTES % 4 == 0, "word stores");
@@ -2239,11 +2239,35 @@ __global__ void k_prepare(DevState *st, const DevParams prm, uint32_t *build_mas
     }
 }
 
+__global__ void k_prepare(DevState *st, const DevParams prm, uint32_t *build_masks, const PrepareInit init)
+{
+    prepare_body(st, prm, build_masks, init);
+}
+
+// The registrations an engine takes in one pump (cvo_engine.cpp): block b prepares entry b; the table's build masks are set
+// once, by the first block
+__global__ void k_prepare_many(const Grp<PrepareEntry> grp, uint32_t *build_masks)
+{
+    const PrepareEntry &e = grp.a[blockIdx.x];
+    prepare_body(e.st, e.prm, blockIdx.x == 0 ? build_masks : nullptr, e.init);
+}
+
 void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t *build_masks, const PrepareInit *init)
 {
     PrepareInit in{};
     if (init) in = *init;
     hipLaunchKernelGGL(k_prepare, dim3(1), dim3(BLOCK), 0, s, st, prm, build_masks, in);
+}
+
+void launch_prepare_many(const PrepareEntry *e, int n, hipStream_t s, uint32_t *build_masks)
+{
+    for (int at = 0; at < n; at += MAXG) {
+        const int m = n - at < MAXG ? n - at : MAXG;
+        Grp<PrepareEntry> g;
+        for (int i = 0; i < m; ++i) g.a[i] = e[at + i];
+        for (int i = m; i < MAXG; ++i) g.a[i] = e[at];   // (never read: the launch has m blocks)
+        hipLaunchKernelGGL(k_prepare_many, dim3((unsigned)m), dim3(BLOCK), 0, s, g, build_masks);
+    }
 }
 
 void launch_post_flow_group(const PostFlowArgs *a, int n, hipStream_t s)

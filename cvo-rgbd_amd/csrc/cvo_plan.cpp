@@ -648,8 +648,9 @@ int enqueue_step(cvo_hip_ctx *ctx, int check_done, bool do_math, cvo_hip_trace *
         }
     }
     if (ctx->plan_recording && ctx->lone) pa.hint_mirror = ctx->hint_mirror;
-    // (one registration on its own, one rank: its final head goes to pinned memory with the verdict, job_pump)
-    if (ctx->plan_recording && ctx->lone && !multi_rank(ctx) && !ctx->opt.no_final_mirror) pa.final_mirror = ctx->final_mirror;
+    // (one rank: the final head goes to pinned memory with the verdict -- job_pump for a registration on its own, the engine's
+    // collect_stopped for a member of a fused group, which are single-rank by fusable())
+    if (ctx->plan_recording && !multi_rank(ctx) && !ctx->opt.no_final_mirror) pa.final_mirror = ctx->final_mirror;
     if (host_reduce(ctx)) {
         pa.flags = POST_REDUCE;
         emit_post_step(ctx, pa);
