@@ -205,7 +205,23 @@ int cvo_hip_range_filter_grid_average(int device, const float *xyz, const unsign
 
 /* Multi-GPU: this context owns target rows [row_lo,row_hi) of the fixed cloud
  * (and rows [srow_lo,srow_hi) of the moving cloud for the acvo Ayy sweep).
- * Default = everything. */
+ * Default = everything.
+ *
+ * Rows are rows of the cloud AS THE DEVICE HOLDS IT (Morton order after the hand-over:
+ * cvo_hip_get_device_cloud), not the caller's.  row_hi / srow_hi beyond the cloud are clamped to
+ * it, and a range that is empty after the clamp is a rank without rows: every sum of its own is
+ * exactly zero (cvo_hip_function_inner_product: NaN), and it still takes part in every exchange.
+ * The acvo Ayy SUM of a shard runs over its rows whose CALLER's index is >= n_fixed (the
+ * reference's row rule is about the cloud as it was handed over); the Ayy count is of all its rows.
+ *
+ * A shard with no exchange attached (no communicator, mailboxes or all-reduce hook): the low-level
+ * calls and the pose queries return the sums over its own rows, and cvo_hip_align registers those
+ * rows alone -- rows [row_lo, row_hi) of the fixed cloud against the WHOLE moving cloud, for acvo
+ * with Axx over the same rows and Ayy over [srow_lo, srow_hi) -- as if the other fixed rows did not
+ * exist.  It runs the plan an unsharded context runs (head mode, asynchronous builds, resident
+ * runs, engines of cvo_hip_align_many) with its filters confined to those rows, and gives the same
+ * iterations and the same state bit for bit in every form of the loop
+ * (tests/test_gpu_shard_ref.py). */
 int cvo_hip_set_shard(cvo_hip_ctx *ctx, int row_lo, int row_hi, int srow_lo, int srow_hi);
 /* Even contiguous split helper: rows of `n` owned by `rank` of `world`. */
 int cvo_hip_shard_range(int n, int rank, int world, int *lo, int *hi);

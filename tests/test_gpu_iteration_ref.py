@@ -18,6 +18,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cvo_iteration_ref as ref  # noqa: E402
 import iteration_ref_cases as ic  # noqa: E402
+from iteration_ref_judge import Ref as _Ref, check_flow as _check_flow, check_step as _check_step  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -38,65 +39,6 @@ def _params(pkg, mode, over=None):
     for key, value in (over or {}).items():
         setattr(p, key, value)
     return p
-
-
-class _Ref:
-    """The reference of one cloud pair at one length scale: its own members, the borderline pairs, the float64 weights."""
-
-    def __init__(self, p, ell, xa, fa, xb, fb):
-        self.p, self.ell, self.xa, self.xb = p, ell, xa, xb
-        self.a, _, _, margin = ref.weights(p, ell, xa, fa, xb, fb, c_sp=ic.c_sp_of(p))
-        self.rows, self.cols = ic.dense_members(p, margin)
-        sure_in, border, _ = ref.classify(margin)
-        self.sure_in, self.brows, self.bcols = int(sure_in.sum()), *np.nonzero(border)
-        self.am = self.a[self.rows, self.cols]
-
-    def count_ok(self, nnz):
-        return self.sure_in <= int(nnz) <= self.sure_in + len(self.brows)
-
-    def flow(self):
-        fl = ref.flow(self.p, self.ell, self.xa, self.xb, self.rows, self.cols, self.am)
-        tol = ic.flow_tol(self.p, fl)
-        if len(self.brows):
-            b = ref.flow(self.p, self.ell, self.xa, self.xb, self.brows, self.bcols, self.a[self.brows, self.bcols])
-            for k, s in (("omega_d", "s_omega"), ("v_d", "s_v"), ("sum_a", "s_a"), ("sum_a_d2", "s_a_d2")):
-                tol[k] = tol[k] + b[s]
-        return fl, tol
-
-    def step(self, omega, v):
-        st = ref.step_terms(self.ell, omega, v, self.xa, self.xb, self.rows, self.cols, self.am)
-        tol = ic.step_tol(self.p, st)
-        if len(self.brows):
-            tol = tol + ref.step_terms(self.ell, omega, v, self.xa, self.xb, self.brows, self.bcols,
-                                       self.a[self.brows, self.bcols])["coeff_scales"]
-        return st, tol
-
-    def self_sum(self, first_row=0):
-        """(sum (1/l^3) a d2 over the members in rows >= first_row, its tolerance): the Axx / Ayy sums of dl."""
-        keep = self.rows >= first_row
-        fl = ref.flow(self.p, self.ell, self.xa, self.xb, self.rows[keep], self.cols[keep], self.am[keep])
-        tol = ic.flow_tol(self.p, fl)["sum_a_d2"]
-        if len(self.brows):
-            tol += ref.flow(self.p, self.ell, self.xa, self.xb, self.brows, self.bcols, self.a[self.brows, self.bcols])["s_a_d2"]
-        return fl["sum_a_d2"], tol
-
-
-def _check_flow(out, R_):
-    fl, tol = R_.flow()
-    assert R_.count_ok(out[8]), (out[8], R_.sure_in, len(R_.brows))
-    assert np.all(np.abs(out[0:3] - fl["omega_d"]) <= tol["omega_d"]), (out[0:3], fl["omega_d"], tol["omega_d"])
-    assert np.all(np.abs(out[3:6] - fl["v_d"]) <= tol["v_d"]), (out[3:6], fl["v_d"], tol["v_d"])
-    assert abs(out[6] - fl["sum_a"]) <= tol["sum_a"] and abs(out[7] - fl["sum_a_d2"]) <= tol["sum_a_d2"]
-    return fl
-
-
-def _check_step(pkg, c, R_, omega, v, ell):
-    bcde = c.step_coeffs(omega, v, ell)
-    st, tol = R_.step(omega, v)
-    assert np.all(np.abs(bcde - st["bcde"]) <= tol), (bcde, st["bcde"], tol)
-    want = ic.roots_step(bcde)
-    if want is not None:
-        assert pkg.capi.pick_step(bcde) == pytest.approx(want, rel=1e-5), bcde
 
 
 @pytest.mark.parametrize("n,m", SIZES)
