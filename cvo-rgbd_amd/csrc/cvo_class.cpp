@@ -60,7 +60,7 @@ registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
-      stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4)
+      stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -91,6 +91,7 @@ void registration::apply_stored_settings()
         if (have_stereo_) fe_check(cvo_fe_set_stereo(fe_, &stereo_), "cvo_fe_set_stereo");
         if (have_stereo_rig_) fe_check(cvo_fe_set_stereo_rig(fe_, &stereo_rig_), "cvo_fe_set_stereo_rig");
         fe_check(cvo_fe_set_stereo_paths(fe_, stereo_paths_), "cvo_fe_set_stereo_paths");
+        if (have_stereo_speckle_) fe_check(cvo_fe_set_stereo_speckle(fe_, &stereo_speckle_), "cvo_fe_set_stereo_speckle");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -223,6 +224,18 @@ void registration::set_stereo_paths(unsigned mask)
         throw std::runtime_error("set_stereo_paths(): a non-empty subset of the eight bits, 1 <= mask <= 0xFF");
     if (fe_) fe_check(cvo_fe_set_stereo_paths(fe_, mask), "cvo_fe_set_stereo_paths");
     stereo_paths_ = mask;
+}
+
+void registration::set_stereo_speckle(const cvo_fe_speckle &speckle)
+{
+    if (!fe_ && cvo_fe_check_speckle(&speckle) != CVO_HIP_OK)
+        throw std::runtime_error("set_stereo_speckle(): max_size in [1, 2^26], max_diff in [0, 65535]");
+    store<cvo_fe_speckle>(cvo_fe_set_stereo_speckle, "cvo_fe_set_stereo_speckle", &speckle, stereo_speckle_, have_stereo_speckle_);
+}
+
+void registration::clear_stereo_speckle()
+{
+    store<cvo_fe_speckle>(cvo_fe_set_stereo_speckle, "cvo_fe_set_stereo_speckle", nullptr, stereo_speckle_, have_stereo_speckle_);
 }
 
 void registration::set_stereo_rig(const cvo_fe_stereo_rig &rig)

@@ -21,6 +21,7 @@
 
 #include "cvo_frontend.h"
 #include "cvo_lock.h"
+#include "cvo_speckle.h"
 #include "cvo_stereo.h"
 
 namespace {
@@ -1115,6 +1116,12 @@ struct cvo_fe_ctx {
     bool has_stereo = false;
     // the path mask (cvo_fe_set_stereo_paths): a setting of the context beside `stereo`, read by stereo frames only
     uint32_t stereo_paths = CVO_FE_PATHS_4;
+    // the speckle filter (cvo_fe_set_stereo_speckle): a setting of the context likewise; with it a stereo frame passes
+    // the kernels of cvo_speckle.hip behind k_fe_stereo_final
+    cvo_fe_speckle speckle{};
+    bool has_speckle = false;
+    // with the filter, and gone with it: parents, sums and sizes (np words each) and the count of removed pixels
+    Dev<uint32_t> speckle_words;
     // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
     // table U(q) with its staging copy; the cost sums follow max_disp
     Dev<uint8_t> right_img, right_gray, stereo_flags;
@@ -1465,6 +1472,13 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         a.min_disp = st.min_disp; a.p1 = st.p1; a.p2 = st.p2; a.uniqueness = st.uniqueness; a.lr_max = st.lr_max;
         a.paths = ctx->stereo_paths;
         fe_stereo_enqueue(a, s);
+        if (ctx->has_speckle) {   // (the speckle contract: on the plane the gate, if any, and level 0 read next)
+            FeSpeckleArgs f{};
+            f.plane = a.disparity; f.flags = a.flags; f.depth = plane;
+            f.labels = ctx->speckle_words.get(); f.sums = f.labels + np; f.sizes = f.sums + np; f.removed = f.sizes + np;
+            f.w = w; f.h = h; f.max_size = ctx->speckle.max_size; f.max_diff = ctx->speckle.max_diff;
+            fe_speckle_enqueue(f, s);
+        }
     }
     if (ctx->rectify)
         hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img.get(),
@@ -1862,6 +1876,38 @@ int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask)
     cvo_lock::Api api_guard;
     if (!ctx || !mask) return CVO_HIP_ERR_INVALID;
     *mask = ctx->stereo_paths;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_stereo_speckle(cvo_fe_ctx *ctx, const cvo_fe_speckle *sp)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_speckle: a frame is in flight");
+    if (sp && cvo_fe_check_speckle(sp) != CVO_HIP_OK)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_speckle: max_size in [1, 2^26], max_diff in [0, 65535]");
+    if (!sp && !ctx->has_speckle) return CVO_HIP_OK;
+    if (sp && ctx->has_speckle && std::memcmp(sp, &ctx->speckle, sizeof(*sp)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint32_t> words;
+    if (sp && !ctx->speckle_words && !dev_alloc(words, 3 * (size_t)ctx->np + 1))
+        return no_memory(ctx, "set_stereo_speckle: device memory for the parents, the sums and the sizes");
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->speckle_words, words);
+    if (!sp) ctx->speckle_words.reset();
+    ctx->has_speckle = sp != nullptr;
+    ctx->speckle = sp ? *sp : cvo_fe_speckle{};
+    drop_graphs(ctx);   // (whether a frame has the filter's launches, their numbers and planes are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_speckle ? ctx->speckle : cvo_fe_speckle{};
+    if (set) *set = ctx->has_speckle ? 1 : 0;
     return CVO_HIP_OK;
 }
 
@@ -2423,12 +2469,15 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_STEREO: src = ctx->stereo_flags.get(); need = np; break;
     case CVO_FE_STAGE_RIGHT_BGR: src = ctx->right_img.get(); need = np * 3; break;
     case CVO_FE_STAGE_STEREO_VALID: src = ctx->srig_valid.get(); need = np; break;
+    case CVO_FE_STAGE_SPECKLE_SIZE: src = ctx->speckle_words ? ctx->speckle_words.get() + 2 * np : nullptr; need = np * 4; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if (stage >= CVO_FE_STAGE_RIGHT_GRAY && !ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a stage of a stereo frame, and stereo is not set");
     if (stage == CVO_FE_STAGE_STEREO_VALID && !ctx->has_srig)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the validity plane of a stereo rig, and no rig is set");
+    if (stage == CVO_FE_STAGE_SPECKLE_SIZE && !ctx->has_speckle)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the sizes of the speckle filter, and no filter is set");
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");
     FE_HIP(hipSetDevice(ctx->device));
     FE_HIP(hipStreamSynchronize(ctx->stream));

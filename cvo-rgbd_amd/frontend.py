@@ -12,6 +12,7 @@ A rectified stereo pair in place of the depth image (the stereo contract of incl
     gen = PcdGenerator(width=1241, height=376)
     gen.set_stereo(Stereo(baseline=0.54, max_disp=128))
     gen.set_stereo_paths(PATHS_8)       # optional: the four diagonal paths beside rows and columns (PATHS_4 otherwise)
+    gen.set_stereo_speckle(Speckle(max_size=100, max_diff=16))   # optional: small islands of disparity give no point
     xyz, feat = gen.create_pointcloud_stereo(left, right, dataset_seq=4)
 
 A RAW pair with its rig (the rig contract of include/cvo_frontend.h): both images are rectified on the device
@@ -40,9 +41,9 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
  STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
  STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
- STAGE_STEREO_VALID) = range(23)
+ STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE) = range(24)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
-STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE = 1, 2, 4, 8, 16   # the flags of STAGE_STEREO
+STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
 
@@ -54,7 +55,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_set_mask", "cvo_fe_check_stereo", "cvo_fe_set_stereo", "cvo_fe_get_stereo", "cvo_fe_submit_stereo",
            "cvo_fe_create_pointcloud_stereo", "cvo_fe_stereo_depth_table", "cvo_fe_set_stereo_rig", "cvo_fe_get_stereo_rig",
            "cvo_fe_check_stereo_rig", "cvo_fe_stereo_rectify", "cvo_fe_stereo_rig_map", "cvo_fe_check_stereo_paths",
-           "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths")
+           "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths", "cvo_fe_check_speckle", "cvo_fe_set_stereo_speckle",
+           "cvo_fe_get_stereo_speckle", "cvo_fe_filter_speckles")
 
 
 class Info(C.Structure):
@@ -133,6 +135,16 @@ class Stereo(_Settings):
 
     def __init__(self, baseline=0.54, max_disp=64, min_disp=1, p1=8, p2=32, uniqueness=10, lr_max=1, pad_=0):
         super().__init__(baseline, int(max_disp), int(min_disp), int(p1), int(p2), int(uniqueness), int(lr_max), int(pad_))
+
+
+class Speckle(_Settings):
+    """cvo_fe_speckle: the speckle filter on the matcher's disparities (the speckle contract of include/cvo_frontend.h).
+    Components of 4-neighbours whose values differ by `max_diff` at the most (units of the plane: 1/16 pixel of a
+    disparity) and that hold `max_size` pixels at the most lose their disparity."""
+    _fields_ = [("max_size", C.c_int32), ("max_diff", C.c_int32)]
+
+    def __init__(self, max_size=100, max_diff=16):
+        super().__init__(int(max_size), int(max_diff))
 
 
 class Lens(_Settings):
@@ -249,6 +261,11 @@ def lib():
         L.cvo_fe_check_stereo_paths.argtypes = [C.c_uint32]
         L.cvo_fe_set_stereo_paths.argtypes = [vp, C.c_uint32]
         L.cvo_fe_get_stereo_paths.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.cvo_fe_check_speckle.argtypes = [C.POINTER(Speckle)]
+        L.cvo_fe_set_stereo_speckle.argtypes = [vp, C.POINTER(Speckle)]
+        L.cvo_fe_get_stereo_speckle.argtypes = [vp, C.POINTER(Speckle), C.POINTER(C.c_int)]
+        L.cvo_fe_filter_speckles.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Speckle),
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
         L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
         L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
@@ -320,6 +337,32 @@ def check_stereo_paths(mask):
     """True for a path mask set_stereo_paths() accepts (cvo_fe_check_stereo_paths): 1 <= mask <= 0xFF.  Host only."""
     mask = int(mask)
     return 0 <= mask <= 0xFFFFFFFF and lib().cvo_fe_check_stereo_paths(mask) == 0
+
+
+def check_speckle(speckle):
+    """True for a Speckle set_stereo_speckle() accepts (cvo_fe_check_speckle): max_size in [1, 2^26], max_diff in
+    [0, 65535]; None is refused.  Host only."""
+    if speckle is None:
+        return lib().cvo_fe_check_speckle(None) == 0
+    ok = all(-2 ** 31 <= int(v) < 2 ** 31 for v in (speckle.max_size, speckle.max_diff))
+    return ok and lib().cvo_fe_check_speckle(C.byref(speckle)) == 0
+
+
+def filter_speckles(plane, speckle, device=0):
+    """The speckle filter on any h x w uint16 plane with 0 = none (cvo_fe_filter_speckles: the kernels a stereo frame
+    runs, without a generator).  Returns (the filtered plane, SIZE as h x w uint32, the number of pixels zeroed); the
+    argument is left as it is."""
+    plane = np.array(plane, np.uint16, order="C")
+    if plane.ndim != 2:
+        raise ValueError("expected an h x w uint16 plane")
+    h, w = plane.shape
+    sizes = np.empty((h, w), np.uint32)
+    removed = C.c_int(0)
+    capi.check(lib().cvo_fe_filter_speckles(int(device), plane.ctypes.data_as(C.POINTER(C.c_uint16)), w * 2, w, h,
+                                            None if speckle is None else C.byref(speckle),
+                                            sizes.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(removed)),
+               what="filter_speckles")
+    return plane, sizes, removed.value
 
 
 def stereo_depth_table(stereo, fx, depth_scale):
@@ -525,6 +568,19 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_stereo_paths(self._h, C.byref(out)), "get_stereo_paths")
         return int(out.value)
 
+    def set_stereo_speckle(self, speckle):
+        """A Speckle for every following stereo frame: components of the disparity plane of `max_size` pixels at the
+        most lose their disparity and their depth (the speckle contract of include/cvo_frontend.h); None: no filter, as
+        for a new object.  A setting of its own: it may be made with or without stereo set and survives set_stereo()."""
+        self._chk(lib().cvo_fe_set_stereo_speckle(self._h, None if speckle is None else C.byref(speckle)),
+                  "set_stereo_speckle")
+
+    def stereo_speckle(self):
+        """The Speckle set, or None."""
+        out, isset = Speckle(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_stereo_speckle(self._h, C.byref(out), C.byref(isset)), "get_stereo_speckle")
+        return out if isset.value else None
+
     def set_stereo_rig(self, rig):
         """A StereoRig for every following frame: submit_stereo / create_pointcloud_stereo then take the RAW pair and
         both images are rectified on the device in front of the matcher (the rig contract of include/cvo_frontend.h);
@@ -583,7 +639,7 @@ class PcdGenerator:
                   STAGE_CENSUS_L: ((h, w), np.uint64), STAGE_CENSUS_R: ((h, w), np.uint64),
                   STAGE_SGM_SUM: ((h, w, self._max_disp), np.uint16), STAGE_DISPARITY: ((h, w), np.uint16),
                   STAGE_STEREO: ((h, w), np.uint8), STAGE_RIGHT_BGR: ((h, w, 3), np.uint8),
-                  STAGE_STEREO_VALID: ((h, w), np.uint8)}
+                  STAGE_STEREO_VALID: ((h, w), np.uint8), STAGE_SPECKLE_SIZE: ((h, w), np.uint32)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -629,13 +685,15 @@ def load_img(rgb_path, depth_path):
 
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
-               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None):
+               camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
+               stereo_speckle=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
     pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
     `stereo_rig`: a StereoRig for the generator, beside `stereo`: the pairs are then RAW and are rectified on the
     device (`dataset_seq` is ignored: the rig is the camera); None leaves the generator as it is.
     `stereo_paths`: a path mask for the generator's matcher (PATHS_4, PATHS_8, ...); None leaves the generator as it is.
+    `stereo_speckle`: a Speckle for the generator's matcher; None leaves the generator as it is.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -671,6 +729,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_stereo_rig(stereo_rig)
     if stereo_paths is not None:
         gen.set_stereo_paths(stereo_paths)
+    if stereo_speckle is not None:
+        gen.set_stereo_speckle(stereo_speckle)
     submit = gen.submit_stereo if stereo is not None else gen.submit
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype)
@@ -723,12 +783,12 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                         stereo_rig=None, stereo_paths=None):
+                         stereo_rig=None, stereo_paths=None, stereo_speckle=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
-    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`: as in run_frames."""
+    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`: as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -744,4 +804,4 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
-                      stereo_paths=stereo_paths)
+                      stereo_paths=stereo_paths, stereo_speckle=stereo_speckle)

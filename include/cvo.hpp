@@ -145,6 +145,12 @@ class registration {
     // subset of the eight bits; one launch per path).  A setting of its own beside set_stereo(): with or without
     // stereo settings, before or after the first image; throws for a mask the front end refuses.
     void set_stereo_paths(unsigned mask);
+    // The matcher's speckle filter: cvo_fe_set_stereo_speckle (the speckle contract: cvo_frontend.h).  Components of the
+    // disparity plane of max_size pixels at the most give no point.  A setting of its own beside set_stereo(), kept
+    // across frames: with or without stereo settings, before or after the first image; throws for settings the front
+    // end refuses.  clear_stereo_speckle(): no filter, a new object's state.
+    void set_stereo_speckle(const cvo_fe_speckle &speckle);
+    void clear_stereo_speckle();
     void set_stereo_rig(const cvo_fe_stereo_rig &rig);
     void clear_stereo_rig();
     void set_pcd_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
@@ -182,6 +188,8 @@ class registration {
     cvo_fe_stereo_rig stereo_rig_;       // what set_stereo_rig() gave, likewise
     bool have_stereo_rig_;
     uint32_t stereo_paths_;              // what set_stereo_paths() gave, likewise (CVO_FE_PATHS_4 without a call)
+    cvo_fe_speckle stereo_speckle_;      // what set_stereo_speckle() gave, likewise
+    bool have_stereo_speckle_;
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();

@@ -41,7 +41,9 @@
  * fills the depth plane.  The stereo contract is stated at cvo_fe_stereo below.  And the rig behind such a pair
  * (cvo_fe_set_stereo_rig): two cameras with lenses of their own that are not parallel; every frame then takes
  * the RAW pair and rectifies both images on the device in front of the matcher.  The rig contract is stated at
- * cvo_fe_stereo_rig below; cvo_fe_stereo_rectify makes a rig from what a calibration tool gives.
+ * cvo_fe_stereo_rig below; cvo_fe_stereo_rectify makes a rig from what a calibration tool gives.  And a speckle
+ * filter on the matcher's disparities (cvo_fe_set_stereo_speckle; cvo_fe_filter_speckles for any uint16 plane):
+ * small connected components lose their disparity.  The speckle contract is stated at cvo_fe_speckle below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -92,14 +94,17 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_STEREO = 20,      /* w*h uint8: an OR of CVO_FE_STEREO_* */
        CVO_FE_STAGE_RIGHT_BGR = 21,   /* the right colour image the matcher read: w*h*3 uint8.  Without a stereo rig
                                          the image as uploaded, with one the rectified one */
-       CVO_FE_STAGE_STEREO_VALID = 22 };  /* of a frame under a stereo rig (CVO_HIP_ERR_INVALID without one): w*h
+       CVO_FE_STAGE_STEREO_VALID = 22,    /* of a frame under a stereo rig (CVO_HIP_ERR_INVALID without one): w*h
                                              uint8, bit 0 = V_L, bit 1 = V_R of the rig contract */
+       CVO_FE_STAGE_SPECKLE_SIZE = 23 };  /* of a stereo frame under a speckle filter (CVO_HIP_ERR_INVALID without
+                                             one): w*h uint32, SIZE of the speckle contract */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
 /* flags of CVO_FE_STAGE_STEREO (the stereo contract at cvo_fe_stereo) */
 enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CVO_FE_STEREO_DEPTH = 8,
-       CVO_FE_STEREO_OUTSIDE = 16 };   /* (only under a stereo rig: the rig contract at cvo_fe_stereo_rig) */
+       CVO_FE_STEREO_OUTSIDE = 16,     /* (only under a stereo rig: the rig contract at cvo_fe_stereo_rig) */
+       CVO_FE_STEREO_SPECKLE = 32 };   /* (only under a speckle filter: the speckle contract at cvo_fe_speckle) */
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
@@ -299,6 +304,29 @@ typedef struct cvo_fe_stereo {
     int32_t pad_;          /* must be 0 */
 } cvo_fe_stereo;           /* 32 bytes */
 
+/* A speckle filter on the disparities of a stereo frame: small islands of confident but wrong disparity -- on
+ * repetitive texture, sky, occlusion borders and glass they pass the uniqueness and the left-right test -- lose
+ * their disparity before they become points that float off every surface.
+ *
+ * THE SPECKLE CONTRACT.  It is defined by the arithmetic below, not by the device.  It follows the rule of
+ * cv::filterSpeckles as its documentation states it, and it is NOT pinned against OpenCV.
+ * Let Q be the DISPARITY plane as step 10 of the stereo contract leaves it; under a rig that is with OUTSIDE applied.
+ *   Valid pixels: those with Q != 0.
+ *   Joined: two valid pixels are joined iff they are 4-neighbours (left, right, up, down; no diagonals) and
+ *     |Q(p) - Q(n)| <= max_diff, the difference of signed integers (1 beside 65535 differ by 65534).
+ *   Components: the classes of the transitive closure of "joined".  A chain of small steps is one component, however
+ *     far its ends are apart.
+ *   SIZE(p) is the pixel count of p's component, and 0 where Q(p) == 0 (CVO_FE_STAGE_SPECKLE_SIZE).
+ *   SPECKLE is set at p iff Q(p) != 0 and SIZE(p) <= max_size.  Such a pixel has STEREO |= CVO_FE_STEREO_SPECKLE,
+ *     DISPARITY = 0 and depth plane 0.  Every other byte of the frame's planes is what it is without the filter.
+ * The gate, if one is set, and level 0 read the filtered plane.  The result does not depend on the order in which
+ * the device meets the pixels: sizes are integer counts.  Not part of it: hole filling and a median filter. */
+typedef struct cvo_fe_speckle {
+    int32_t max_size;   /* components of at most this many pixels lose their disparity; 1 .. 2^26 */
+    int32_t max_diff;   /* largest |Q(p) - Q(n)| that joins two neighbours, in units of the plane (1/16 pixel for
+                           DISPARITY); 0 .. 65535 */
+} cvo_fe_speckle;       /* 8 bytes */
+
 /* One camera of a stereo rig: its pinhole and its lens (k1 k2 p1 p2 k3, as cvo_fe_camera_model's dist). */
 typedef struct cvo_fe_lens {
     float fx, fy, cx, cy;
@@ -495,6 +523,15 @@ enum { CVO_FE_PATHS_4 = 0x0F, CVO_FE_PATHS_8 = 0xFF };
  * submitted and not collected; a mask cvo_fe_check_stereo_paths refuses. */
 int cvo_fe_set_stereo_paths(cvo_fe_ctx *ctx, uint32_t mask);
 int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask);
+/* The speckle filter of the stereo matcher (the speckle contract at cvo_fe_speckle); sp == NULL: no filter (the state
+ * of a new context).  A setting of the context, like the path mask: it may be set with or without stereo set, survives
+ * cvo_fe_set_stereo (settings or NULL) and changes of the rig, and is read by stereo frames only.  Without it a frame
+ * launches no kernel of the filter.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame
+ * submitted and not collected; settings cvo_fe_check_speckle refuses.  The filter's planes (parents, sums, sizes)
+ * take device memory only once it has been set and are given back when it is cleared. */
+int cvo_fe_set_stereo_speckle(cvo_fe_ctx *ctx, const cvo_fe_speckle *sp);
+/* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *set);
 /* cvo_fe_submit / cvo_fe_create_pointcloud for a stereo pair: `left` and `right` are height rows of
  * width*3 bytes each, as `img` there (a caller whose right image is grey replicates it); the left image
  * is the colour image of the frame.  CVO_HIP_ERR_INVALID without stereo set.  collect, collect_device,
@@ -570,6 +607,17 @@ int cvo_fe_stereo_rectify(const cvo_fe_stereo_calib *calib, int width, int heigh
  * `which` not 0 or 1 and a rig cvo_fe_check_stereo_rig refuses. */
 int cvo_fe_stereo_rig_map(const cvo_fe_stereo_rig *rig, int which, int width, int height, int32_t *qu, int32_t *qv);
 
+/* CVO_HIP_OK for settings cvo_fe_set_stereo_speckle() would accept on an idle context, CVO_HIP_ERR_INVALID otherwise:
+ * NULL; max_size outside [1, 2^26]; max_diff outside [0, 65535].  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_speckle(const cvo_fe_speckle *sp);
+/* The filter of the speckle contract on any uint16 plane with 0 = none -- a disparity map of another matcher, a depth
+ * image -- by the kernels a stereo frame runs, without a context: host arrays in and out.  `plane` is height rows of
+ * width uint16, `stride_bytes` BYTES apart, and is filtered in place; `sizes`, if not NULL, receives SIZE (width*height
+ * uint32, dense); *removed the number of pixels zeroed.  CVO_HIP_ERR_INVALID for a null plane or `removed`, width or
+ * height outside [1, 8192], stride_bytes < width*2 and settings cvo_fe_check_speckle refuses; CVO_HIP_ERR_NODEVICE
+ * without such a device. */
+int cvo_fe_filter_speckles(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
+                           const cvo_fe_speckle *sp, uint32_t *sizes, int *removed);
 #ifdef __cplusplus
 }
 #endif
