@@ -60,7 +60,8 @@ registration::registration(int mode, int device, void *stream)
     : init(false), iter(0), ctx_(nullptr), have_moving_(false), n_iter_(0), fe_(nullptr), fe_w_(0), fe_h_(0),
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
-      stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false)
+      stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
+      select_mode_(CVO_FE_SELECT_IMAGE)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -92,6 +93,7 @@ void registration::apply_stored_settings()
         if (have_stereo_rig_) fe_check(cvo_fe_set_stereo_rig(fe_, &stereo_rig_), "cvo_fe_set_stereo_rig");
         fe_check(cvo_fe_set_stereo_paths(fe_, stereo_paths_), "cvo_fe_set_stereo_paths");
         if (have_stereo_speckle_) fe_check(cvo_fe_set_stereo_speckle(fe_, &stereo_speckle_), "cvo_fe_set_stereo_speckle");
+        fe_check(cvo_fe_set_select_mode(fe_, select_mode_), "cvo_fe_set_select_mode");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -202,6 +204,14 @@ void registration::set_depth_gate(const cvo_fe_depth_gate &gate)
 void registration::clear_depth_gate()
 {
     store<cvo_fe_depth_gate>(cvo_fe_set_depth_gate, "cvo_fe_set_depth_gate", nullptr, depth_gate_, have_depth_gate_);
+}
+
+void registration::set_select_mode(int mode)
+{
+    if (!fe_ && cvo_fe_check_select_mode(mode) != CVO_HIP_OK)
+        throw std::runtime_error("set_select_mode(): CVO_FE_SELECT_IMAGE or CVO_FE_SELECT_DEPTH");
+    if (fe_) fe_check(cvo_fe_set_select_mode(fe_, mode), "cvo_fe_set_select_mode");
+    select_mode_ = mode;
 }
 
 void registration::set_stereo(const cvo_fe_stereo &stereo)

@@ -619,6 +619,7 @@ struct SelectArgs {
     FeCtrl *ctrl;
     int *blk_cnt;   // [block][3]: pixels chosen at level 0 / 1 / 2 by that block
     int w, h, w32, ncell, pass;
+    const uint16_t *depth;   // the final depth plane: read by the DEPTH instance only (the selection contract)
 };
 
 // PixelSelector::select (ref thirdparty/PixelSelector2.cpp:240-437), direction
@@ -636,6 +637,10 @@ struct SelectArgs {
 // "first" in the reference's visiting order (B3s, their B2s, rows, columns).  One wave
 // takes one B4: its lanes test the pixels (coalesced rows) and post (value, order) keys
 // to 21 LDS slots with 64-bit atomic max; 21 lanes then write the picks.
+// DEPTH (CVO_FE_SELECT_DEPTH, the selection contract): a pixel without depth leaves where a pixel
+// outside the margin leaves -- its depth is loaded beside its ag0 in the same sweep, and the test
+// is one more term of the margin's `continue`; the instance without it is the code it was.
+template <bool DEPTH>
 __global__ void __launch_bounds__(FE_BLOCK) k_fe_select(const SelectArgs a)
 {
     if (a.pass == 1 && !a.ctrl->redo) return;
@@ -660,7 +665,9 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_select(const SelectArgs a)
             if (xf >= w || yf >= h) continue;
             const int idx = xf + w * yf;
             a.map[idx] = 0.0f;   // (ref :276)
-            if (xf < 4 || xf >= w - 5 || yf < 4 || yf > h - 4) continue;
+            if (DEPTH) {
+                if (xf < 4 || xf >= w - 5 || yf < 4 || yf > h - 4 || a.depth[idx] == 0) continue;
+            } else if (xf < 4 || xf >= w - 5 || yf < 4 || yf > h - 4) continue;
             const int bx3 = lx / (2 * pot), by3 = ly / (2 * pot);
             const int rx = lx - bx3 * 2 * pot, ry = ly - by3 * 2 * pot;
             const int bx2 = rx / pot, by2 = ry / pot;
@@ -983,8 +990,10 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_hyst(uint8_t *st, int w, int h,
 }
 
 // select_point, the top-up itself (ref src/pcd_generator.cpp:153-174): one thread per
-// 8x8 block, first free edge pixel in row order
-__global__ void __launch_bounds__(FE_BLOCK) k_fe_topup(const uint8_t *st, int w, int h, float *map)
+// 8x8 block, first free edge pixel in row order (DEPTH, the selection contract: the first
+// one that also has a depth)
+template <bool DEPTH>
+__global__ void __launch_bounds__(FE_BLOCK) k_fe_topup(const uint8_t *st, int w, int h, float *map, const uint16_t *depth)
 {
     const int bw = (w + 7) / 8, bh = (h + 7) / 8;
     const int b = blockIdx.x * FE_BLOCK + threadIdx.x;
@@ -994,7 +1003,7 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_topup(const uint8_t *st, int w,
         for (int i = 0; i < 8; ++i) {
             if (x + i >= w || y + j >= h) continue;
             const int p = (y + j) * w + x + i;
-            if (st[p] == 2 && map[p] == 0.0f) { map[p] = 1.0f; return; }
+            if (st[p] == 2 && map[p] == 0.0f && (!DEPTH || depth[p] != 0)) { map[p] = 1.0f; return; }
         }
 }
 
@@ -1116,6 +1125,8 @@ struct cvo_fe_ctx {
     bool has_stereo = false;
     // the path mask (cvo_fe_set_stereo_paths): a setting of the context beside `stereo`, read by stereo frames only
     uint32_t stereo_paths = CVO_FE_PATHS_4;
+    // the selector's mode (cvo_fe_set_select_mode): a setting of the context likewise, read by every frame
+    int select_mode = CVO_FE_SELECT_IMAGE;
     // the speckle filter (cvo_fe_set_stereo_speckle): a setting of the context likewise; with it a stereo frame passes
     // the kernels of cvo_speckle.hip behind k_fe_stereo_final
     cvo_fe_speckle speckle{};
@@ -1400,8 +1411,12 @@ int run_canny(cvo_fe_ctx *ctx)
         if (!ctx->h_ctrl->changed) break;
     }
     hipLaunchKernelGGL(k_fe_edges, dim3(blocks(np)), dim3(FE_BLOCK), 0, s, st8, np, ctx->edges.get());
-    hipLaunchKernelGGL(k_fe_topup, dim3(blocks(((w + 7) / 8) * ((h + 7) / 8))), dim3(FE_BLOCK), 0, s, st8, w, h,
-                       ctx->map.get());
+    const dim3 topup_grid(blocks(((w + 7) / 8) * ((h + 7) / 8)));
+    if (ctx->select_mode == CVO_FE_SELECT_DEPTH)
+        hipLaunchKernelGGL(k_fe_topup<true>, topup_grid, dim3(FE_BLOCK), 0, s, st8, w, h, ctx->map.get(), ctx->depth.get());
+    else
+        hipLaunchKernelGGL(k_fe_topup<false>, topup_grid, dim3(FE_BLOCK), 0, s, st8, w, h, ctx->map.get(),
+                           (const uint16_t *)nullptr);
     FE_HIP(hipGetLastError());
     return CVO_HIP_OK;
 }
@@ -1534,13 +1549,17 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     int *blk_cnt = ctx->blk_cnt.get(), *cnt = ctx->cnt.get();
     hipLaunchKernelGGL(k_fe_hist, dim3(ncell), dim3(FE_BLOCK), 0, s, ctx->ag[0].get(), w, h, d.w32, ctx->ths.get());
     hipLaunchKernelGGL(k_fe_smooth, dim3(blocks(ncell)), dim3(FE_BLOCK), 0, s, ctx->ths.get(), d.w32, d.h32, ctx->ths_s.get());
-    SelectArgs sa{ctx->ag[0].get(), ctx->ag[1].get(), ctx->ag[2].get(), ctx->ths_s.get(), map, ctrl, blk_cnt, w, h, d.w32, ncell, 0};
+    // the selection contract: among the pixels of the final depth plane, which is complete here
+    const bool by_depth = ctx->select_mode == CVO_FE_SELECT_DEPTH;
+    SelectArgs sa{ctx->ag[0].get(), ctx->ag[1].get(), ctx->ag[2].get(), ctx->ths_s.get(), map, ctrl, blk_cnt, w, h, d.w32, ncell, 0,
+                  by_depth ? ctx->depth.get() : nullptr};
+    const auto select = by_depth ? k_fe_select<true> : k_fe_select<false>;
     const int nb0 = (((w + 11) / 12) * ((h + 11) / 12) + 3) / 4;   // potential 3: one wave per 12 x 12 block
-    hipLaunchKernelGGL(k_fe_select, dim3(nb0), dim3(FE_BLOCK), 0, s, sa);
+    hipLaunchKernelGGL(select, dim3(nb0), dim3(FE_BLOCK), 0, s, sa);
     hipLaunchKernelGGL(k_fe_decide, dim3(1), dim3(FE_BLOCK), 0, s, ctrl, blk_cnt, nb0, 0, (float)ctx->num_want);
     sa.pass = 1;
     const int nb1 = (((w + 3) / 4) * ((h + 3) / 4) + 3) / 4;       // any potential >= 1
-    hipLaunchKernelGGL(k_fe_select, dim3(nb1), dim3(FE_BLOCK), 0, s, sa);
+    hipLaunchKernelGGL(select, dim3(nb1), dim3(FE_BLOCK), 0, s, sa);
     hipLaunchKernelGGL(k_fe_decide, dim3(1), dim3(FE_BLOCK), 0, s, ctrl, blk_cnt, nb1, 1, (float)ctx->num_want);
     hipLaunchKernelGGL(k_fe_count<0>, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, map, ctx->depth.get(), np, ctrl, cnt);
     hipLaunchKernelGGL(k_fe_subsample, dim3(ctx->nchunks), dim3(FE_BLOCK), 0, s, map, np, ctx->pattern.get(), cnt, ctrl);
@@ -1876,6 +1895,32 @@ int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask)
     cvo_lock::Api api_guard;
     if (!ctx || !mask) return CVO_HIP_ERR_INVALID;
     *mask = ctx->stereo_paths;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_check_select_mode(int mode)
+{
+    return mode == CVO_FE_SELECT_IMAGE || mode == CVO_FE_SELECT_DEPTH ? CVO_HIP_OK : CVO_HIP_ERR_INVALID;
+}
+
+int cvo_fe_set_select_mode(cvo_fe_ctx *ctx, int mode)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_select_mode: a frame is in flight");
+    if (cvo_fe_check_select_mode(mode) != CVO_HIP_OK)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_select_mode: CVO_FE_SELECT_IMAGE or CVO_FE_SELECT_DEPTH");
+    if (mode == ctx->select_mode) return CVO_HIP_OK;
+    ctx->select_mode = mode;
+    drop_graphs(ctx);   // (which instance of the selector a frame launches is part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_select_mode(const cvo_fe_ctx *ctx, int *mode)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !mode) return CVO_HIP_ERR_INVALID;
+    *mode = ctx->select_mode;
     return CVO_HIP_OK;
 }
 

@@ -46,6 +46,9 @@ GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
+# modes of the selector (set_select_mode): by the image alone (the reference; a new object's), or among the pixels
+# that have a depth (the selection contract of include/cvo_frontend.h)
+SELECT_IMAGE, SELECT_DEPTH = 0, 1
 
 SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_num_want",
            "cvo_fe_create_pointcloud", "cvo_fe_submit", "cvo_fe_collect", "cvo_fe_collect_device", "cvo_fe_set_device_output", "cvo_fe_host_buffers", "cvo_fe_get_info", "cvo_fe_read_stage", "cvo_fe_random_pattern",
@@ -56,7 +59,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_create_pointcloud_stereo", "cvo_fe_stereo_depth_table", "cvo_fe_set_stereo_rig", "cvo_fe_get_stereo_rig",
            "cvo_fe_check_stereo_rig", "cvo_fe_stereo_rectify", "cvo_fe_stereo_rig_map", "cvo_fe_check_stereo_paths",
            "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths", "cvo_fe_check_speckle", "cvo_fe_set_stereo_speckle",
-           "cvo_fe_get_stereo_speckle", "cvo_fe_filter_speckles")
+           "cvo_fe_get_stereo_speckle", "cvo_fe_filter_speckles", "cvo_fe_check_select_mode", "cvo_fe_set_select_mode",
+           "cvo_fe_get_select_mode")
 
 
 class Info(C.Structure):
@@ -261,6 +265,9 @@ def lib():
         L.cvo_fe_check_stereo_paths.argtypes = [C.c_uint32]
         L.cvo_fe_set_stereo_paths.argtypes = [vp, C.c_uint32]
         L.cvo_fe_get_stereo_paths.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.cvo_fe_check_select_mode.argtypes = [C.c_int]
+        L.cvo_fe_set_select_mode.argtypes = [vp, C.c_int]
+        L.cvo_fe_get_select_mode.argtypes = [vp, C.POINTER(C.c_int)]
         L.cvo_fe_check_speckle.argtypes = [C.POINTER(Speckle)]
         L.cvo_fe_set_stereo_speckle.argtypes = [vp, C.POINTER(Speckle)]
         L.cvo_fe_get_stereo_speckle.argtypes = [vp, C.POINTER(Speckle), C.POINTER(C.c_int)]
@@ -337,6 +344,12 @@ def check_stereo_paths(mask):
     """True for a path mask set_stereo_paths() accepts (cvo_fe_check_stereo_paths): 1 <= mask <= 0xFF.  Host only."""
     mask = int(mask)
     return 0 <= mask <= 0xFFFFFFFF and lib().cvo_fe_check_stereo_paths(mask) == 0
+
+
+def check_select_mode(mode):
+    """True for a mode set_select_mode() accepts (cvo_fe_check_select_mode): SELECT_IMAGE or SELECT_DEPTH.  Host only."""
+    mode = int(mode)
+    return -2 ** 31 <= mode < 2 ** 31 and lib().cvo_fe_check_select_mode(mode) == 0
 
 
 def check_speckle(speckle):
@@ -581,6 +594,21 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_stereo_speckle(self._h, C.byref(out), C.byref(isset)), "get_stereo_speckle")
         return out if isset.value else None
 
+    def set_select_mode(self, mode):
+        """The selector's mode for every following frame (the selection contract of include/cvo_frontend.h): SELECT_IMAGE
+        (a new object's: the reference's selector, by the image alone) or SELECT_DEPTH (a pixel without depth does not
+        compete, so the cloud holds the num_want asked for).  A setting of its own: it survives every other setter."""
+        mode = int(mode)
+        if not -2 ** 31 <= mode < 2 ** 31:
+            raise capi.CvoHipError("set_select_mode: SELECT_IMAGE or SELECT_DEPTH")
+        self._chk(lib().cvo_fe_set_select_mode(self._h, mode), "set_select_mode")
+
+    def select_mode(self):
+        """The selector's mode in force."""
+        out = C.c_int(0)
+        self._chk(lib().cvo_fe_get_select_mode(self._h, C.byref(out)), "get_select_mode")
+        return int(out.value)
+
     def set_stereo_rig(self, rig):
         """A StereoRig for every following frame: submit_stereo / create_pointcloud_stereo then take the RAW pair and
         both images are rectified on the device in front of the matcher (the rig contract of include/cvo_frontend.h);
@@ -686,7 +714,7 @@ def load_img(rgb_path, depth_path):
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
-               stereo_speckle=None):
+               stereo_speckle=None, select_mode=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
     pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
@@ -694,6 +722,7 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
     device (`dataset_seq` is ignored: the rig is the camera); None leaves the generator as it is.
     `stereo_paths`: a path mask for the generator's matcher (PATHS_4, PATHS_8, ...); None leaves the generator as it is.
     `stereo_speckle`: a Speckle for the generator's matcher; None leaves the generator as it is.
+    `select_mode`: SELECT_IMAGE or SELECT_DEPTH for the generator's selector; None leaves the generator as it is.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -731,6 +760,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_stereo_paths(stereo_paths)
     if stereo_speckle is not None:
         gen.set_stereo_speckle(stereo_speckle)
+    if select_mode is not None:
+        gen.set_select_mode(select_mode)
     submit = gen.submit_stereo if stereo is not None else gen.submit
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype)
@@ -760,14 +791,15 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
-                  generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None):
+                  generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None, select_mode=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
     features, acvo the HSV ones (ref src/cvo.cpp:329, src/adaptive_cvo.cpp:451).  `camera`: as in
     run_frames, e.g. TUM_CAMERAS["fr1"] for a freiburg1 sequence with its lens distortion removed.
     `depth_camera`: as in run_frames, for a recording whose depth images are not registered to colour.
-    `depth_gate`, `mask`: as in run_frames, e.g. DepthGate(0.8, 4.0, 0.05, 1) for a Kinect-class sensor."""
+    `depth_gate`, `mask`: as in run_frames, e.g. DepthGate(0.8, 4.0, 0.05, 1) for a Kinect-class sensor.
+    `select_mode`: as in run_frames, e.g. SELECT_DEPTH beside a gate, which removes the pixels the selector likes best."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -778,17 +810,18 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
             yield name, bgr, depth
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
-                      depth_camera=depth_camera, depth_gate=depth_gate, mask=mask)
+                      depth_camera=depth_camera, depth_gate=depth_gate, mask=mask, select_mode=select_mode)
 
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                         stereo_rig=None, stereo_paths=None, stereo_speckle=None):
+                         stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
-    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`: as in run_frames."""
+    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`: as in
+    run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -804,4 +837,4 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
-                      stereo_paths=stereo_paths, stereo_speckle=stereo_speckle)
+                      stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode)

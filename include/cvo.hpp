@@ -121,6 +121,11 @@ class registration {
     // before the first image; throws for a gate the front end refuses.  clear_depth_gate(): no gate.
     void set_depth_gate(const cvo_fe_depth_gate &gate);
     void clear_depth_gate();
+    // The selector's mode for the image form of set_pcd() / run_cvo(), depth or stereo: cvo_fe_set_select_mode
+    // (CVO_FE_SELECT_IMAGE, a new object's: the reference's selector; CVO_FE_SELECT_DEPTH: a pixel without depth does
+    // not compete, so the cloud holds the points asked for -- the selection contract: cvo_frontend.h).  A setting of
+    // its own, before or after the first image; throws for a mode the front end refuses.
+    void set_select_mode(int mode);
     // A mask for every following frame: rows x cols bytes of the colour image's size, `step` bytes apart,
     // non-zero = no point from this pixel (cvo_fe_set_mask).  The bytes are copied.  May be called before the
     // first image: the copy is handed to the front end when it is created, and a mask of another size than that
@@ -190,6 +195,7 @@ class registration {
     uint32_t stereo_paths_;              // what set_stereo_paths() gave, likewise (CVO_FE_PATHS_4 without a call)
     cvo_fe_speckle stereo_speckle_;      // what set_stereo_speckle() gave, likewise
     bool have_stereo_speckle_;
+    int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();

@@ -43,7 +43,10 @@
  * the RAW pair and rectifies both images on the device in front of the matcher.  The rig contract is stated at
  * cvo_fe_stereo_rig below; cvo_fe_stereo_rectify makes a rig from what a calibration tool gives.  And a speckle
  * filter on the matcher's disparities (cvo_fe_set_stereo_speckle; cvo_fe_filter_speckles for any uint16 plane):
- * small connected components lose their disparity.  The speckle contract is stated at cvo_fe_speckle below.
+ * small connected components lose their disparity.  The speckle contract is stated at cvo_fe_speckle below.  And a
+ * mode of the selector in which a pixel without depth does not compete (cvo_fe_set_select_mode), so that the cloud
+ * holds the num_want the caller asked for whatever the stages above removed.  The selection contract is stated at
+ * cvo_fe_set_select_mode below; a new context selects by the image alone, as the reference does.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -107,7 +110,8 @@ enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CV
        CVO_FE_STEREO_SPECKLE = 32 };   /* (only under a speckle filter: the speckle contract at cvo_fe_speckle) */
 
 typedef struct cvo_fe_info {
-    int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141 */
+    int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141; under
+                               CVO_FE_SELECT_DEPTH they all have a depth (the selection contract) */
     int32_t pot_used;       /* potential of the selection pass that produced the map */
     int32_t reselected;     /* 1: the first pass missed the density band and a second one ran */
     int32_t canny_used;     /* 1: fewer than num_want/3 were kept, edges were added */
@@ -553,6 +557,50 @@ int cvo_fe_create_pointcloud_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t
 int cvo_fe_set_stereo_rig(cvo_fe_ctx *ctx, const cvo_fe_stereo_rig *rig);
 /* *set = 1 and the rig, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_stereo_rig(const cvo_fe_ctx *ctx, cvo_fe_stereo_rig *out, int *set);
+
+/* THE SELECTION CONTRACT (this library's own definition, in arithmetic; not pinned against anything).
+ *
+ * CVO_FE_SELECT_IMAGE is the reference's selector, held to thirdparty/PixelSelector2.cpp bit for bit (the opening
+ * comment): about num_want pixels by the image's gradients alone; back-projection then drops every pick whose depth
+ * is 0, so num_points is an unknown fraction of num_selected.  Under CVO_FE_SELECT_DEPTH a pixel without depth does
+ * not compete.  Let Z be CVO_FE_STAGE_RECT_DEPTH: the plane the cloud is made from, behind rectification, the depth
+ * camera's registration, the stereo matcher, the speckle filter and the gate; valid(x, y) := Z(x, y) != 0.
+ *
+ *   1. Thresholds.  makeHists is unchanged and reads every pixel, valid or not: CVO_FE_STAGE_THS is the plane of
+ *      CVO_FE_SELECT_IMAGE.  The thresholds describe the image's texture; a hole in the depth image must not move,
+ *      through the 3x3 smoothing, the threshold of a cell three cells away.
+ *   2. select.  A pixel (xf, yf) with !valid(xf, yf) is skipped exactly where, and exactly as, a pixel outside the
+ *      margin is: the test is  xf < 4 || xf >= w-5 || yf < 4 || yf > h-4 || Z(xf, yf) == 0.  Such a pixel is a
+ *      candidate at no level, sets no "-2" mark, and its map value is 0.  Validity is always that of the level-0
+ *      pixel (xf, yf), also for the level-1 and level-2 tests, which look up ag1 at (xf/2, yf/2) and ag2 at
+ *      (xf/4, yf/4) FOR that pixel.  Blocks, visiting order, "first largest" and the precedence of the levels are
+ *      otherwise unchanged; in closed form, over the pixels inside the margin that are valid:
+ *        every B2 (pot x pot) holding a pixel with ag0 > th0 keeps the first largest ag0 among them (map 1);
+ *        every B3 (2pot x 2pot) without such a pixel that holds one with ag1 > th1 keeps the first largest ag1 (map 2);
+ *        every B4 (4pot x 4pot) without either that holds one with ag2 > th2 keeps the first largest ag2 (map 4).
+ *      "A B3 without a level-0 hit" thus means: without one among pixels with depth.
+ *   3. makeMaps is unchanged, on the counts select now gives: numHave, the one re-selection and its ideal potential
+ *      (numHave == 0: the float divisions by zero as IEEE does them -- quotia = +inf, the ideal potential 1, a second
+ *      pass at potential 1 that finds nothing, no sub-sampling), charTH, and the running index rn into the random
+ *      bytes over the chosen pixels in scan order.
+ *   4. The Canny top-up.  The trigger is unchanged, num_selected < num_want / 3, and num_selected now counts pixels
+ *      with depth.  Canny itself is unchanged and reads the image only.  Per 8x8 block the top-up takes the first
+ *      pixel in row order that is an edge, is free in the map and is valid.
+ *
+ * Consequences: every non-zero pixel of CVO_FE_STAGE_MAP is valid; num_points == num_selected where no top-up ran
+ * and num_points == num_selected + (pixels topped up) where one ran; on a frame that is valid everywhere every plane
+ * and every point is that of CVO_FE_SELECT_IMAGE.  num_selected is "pixels the selector kept" in both modes. */
+enum { CVO_FE_SELECT_IMAGE = 0,    /* the reference: by the image alone (a new context) */
+       CVO_FE_SELECT_DEPTH = 1 };  /* among the pixels that have a depth */
+/* The mode is a setting of the context, like the path mask: it survives every other setter, is read by every frame
+ * (depth, stereo, under a rig, a gate, a mask) and takes no memory; both modes issue the same launches in the same
+ * order.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame submitted and not collected;
+ * a mode cvo_fe_check_select_mode refuses. */
+int cvo_fe_set_select_mode(cvo_fe_ctx *ctx, int mode);
+int cvo_fe_get_select_mode(const cvo_fe_ctx *ctx, int *mode);
+/* CVO_HIP_OK for a mode cvo_fe_set_select_mode() would accept on an idle context: one of the two above.  The one
+ * statement of what is accepted.  Host only. */
+int cvo_fe_check_select_mode(int mode);
 
 /* what the last create_pointcloud / collect did */
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out);
