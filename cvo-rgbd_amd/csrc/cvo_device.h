@@ -514,6 +514,10 @@ CVO_HD KernConsts make_kconsts(const DevParams &p, float ell)
     // MATLAB keeps K >= sp (ref rkhs_se3_registration.m:70): the radius is widened by 1e-5 so
     // that the exact test on K in pair_weight decides, not the rounding of tau
     if (k.cscale > 0.0f) k.tau = (float)((double)k.tau * 1.00001);
+    // sp_thres >= sigma^2 makes tau zero or negative.  No pair has d2 < tau then, and none has d2 < 0 either: the member
+    // rule is the same with tau = 0, and every radius the plans and the culls take from sqrt(tau) stays a number (with a
+    // NaN radius align() ended "without a verdict": tests/test_gpu_pair_weight.py, the set cvo_no_radius_x4)
+    if (!(k.tau > 0.0f)) k.tau = 0.0f;
     k.s2_d = p.s2_d;
     k.cs2_d = p.cs2_d;
     k.ninv_2l2 = -1.0 / (2.0 * l * l);

@@ -25,8 +25,14 @@ __device__ __forceinline__ float d2_feat(const float4 fa0, const float fa4, cons
 // overload of exp).  2^(k/64) table + degree-5 polynomial on |r| <= ln2/128, the
 // scheme of every libm: at most one ulp from glibc's exp (differs from it in the
 // last bit for 25 % of the arguments) and -- what the arithmetic contract needs --
-// the float32 value of sigma^2 exp(x) was the same for all of 2*10^8 random
-// arguments in [-6, 0].  14 float64 operations instead of ~30 in the device libm;
+// the float32 values of sigma^2 exp(x) and c_sigma^2 exp(x) are libm's, which the
+// suite holds pair by pair: tests/test_gpu_pair_weight.py compares every kept weight
+// of the stars of tests/pair_weight_cases.py with the oracle's (libm's exp) by bits,
+// at exponents down to -83 on the spatial and -64 on the colour side, results down
+// to float32 subnormals, and both with the float64 reference (whose own exp
+// tests/test_pair_weight_cpu.py holds to 60-digit arithmetic).  With the low part of
+// ln2/64 below set to zero that test fails at the far exponents.
+// 14 float64 operations instead of ~30 in the device libm;
 // the two exp are the largest single item of the per-pair work.
 __device__ const double c_exp2_64[64] = {
     0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,

@@ -144,6 +144,14 @@ int cvo_hip_init_state(const cvo_hip_params *p, cvo_hip_state *s);
  * to let the context create its own non-blocking stream. */
 int cvo_hip_create(int device, void *stream, const cvo_hip_params *p, cvo_hip_ctx **out);
 int cvo_hip_destroy(cvo_hip_ctx *ctx);
+/* Parameters: ell_init, sigma, sp_thres, c, d, c_ell, c_sigma (acvo: c_sp_thres too) must be positive and finite, or the
+ * call is refused with CVO_HIP_ERR_INVALID and a text in cvo_hip_last_error.  Inside that the kernel scales and thresholds
+ * are the caller's: the pair weight equals the oracle's by bits at the sets of tests/pair_weight_cases.py as well as at
+ * the shipped constants -- sp_thres from 0.9 sigma^2 down to 1e-38 (exponents up to 83, weights below FLT_MIN: float32
+ * subnormals are kept, not flushed), c_ell 5 to 200, sigma up to 2, c_sigma up to 3.  A threshold at or above its kernel's
+ * peak is not an error: with sp_thres >= sigma^2 (tau <= 0) or, acvo, c_sp_thres >= c_sigma^2 (tau_c <= 0) no pair is a
+ * member, every query returns zeros and CVO_HIP_OK, and cvo_hip_align stops after one iteration with step = min_step and
+ * the pose untouched, as for clouds out of each other's reach. */
 int cvo_hip_set_params(cvo_hip_ctx *ctx, const cvo_hip_params *p);
 
 /* Cloud hand-over: tail of set_pcd() (ref src/cvo.cpp:344-356).  At most 2^26 points per cloud

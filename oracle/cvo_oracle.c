@@ -331,13 +331,18 @@ static int grid_build(grid *g, const float *xb, int nb, float tau)
     double h = sqrt((double)(tau > 0 ? tau : 0)) * (1.0 + 1e-4);
     if (!(h > 1e-9)) h = 1e-9;
     for (;;) {
-        double nc = 1;
+        /* (the cell counts stay doubles until they are known to fit: with tau <= 0 the first h is 1e-9 and a cloud's
+         * extent over it is past INT_MAX) */
+        double nc = 1, dim[3];
         for (int a = 0; a < 3; ++a) {
             double e = nb > 0 ? (hi[a] - lo[a]) / h : 0;
-            g->dim[a] = (int)floor(e) + 1;
-            nc *= g->dim[a];
+            dim[a] = floor(e) + 1;
+            nc *= dim[a];
         }
-        if (nc <= 16777216.0) break;
+        if (nc <= 16777216.0) {
+            for (int a = 0; a < 3; ++a) g->dim[a] = (int)dim[a];
+            break;
+        }
         h *= 1.5;
     }
     for (int a = 0; a < 3; ++a) g->org[a] = nb > 0 ? lo[a] : 0;

@@ -75,7 +75,10 @@ def weights(p, ell, x, fx, y, fy, c_sp, two_divisions=False):
             margin = np.where(a != 0.0, sp / k - 1.0, np.inf)
         else:
             a = cs2 * np.exp(-d2c / (2.0 * c_ell * c_ell)) * k
-            margin = np.maximum(np.maximum(d2 / tau - 1.0, d2c / tau_c - 1.0), sp / a - 1.0)
+            # (a threshold at or above sigma^2 or c_sigma^2 makes tau or tau_c zero or negative: d2 < tau holds for no pair)
+            m1 = d2 / tau - 1.0 if tau > 0.0 else np.full_like(d2, np.inf)
+            m2 = d2c / tau_c - 1.0 if tau_c > 0.0 else np.full_like(d2c, np.inf)
+            margin = np.maximum(np.maximum(m1, m2), sp / a - 1.0)
     return a, d2, d2c, margin
 
 
