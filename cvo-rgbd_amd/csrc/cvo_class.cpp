@@ -61,7 +61,7 @@ registration::registration(int mode, int device, void *stream)
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
-      select_mode_(CVO_FE_SELECT_IMAGE)
+      depth_median_(), have_depth_median_(false), select_mode_(CVO_FE_SELECT_IMAGE)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -94,6 +94,7 @@ void registration::apply_stored_settings()
         fe_check(cvo_fe_set_stereo_paths(fe_, stereo_paths_), "cvo_fe_set_stereo_paths");
         if (have_stereo_speckle_) fe_check(cvo_fe_set_stereo_speckle(fe_, &stereo_speckle_), "cvo_fe_set_stereo_speckle");
         fe_check(cvo_fe_set_select_mode(fe_, select_mode_), "cvo_fe_set_select_mode");
+        if (have_depth_median_) fe_check(cvo_fe_set_depth_median(fe_, &depth_median_), "cvo_fe_set_depth_median");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -204,6 +205,18 @@ void registration::set_depth_gate(const cvo_fe_depth_gate &gate)
 void registration::clear_depth_gate()
 {
     store<cvo_fe_depth_gate>(cvo_fe_set_depth_gate, "cvo_fe_set_depth_gate", nullptr, depth_gate_, have_depth_gate_);
+}
+
+void registration::set_depth_median(const cvo_fe_depth_median &median)
+{
+    if (!fe_ && cvo_fe_check_depth_median(&median) != CVO_HIP_OK)
+        throw std::runtime_error("set_depth_median(): radius 1 or 2, fill_min in [0, (2*radius+1)^2 - 1], pad_ 0");
+    store<cvo_fe_depth_median>(cvo_fe_set_depth_median, "cvo_fe_set_depth_median", &median, depth_median_, have_depth_median_);
+}
+
+void registration::clear_depth_median()
+{
+    store<cvo_fe_depth_median>(cvo_fe_set_depth_median, "cvo_fe_set_depth_median", nullptr, depth_median_, have_depth_median_);
 }
 
 void registration::set_select_mode(int mode)

@@ -21,6 +21,7 @@
 
 #include "cvo_frontend.h"
 #include "cvo_lock.h"
+#include "cvo_median.h"
 #include "cvo_speckle.h"
 #include "cvo_stereo.h"
 
@@ -1133,6 +1134,13 @@ struct cvo_fe_ctx {
     bool has_speckle = false;
     // with the filter, and gone with it: parents, sums and sizes (np words each) and the count of removed pixels
     Dev<uint32_t> speckle_words;
+    // the median stage (cvo_fe_set_depth_median): a setting of the context likewise, read by every frame; with it
+    // whatever fills the depth plane fills `unfiltered`, and k_fe_median of cvo_median.hip writes that plane
+    cvo_fe_depth_median median{};
+    bool has_median = false;
+    // with the filter, and gone with it: A of the median contract (rect_plane(np) entries) and the flags
+    Dev<uint16_t> unfiltered;
+    Dev<uint8_t> median_flags;
     // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
     // table U(q) with its staging copy; the cost sums follow max_disp
     Dev<uint8_t> right_img, right_gray, stereo_flags;
@@ -1342,11 +1350,15 @@ inline bool gate_active(const cvo_fe_ctx *ctx) { return ctx->has_gate || ctx->ha
 // the depth plane the stages in front of level 0 write: the gate's input while it runs
 inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? ctx->ungated.get() : ctx->depth.get(); }
 
+// the plane the producers of depth write (an upload, k_fe_rectify, the depth camera's warp, the stereo matcher and its
+// speckle filter): the median stage's input while it runs, else the depth plane itself
+inline uint16_t *filled_plane(const cvo_fe_ctx *ctx) { return ctx->has_median ? ctx->unfiltered.get() : depth_plane(ctx); }
+
 // where the uploaded depth image lands: the raw buffer of a depth camera's size, else the raw depth that
-// k_fe_rectify resamples, else the depth plane itself
+// k_fe_rectify resamples, else the plane the producers write
 inline uint16_t *depth_upload(const cvo_fe_ctx *ctx)
 {
-    return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : depth_plane(ctx);
+    return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : filled_plane(ctx);
 }
 
 // the points of the cloud that follow the control block to the host before their number is known: enough for
@@ -1456,7 +1468,8 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
-    uint16_t *plane = depth_plane(ctx);
+    // (a median filter: whatever fills the depth plane fills the stage's input, and k_fe_median fills what is named above)
+    uint16_t *plane = filled_plane(ctx);
     if (ctx->has_stereo)
         FE_HIP(hipMemcpyAsync(ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3,
                               hipMemcpyHostToDevice, s));
@@ -1509,6 +1522,12 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         camera_in_force(ctx, dataset_seq, a.cam);
         hipLaunchKernelGGL(k_fe_depth_warp, dim3(blocks(a.dw * a.dh)), dim3(FE_BLOCK), 0, s, a);
         hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf.get(), np, plane);
+    }
+    if (ctx->has_median) {   // (the median contract: directly in front of the gate, for every kind of frame)
+        FeMedianArgs m{};
+        m.a = plane; m.b = depth_plane(ctx); m.flags = ctx->median_flags.get();
+        m.w = w; m.h = h; m.radius = ctx->median.radius; m.fill_min = ctx->median.fill_min;
+        fe_median_enqueue(m, s);
     }
     if (gate_active(ctx)) {
         GateArgs g{};
@@ -1953,6 +1972,43 @@ int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *s
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     *out = ctx->has_speckle ? ctx->speckle : cvo_fe_speckle{};
     if (set) *set = ctx->has_speckle ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_depth_median(cvo_fe_ctx *ctx, const cvo_fe_depth_median *m)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_median: a frame is in flight");
+    if (m && cvo_fe_check_depth_median(m) != CVO_HIP_OK)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_median: radius 1 or 2, fill_min in [0, (2*radius+1)^2 - 1], pad_ 0");
+    if (!m && !ctx->has_median) return CVO_HIP_OK;
+    if (m && ctx->has_median && std::memcmp(m, &ctx->median, sizeof(*m)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint16_t> unfiltered;
+    Dev<uint8_t> flags;
+    if (m && !ctx->unfiltered && !(dev_alloc(unfiltered, rect_plane(ctx->np)) && dev_alloc(flags, rect_plane(ctx->np))))
+        return no_memory(ctx, "set_depth_median: device memory for the unfiltered depth and the stage's flags");
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->unfiltered, unfiltered);
+    hand_over(ctx->median_flags, flags);
+    if (!m) {
+        ctx->unfiltered.reset();
+        ctx->median_flags.reset();
+    }
+    ctx->has_median = m != nullptr;
+    ctx->median = m ? *m : cvo_fe_depth_median{};
+    drop_graphs(ctx);   // (whether a frame has the stage's launch, its numbers and where the producers write are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_median ? ctx->median : cvo_fe_depth_median{};
+    if (set) *set = ctx->has_median ? 1 : 0;
     return CVO_HIP_OK;
 }
 
@@ -2515,9 +2571,13 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_RIGHT_BGR: src = ctx->right_img.get(); need = np * 3; break;
     case CVO_FE_STAGE_STEREO_VALID: src = ctx->srig_valid.get(); need = np; break;
     case CVO_FE_STAGE_SPECKLE_SIZE: src = ctx->speckle_words ? ctx->speckle_words.get() + 2 * np : nullptr; need = np * 4; break;
+    case CVO_FE_STAGE_UNFILTERED_DEPTH: src = ctx->unfiltered.get(); need = np * 2; break;
+    case CVO_FE_STAGE_MEDIAN: src = ctx->median_flags.get(); need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
-    if (stage >= CVO_FE_STAGE_RIGHT_GRAY && !ctx->has_stereo)
+    if ((stage == CVO_FE_STAGE_UNFILTERED_DEPTH || stage == CVO_FE_STAGE_MEDIAN) && !ctx->has_median)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the median filter, and no filter is set");
+    if (stage >= CVO_FE_STAGE_RIGHT_GRAY && stage <= CVO_FE_STAGE_SPECKLE_SIZE && !ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a stage of a stereo frame, and stereo is not set");
     if (stage == CVO_FE_STAGE_STEREO_VALID && !ctx->has_srig)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the validity plane of a stereo rig, and no rig is set");

@@ -7,6 +7,11 @@ device raises).
     gen = PcdGenerator(width=640, height=480)
     xyz, feat = gen.create_pointcloud(bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB)
 
+A median filter on the depth plane in front of every later stage, filling small holes (the median contract of
+include/cvo_frontend.h; frames of either kind):
+
+    gen.set_depth_median(DepthMedian(radius=1, fill_min=5))
+
 A rectified stereo pair in place of the depth image (the stereo contract of include/cvo_frontend.h):
 
     gen = PcdGenerator(width=1241, height=376)
@@ -41,9 +46,10 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
  STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
  STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
- STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE) = range(24)
+ STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE, STAGE_UNFILTERED_DEPTH, STAGE_MEDIAN) = range(26)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
+MEDIAN_CHANGED, MEDIAN_FILLED = 1, 2   # the values of STAGE_MEDIAN
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
 # modes of the selector (set_select_mode): by the image alone (the reference; a new object's), or among the pixels
@@ -60,7 +66,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_check_stereo_rig", "cvo_fe_stereo_rectify", "cvo_fe_stereo_rig_map", "cvo_fe_check_stereo_paths",
            "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths", "cvo_fe_check_speckle", "cvo_fe_set_stereo_speckle",
            "cvo_fe_get_stereo_speckle", "cvo_fe_filter_speckles", "cvo_fe_check_select_mode", "cvo_fe_set_select_mode",
-           "cvo_fe_get_select_mode")
+           "cvo_fe_get_select_mode", "cvo_fe_check_depth_median", "cvo_fe_set_depth_median", "cvo_fe_get_depth_median",
+           "cvo_fe_median_plane")
 
 
 class Info(C.Structure):
@@ -149,6 +156,17 @@ class Speckle(_Settings):
 
     def __init__(self, max_size=100, max_diff=16):
         super().__init__(int(max_size), int(max_diff))
+
+
+class DepthMedian(_Settings):
+    """cvo_fe_depth_median: the median stage on the depth plane, in front of the gate (the median contract of
+    include/cvo_frontend.h).  `radius` 1: a 3 x 3 window, 2: 5 x 5; a pixel with a depth takes the lower median of its
+    window's depths.  `fill_min` 0: a pixel without depth stays without; k >= 1: it takes that median when at least k
+    pixels of its window have a depth."""
+    _fields_ = [("radius", C.c_int32), ("fill_min", C.c_int32), ("pad_", C.c_int32)]
+
+    def __init__(self, radius=1, fill_min=0, pad_=0):
+        super().__init__(int(radius), int(fill_min), int(pad_))
 
 
 class Lens(_Settings):
@@ -273,6 +291,11 @@ def lib():
         L.cvo_fe_get_stereo_speckle.argtypes = [vp, C.POINTER(Speckle), C.POINTER(C.c_int)]
         L.cvo_fe_filter_speckles.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Speckle),
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        L.cvo_fe_check_depth_median.argtypes = [C.POINTER(DepthMedian)]
+        L.cvo_fe_set_depth_median.argtypes = [vp, C.POINTER(DepthMedian)]
+        L.cvo_fe_get_depth_median.argtypes = [vp, C.POINTER(DepthMedian), C.POINTER(C.c_int)]
+        L.cvo_fe_median_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthMedian), u8p,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
         L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
         L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
@@ -376,6 +399,31 @@ def filter_speckles(plane, speckle, device=0):
                                             sizes.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(removed)),
                what="filter_speckles")
     return plane, sizes, removed.value
+
+
+def check_depth_median(median):
+    """True for a DepthMedian set_depth_median() accepts (cvo_fe_check_depth_median): radius 1 or 2, fill_min in
+    [0, (2*radius+1)^2 - 1], pad_ 0; None is refused.  Host only."""
+    if median is None:
+        return lib().cvo_fe_check_depth_median(None) == 0
+    return lib().cvo_fe_check_depth_median(C.byref(median)) == 0
+
+
+def median_plane(plane, median, device=0):
+    """The median stage on any h x w uint16 plane with 0 = none (cvo_fe_median_plane: the kernel a frame runs, without
+    a generator).  Returns (the filtered plane, the flags as h x w uint8 of MEDIAN_CHANGED / MEDIAN_FILLED, the number
+    of pixels changed, the number filled); the argument is left as it is."""
+    plane = np.array(plane, np.uint16, order="C")
+    if plane.ndim != 2:
+        raise ValueError("expected an h x w uint16 plane")
+    h, w = plane.shape
+    flags = np.empty((h, w), np.uint8)
+    changed, filled = C.c_int(0), C.c_int(0)
+    capi.check(lib().cvo_fe_median_plane(int(device), plane.ctypes.data_as(C.POINTER(C.c_uint16)), w * 2, w, h,
+                                         None if median is None else C.byref(median),
+                                         flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(changed), C.byref(filled)),
+               what="median_plane")
+    return plane, flags, changed.value, filled.value
 
 
 def stereo_depth_table(stereo, fx, depth_scale):
@@ -594,6 +642,18 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_stereo_speckle(self._h, C.byref(out), C.byref(isset)), "get_stereo_speckle")
         return out if isset.value else None
 
+    def set_depth_median(self, median):
+        """A DepthMedian for every following frame of any kind: the depth plane passes the median stage in front of the
+        gate (the median contract of include/cvo_frontend.h); None: no filter, as for a new object.  A setting of its
+        own: it survives every other setter."""
+        self._chk(lib().cvo_fe_set_depth_median(self._h, None if median is None else C.byref(median)), "set_depth_median")
+
+    def depth_median(self):
+        """The DepthMedian set, or None."""
+        out, isset = DepthMedian(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_depth_median(self._h, C.byref(out), C.byref(isset)), "get_depth_median")
+        return out if isset.value else None
+
     def set_select_mode(self, mode):
         """The selector's mode for every following frame (the selection contract of include/cvo_frontend.h): SELECT_IMAGE
         (a new object's: the reference's selector, by the image alone) or SELECT_DEPTH (a pixel without depth does not
@@ -667,7 +727,8 @@ class PcdGenerator:
                   STAGE_CENSUS_L: ((h, w), np.uint64), STAGE_CENSUS_R: ((h, w), np.uint64),
                   STAGE_SGM_SUM: ((h, w, self._max_disp), np.uint16), STAGE_DISPARITY: ((h, w), np.uint16),
                   STAGE_STEREO: ((h, w), np.uint8), STAGE_RIGHT_BGR: ((h, w, 3), np.uint8),
-                  STAGE_STEREO_VALID: ((h, w), np.uint8), STAGE_SPECKLE_SIZE: ((h, w), np.uint32)}
+                  STAGE_STEREO_VALID: ((h, w), np.uint8), STAGE_SPECKLE_SIZE: ((h, w), np.uint32),
+                  STAGE_UNFILTERED_DEPTH: ((h, w), np.uint16), STAGE_MEDIAN: ((h, w), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -714,7 +775,7 @@ def load_img(rgb_path, depth_path):
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
-               stereo_speckle=None, select_mode=None):
+               stereo_speckle=None, select_mode=None, depth_median=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
     pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
@@ -723,6 +784,7 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
     `stereo_paths`: a path mask for the generator's matcher (PATHS_4, PATHS_8, ...); None leaves the generator as it is.
     `stereo_speckle`: a Speckle for the generator's matcher; None leaves the generator as it is.
     `select_mode`: SELECT_IMAGE or SELECT_DEPTH for the generator's selector; None leaves the generator as it is.
+    `depth_median`: a DepthMedian for the generator, for frames of either kind; None leaves the generator as it is.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -762,6 +824,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_stereo_speckle(stereo_speckle)
     if select_mode is not None:
         gen.set_select_mode(select_mode)
+    if depth_median is not None:
+        gen.set_depth_median(depth_median)
     submit = gen.submit_stereo if stereo is not None else gen.submit
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype)
@@ -791,7 +855,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
-                  generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None, select_mode=None):
+                  generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None, select_mode=None,
+                  depth_median=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
@@ -799,7 +864,8 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
     run_frames, e.g. TUM_CAMERAS["fr1"] for a freiburg1 sequence with its lens distortion removed.
     `depth_camera`: as in run_frames, for a recording whose depth images are not registered to colour.
     `depth_gate`, `mask`: as in run_frames, e.g. DepthGate(0.8, 4.0, 0.05, 1) for a Kinect-class sensor.
-    `select_mode`: as in run_frames, e.g. SELECT_DEPTH beside a gate, which removes the pixels the selector likes best."""
+    `select_mode`: as in run_frames, e.g. SELECT_DEPTH beside a gate, which removes the pixels the selector likes best.
+    `depth_median`: as in run_frames, e.g. DepthMedian(1, 5) for a sensor with salt and pinholes."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -810,18 +876,19 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
             yield name, bgr, depth
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
-                      depth_camera=depth_camera, depth_gate=depth_gate, mask=mask, select_mode=select_mode)
+                      depth_camera=depth_camera, depth_gate=depth_gate, mask=mask, select_mode=select_mode,
+                      depth_median=depth_median)
 
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                         stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None):
+                         stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None, depth_median=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
-    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`: as in
-    run_frames."""
+    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`, `depth_median`:
+    as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -837,4 +904,5 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
-                      stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode)
+                      stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode,
+                      depth_median=depth_median)

@@ -121,6 +121,12 @@ class registration {
     // before the first image; throws for a gate the front end refuses.  clear_depth_gate(): no gate.
     void set_depth_gate(const cvo_fe_depth_gate &gate);
     void clear_depth_gate();
+    // The median stage on the depth plane, in front of the gate, for the image form of set_pcd() / run_cvo(), depth or
+    // stereo: cvo_fe_set_depth_median (the median contract: cvo_frontend.h).  A pixel with a depth takes the lower median
+    // of its 3 x 3 or 5 x 5 window, and with fill_min > 0 a small hole is filled.  May be called before the first image;
+    // throws for settings the front end refuses.  clear_depth_median(): no filter, a new object's state.
+    void set_depth_median(const cvo_fe_depth_median &median);
+    void clear_depth_median();
     // The selector's mode for the image form of set_pcd() / run_cvo(), depth or stereo: cvo_fe_set_select_mode
     // (CVO_FE_SELECT_IMAGE, a new object's: the reference's selector; CVO_FE_SELECT_DEPTH: a pixel without depth does
     // not compete, so the cloud holds the points asked for -- the selection contract: cvo_frontend.h).  A setting of
@@ -195,6 +201,8 @@ class registration {
     uint32_t stereo_paths_;              // what set_stereo_paths() gave, likewise (CVO_FE_PATHS_4 without a call)
     cvo_fe_speckle stereo_speckle_;      // what set_stereo_speckle() gave, likewise
     bool have_stereo_speckle_;
+    cvo_fe_depth_median depth_median_;   // what set_depth_median() gave, likewise
+    bool have_depth_median_;
     int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);

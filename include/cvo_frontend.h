@@ -46,7 +46,10 @@
  * small connected components lose their disparity.  The speckle contract is stated at cvo_fe_speckle below.  And a
  * mode of the selector in which a pixel without depth does not compete (cvo_fe_set_select_mode), so that the cloud
  * holds the num_want the caller asked for whatever the stages above removed.  The selection contract is stated at
- * cvo_fe_set_select_mode below; a new context selects by the image alone, as the reference does.
+ * cvo_fe_set_select_mode below; a new context selects by the image alone, as the reference does.  And a median
+ * filter on the depth plane itself, in front of the gate, for every kind of frame (cvo_fe_set_depth_median;
+ * cvo_fe_median_plane for any uint16 plane): a lone outlier takes its neighbourhood's value and, if asked for, a small
+ * hole is filled.  The median contract is stated at cvo_fe_depth_median below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -99,8 +102,12 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
                                          the image as uploaded, with one the rectified one */
        CVO_FE_STAGE_STEREO_VALID = 22,    /* of a frame under a stereo rig (CVO_HIP_ERR_INVALID without one): w*h
                                              uint8, bit 0 = V_L, bit 1 = V_R of the rig contract */
-       CVO_FE_STAGE_SPECKLE_SIZE = 23 };  /* of a stereo frame under a speckle filter (CVO_HIP_ERR_INVALID without
+       CVO_FE_STAGE_SPECKLE_SIZE = 23,    /* of a stereo frame under a speckle filter (CVO_HIP_ERR_INVALID without
                                              one): w*h uint32, SIZE of the speckle contract */
+       /* of a frame under a median filter (cvo_fe_set_depth_median; CVO_HIP_ERR_INVALID on a context without one).
+          With the filter UNGATED_DEPTH, "the plane the gate read", is B of the median contract. */
+       CVO_FE_STAGE_UNFILTERED_DEPTH = 24,    /* A of the median contract: w*h uint16 */
+       CVO_FE_STAGE_MEDIAN = 25 };        /* MEDIAN of the median contract: w*h uint8, CVO_FE_MEDIAN_* */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
@@ -108,6 +115,8 @@ enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
 enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CVO_FE_STEREO_DEPTH = 8,
        CVO_FE_STEREO_OUTSIDE = 16,     /* (only under a stereo rig: the rig contract at cvo_fe_stereo_rig) */
        CVO_FE_STEREO_SPECKLE = 32 };   /* (only under a speckle filter: the speckle contract at cvo_fe_speckle) */
+/* values of CVO_FE_STAGE_MEDIAN (the median contract at cvo_fe_depth_median) */
+enum { CVO_FE_MEDIAN_CHANGED = 1, CVO_FE_MEDIAN_FILLED = 2 };
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141; under
@@ -198,7 +207,8 @@ typedef struct cvo_fe_camera_model {
  * footprint is the set of pixel centres inside the projected cell, half-open, capped at 8 x 8 so
  * that a pixel's work is bounded; a rig that is the colour camera itself (same size and pinhole,
  * R = I, T = 0) returns the depth image byte for byte; the result does not depend on the order
- * of the writes.  Holes a forward warp leaves are not filled. */
+ * of the writes.  Holes a forward warp leaves are not filled here; the median stage (the median contract at
+ * cvo_fe_depth_median) fills the small ones if it is asked to. */
 typedef struct cvo_fe_depth_camera {
     int32_t width, height;               /* of the DEPTH image; may differ from the context's (colour) size */
     float depth_scale, fx, fy, cx, cy;   /* units per metre of the depth image's values; the depth camera's pinhole */
@@ -214,7 +224,8 @@ typedef struct cvo_fe_depth_camera {
  * uint16, called U here -- through one more stage before anything else reads it; level 0, the
  * selector, the Canny top-up and the back-projection then run unchanged on the gated plane.  The
  * results are defined by the arithmetic below, not by the device.  It is this library's own
- * definition and is NOT pinned against any SDK's filter.
+ * definition and is NOT pinned against any SDK's filter.  (Under a median filter U is that stage's
+ * output, B of the median contract at cvo_fe_depth_median.)
  *
  * `scale` is depth_scale of the colour camera in force for the frame (the cvo_fe_set_camera model,
  * else the table row of dataset_seq).  For a pixel p with U(p) != 0:
@@ -295,7 +306,8 @@ typedef struct cvo_fe_depth_gate {
  *      U(q) up.  DEPTH iff the pixel has no other flag and U(q) == 0.
  *  10. Output.  STEREO(p) is the OR of the flags; DISPARITY(p) = STEREO(p) ? 0 : q; the depth plane gets
  *      STEREO(p) ? 0 : U(q).
- * Diagonal paths are part of it where the path mask names them; hole filling and a median filter are not; what the
+ * Diagonal paths are part of it where the path mask names them; hole filling and a median filter are not: they are
+ * the median stage behind the matcher (the median contract at cvo_fe_depth_median); what the
  * diagonals are worth in accuracy on real pairs is not measured.  A pair that is not rectified goes in
  * with its rig (cvo_fe_set_stereo_rig, the rig contract below). */
 typedef struct cvo_fe_stereo {
@@ -324,12 +336,49 @@ typedef struct cvo_fe_stereo {
  *   SPECKLE is set at p iff Q(p) != 0 and SIZE(p) <= max_size.  Such a pixel has STEREO |= CVO_FE_STEREO_SPECKLE,
  *     DISPARITY = 0 and depth plane 0.  Every other byte of the frame's planes is what it is without the filter.
  * The gate, if one is set, and level 0 read the filtered plane.  The result does not depend on the order in which
- * the device meets the pixels: sizes are integer counts.  Not part of it: hole filling and a median filter. */
+ * the device meets the pixels: sizes are integer counts.  Not part of it: hole filling and a median filter, which are
+ * the median stage behind this one (the median contract at cvo_fe_depth_median). */
 typedef struct cvo_fe_speckle {
     int32_t max_size;   /* components of at most this many pixels lose their disparity; 1 .. 2^26 */
     int32_t max_diff;   /* largest |Q(p) - Q(n)| that joins two neighbours, in units of the plane (1/16 pixel for
                            DISPARITY); 0 .. 65535 */
 } cvo_fe_speckle;       /* 8 bytes */
+
+/* A median filter on the depth plane, filling small holes: a single outlier of a sensor or of the matcher, at the
+ * strong gradients the selector picks, becomes a point floating off its surface, and a one-pixel hole there loses the
+ * pixel that was picked.
+ *
+ * THE MEDIAN CONTRACT.  While a filter is set every frame of the context, of every kind, passes its depth plane through
+ * one more stage directly in front of the gate.  The results are defined by the integer arithmetic below, not by the
+ * device.  It is this library's own definition and is NOT pinned against cv::medianBlur or any SDK's filter.
+ * Let A be the depth plane as it stands after the rectification, the depth camera's registration, or the stereo
+ * matcher and its speckle filter: w x h uint16 with 0 = none -- what the gate contract calls U without this stage.
+ * For a pixel p:
+ *   W(p) is the set of pixels q inside the image with max(|dx|, |dy|) <= radius.  Pixels outside the image are not in
+ *     it: no replicated border.
+ *   V(p) is the multiset of A(q) over q in W(p) with A(q) != 0; n = |V(p)|; v_0 <= ... <= v_(n-1) its members in
+ *     ascending order.
+ *   med(p) = v_((n-1) >> 1): the lower median, always a value some pixel of the window holds, never an average.
+ *   B(p) = med(p) if A(p) != 0 (then n >= 1: p counts itself); otherwise med(p) if fill_min > 0 and n >= fill_min;
+ *     otherwise 0.
+ *   MEDIAN(p) = CVO_FE_MEDIAN_CHANGED where A(p) != 0 and B(p) != A(p); CVO_FE_MEDIAN_FILLED where A(p) == 0 and
+ *     B(p) != 0; 0 elsewhere (CVO_FE_STAGE_MEDIAN).
+ * Every pixel's result is a function of A alone: it does not depend on the order in which the device meets the pixels,
+ * and it is not computed in place.  65535 is a depth like any other.
+ * B is the plane the gate reads (the U of the gate contract, CVO_FE_STAGE_UNGATED_DEPTH); without a gate or mask
+ * level 0, the selector under CVO_FE_SELECT_DEPTH and the back-projection read it, all unchanged.  Range, jump marks and
+ * mask therefore act on B; a caller who wants a region kept free of filled depth masks it.  A is
+ * CVO_FE_STAGE_UNFILTERED_DEPTH; CVO_FE_STAGE_RAW_DEPTH keeps its meaning.
+ * Under stereo CVO_FE_STAGE_DISPARITY and CVO_FE_STAGE_STEREO stay the matcher's: the stage works on depths only.  A
+ * filled pixel has a depth and DISPARITY 0; a changed pixel has its neighbour's depth and its own disparity.  The table
+ * U(q) of the stereo contract is monotone (a larger disparity is a smaller depth), so the lower median of the depths is
+ * the upper median of the disparities. */
+typedef struct cvo_fe_depth_median {
+    int32_t radius;     /* 1: 3 x 3, 2: 5 x 5 */
+    int32_t fill_min;   /* 0: a pixel without depth stays without; k >= 1: it takes the window's median when at
+                           least k pixels of its window have a depth; at most (2*radius+1)^2 - 1 */
+    int32_t pad_;       /* must be 0 */
+} cvo_fe_depth_median;  /* 12 bytes */
 
 /* One camera of a stereo rig: its pinhole and its lens (k1 k2 p1 p2 k3, as cvo_fe_camera_model's dist). */
 typedef struct cvo_fe_lens {
@@ -536,6 +585,15 @@ int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask);
 int cvo_fe_set_stereo_speckle(cvo_fe_ctx *ctx, const cvo_fe_speckle *sp);
 /* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *set);
+/* The median stage (the median contract at cvo_fe_depth_median); m == NULL: no filter (the state of a new context).  A
+ * setting of the context, like the path mask: every kind of frame reads it and it survives every other setter.  Without
+ * it a frame launches no kernel of the stage and every stage writes where it writes without.  CVO_HIP_ERR_INVALID, the
+ * context keeping what it had: a null context; a frame submitted and not collected; settings cvo_fe_check_depth_median
+ * refuses.  The stage's two planes (A and the flags) take device memory only once it has been set and are given back
+ * when it is cleared. */
+int cvo_fe_set_depth_median(cvo_fe_ctx *ctx, const cvo_fe_depth_median *m);
+/* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int *set);
 /* cvo_fe_submit / cvo_fe_create_pointcloud for a stereo pair: `left` and `right` are height rows of
  * width*3 bytes each, as `img` there (a caller whose right image is grey replicates it); the left image
  * is the colour image of the frame.  CVO_HIP_ERR_INVALID without stereo set.  collect, collect_device,
@@ -666,6 +724,19 @@ int cvo_fe_check_speckle(const cvo_fe_speckle *sp);
  * without such a device. */
 int cvo_fe_filter_speckles(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
                            const cvo_fe_speckle *sp, uint32_t *sizes, int *removed);
+
+/* CVO_HIP_OK for settings cvo_fe_set_depth_median() would accept on an idle context, CVO_HIP_ERR_INVALID otherwise:
+ * NULL; a radius that is not 1 or 2; fill_min outside [0, (2*radius+1)^2 - 1]; pad_ != 0.  The one statement of what is
+ * accepted.  Host only. */
+int cvo_fe_check_depth_median(const cvo_fe_depth_median *m);
+/* The stage of the median contract on any uint16 plane with 0 = none -- a depth image of another pipeline, a disparity
+ * map -- by the kernel a frame runs, without a context: host arrays in and out.  `plane` is height rows of width uint16,
+ * `stride_bytes` BYTES apart; it is A on entry and B on return (the bytes between the rows stay); `flags`, if not NULL,
+ * receives MEDIAN (width*height uint8, dense); *changed and *filled the numbers of pixels with either value.
+ * CVO_HIP_ERR_INVALID for a null plane, `changed` or `filled`, width or height outside [1, 8192],
+ * stride_bytes < width*2 and settings cvo_fe_check_depth_median refuses; CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_median_plane(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
+                        const cvo_fe_depth_median *m, uint8_t *flags, int *changed, int *filled);
 #ifdef __cplusplus
 }
 #endif
