@@ -61,7 +61,7 @@ registration::registration(int mode, int device, void *stream)
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
-      depth_median_(), have_depth_median_(false), select_mode_(CVO_FE_SELECT_IMAGE)
+      depth_median_(), have_depth_median_(false), lidar_(), have_lidar_(false), select_mode_(CVO_FE_SELECT_IMAGE)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -95,6 +95,7 @@ void registration::apply_stored_settings()
         if (have_stereo_speckle_) fe_check(cvo_fe_set_stereo_speckle(fe_, &stereo_speckle_), "cvo_fe_set_stereo_speckle");
         fe_check(cvo_fe_set_select_mode(fe_, select_mode_), "cvo_fe_set_select_mode");
         if (have_depth_median_) fe_check(cvo_fe_set_depth_median(fe_, &depth_median_), "cvo_fe_set_depth_median");
+        if (have_lidar_) fe_check(cvo_fe_set_lidar(fe_, &lidar_), "cvo_fe_set_lidar");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -113,8 +114,13 @@ void registration::apply_stored_settings()
 // src/adaptive_cvo.cpp:451,462).  The cloud never leaves the device: the front end's
 // output arrays go straight into cvo_hip_set_*_device.
 // `stereo`: `dep` is the right colour image of a rectified pair (cvo_fe_submit_stereo) and `rgb` the left one.
-void registration::cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo)
+// `scan`: a LiDAR frame (cvo_fe_submit_lidar); `dep` is `rgb` again and is not read.
+void registration::cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo,
+                                     const scan_view *scan)
 {
+    if (scan && !have_lidar_) throw std::runtime_error("set_pcd_lidar(): no scan source: set_lidar() first");
+    if (!scan && have_lidar_)
+        throw std::runtime_error("set_pcd(): a scan source is set, a frame is an image and a scan: set_pcd_lidar()");
     if (stereo && !have_stereo_) throw std::runtime_error("set_pcd_stereo(): no stereo settings: set_stereo() first");
     if (!stereo && have_stereo_)
         throw std::runtime_error("set_pcd(): stereo is set, a frame is a pair of colour images: set_pcd_stereo()");
@@ -134,7 +140,9 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
     if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
         throw std::runtime_error("set_pcd(): the image size changed within a sequence");
     const int ftype = params_.mode == CVO_HIP_MODE_ACVO ? CVO_FE_FEATURES_HSV : CVO_FE_FEATURES_RGB;
-    int rc = stereo ? cvo_fe_submit_stereo(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint8_t *)dep.data, dep.step,
+    int rc = scan   ? cvo_fe_submit_lidar(fe_, (const uint8_t *)rgb.data, rgb.step, scan->points, scan->stride_bytes,
+                                          scan->num_points, dataset_seq, ftype)
+             : stereo ? cvo_fe_submit_stereo(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint8_t *)dep.data, dep.step,
                                            dataset_seq, ftype)
                     : cvo_fe_submit(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint16_t *)dep.data, dep.step,
                                     dataset_seq, ftype);
@@ -186,6 +194,7 @@ void registration::set_depth_camera(const cvo_fe_depth_camera &rig)
     if (!fe_ && cvo_fe_check_depth_camera(&rig) != CVO_HIP_OK)
         throw std::runtime_error("set_depth_camera(): size in [8, 8192], finite members, fx, fy, depth_scale "
                                  "positive, max_range above min_range, R a rotation");
+    if (!fe_ && have_lidar_) throw std::runtime_error("set_depth_camera(): a scan source is set");
     store<cvo_fe_depth_camera>(cvo_fe_set_depth_camera, "cvo_fe_set_depth_camera", &rig, depth_camera_, have_depth_camera_);
 }
 
@@ -219,6 +228,21 @@ void registration::clear_depth_median()
     store<cvo_fe_depth_median>(cvo_fe_set_depth_median, "cvo_fe_set_depth_median", nullptr, depth_median_, have_depth_median_);
 }
 
+void registration::set_lidar(const cvo_fe_lidar &lidar)
+{
+    if (!fe_ && cvo_fe_check_lidar(&lidar) != CVO_HIP_OK)
+        throw std::runtime_error("set_lidar(): max_points in [1, 2^21], splat in [0, 3], finite members, occl_rel >= 0, "
+                                 "occl_rx and occl_ry in [0, 7], max_range above min_range, R a rotation, pad_ 0");
+    if (!fe_ && (have_stereo_ || have_depth_camera_))
+        throw std::runtime_error("set_lidar(): stereo or a depth camera is set");
+    store<cvo_fe_lidar>(cvo_fe_set_lidar, "cvo_fe_set_lidar", &lidar, lidar_, have_lidar_);
+}
+
+void registration::clear_lidar()
+{
+    store<cvo_fe_lidar>(cvo_fe_set_lidar, "cvo_fe_set_lidar", nullptr, lidar_, have_lidar_);
+}
+
 void registration::set_select_mode(int mode)
 {
     if (!fe_ && cvo_fe_check_select_mode(mode) != CVO_HIP_OK)
@@ -232,6 +256,7 @@ void registration::set_stereo(const cvo_fe_stereo &stereo)
     if (!fe_ && cvo_fe_check_stereo(&stereo) != CVO_HIP_OK)
         throw std::runtime_error("set_stereo(): baseline positive and finite, max_disp a multiple of 8 in [8, 128], "
                                  "min_disp >= 1, 1 <= p1 <= p2 <= 255, uniqueness in [0, 99], lr_max in [-1, 8], pad_ 0");
+    if (!fe_ && have_lidar_) throw std::runtime_error("set_stereo(): a scan source is set");
     store<cvo_fe_stereo>(cvo_fe_set_stereo, "cvo_fe_set_stereo", &stereo, stereo_, have_stereo_);
 }
 
@@ -321,6 +346,20 @@ void registration::set_pcd_stereo(const int dataset_seq, const image_view &left_
     cloud_from_images(dataset_seq, left_img, right_img, true);
 }
 
+void registration::set_pcd_lidar(const int dataset_seq, const image_view &RGB_img, const void *points, size_t stride_bytes,
+                                 int num_points)
+{
+    const scan_view scan{points, stride_bytes, num_points};
+    cloud_from_images(dataset_seq, RGB_img, RGB_img, false, &scan);
+}
+
+void registration::run_cvo_lidar(const int dataset_seq, const image_view &RGB_img, const void *points, size_t stride_bytes,
+                                 int num_points)
+{
+    const scan_view scan{points, stride_bytes, num_points};
+    run_images(dataset_seq, RGB_img, RGB_img, false, &scan);
+}
+
 void registration::run_cvo(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img,
                            const std::string &, const std::string &)
 {
@@ -332,10 +371,11 @@ void registration::run_cvo_stereo(const int dataset_seq, const image_view &left_
     run_images(dataset_seq, left_img, right_img, true);
 }
 
-void registration::run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo)
+void registration::run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo,
+                              const scan_view *scan)
 {   // ref src/cvo.cpp:422-435
     const bool first = !init;
-    cloud_from_images(dataset_seq, rgb, second, stereo);
+    cloud_from_images(dataset_seq, rgb, second, stereo, scan);
     if (first) return;
     align();
     std::cout << "Total iterations: " << iter << std::endl;

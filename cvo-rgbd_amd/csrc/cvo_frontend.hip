@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "cvo_frontend.h"
+#include "cvo_lidar.h"
 #include "cvo_lock.h"
 #include "cvo_median.h"
 #include "cvo_speckle.h"
@@ -1141,6 +1142,17 @@ struct cvo_fe_ctx {
     // with the filter, and gone with it: A of the median contract (rect_plane(np) entries) and the flags
     Dev<uint16_t> unfiltered;
     Dev<uint8_t> median_flags;
+    // the caller's scan source (cvo_fe_set_lidar); with it a frame is a colour image and a scan, and the kernels of
+    // cvo_lidar.hip with k_fe_depth_final between them fill the plane an uploaded depth image fills otherwise
+    cvo_fe_lidar lidar{};
+    bool has_lidar = false;
+    // with a scan source, and gone with it: the scan's staging, pinned and on the device (a header of FE_LIDAR_HEADER
+    // bytes whose first word is the frame's number of points, then max_points packed points), the z-buffer above, and,
+    // with an occlusion test, P0 (rect_plane(np) entries) and the flags
+    Pin<uint8_t> h_scan;
+    Dev<uint8_t> d_scan;
+    Dev<uint16_t> lidar_p0;
+    Dev<uint8_t> lidar_flags;
     // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
     // table U(q) with its staging copy; the cost sums follow max_disp
     Dev<uint8_t> right_img, right_gray, stereo_flags;
@@ -1265,6 +1277,37 @@ bool srig_ok(const cvo_fe_stereo_rig &r)
     return rotation_ok(r.R_left) && rotation_ok(r.R_right);
 }
 
+// what cvo_fe_set_lidar accepts
+bool lidar_ok(const cvo_fe_lidar &l)
+{
+    static_assert(sizeof(cvo_fe_lidar) == 5 * sizeof(int32_t) + 15 * sizeof(float), "80 bytes, no padding");
+    if (l.max_points < 1 || l.max_points > FE_LIDAR_MAX_POINTS || l.splat < 0 || l.splat > 3) return false;
+    const float *f = l.R;   // the 15 floats after the two sizes
+    for (int q = 0; q < 15; ++q)
+        if (!std::isfinite(f[q])) return false;
+    if (l.occl_rel < 0.0f) return false;
+    if (l.occl_rx < 0 || l.occl_rx > FE_LIDAR_RMAX || l.occl_ry < 0 || l.occl_ry > FE_LIDAR_RMAX) return false;
+    if (l.max_range > 0.0f && l.max_range <= l.min_range) return false;
+    return rotation_ok(l.R) && l.pad_ == 0;
+}
+
+inline bool lidar_stride_ok(size_t stride_bytes) { return stride_bytes >= 12 && stride_bytes % 4 == 0; }
+
+inline size_t lidar_scan_bytes(int capacity) { return (size_t)FE_LIDAR_HEADER + (size_t)capacity * 12; }
+
+// `n` points of records `stride` bytes apart into a scan's staging: the count in the header, the points packed
+void lidar_stage(uint8_t *scan, const void *points, size_t stride, int n)
+{
+    int32_t header[FE_LIDAR_HEADER / 4] = {n, 0, 0, 0};
+    std::memcpy(scan, header, sizeof(header));
+    uint8_t *dst = scan + FE_LIDAR_HEADER;
+    if (stride == 12) {
+        if (n) std::memcpy(dst, points, (size_t)n * 12);
+        return;
+    }
+    for (int i = 0; i < n; ++i) std::memcpy(dst + (size_t)i * 12, (const uint8_t *)points + (size_t)i * stride, 12);
+}
+
 // what cvo_fe_set_depth_gate accepts
 bool gate_ok(const cvo_fe_depth_gate &g)
 {
@@ -1355,9 +1398,11 @@ inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? 
 inline uint16_t *filled_plane(const cvo_fe_ctx *ctx) { return ctx->has_median ? ctx->unfiltered.get() : depth_plane(ctx); }
 
 // where the uploaded depth image lands: the raw buffer of a depth camera's size, else the raw depth that
-// k_fe_rectify resamples, else the plane the producers write
+// k_fe_rectify resamples, else the plane the producers write (a scan source: no image is uploaded, and the plane the
+// projected scan fills stands in its place)
 inline uint16_t *depth_upload(const cvo_fe_ctx *ctx)
 {
+    if (ctx->has_lidar) return filled_plane(ctx);
     return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : filled_plane(ctx);
 }
 
@@ -1470,9 +1515,12 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
     // (a median filter: whatever fills the depth plane fills the stage's input, and k_fe_median fills what is named above)
     uint16_t *plane = filled_plane(ctx);
+    // (a scan source: the scan is uploaded in place of a depth image, its count in front, and the projection fills that plane)
     if (ctx->has_stereo)
         FE_HIP(hipMemcpyAsync(ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3,
                               hipMemcpyHostToDevice, s));
+    else if (ctx->has_lidar)
+        FE_HIP(hipMemcpyAsync(ctx->d_scan.get(), ctx->h_scan.get(), lidar_scan_bytes(ctx->lidar.max_points), hipMemcpyHostToDevice, s));
     else
         FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
@@ -1510,7 +1558,8 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     }
     if (ctx->rectify)
         hipLaunchKernelGGL(k_fe_rectify, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->raw_img.get(),
-                           ctx->has_rig ? (const uint16_t *)nullptr : ctx->raw_depth.get(), qu, qv, w, h, img, plane);
+                           ctx->has_rig || ctx->has_lidar ? (const uint16_t *)nullptr : ctx->raw_depth.get(), qu, qv, w, h, img,
+                           plane);
     if (ctx->has_rig) {
         const cvo_fe_depth_camera &r = ctx->rig;
         DepthWarpArgs a{};
@@ -1522,6 +1571,26 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         camera_in_force(ctx, dataset_seq, a.cam);
         hipLaunchKernelGGL(k_fe_depth_warp, dim3(blocks(a.dw * a.dh)), dim3(FE_BLOCK), 0, s, a);
         hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf.get(), np, plane);
+    }
+    if (ctx->has_lidar) {   // (the LiDAR contract; neither stereo nor a depth camera beside it: cvo_fe_set_lidar)
+        const cvo_fe_lidar &l = ctx->lidar;
+        FeLidarProjectArgs a{};
+        a.count = (const int32_t *)ctx->d_scan.get(); a.points = (const float *)(ctx->d_scan.get() + FE_LIDAR_HEADER);
+        a.z = ctx->zbuf.get(); a.capacity = l.max_points; a.w = w; a.h = h; a.splat = l.splat;
+        a.min_range = l.min_range; a.max_range = l.max_range;
+        for (int q = 0; q < 9; ++q) a.R[q] = l.R[q];
+        for (int q = 0; q < 3; ++q) a.T[q] = l.T[q];
+        camera_in_force(ctx, dataset_seq, a.cam);
+        fe_lidar_project_enqueue(a, s);
+        const bool cull = l.occl_rel > 0.0f;   // (without the test P is P0, written where P goes)
+        hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf.get(), np,
+                           cull ? ctx->lidar_p0.get() : plane);
+        if (cull) {
+            FeLidarCullArgs c{};
+            c.p0 = ctx->lidar_p0.get(); c.p = plane; c.flags = ctx->lidar_flags.get();
+            c.w = w; c.h = h; c.rx = l.occl_rx; c.ry = l.occl_ry; c.occl_rel = l.occl_rel;
+            fe_lidar_cull_enqueue(c, s);
+        }
     }
     if (ctx->has_median) {   // (the median contract: directly in front of the gate, for every kind of frame)
         FeMedianArgs m{};
@@ -1713,6 +1782,8 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
                     "max_range above min_range, R a rotation");
     if (rig && ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: stereo is set, there is no depth image");
+    if (rig && ctx->has_lidar)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: a scan source is set, there is no depth image");
     if (!rig && !ctx->has_rig) return CVO_HIP_OK;
     if (rig && ctx->has_rig && std::memcmp(rig, &ctx->rig, sizeof(*rig)) == 0) return CVO_HIP_OK;
     FE_HIP(hipSetDevice(ctx->device));
@@ -1842,6 +1913,7 @@ int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
                     "set_stereo: baseline positive and finite, max_disp a multiple of 8 in [8, 128], min_disp >= 1, "
                     "1 <= p1 <= p2 <= 255, uniqueness in [0, 99], lr_max in [-1, 8], pad_ 0");
     if (st && ctx->has_rig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a depth camera is set");
+    if (st && ctx->has_lidar) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a scan source is set");
     if (st && ctx->rectify)
         return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: the camera model has a lens distortion; the pair must be rectified");
     if (!st && ctx->has_srig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a stereo rig is set: clear the rig first");
@@ -2009,6 +2081,75 @@ int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     *out = ctx->has_median ? ctx->median : cvo_fe_depth_median{};
     if (set) *set = ctx->has_median ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_check_lidar(const cvo_fe_lidar *l) { return l && lidar_ok(*l) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
+
+int cvo_fe_set_lidar(cvo_fe_ctx *ctx, const cvo_fe_lidar *l)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar: a frame is in flight");
+    if (l && !lidar_ok(*l))
+        return fail(ctx, CVO_HIP_ERR_INVALID,
+                    "set_lidar: max_points in [1, 2^21], splat in [0, 3], finite members, occl_rel >= 0, occl_rx and occl_ry "
+                    "in [0, 7], max_range above min_range, R a rotation, pad_ 0");
+    if (l && ctx->has_stereo) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar: stereo is set");
+    if (l && ctx->has_rig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar: a depth camera is set");
+    if (!l && !ctx->has_lidar) return CVO_HIP_OK;
+    if (l && ctx->has_lidar && std::memcmp(l, &ctx->lidar, sizeof(*l)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Pin<uint8_t> h_scan;
+    Dev<uint8_t> d_scan, flags;
+    Dev<uint16_t> p0;
+    Dev<uint32_t> z;
+    const size_t nz = rect_plane(ctx->np);
+    if (l) {
+        const size_t bytes = lidar_scan_bytes(l->max_points);
+        const bool resize = !ctx->has_lidar || l->max_points != ctx->lidar.max_points;
+        if (resize && !(pin_alloc(h_scan, bytes) && dev_alloc(d_scan, bytes)))
+            return no_memory(ctx, "set_lidar: pinned and device memory for a scan of max_points points");
+        if (!ctx->zbuf && !dev_alloc(z, nz)) return no_memory(ctx, "set_lidar: device memory for the z-buffer");
+        if (l->occl_rel > 0.0f && !ctx->lidar_p0 && !(dev_alloc(p0, nz) && dev_alloc(flags, nz)))
+            return no_memory(ctx, "set_lidar: device memory for the plane before culling and the flags");
+        if (h_scan) std::memset(h_scan.get(), 0, FE_LIDAR_HEADER);   // (a scan of no points until the first frame)
+    }
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    // a new z-buffer is armed here; every frame's k_fe_depth_final arms it after that
+    if (e == hipSuccess && z) e = hipMemset(z.get(), 0xFF, nz * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, CVO_HIP_ERR_HIP, "set_lidar", e);
+    }
+    hand_over(ctx->h_scan, h_scan);
+    hand_over(ctx->d_scan, d_scan);
+    hand_over(ctx->zbuf, z);
+    hand_over(ctx->lidar_p0, p0);
+    hand_over(ctx->lidar_flags, flags);
+    if (!l) {   // (given back: a depth camera set later makes its own z-buffer)
+        ctx->h_scan.reset();
+        ctx->d_scan.reset();
+        ctx->zbuf.reset();
+    }
+    if (!l || !(l->occl_rel > 0.0f)) {
+        ctx->lidar_p0.reset();
+        ctx->lidar_flags.reset();
+    }
+    ctx->has_lidar = l != nullptr;
+    ctx->lidar = l ? *l : cvo_fe_lidar{};
+    drop_graphs(ctx);   // (the kind of a frame, the settings, the scan's capacity and the planes are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_lidar(const cvo_fe_ctx *ctx, cvo_fe_lidar *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_lidar ? ctx->lidar : cvo_fe_lidar{};
+    if (set) *set = ctx->has_lidar ? 1 : 0;
     return CVO_HIP_OK;
 }
 
@@ -2377,17 +2518,26 @@ int cvo_fe_set_num_want(cvo_fe_ctx *ctx, int num_want)
 
 namespace {
 
-// submit() of either kind of frame: `second` is the depth image (uint16 rows) of a depth frame and the right colour
-// image of a stereo frame (`stereo`); the kind must be the one the context is set up for
+// submit() of any kind of frame: `second` is the depth image (uint16 rows) of a depth frame, the right colour image of
+// a stereo frame (`stereo`), and the `num_points` records of a scan, second_stride bytes apart, of a LiDAR frame
+// (`lidar`); the kind must be the one the context is set up for
 int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *second, size_t second_stride,
-                 int dataset_seq, int feature_type, bool stereo)
+                 int dataset_seq, int feature_type, bool stereo, bool lidar = false, int num_points = 0)
 {
     const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
     const int dw = ctx->dw, dh = ctx->dh;   // (the depth camera's image, if the context has one)
+    if (lidar != ctx->has_lidar)
+        return fail(ctx, CVO_HIP_ERR_INVALID, lidar ? "submit_lidar: no scan source (cvo_fe_set_lidar)"
+                                                    : "submit: a scan source is set, a frame is an image and a scan (cvo_fe_submit_lidar)");
     if (stereo != ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, stereo ? "submit_stereo: no stereo settings (cvo_fe_set_stereo)"
                                                      : "submit: stereo is set, a frame is a stereo pair (cvo_fe_submit_stereo)");
-    if (!img || !second || img_stride < (size_t)w * 3 || second_stride < (stereo ? (size_t)w * 3 : (size_t)dw * 2) ||
+    if (lidar && (num_points < 0 || num_points > ctx->lidar.max_points || !lidar_stride_ok(second_stride) ||
+                  (!second && num_points > 0)))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "submit_lidar: num_points in [0, max_points], a stride of at least 12 bytes "
+                                              "and a multiple of 4, points not null");
+    if (!img || (!second && !lidar) || img_stride < (size_t)w * 3 ||
+        (!lidar && second_stride < (stereo ? (size_t)w * 3 : (size_t)dw * 2)) ||
         (feature_type != CVO_FE_FEATURES_HSV && feature_type != CVO_FE_FEATURES_RGB))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit: bad argument");
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the previous frame was not collected");
@@ -2411,7 +2561,9 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
             ctx->table_fx = cam[1];
             ctx->table_scale = cam[0];
         }
-    } else if (!(second == ctx->h_depth.get() && second_stride == (size_t)dw * 2))
+    } else if (lidar)
+        lidar_stage(ctx->h_scan.get(), second, second_stride, num_points);
+    else if (!(second == ctx->h_depth.get() && second_stride == (size_t)dw * 2))
         copy_rows(ctx->h_depth.get(), second, second_stride, (size_t)dw * 2, dh);
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
@@ -2485,6 +2637,14 @@ int cvo_fe_submit_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_strid
     return submit_frame(ctx, left, left_stride, right, right_stride, dataset_seq, feature_type, true);
 }
 
+int cvo_fe_submit_lidar(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *points, size_t stride_bytes,
+                        int num_points, int dataset_seq, int feature_type)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    return submit_frame(ctx, img, img_stride, points, stride_bytes, dataset_seq, feature_type, false, true, num_points);
+}
+
 int cvo_fe_collect(cvo_fe_ctx *ctx, float *positions, float *features, int capacity, int *num_points)
 {
     cvo_lock::Api api_guard;
@@ -2531,6 +2691,19 @@ int cvo_fe_create_pointcloud_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t
     return cvo_fe_collect(ctx, positions, features, capacity, num_points);
 }
 
+int cvo_fe_create_pointcloud_lidar(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *points,
+                                   size_t stride_bytes, int num_points, int dataset_seq, int feature_type,
+                                   float *positions, float *features, int capacity, int *num_points_out)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (!num_points_out || capacity < 0 || (capacity > 0 && (!positions || !features)))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "create_pointcloud_lidar: bad argument");
+    const int rc = cvo_fe_submit_lidar(ctx, img, img_stride, points, stride_bytes, num_points, dataset_seq, feature_type);
+    if (rc) return rc;
+    return cvo_fe_collect(ctx, positions, features, capacity, num_points_out);
+}
+
 int cvo_fe_get_info(const cvo_fe_ctx *ctx, cvo_fe_info *out)
 {
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
@@ -2573,10 +2746,15 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_SPECKLE_SIZE: src = ctx->speckle_words ? ctx->speckle_words.get() + 2 * np : nullptr; need = np * 4; break;
     case CVO_FE_STAGE_UNFILTERED_DEPTH: src = ctx->unfiltered.get(); need = np * 2; break;
     case CVO_FE_STAGE_MEDIAN: src = ctx->median_flags.get(); need = np; break;
+    // (without the occlusion test P0 is P, and the flags are made from it below: no plane of their own)
+    case CVO_FE_STAGE_LIDAR_DEPTH: src = ctx->lidar_p0 ? ctx->lidar_p0.get() : filled_plane(ctx); need = np * 2; break;
+    case CVO_FE_STAGE_LIDAR: src = ctx->lidar_flags.get(); need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if ((stage == CVO_FE_STAGE_UNFILTERED_DEPTH || stage == CVO_FE_STAGE_MEDIAN) && !ctx->has_median)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the median filter, and no filter is set");
+    if ((stage == CVO_FE_STAGE_LIDAR_DEPTH || stage == CVO_FE_STAGE_LIDAR) && !ctx->has_lidar)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of a scan source, and none is set");
     if (stage >= CVO_FE_STAGE_RIGHT_GRAY && stage <= CVO_FE_STAGE_SPECKLE_SIZE && !ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a stage of a stereo frame, and stereo is not set");
     if (stage == CVO_FE_STAGE_STEREO_VALID && !ctx->has_srig)
@@ -2586,6 +2764,13 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     if (bytes < need) return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: buffer too small");
     FE_HIP(hipSetDevice(ctx->device));
     FE_HIP(hipStreamSynchronize(ctx->stream));
+    if (stage == CVO_FE_STAGE_LIDAR && !src) {   // (no occlusion test: HIT where the plane holds a depth)
+        std::vector<uint16_t> p0;
+        try { p0.resize(np); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "read_stage"); }
+        FE_HIP(hipMemcpy(p0.data(), filled_plane(ctx), np * 2, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < np; ++i) ((uint8_t *)out)[i] = p0[i] ? (uint8_t)CVO_FE_LIDAR_HIT : (uint8_t)0;
+        return CVO_HIP_OK;
+    }
     if (!src) {   // (the flags of a context without gate and mask: there is no such plane, and nothing is flagged)
         std::memset(out, 0, need);
         return CVO_HIP_OK;
@@ -2609,3 +2794,90 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
 }
 
 }   // extern "C"
+
+namespace {
+
+// the device memory and the stream of one cvo_fe_project_points call
+struct ProjectCall {
+    Dev<uint8_t> scan, flags;
+    Dev<uint32_t> z;
+    Dev<uint16_t> planes;
+    hipStream_t s = nullptr;
+    ~ProjectCall()
+    {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+}   // namespace
+
+extern "C" int cvo_fe_project_points(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
+                                     const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled,
+                                     uint8_t *flags, int *hits, int *occluded)
+{
+    cvo_lock::Api api_guard;
+    if (!plane || !cam || !hits || !occluded || n < 0 || n > FE_LIDAR_MAX_POINTS || (!points && n > 0) ||
+        !lidar_stride_ok(stride_bytes) || width < 1 || height < 1 || width > 8192 || height > 8192)
+        return CVO_HIP_ERR_INVALID;
+    for (int q = 0; q < 5; ++q)
+        if (!std::isfinite(cam[q])) return CVO_HIP_ERR_INVALID;
+    if (!(cam[0] > 0.0f && cam[1] > 0.0f && cam[2] > 0.0f)) return CVO_HIP_ERR_INVALID;
+    if (!l) return CVO_HIP_ERR_INVALID;
+    cvo_fe_lidar checked = *l;
+    checked.max_points = 1;   // (not read beyond n <= 2^21)
+    if (!lidar_ok(checked)) return CVO_HIP_ERR_INVALID;
+    *hits = 0;
+    *occluded = 0;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return CVO_HIP_ERR_NODEVICE; }
+#define LD_TRY(e) do { if ((e) != hipSuccess) { (void)hipGetLastError(); return CVO_HIP_ERR_HIP; } } while (0)
+    const int np = width * height;
+    const size_t cells = rect_plane(np), scan_bytes = lidar_scan_bytes(n);
+    const bool cull = l->occl_rel > 0.0f;
+    std::vector<uint8_t> scan, fl;
+    std::vector<uint16_t> p0;
+    try { scan.resize(scan_bytes); fl.resize((size_t)np); p0.resize((size_t)np); } catch (const std::bad_alloc &) { return CVO_HIP_ERR_NOMEM; }
+    lidar_stage(scan.data(), points, stride_bytes, n);
+    ProjectCall c;
+    if (!dev_alloc(c.scan, scan_bytes) || !dev_alloc(c.z, cells) || !dev_alloc(c.planes, 2 * cells) || !dev_alloc(c.flags, cells)) {
+        (void)hipGetLastError();
+        return CVO_HIP_ERR_NOMEM;
+    }
+    uint16_t *d_p0 = c.planes.get(), *d_p = c.planes.get() + cells;
+    LD_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
+    LD_TRY(hipMemcpyAsync(c.scan.get(), scan.data(), scan_bytes, hipMemcpyHostToDevice, c.s));
+    LD_TRY(hipMemsetAsync(c.z.get(), 0xFF, cells * sizeof(uint32_t), c.s));
+    if (n > 0) {
+        FeLidarProjectArgs a{};
+        a.count = (const int32_t *)c.scan.get(); a.points = (const float *)(c.scan.get() + FE_LIDAR_HEADER);
+        a.z = c.z.get(); a.capacity = n; a.w = width; a.h = height; a.splat = l->splat;
+        a.min_range = l->min_range; a.max_range = l->max_range;
+        for (int q = 0; q < 9; ++q) a.R[q] = l->R[q];
+        for (int q = 0; q < 3; ++q) a.T[q] = l->T[q];
+        for (int q = 0; q < 5; ++q) a.cam[q] = cam[q];
+        fe_lidar_project_enqueue(a, c.s);
+    }
+    hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, c.s, c.z.get(), np, d_p0);
+    if (cull) {
+        FeLidarCullArgs g{};
+        g.p0 = d_p0; g.p = d_p; g.flags = c.flags.get();
+        g.w = width; g.h = height; g.rx = l->occl_rx; g.ry = l->occl_ry; g.occl_rel = l->occl_rel;
+        fe_lidar_cull_enqueue(g, c.s);
+    }
+    LD_TRY(hipGetLastError());
+    LD_TRY(hipMemcpyAsync(p0.data(), d_p0, (size_t)np * 2, hipMemcpyDeviceToHost, c.s));
+    LD_TRY(hipMemcpyAsync(plane, cull ? d_p : d_p0, (size_t)np * 2, hipMemcpyDeviceToHost, c.s));
+    if (cull) LD_TRY(hipMemcpyAsync(fl.data(), c.flags.get(), (size_t)np, hipMemcpyDeviceToHost, c.s));
+    LD_TRY(hipStreamSynchronize(c.s));
+#undef LD_TRY
+    int nh = 0, no = 0;
+    for (int i = 0; i < np; ++i) {
+        if (!cull) fl[i] = p0[i] ? (uint8_t)CVO_FE_LIDAR_HIT : (uint8_t)0;
+        nh += (fl[i] & CVO_FE_LIDAR_HIT) ? 1 : 0;
+        no += (fl[i] & CVO_FE_LIDAR_OCCLUDED) ? 1 : 0;
+    }
+    if (unculled) std::memcpy(unculled, p0.data(), (size_t)np * 2);
+    if (flags) std::memcpy(flags, fl.data(), (size_t)np);
+    *hits = nh;
+    *occluded = no;
+    return CVO_HIP_OK;
+}

@@ -12,6 +12,12 @@ include/cvo_frontend.h; frames of either kind):
 
     gen.set_depth_median(DepthMedian(radius=1, fill_min=5))
 
+A LiDAR scan in place of the depth image, projected into the colour camera on the device (the LiDAR contract of
+include/cvo_frontend.h; KITTI: R, T from R_rect_00 * Tr_velo_to_cam):
+
+    gen.set_lidar(Lidar(max_points=130000, R=R, T=T, splat=1, occl_rel=0.25, occl_rx=7, occl_ry=1))
+    xyz, feat = gen.create_pointcloud_lidar(bgr, scan, dataset_seq=4)   # scan: n x 4 float32, x y z reflectance
+
 A rectified stereo pair in place of the depth image (the stereo contract of include/cvo_frontend.h):
 
     gen = PcdGenerator(width=1241, height=376)
@@ -46,10 +52,12 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
 (STAGE_GRAY, STAGE_HSV, STAGE_MAP, STAGE_AG0, STAGE_AG1, STAGE_AG2, STAGE_THS, STAGE_DX0, STAGE_DY0,
  STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
  STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
- STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE, STAGE_UNFILTERED_DEPTH, STAGE_MEDIAN) = range(26)
+ STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE, STAGE_UNFILTERED_DEPTH, STAGE_MEDIAN, STAGE_LIDAR_DEPTH,
+ STAGE_LIDAR) = range(28)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 MEDIAN_CHANGED, MEDIAN_FILLED = 1, 2   # the values of STAGE_MEDIAN
+LIDAR_HIT, LIDAR_OCCLUDED = 1, 2       # the bits of STAGE_LIDAR
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
 # modes of the selector (set_select_mode): by the image alone (the reference; a new object's), or among the pixels
@@ -67,7 +75,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths", "cvo_fe_check_speckle", "cvo_fe_set_stereo_speckle",
            "cvo_fe_get_stereo_speckle", "cvo_fe_filter_speckles", "cvo_fe_check_select_mode", "cvo_fe_set_select_mode",
            "cvo_fe_get_select_mode", "cvo_fe_check_depth_median", "cvo_fe_set_depth_median", "cvo_fe_get_depth_median",
-           "cvo_fe_median_plane")
+           "cvo_fe_median_plane", "cvo_fe_check_lidar", "cvo_fe_set_lidar", "cvo_fe_get_lidar", "cvo_fe_submit_lidar",
+           "cvo_fe_create_pointcloud_lidar", "cvo_fe_project_points")
 
 
 class Info(C.Structure):
@@ -167,6 +176,26 @@ class DepthMedian(_Settings):
 
     def __init__(self, radius=1, fill_min=0, pad_=0):
         super().__init__(int(radius), int(fill_min), int(pad_))
+
+
+class Lidar(_Settings):
+    """cvo_fe_lidar: a LiDAR scan in place of the depth image (the LiDAR contract of include/cvo_frontend.h).
+    `max_points`: the capacity of a scan, 1 .. 2^21 (a frame copies a staging of this size); `splat` 0..3: a point writes
+    the (2*splat+1)^2 pixels around its nearest pixel; p_colour = R p_lidar + T (R row-major, T in metres);
+    `min_range` / `max_range` in metres along the colour camera's axis, <= 0: no limit on that side; `occl_rel` 0: no
+    occlusion test, > 0: a pixel farther than (1 + occl_rel) times the nearest depth of its window of half-widths
+    (`occl_rx`, `occl_ry`), 0..7 each, is dropped."""
+    _fields_ = [("max_points", C.c_int32), ("splat", C.c_int32), ("R", C.c_float * 9), ("T", C.c_float * 3),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("occl_rel", C.c_float), ("occl_rx", C.c_int32),
+                ("occl_ry", C.c_int32), ("pad_", C.c_int32)]
+
+    def __init__(self, max_points=131072, splat=0, R=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), T=(0.0, 0.0, 0.0),
+                 min_range=0.0, max_range=0.0, occl_rel=0.0, occl_rx=0, occl_ry=0, pad_=0):
+        R = [float(v) for v in np.asarray(R, np.float64).reshape(-1)]
+        if len(R) != 9 or len(T) != 3:
+            raise ValueError("R is 3 x 3; T holds 3 numbers")
+        super().__init__(int(max_points), int(splat), (C.c_float * 9)(*R), (C.c_float * 3)(*T), min_range, max_range,
+                         occl_rel, int(occl_rx), int(occl_ry), int(pad_))
 
 
 class Lens(_Settings):
@@ -296,6 +325,14 @@ def lib():
         L.cvo_fe_get_depth_median.argtypes = [vp, C.POINTER(DepthMedian), C.POINTER(C.c_int)]
         L.cvo_fe_median_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthMedian), u8p,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.cvo_fe_check_lidar.argtypes = [C.POINTER(Lidar)]
+        L.cvo_fe_set_lidar.argtypes = [vp, C.POINTER(Lidar)]
+        L.cvo_fe_get_lidar.argtypes = [vp, C.POINTER(Lidar), C.POINTER(C.c_int)]
+        L.cvo_fe_submit_lidar.argtypes = [vp, u8p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]
+        L.cvo_fe_create_pointcloud_lidar.argtypes = [vp, u8p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                                     fp, fp, C.c_int, C.POINTER(C.c_int)]
+        L.cvo_fe_project_points.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Lidar), fp, C.c_int, C.c_int,
+                                            u16p, u16p, u8p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
         L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
         L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
@@ -424,6 +461,51 @@ def median_plane(plane, median, device=0):
                                          flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(changed), C.byref(filled)),
                what="median_plane")
     return plane, flags, changed.value, filled.value
+
+
+def check_lidar(lidar):
+    """True for a Lidar set_lidar() accepts on a generator without stereo and depth camera (cvo_fe_check_lidar); None is
+    refused.  Host only."""
+    if lidar is None:
+        return lib().cvo_fe_check_lidar(None) == 0
+    return lib().cvo_fe_check_lidar(C.byref(lidar)) == 0
+
+
+def _scan(points):
+    """A scan as the C side takes it: (a float32 array that owns the records, its address, the stride in bytes, n).
+    `points` is n x k float32 with k >= 3, x y z first (KITTI: n x 4); any row stride that is a multiple of 4."""
+    pts = np.asarray(points)
+    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] < 3:
+        pts = np.asarray(points, np.float32)
+        if pts.ndim != 2 or pts.shape[1] < 3:
+            raise ValueError("expected an n x k float32 array of points, k >= 3, x y z first")
+    n = pts.shape[0]
+    if n and (pts.strides[1] != 4 or pts.strides[0] < 12 or pts.strides[0] % 4):
+        pts = np.ascontiguousarray(pts)
+    stride = pts.strides[0] if n else max(12, 4 * pts.shape[1])
+    return pts, (pts.ctypes.data if n else None), stride, n
+
+
+def project_points(points, lidar, cam, width, height, device=0):
+    """The stage of the LiDAR contract on any scan (cvo_fe_project_points: the kernels a frame runs, without a
+    generator).  `points`: n x k float32, x y z first; `cam`: the colour camera (depth scale, fx, fy, cx, cy), e.g.
+    tuple(camera(4).values()).  Returns (P as h x w uint16, P0 likewise, the flags as h x w uint8 of LIDAR_HIT /
+    LIDAR_OCCLUDED, the number of pixels hit, the number of those dropped as occluded)."""
+    pts, addr, stride, n = _scan(points)
+    cam = np.ascontiguousarray(cam, np.float32)
+    if cam.shape != (5,):
+        raise ValueError("cam holds depth scale, fx, fy, cx, cy")
+    w, h = int(width), int(height)
+    if not (1 <= w <= 8192 and 1 <= h <= 8192):
+        raise capi.CvoHipError("project_points: width and height in [1, 8192]")
+    plane, p0, flags = np.empty((h, w), np.uint16), np.empty((h, w), np.uint16), np.empty((h, w), np.uint8)
+    hits, occluded = C.c_int(0), C.c_int(0)
+    u16p = C.POINTER(C.c_uint16)
+    capi.check(lib().cvo_fe_project_points(int(device), addr, stride, n, None if lidar is None else C.byref(lidar),
+                                           cam.ctypes.data_as(C.POINTER(C.c_float)), w, h, plane.ctypes.data_as(u16p),
+                                           p0.ctypes.data_as(u16p), flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           C.byref(hits), C.byref(occluded)), what="project_points")
+    return plane, p0, flags, hits.value, occluded.value
 
 
 def stereo_depth_table(stereo, fx, depth_scale):
@@ -654,6 +736,46 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_depth_median(self._h, C.byref(out), C.byref(isset)), "get_depth_median")
         return out if isset.value else None
 
+    def set_lidar(self, lidar):
+        """A Lidar for every following frame: a frame is then a colour image and a scan (submit_lidar /
+        create_pointcloud_lidar), projected into the colour camera on the device (the LiDAR contract of
+        include/cvo_frontend.h); None: back to depth images, as for a new object.  Refused beside stereo and a depth
+        camera, and they beside it."""
+        self._chk(lib().cvo_fe_set_lidar(self._h, None if lidar is None else C.byref(lidar)), "set_lidar")
+
+    def lidar(self):
+        """The Lidar set, or None."""
+        out, isset = Lidar(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_lidar(self._h, C.byref(out), C.byref(isset)), "get_lidar")
+        return out if isset.value else None
+
+    def _image(self, bgr):
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        if bgr.shape != (self.height, self.width, 3):
+            raise ValueError("expected a %dx%dx3 uint8 image" % (self.height, self.width))
+        return bgr
+
+    def create_pointcloud_lidar(self, bgr, points, dataset_seq=4, feature_type=FEATURES_RGB):
+        """create_pointcloud() for a colour image and a scan: `points` is n x k float32, x y z first (KITTI's .bin read
+        with np.fromfile(..., np.float32).reshape(-1, 4))."""
+        bgr = self._image(bgr)
+        pts, addr, stride, npts = _scan(points)
+        n = C.c_int(0)
+        fp = C.POINTER(C.c_float)
+        st = lib().cvo_fe_create_pointcloud_lidar(
+            self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3, addr, stride, npts, int(dataset_seq),
+            int(feature_type), self._pos.ctypes.data_as(fp), self._feat.ctypes.data_as(fp), self.capacity, C.byref(n))
+        self._chk(st, "create_pointcloud_lidar")
+        return self._pos[:n.value].copy(), self._feat[:n.value].copy()
+
+    def submit_lidar(self, bgr, points, dataset_seq=4, feature_type=FEATURES_RGB):
+        """submit() for a colour image and a scan; collect() / collect_device() as for any other frame.  The points are
+        copied before the call returns."""
+        bgr = self._image(bgr)
+        pts, addr, stride, npts = _scan(points)
+        self._chk(lib().cvo_fe_submit_lidar(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3, addr, stride,
+                                            npts, int(dataset_seq), int(feature_type)), "submit_lidar")
+
     def set_select_mode(self, mode):
         """The selector's mode for every following frame (the selection contract of include/cvo_frontend.h): SELECT_IMAGE
         (a new object's: the reference's selector, by the image alone) or SELECT_DEPTH (a pixel without depth does not
@@ -728,7 +850,8 @@ class PcdGenerator:
                   STAGE_SGM_SUM: ((h, w, self._max_disp), np.uint16), STAGE_DISPARITY: ((h, w), np.uint16),
                   STAGE_STEREO: ((h, w), np.uint8), STAGE_RIGHT_BGR: ((h, w, 3), np.uint8),
                   STAGE_STEREO_VALID: ((h, w), np.uint8), STAGE_SPECKLE_SIZE: ((h, w), np.uint32),
-                  STAGE_UNFILTERED_DEPTH: ((h, w), np.uint16), STAGE_MEDIAN: ((h, w), np.uint8)}
+                  STAGE_UNFILTERED_DEPTH: ((h, w), np.uint16), STAGE_MEDIAN: ((h, w), np.uint8),
+                  STAGE_LIDAR_DEPTH: ((h, w), np.uint16), STAGE_LIDAR: ((h, w), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -775,8 +898,10 @@ def load_img(rgb_path, depth_path):
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
-               stereo_speckle=None, select_mode=None, depth_median=None):
+               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `lidar`: a Lidar for the generator: `frames` then yields (name, bgr, points), a colour image and a scan (n x k
+    float32, x y z first), and the depth comes from the scan projected on the device; None leaves the generator as it is.
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
     pair, and the depth comes from the matcher on the device; None leaves the generator as it is and takes depth frames.
     `stereo_rig`: a StereoRig for the generator, beside `stereo`: the pairs are then RAW and are rectified on the
@@ -826,7 +951,9 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_select_mode(select_mode)
     if depth_median is not None:
         gen.set_depth_median(depth_median)
-    submit = gen.submit_stereo if stereo is not None else gen.submit
+    if lidar is not None:
+        gen.set_lidar(lidar)
+    submit = gen.submit_stereo if stereo is not None else gen.submit_lidar if lidar is not None else gen.submit
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype)
     while cur is not None:
@@ -906,3 +1033,30 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
                       stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode,
                       depth_median=depth_median)
+
+
+def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, image="image_2", scans="velodyne",
+                        times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
+                        select_mode=None, depth_median=None):
+    """run_directory() for the KITTI odometry layout with its scans: one line of `folder`/`times` per frame (the line is
+    the frame's name), the colour image in `folder`/`image`/%06d.png, decoded by PIL as load_img does (B, G, R; a grey
+    image is replicated), and the scan in `folder`/`scans`/%06d.bin, records of four float32 (x y z reflectance).
+    `lidar`: the Lidar for the generator, e.g. Lidar(130000, 1, R, T, occl_rel=0.25, occl_rx=7, occl_ry=1) with R, T of
+    R_rect_00 * Tr_velo_to_cam and dataset_seq 4.  `camera`, `depth_gate`, `mask`, `select_mode`, `depth_median`: as in
+    run_frames, e.g. SELECT_DEPTH and DepthMedian(1, 3) for a plane as sparse as a projected scan."""
+    with open(os.path.join(folder, times)) as fh:
+        names = [line.strip() for line in fh if line.strip()]
+    if limit is not None:
+        names = names[:limit]
+
+    def colour(path):
+        from PIL import Image
+        return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"), np.uint8)[:, :, ::-1])
+
+    def decoded():
+        for k, name in enumerate(names):
+            yield (name, colour(os.path.join(folder, image, "%06d.png" % k)),
+                   np.fromfile(os.path.join(folder, scans, "%06d.bin" % k), np.float32).reshape(-1, 4))
+
+    return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
+                      depth_gate=depth_gate, mask=mask, select_mode=select_mode, depth_median=depth_median, lidar=lidar)

@@ -166,6 +166,17 @@ class registration {
     void clear_stereo_rig();
     void set_pcd_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
     void run_cvo_stereo(const int dataset_seq, const image_view &left_img, const image_view &right_img);
+    // A LiDAR scan in place of the depth image: cvo_fe_set_lidar.  A frame is then a colour image and a scan and goes in
+    // through set_pcd_lidar() / run_cvo_lidar() -- the image form of set_pcd() / run_cvo() with `num_points` records
+    // `stride_bytes` apart, x y z first, in place of the depth image; the scan is projected into the colour camera on
+    // the device (the LiDAR contract: cvo_frontend.h).  May be called before the first image; throws for settings the
+    // front end refuses, and beside stereo or a depth camera.  clear_lidar(): depth images again.
+    void set_lidar(const cvo_fe_lidar &lidar);
+    void clear_lidar();
+    void set_pcd_lidar(const int dataset_seq, const image_view &RGB_img, const void *points, size_t stride_bytes,
+                       int num_points);
+    void run_cvo_lidar(const int dataset_seq, const image_view &RGB_img, const void *points, size_t stride_bytes,
+                       int num_points);
     int num_points_last_frame() const { return fe_points_; }
     // Batched mode: align() of `count` objects (each with its moving cloud set) in
     // one call, their kernel launches shared (cvo_hip_align_many).  The result of
@@ -203,6 +214,8 @@ class registration {
     bool have_stereo_speckle_;
     cvo_fe_depth_median depth_median_;   // what set_depth_median() gave, likewise
     bool have_depth_median_;
+    cvo_fe_lidar lidar_;                 // what set_lidar() gave, likewise
+    bool have_lidar_;
     int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
@@ -211,8 +224,15 @@ class registration {
     void store(int (*set)(cvo_fe_ctx *, const S *), const char *what, const S *value, S &kept, bool &have);
     void store_mask(const image_view *mask);
     void publish();
-    void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo);
-    void run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo);
+    struct scan_view {   // the scan of a LiDAR frame: what stands in the depth image's place
+        const void *points;
+        size_t stride_bytes;
+        int num_points;
+    };
+    void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo,
+                           const scan_view *scan = nullptr);
+    void run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo,
+                    const scan_view *scan = nullptr);
 };
 
 }   // namespace cvo_hip

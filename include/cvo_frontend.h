@@ -49,7 +49,10 @@
  * cvo_fe_set_select_mode below; a new context selects by the image alone, as the reference does.  And a median
  * filter on the depth plane itself, in front of the gate, for every kind of frame (cvo_fe_set_depth_median;
  * cvo_fe_median_plane for any uint16 plane): a lone outlier takes its neighbourhood's value and, if asked for, a small
- * hole is filled.  The median contract is stated at cvo_fe_depth_median below.
+ * hole is filled.  The median contract is stated at cvo_fe_depth_median below.  And a LiDAR scan in place of the depth
+ * image (cvo_fe_set_lidar, cvo_fe_submit_lidar; cvo_fe_project_points for any scan without a context): the points are
+ * projected into the colour camera on the device, nearest surface wins, and what the scanner sees between the points of
+ * a nearer object is culled.  The LiDAR contract is stated at cvo_fe_lidar below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -107,7 +110,11 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        /* of a frame under a median filter (cvo_fe_set_depth_median; CVO_HIP_ERR_INVALID on a context without one).
           With the filter UNGATED_DEPTH, "the plane the gate read", is B of the median contract. */
        CVO_FE_STAGE_UNFILTERED_DEPTH = 24,    /* A of the median contract: w*h uint16 */
-       CVO_FE_STAGE_MEDIAN = 25 };        /* MEDIAN of the median contract: w*h uint8, CVO_FE_MEDIAN_* */
+       CVO_FE_STAGE_MEDIAN = 25,          /* MEDIAN of the median contract: w*h uint8, CVO_FE_MEDIAN_* */
+       /* of a frame under a scan source (cvo_fe_set_lidar; CVO_HIP_ERR_INVALID on a context without one).  With it
+          RAW_DEPTH is P of the LiDAR contract. */
+       CVO_FE_STAGE_LIDAR_DEPTH = 26,     /* P0 of the LiDAR contract, the plane before culling: w*h uint16 */
+       CVO_FE_STAGE_LIDAR = 27 };         /* w*h uint8, CVO_FE_LIDAR_* */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
@@ -117,6 +124,9 @@ enum { CVO_FE_STEREO_UNIQUE = 1, CVO_FE_STEREO_LR = 2, CVO_FE_STEREO_MIN = 4, CV
        CVO_FE_STEREO_SPECKLE = 32 };   /* (only under a speckle filter: the speckle contract at cvo_fe_speckle) */
 /* values of CVO_FE_STAGE_MEDIAN (the median contract at cvo_fe_depth_median) */
 enum { CVO_FE_MEDIAN_CHANGED = 1, CVO_FE_MEDIAN_FILLED = 2 };
+/* bits of CVO_FE_STAGE_LIDAR (the LiDAR contract at cvo_fe_lidar): HIT where P0 != 0; OCCLUDED beside it where the
+   occlusion test dropped the pixel */
+enum { CVO_FE_LIDAR_HIT = 1, CVO_FE_LIDAR_OCCLUDED = 2 };
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141; under
@@ -380,6 +390,59 @@ typedef struct cvo_fe_depth_median {
     int32_t pad_;       /* must be 0 */
 } cvo_fe_depth_median;  /* 12 bytes */
 
+/* A LiDAR scan in place of the depth image: a camera beside a Velodyne, an Ouster or a Livox (KITTI's rig ships a scan
+ * per frame and Tr_velo_to_cam in every sequence's calib.txt).  A scan projected into the image is one small launch and
+ * is as accurate at 60 m as at 6 m, where a stereo pair's depth error grows with the square of the range.  The plane it
+ * leaves has many holes; everything behind it is built for such a plane: CVO_FE_SELECT_DEPTH keeps the cloud at
+ * num_want, the median stage with fill_min closes the gaps between scan lines, the gate drops range and jumps.
+ *
+ * THE LIDAR CONTRACT.  While a scan source is set a frame of the context is one colour image and n points,
+ * 0 <= n <= max_points.  The results are defined by the arithmetic below, not by the device.  It is this library's own
+ * definition and is NOT pinned against any SDK.
+ * The points are the first three floats (x y z) of records stride_bytes apart; stride_bytes is at least 12 and a
+ * multiple of 4 (KITTI's .bin: 16; the reflectance is not read).
+ * The colour camera in force, c, is the cvo_fe_set_camera model if one is set, otherwise the table row of dataset_seq.
+ * If that model distorts, the colour image alone goes through the rectification, as under a depth camera, and c is its
+ * rectified pinhole (fxc, fyc, cxc, cyc, depth_scale_c).  The colour image is w x h.
+ * Per point, all arithmetic in float32, every operation explicit in this order, division correctly rounded, nothing
+ * fused.  "skip" ends the point:
+ *   1. Skip unless x, y and z are all finite.
+ *   2. Q.k = ((R[k][0]*x + R[k][1]*y) + R[k][2]*z) + T[k], k = 0, 1, 2.
+ *   3. Skip unless Q.z > 0.
+ *   4. Skip if (min_range > 0 && Q.z < min_range) || (max_range > 0 && Q.z > max_range).
+ *   5. u = fxc*(Q.x/Q.z) + cxc;  v = fyc*(Q.y/Q.z) + cyc.
+ *   6. Skip unless u and v are both finite.
+ *   7. q = rintf(Q.z * depth_scale_c).  Skip unless 1 <= q <= 65535.
+ *   8. xi = (int)rintf(clamp(u, -8, w + 8)), ties to even; yi likewise with h.
+ *   9. For every pixel (x, y) inside the image with |x - xi| <= splat and |y - yi| <= splat: Z[y][x] = min(Z[y][x], q).
+ * The plane before culling, P0, is Z where something was written and 0 elsewhere (CVO_FE_STAGE_LIDAR_DEPTH).  Nearest
+ * surface wins; the result does not depend on the order of the points.
+ * Occlusion.  The scanner is not at the camera: between the points of a near object it sees background that the camera
+ * does not.  For a pixel p with P0(p) != 0:
+ *   m(p) is the minimum of P0(q) over q inside the image with |dx| <= occl_rx, |dy| <= occl_ry and P0(q) != 0; p counts
+ *     itself.  65535 is a depth like any other.
+ *   OCCLUDED(p) holds iff occl_rel > 0 and (float)(P0(p) - m) > occl_rel * (float)m: one float32 multiplication and one
+ *     comparison, the shape of the gate's jump test.  At occl_rel 0.25 beside a 4000, a 5000 is kept and a 5001 dropped.
+ *   P(p) = OCCLUDED(p) ? 0 : P0(p).  P is a function of P0 alone and is not computed in place.
+ * The window has two half-widths because a threshold relative to depth also fires across rows on a ground plane near
+ * the horizon: a caller whose scanner sits above the camera wants the window wide and flat (occl_ry 0 or 1).
+ * CVO_FE_STAGE_LIDAR holds CVO_FE_LIDAR_HIT where P0 != 0, and CVO_FE_LIDAR_OCCLUDED beside it where OCCLUDED.
+ * P is the plane an uploaded depth image fills otherwise: the input of the median stage, the gate and level 0, all
+ * unchanged.  It is CVO_FE_STAGE_RAW_DEPTH; without median or gate it is also UNGATED_DEPTH and RECT_DEPTH.
+ * Not part of it: motion compensation of a spinning scan (the caller's, before the points come here); a lens in the
+ * projection (the colour image is rectified instead); reflectance as a feature; densifying beyond splat and the median
+ * stage's fill. */
+typedef struct cvo_fe_lidar {
+    int32_t max_points;          /* capacity of a scan, 1 .. 2^21; the staging a frame copies has this size */
+    int32_t splat;               /* 0..3: a point writes the (2*splat+1)^2 pixels around its nearest pixel */
+    float   R[9], T[3];          /* p_colour = R p_lidar + T, R row-major, T in metres (KITTI: R_rect_00 *
+                                    Tr_velo_to_cam, the caller multiplies) */
+    float   min_range, max_range;/* metres along the colour camera's axis; <= 0: no limit on that side */
+    float   occl_rel;            /* 0: no occlusion test; > 0: see above */
+    int32_t occl_rx, occl_ry;    /* 0..7 each: half-widths of the occlusion window */
+    int32_t pad_;                /* must be 0 */
+} cvo_fe_lidar;                  /* 80 bytes, no padding */
+
 /* One camera of a stereo rig: its pinhole and its lens (k1 k2 p1 p2 k3, as cvo_fe_camera_model's dist). */
 typedef struct cvo_fe_lens {
     float fx, fy, cx, cy;
@@ -594,6 +657,27 @@ int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *s
 int cvo_fe_set_depth_median(cvo_fe_ctx *ctx, const cvo_fe_depth_median *m);
 /* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int *set);
+/* A scan source (the LiDAR contract at cvo_fe_lidar); l == NULL: depth images again (the state of a new context).
+ * While it is set a frame goes in through cvo_fe_submit_lidar / cvo_fe_create_pointcloud_lidar; cvo_fe_submit and
+ * cvo_fe_create_pointcloud refuse, and cvo_fe_set_stereo and cvo_fe_set_depth_camera refuse settings and rigs.
+ * CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame submitted and not collected; settings
+ * cvo_fe_check_lidar refuses; stereo set; a depth camera set.  The staging of a scan (pinned and device memory of
+ * max_points points), the z-buffer and the planes of the stage take memory only once it has been set and are given back
+ * when it is cleared. */
+int cvo_fe_set_lidar(cvo_fe_ctx *ctx, const cvo_fe_lidar *l);
+/* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_lidar(const cvo_fe_ctx *ctx, cvo_fe_lidar *out, int *set);
+/* cvo_fe_submit / cvo_fe_create_pointcloud for a colour image and a scan: `img` as there; `points` are num_points
+ * records `stride_bytes` apart whose first three floats are x, y, z.  The points are copied to the context's pinned
+ * staging before the call returns.  CVO_HIP_ERR_INVALID without a scan source, for num_points outside
+ * [0, max_points], a stride below 12 or not a multiple of 4, and null points with num_points > 0.  collect,
+ * collect_device, get_info, set_device_output, set_num_want, the mask, the gate, the median and the select mode work on
+ * such a frame as on any other. */
+int cvo_fe_submit_lidar(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *points, size_t stride_bytes,
+                        int num_points, int dataset_seq, int feature_type);
+int cvo_fe_create_pointcloud_lidar(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *points,
+                                   size_t stride_bytes, int num_points, int dataset_seq, int feature_type,
+                                   float *positions, float *features, int capacity, int *num_points_out);
 /* cvo_fe_submit / cvo_fe_create_pointcloud for a stereo pair: `left` and `right` are height rows of
  * width*3 bytes each, as `img` there (a caller whose right image is grey replicates it); the left image
  * is the colour image of the frame.  CVO_HIP_ERR_INVALID without stereo set.  collect, collect_device,
@@ -737,6 +821,24 @@ int cvo_fe_check_depth_median(const cvo_fe_depth_median *m);
  * stride_bytes < width*2 and settings cvo_fe_check_depth_median refuses; CVO_HIP_ERR_NODEVICE without such a device. */
 int cvo_fe_median_plane(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
                         const cvo_fe_depth_median *m, uint8_t *flags, int *changed, int *filled);
+
+/* CVO_HIP_OK for settings cvo_fe_set_lidar() would accept on an idle context without stereo and depth camera,
+ * CVO_HIP_ERR_INVALID otherwise: NULL; max_points outside [1, 2^21]; splat outside [0, 3]; a float that is not finite;
+ * occl_rel < 0; occl_rx or occl_ry outside [0, 7]; max_range > 0 && max_range <= min_range; R failing the depth
+ * camera's rotation rule (within 1e-3 of orthonormal, positive determinant); pad_ != 0.  The one statement of what is
+ * accepted.  Host only. */
+int cvo_fe_check_lidar(const cvo_fe_lidar *l);
+/* The stage of the LiDAR contract on any scan by the kernels a frame runs, without a context: host arrays in and out.
+ * `points` are n records `stride_bytes` apart (x, y, z first); `cam` is the colour camera as cvo_fe_camera gives it
+ * (depth scale, fx, fy, cx, cy).  `plane` receives P (width*height uint16, dense), `unculled`, if not NULL, P0, and
+ * `flags`, if not NULL, the bytes of CVO_FE_STAGE_LIDAR; *hits the number of pixels with P0 != 0 and *occluded the
+ * number of those the occlusion test dropped.  max_points is not read beyond n <= 2^21.  CVO_HIP_ERR_INVALID for a
+ * null `plane`, `cam`, `hits` or `occluded`, null points with n > 0, n outside [0, 2^21], a stride below 12 or not a
+ * multiple of 4, width or height outside [1, 8192], a camera that is not finite and positive in scale and focal lengths,
+ * and settings cvo_fe_check_lidar refuses; CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_project_points(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
+                          const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled, uint8_t *flags,
+                          int *hits, int *occluded);
 #ifdef __cplusplus
 }
 #endif
