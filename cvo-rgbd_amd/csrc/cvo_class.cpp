@@ -61,7 +61,7 @@ registration::registration(int mode, int device, void *stream)
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
-      depth_median_(), have_depth_median_(false), lidar_(), have_lidar_(false), select_mode_(CVO_FE_SELECT_IMAGE)
+      depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), select_mode_(CVO_FE_SELECT_IMAGE)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -95,6 +95,7 @@ void registration::apply_stored_settings()
         if (have_stereo_speckle_) fe_check(cvo_fe_set_stereo_speckle(fe_, &stereo_speckle_), "cvo_fe_set_stereo_speckle");
         fe_check(cvo_fe_set_select_mode(fe_, select_mode_), "cvo_fe_set_select_mode");
         if (have_depth_median_) fe_check(cvo_fe_set_depth_median(fe_, &depth_median_), "cvo_fe_set_depth_median");
+        if (have_depth_infill_) fe_check(cvo_fe_set_depth_infill(fe_, &depth_infill_), "cvo_fe_set_depth_infill");
         if (have_lidar_) fe_check(cvo_fe_set_lidar(fe_, &lidar_), "cvo_fe_set_lidar");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
@@ -226,6 +227,18 @@ void registration::set_depth_median(const cvo_fe_depth_median &median)
 void registration::clear_depth_median()
 {
     store<cvo_fe_depth_median>(cvo_fe_set_depth_median, "cvo_fe_set_depth_median", nullptr, depth_median_, have_depth_median_);
+}
+
+void registration::set_depth_infill(const cvo_fe_depth_infill &infill)
+{
+    if (!fe_ && cvo_fe_check_depth_infill(&infill) != CVO_HIP_OK)
+        throw std::runtime_error("set_depth_infill(): gap_x in [0, 15], gap_y in [0, 31], jump_rel finite and >= 0, pad_ 0");
+    store<cvo_fe_depth_infill>(cvo_fe_set_depth_infill, "cvo_fe_set_depth_infill", &infill, depth_infill_, have_depth_infill_);
+}
+
+void registration::clear_depth_infill()
+{
+    store<cvo_fe_depth_infill>(cvo_fe_set_depth_infill, "cvo_fe_set_depth_infill", nullptr, depth_infill_, have_depth_infill_);
 }
 
 void registration::set_lidar(const cvo_fe_lidar &lidar)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "cvo_frontend.h"
+#include "cvo_infill.h"
 #include "cvo_lidar.h"
 #include "cvo_lock.h"
 #include "cvo_median.h"
@@ -1142,6 +1143,13 @@ struct cvo_fe_ctx {
     // with the filter, and gone with it: A of the median contract (rect_plane(np) entries) and the flags
     Dev<uint16_t> unfiltered;
     Dev<uint8_t> median_flags;
+    // the infill stage (cvo_fe_set_depth_infill): a setting of the context likewise, read by every frame; with it
+    // whatever fills the depth plane fills `sparse`, and k_fe_infill of cvo_infill.hip writes the plane they filled before
+    cvo_fe_depth_infill infill{};
+    bool has_infill = false;
+    // with the stage, and gone with it: S of the infill contract (rect_plane(np) entries) and the flags
+    Dev<uint16_t> sparse;
+    Dev<uint8_t> infill_flags;
     // the caller's scan source (cvo_fe_set_lidar); with it a frame is a colour image and a scan, and the kernels of
     // cvo_lidar.hip with k_fe_depth_final between them fill the plane an uploaded depth image fills otherwise
     cvo_fe_lidar lidar{};
@@ -1393,17 +1401,21 @@ inline bool gate_active(const cvo_fe_ctx *ctx) { return ctx->has_gate || ctx->ha
 // the depth plane the stages in front of level 0 write: the gate's input while it runs
 inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? ctx->ungated.get() : ctx->depth.get(); }
 
-// the plane the producers of depth write (an upload, k_fe_rectify, the depth camera's warp, the stereo matcher and its
-// speckle filter): the median stage's input while it runs, else the depth plane itself
+// the plane in front of the median stage: its input while it runs, else the depth plane itself.  The infill stage
+// writes it; without that stage the producers of depth do
 inline uint16_t *filled_plane(const cvo_fe_ctx *ctx) { return ctx->has_median ? ctx->unfiltered.get() : depth_plane(ctx); }
+
+// the plane the producers of depth write (an upload, k_fe_rectify, the depth camera's warp, the stereo matcher and its
+// speckle filter, the LiDAR projection and its cull): the infill stage's input while it runs, else the plane above
+inline uint16_t *source_plane(const cvo_fe_ctx *ctx) { return ctx->has_infill ? ctx->sparse.get() : filled_plane(ctx); }
 
 // where the uploaded depth image lands: the raw buffer of a depth camera's size, else the raw depth that
 // k_fe_rectify resamples, else the plane the producers write (a scan source: no image is uploaded, and the plane the
 // projected scan fills stands in its place)
 inline uint16_t *depth_upload(const cvo_fe_ctx *ctx)
 {
-    if (ctx->has_lidar) return filled_plane(ctx);
-    return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : filled_plane(ctx);
+    if (ctx->has_lidar) return source_plane(ctx);
+    return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : source_plane(ctx);
 }
 
 // the points of the cloud that follow the control block to the host before their number is known: enough for
@@ -1514,7 +1526,8 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
     // (a median filter: whatever fills the depth plane fills the stage's input, and k_fe_median fills what is named above)
-    uint16_t *plane = filled_plane(ctx);
+    // (the infill stage: likewise in front of the median stage, and k_fe_infill fills what is named above)
+    uint16_t *plane = source_plane(ctx);
     // (a scan source: the scan is uploaded in place of a depth image, its count in front, and the projection fills that plane)
     if (ctx->has_stereo)
         FE_HIP(hipMemcpyAsync(ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3,
@@ -1592,9 +1605,15 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
             fe_lidar_cull_enqueue(c, s);
         }
     }
+    if (ctx->has_infill) {   // (the infill contract: directly behind the producers, for every kind of frame)
+        FeInfillArgs f{};
+        f.s = plane; f.f = filled_plane(ctx); f.flags = ctx->infill_flags.get();
+        f.w = w; f.h = h; f.gap_x = ctx->infill.gap_x; f.gap_y = ctx->infill.gap_y; f.jump_rel = ctx->infill.jump_rel;
+        fe_infill_enqueue(f, s);
+    }
     if (ctx->has_median) {   // (the median contract: directly in front of the gate, for every kind of frame)
         FeMedianArgs m{};
-        m.a = plane; m.b = depth_plane(ctx); m.flags = ctx->median_flags.get();
+        m.a = filled_plane(ctx); m.b = depth_plane(ctx); m.flags = ctx->median_flags.get();
         m.w = w; m.h = h; m.radius = ctx->median.radius; m.fill_min = ctx->median.fill_min;
         fe_median_enqueue(m, s);
     }
@@ -2081,6 +2100,43 @@ int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     *out = ctx->has_median ? ctx->median : cvo_fe_depth_median{};
     if (set) *set = ctx->has_median ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_depth_infill(cvo_fe_ctx *ctx, const cvo_fe_depth_infill *f)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_infill: a frame is in flight");
+    if (f && cvo_fe_check_depth_infill(f) != CVO_HIP_OK)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_infill: gap_x in [0, 15], gap_y in [0, 31], jump_rel finite and >= 0, pad_ 0");
+    if (!f && !ctx->has_infill) return CVO_HIP_OK;
+    if (f && ctx->has_infill && std::memcmp(f, &ctx->infill, sizeof(*f)) == 0) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint16_t> sparse;
+    Dev<uint8_t> flags;
+    if (f && !ctx->sparse && !(dev_alloc(sparse, rect_plane(ctx->np)) && dev_alloc(flags, rect_plane(ctx->np))))
+        return no_memory(ctx, "set_depth_infill: device memory for the sparse depth and the stage's flags");
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    hand_over(ctx->sparse, sparse);
+    hand_over(ctx->infill_flags, flags);
+    if (!f) {
+        ctx->sparse.reset();
+        ctx->infill_flags.reset();
+    }
+    ctx->has_infill = f != nullptr;
+    ctx->infill = f ? *f : cvo_fe_depth_infill{};
+    drop_graphs(ctx);   // (whether a frame has the stage's launch, its numbers and where the producers write are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_depth_infill(const cvo_fe_ctx *ctx, cvo_fe_depth_infill *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_infill ? ctx->infill : cvo_fe_depth_infill{};
+    if (set) *set = ctx->has_infill ? 1 : 0;
     return CVO_HIP_OK;
 }
 
@@ -2747,12 +2803,16 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_UNFILTERED_DEPTH: src = ctx->unfiltered.get(); need = np * 2; break;
     case CVO_FE_STAGE_MEDIAN: src = ctx->median_flags.get(); need = np; break;
     // (without the occlusion test P0 is P, and the flags are made from it below: no plane of their own)
-    case CVO_FE_STAGE_LIDAR_DEPTH: src = ctx->lidar_p0 ? ctx->lidar_p0.get() : filled_plane(ctx); need = np * 2; break;
+    case CVO_FE_STAGE_LIDAR_DEPTH: src = ctx->lidar_p0 ? ctx->lidar_p0.get() : source_plane(ctx); need = np * 2; break;
     case CVO_FE_STAGE_LIDAR: src = ctx->lidar_flags.get(); need = np; break;
+    case CVO_FE_STAGE_SPARSE_DEPTH: src = ctx->sparse.get(); need = np * 2; break;
+    case CVO_FE_STAGE_INFILL: src = ctx->infill_flags.get(); need = np; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if ((stage == CVO_FE_STAGE_UNFILTERED_DEPTH || stage == CVO_FE_STAGE_MEDIAN) && !ctx->has_median)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the median filter, and no filter is set");
+    if ((stage == CVO_FE_STAGE_SPARSE_DEPTH || stage == CVO_FE_STAGE_INFILL) && !ctx->has_infill)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the infill stage, and the stage is not set");
     if ((stage == CVO_FE_STAGE_LIDAR_DEPTH || stage == CVO_FE_STAGE_LIDAR) && !ctx->has_lidar)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of a scan source, and none is set");
     if (stage >= CVO_FE_STAGE_RIGHT_GRAY && stage <= CVO_FE_STAGE_SPECKLE_SIZE && !ctx->has_stereo)
@@ -2767,7 +2827,7 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     if (stage == CVO_FE_STAGE_LIDAR && !src) {   // (no occlusion test: HIT where the plane holds a depth)
         std::vector<uint16_t> p0;
         try { p0.resize(np); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "read_stage"); }
-        FE_HIP(hipMemcpy(p0.data(), filled_plane(ctx), np * 2, hipMemcpyDeviceToHost));
+        FE_HIP(hipMemcpy(p0.data(), source_plane(ctx), np * 2, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < np; ++i) ((uint8_t *)out)[i] = p0[i] ? (uint8_t)CVO_FE_LIDAR_HIT : (uint8_t)0;
         return CVO_HIP_OK;
     }

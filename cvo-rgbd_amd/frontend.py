@@ -12,6 +12,11 @@ include/cvo_frontend.h; frames of either kind):
 
     gen.set_depth_median(DepthMedian(radius=1, fill_min=5))
 
+The gaps of a sparse depth plane -- between scan lines, in a warp's holes -- bridged linearly in inverse depth, directly
+behind whatever fills the plane (the infill contract of include/cvo_frontend.h; frames of every kind):
+
+    gen.set_depth_infill(DepthInfill(gap_x=2, gap_y=8, jump_rel=0.25))
+
 A LiDAR scan in place of the depth image, projected into the colour camera on the device (the LiDAR contract of
 include/cvo_frontend.h; KITTI: R, T from R_rect_00 * Tr_velo_to_cam):
 
@@ -53,11 +58,12 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
  STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
  STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
  STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE, STAGE_UNFILTERED_DEPTH, STAGE_MEDIAN, STAGE_LIDAR_DEPTH,
- STAGE_LIDAR) = range(28)
+ STAGE_LIDAR, STAGE_SPARSE_DEPTH, STAGE_INFILL) = range(30)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 MEDIAN_CHANGED, MEDIAN_FILLED = 1, 2   # the values of STAGE_MEDIAN
 LIDAR_HIT, LIDAR_OCCLUDED = 1, 2       # the bits of STAGE_LIDAR
+INFILL_ROW, INFILL_COL, INFILL_JUMP = 1, 2, 4   # the values of STAGE_INFILL
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
 # modes of the selector (set_select_mode): by the image alone (the reference; a new object's), or among the pixels
@@ -75,7 +81,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_set_stereo_paths", "cvo_fe_get_stereo_paths", "cvo_fe_check_speckle", "cvo_fe_set_stereo_speckle",
            "cvo_fe_get_stereo_speckle", "cvo_fe_filter_speckles", "cvo_fe_check_select_mode", "cvo_fe_set_select_mode",
            "cvo_fe_get_select_mode", "cvo_fe_check_depth_median", "cvo_fe_set_depth_median", "cvo_fe_get_depth_median",
-           "cvo_fe_median_plane", "cvo_fe_check_lidar", "cvo_fe_set_lidar", "cvo_fe_get_lidar", "cvo_fe_submit_lidar",
+           "cvo_fe_median_plane", "cvo_fe_check_depth_infill", "cvo_fe_set_depth_infill", "cvo_fe_get_depth_infill",
+           "cvo_fe_infill_plane", "cvo_fe_check_lidar", "cvo_fe_set_lidar", "cvo_fe_get_lidar", "cvo_fe_submit_lidar",
            "cvo_fe_create_pointcloud_lidar", "cvo_fe_project_points")
 
 
@@ -176,6 +183,18 @@ class DepthMedian(_Settings):
 
     def __init__(self, radius=1, fill_min=0, pad_=0):
         super().__init__(int(radius), int(fill_min), int(pad_))
+
+
+class DepthInfill(_Settings):
+    """cvo_fe_depth_infill: the infill stage on the depth plane, directly behind whatever fills it and in front of the
+    median stage (the infill contract of include/cvo_frontend.h).  A run of at most `gap_x` (0..15) pixels without depth
+    in a row, then of at most `gap_y` (0..31) in a column, that has a depth at both ends inside the image takes the
+    values linear in INVERSE depth between them; 0: no pass along that axis.  `jump_rel` 0: every such run is bridged;
+    > 0: not one whose ends differ by more than this relative step."""
+    _fields_ = [("gap_x", C.c_int32), ("gap_y", C.c_int32), ("jump_rel", C.c_float), ("pad_", C.c_int32)]
+
+    def __init__(self, gap_x=0, gap_y=0, jump_rel=0.0, pad_=0):
+        super().__init__(int(gap_x), int(gap_y), float(jump_rel), int(pad_))
 
 
 class Lidar(_Settings):
@@ -323,6 +342,11 @@ def lib():
         L.cvo_fe_check_depth_median.argtypes = [C.POINTER(DepthMedian)]
         L.cvo_fe_set_depth_median.argtypes = [vp, C.POINTER(DepthMedian)]
         L.cvo_fe_get_depth_median.argtypes = [vp, C.POINTER(DepthMedian), C.POINTER(C.c_int)]
+        L.cvo_fe_check_depth_infill.argtypes = [C.POINTER(DepthInfill)]
+        L.cvo_fe_set_depth_infill.argtypes = [vp, C.POINTER(DepthInfill)]
+        L.cvo_fe_get_depth_infill.argtypes = [vp, C.POINTER(DepthInfill), C.POINTER(C.c_int)]
+        L.cvo_fe_infill_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthInfill), u8p,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cvo_fe_median_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthMedian), u8p,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cvo_fe_check_lidar.argtypes = [C.POINTER(Lidar)]
@@ -461,6 +485,40 @@ def median_plane(plane, median, device=0):
                                          flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(changed), C.byref(filled)),
                what="median_plane")
     return plane, flags, changed.value, filled.value
+
+
+def check_depth_infill(infill):
+    """True for a DepthInfill set_depth_infill() accepts (cvo_fe_check_depth_infill): gap_x in [0, 15], gap_y in [0, 31],
+    jump_rel finite and >= 0, pad_ 0; None is refused.  Host only."""
+    if infill is None:
+        return lib().cvo_fe_check_depth_infill(None) == 0
+    return lib().cvo_fe_check_depth_infill(C.byref(infill)) == 0
+
+
+def infill_plane(plane, infill, device=0, stride=None):
+    """The infill stage on any h x w uint16 plane with 0 = none (cvo_fe_infill_plane: the kernel a frame runs, without
+    a generator).  Returns (F, the flags as h x w uint8 of INFILL_ROW / INFILL_COL / INFILL_JUMP, the number of pixels
+    the row pass filled, the number the column pass filled); the argument is left as it is.  `stride`: the plane is
+    handed over in rows that many uint16 apart (at least w), the cells between them holding 65535; they come back as
+    they went."""
+    src = np.asarray(plane, np.uint16)
+    if src.ndim != 2:
+        raise ValueError("expected an h x w uint16 plane")
+    h, w = src.shape
+    pitch = w if stride is None else int(stride)
+    if pitch < w:
+        raise ValueError("stride below the plane's width")
+    buf = np.full((h, pitch), 65535, np.uint16)
+    buf[:, :w] = src
+    flags = np.empty((h, w), np.uint8)
+    rows, cols = C.c_int(0), C.c_int(0)
+    capi.check(lib().cvo_fe_infill_plane(int(device), buf.ctypes.data_as(C.POINTER(C.c_uint16)), pitch * 2, w, h,
+                                         None if infill is None else C.byref(infill),
+                                         flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rows), C.byref(cols)),
+               what="infill_plane")
+    if not (buf[:, w:] == 65535).all():
+        raise RuntimeError("infill_plane: the cells between the rows were written")
+    return np.ascontiguousarray(buf[:, :w]), flags, rows.value, cols.value
 
 
 def check_lidar(lidar):
@@ -736,6 +794,18 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_depth_median(self._h, C.byref(out), C.byref(isset)), "get_depth_median")
         return out if isset.value else None
 
+    def set_depth_infill(self, infill):
+        """A DepthInfill for every following frame of any kind: the depth plane passes the infill stage directly behind
+        whatever fills it (the infill contract of include/cvo_frontend.h); None: no stage, as for a new object.  A setting
+        of its own: it survives every other setter."""
+        self._chk(lib().cvo_fe_set_depth_infill(self._h, None if infill is None else C.byref(infill)), "set_depth_infill")
+
+    def depth_infill(self):
+        """The DepthInfill set, or None."""
+        out, isset = DepthInfill(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_depth_infill(self._h, C.byref(out), C.byref(isset)), "get_depth_infill")
+        return out if isset.value else None
+
     def set_lidar(self, lidar):
         """A Lidar for every following frame: a frame is then a colour image and a scan (submit_lidar /
         create_pointcloud_lidar), projected into the colour camera on the device (the LiDAR contract of
@@ -851,7 +921,8 @@ class PcdGenerator:
                   STAGE_STEREO: ((h, w), np.uint8), STAGE_RIGHT_BGR: ((h, w, 3), np.uint8),
                   STAGE_STEREO_VALID: ((h, w), np.uint8), STAGE_SPECKLE_SIZE: ((h, w), np.uint32),
                   STAGE_UNFILTERED_DEPTH: ((h, w), np.uint16), STAGE_MEDIAN: ((h, w), np.uint8),
-                  STAGE_LIDAR_DEPTH: ((h, w), np.uint16), STAGE_LIDAR: ((h, w), np.uint8)}
+                  STAGE_LIDAR_DEPTH: ((h, w), np.uint16), STAGE_LIDAR: ((h, w), np.uint8),
+                  STAGE_SPARSE_DEPTH: ((h, w), np.uint16), STAGE_INFILL: ((h, w), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -898,7 +969,7 @@ def load_img(rgb_path, depth_path):
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
-               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None):
+               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
     `lidar`: a Lidar for the generator: `frames` then yields (name, bgr, points), a colour image and a scan (n x k
     float32, x y z first), and the depth comes from the scan projected on the device; None leaves the generator as it is.
@@ -910,6 +981,7 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
     `stereo_speckle`: a Speckle for the generator's matcher; None leaves the generator as it is.
     `select_mode`: SELECT_IMAGE or SELECT_DEPTH for the generator's selector; None leaves the generator as it is.
     `depth_median`: a DepthMedian for the generator, for frames of either kind; None leaves the generator as it is.
+    `depth_infill`: a DepthInfill for the generator, for frames of every kind; None leaves the generator as it is.
     `camera`: a CameraModel for the generator (`dataset_seq` is then ignored); None leaves the
     generator as it is -- a new one uses the table.
     `depth_camera`: a DepthCamera for the generator: the frames' depth images are then of its size and
@@ -951,6 +1023,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_select_mode(select_mode)
     if depth_median is not None:
         gen.set_depth_median(depth_median)
+    if depth_infill is not None:
+        gen.set_depth_infill(depth_infill)
     if lidar is not None:
         gen.set_lidar(lidar)
     submit = gen.submit_stereo if stereo is not None else gen.submit_lidar if lidar is not None else gen.submit
@@ -983,7 +1057,7 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
                   generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None, select_mode=None,
-                  depth_median=None):
+                  depth_median=None, depth_infill=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
@@ -992,7 +1066,8 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
     `depth_camera`: as in run_frames, for a recording whose depth images are not registered to colour.
     `depth_gate`, `mask`: as in run_frames, e.g. DepthGate(0.8, 4.0, 0.05, 1) for a Kinect-class sensor.
     `select_mode`: as in run_frames, e.g. SELECT_DEPTH beside a gate, which removes the pixels the selector likes best.
-    `depth_median`: as in run_frames, e.g. DepthMedian(1, 5) for a sensor with salt and pinholes."""
+    `depth_median`: as in run_frames, e.g. DepthMedian(1, 5) for a sensor with salt and pinholes.
+    `depth_infill`: as in run_frames, e.g. DepthInfill(2, 2, 0.05) for the holes a depth camera's registration leaves."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -1004,18 +1079,19 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_camera=depth_camera, depth_gate=depth_gate, mask=mask, select_mode=select_mode,
-                      depth_median=depth_median)
+                      depth_median=depth_median, depth_infill=depth_infill)
 
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                         stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None, depth_median=None):
+                         stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None, depth_median=None,
+                         depth_infill=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
-    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`, `depth_median`:
-    as in run_frames."""
+    image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`, `depth_median`,
+    `depth_infill`: as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1032,18 +1108,19 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
                       stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode,
-                      depth_median=depth_median)
+                      depth_median=depth_median, depth_infill=depth_infill)
 
 
 def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, image="image_2", scans="velodyne",
                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                        select_mode=None, depth_median=None):
+                        select_mode=None, depth_median=None, depth_infill=None):
     """run_directory() for the KITTI odometry layout with its scans: one line of `folder`/`times` per frame (the line is
     the frame's name), the colour image in `folder`/`image`/%06d.png, decoded by PIL as load_img does (B, G, R; a grey
     image is replicated), and the scan in `folder`/`scans`/%06d.bin, records of four float32 (x y z reflectance).
     `lidar`: the Lidar for the generator, e.g. Lidar(130000, 1, R, T, occl_rel=0.25, occl_rx=7, occl_ry=1) with R, T of
     R_rect_00 * Tr_velo_to_cam and dataset_seq 4.  `camera`, `depth_gate`, `mask`, `select_mode`, `depth_median`: as in
-    run_frames, e.g. SELECT_DEPTH and DepthMedian(1, 3) for a plane as sparse as a projected scan."""
+    run_frames, e.g. SELECT_DEPTH and DepthMedian(1, 3) for a plane as sparse as a projected scan.  `depth_infill`: as in
+    run_frames, e.g. DepthInfill(2, 8, 0.25) for scan lines some five rows apart."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1059,4 +1136,5 @@ def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, i
                    np.fromfile(os.path.join(folder, scans, "%06d.bin" % k), np.float32).reshape(-1, 4))
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
-                      depth_gate=depth_gate, mask=mask, select_mode=select_mode, depth_median=depth_median, lidar=lidar)
+                      depth_gate=depth_gate, mask=mask, select_mode=select_mode, depth_median=depth_median, lidar=lidar,
+                      depth_infill=depth_infill)

@@ -127,6 +127,13 @@ class registration {
     // throws for settings the front end refuses.  clear_depth_median(): no filter, a new object's state.
     void set_depth_median(const cvo_fe_depth_median &median);
     void clear_depth_median();
+    // The infill stage on the depth plane, directly behind whatever fills it and in front of the median stage, for the
+    // image form of set_pcd() / run_cvo() of every kind of frame: cvo_fe_set_depth_infill (the infill contract:
+    // cvo_frontend.h).  A run of at most gap_x pixels without depth in a row, then of at most gap_y in a column, bounded
+    // by depths of one surface, is bridged linearly in inverse depth.  May be called before the first image; throws for
+    // settings the front end refuses.  clear_depth_infill(): no stage, a new object's state.
+    void set_depth_infill(const cvo_fe_depth_infill &infill);
+    void clear_depth_infill();
     // The selector's mode for the image form of set_pcd() / run_cvo(), depth or stereo: cvo_fe_set_select_mode
     // (CVO_FE_SELECT_IMAGE, a new object's: the reference's selector; CVO_FE_SELECT_DEPTH: a pixel without depth does
     // not compete, so the cloud holds the points asked for -- the selection contract: cvo_frontend.h).  A setting of
@@ -214,6 +221,8 @@ class registration {
     bool have_stereo_speckle_;
     cvo_fe_depth_median depth_median_;   // what set_depth_median() gave, likewise
     bool have_depth_median_;
+    cvo_fe_depth_infill depth_infill_;   // what set_depth_infill() gave, likewise
+    bool have_depth_infill_;
     cvo_fe_lidar lidar_;                 // what set_lidar() gave, likewise
     bool have_lidar_;
     int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)

@@ -52,7 +52,10 @@
  * hole is filled.  The median contract is stated at cvo_fe_depth_median below.  And a LiDAR scan in place of the depth
  * image (cvo_fe_set_lidar, cvo_fe_submit_lidar; cvo_fe_project_points for any scan without a context): the points are
  * projected into the colour camera on the device, nearest surface wins, and what the scanner sees between the points of
- * a nearer object is culled.  The LiDAR contract is stated at cvo_fe_lidar below.
+ * a nearer object is culled.  The LiDAR contract is stated at cvo_fe_lidar below.  And a stage that bridges the gaps of a
+ * sparse depth plane -- between scan lines, in the holes a forward warp leaves, where the stereo tests drop pixels of a
+ * smooth surface -- linearly in inverse depth, for every kind of frame (cvo_fe_set_depth_infill; cvo_fe_infill_plane for
+ * any uint16 plane).  The infill contract is stated at cvo_fe_depth_infill below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -114,7 +117,11 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        /* of a frame under a scan source (cvo_fe_set_lidar; CVO_HIP_ERR_INVALID on a context without one).  With it
           RAW_DEPTH is P of the LiDAR contract. */
        CVO_FE_STAGE_LIDAR_DEPTH = 26,     /* P0 of the LiDAR contract, the plane before culling: w*h uint16 */
-       CVO_FE_STAGE_LIDAR = 27 };         /* w*h uint8, CVO_FE_LIDAR_* */
+       CVO_FE_STAGE_LIDAR = 27,           /* w*h uint8, CVO_FE_LIDAR_* */
+       /* of a frame under the infill stage (cvo_fe_set_depth_infill; CVO_HIP_ERR_INVALID on a context without it).
+          With it UNFILTERED_DEPTH (under a median filter), else UNGATED_DEPTH, is F of the infill contract. */
+       CVO_FE_STAGE_SPARSE_DEPTH = 28,    /* S of the infill contract: w*h uint16 */
+       CVO_FE_STAGE_INFILL = 29 };        /* INFILL of the infill contract: w*h uint8, CVO_FE_INFILL_* */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
@@ -127,6 +134,8 @@ enum { CVO_FE_MEDIAN_CHANGED = 1, CVO_FE_MEDIAN_FILLED = 2 };
 /* bits of CVO_FE_STAGE_LIDAR (the LiDAR contract at cvo_fe_lidar): HIT where P0 != 0; OCCLUDED beside it where the
    occlusion test dropped the pixel */
 enum { CVO_FE_LIDAR_HIT = 1, CVO_FE_LIDAR_OCCLUDED = 2 };
+/* values of CVO_FE_STAGE_INFILL (the infill contract at cvo_fe_depth_infill) */
+enum { CVO_FE_INFILL_ROW = 1, CVO_FE_INFILL_COL = 2, CVO_FE_INFILL_JUMP = 4 };
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141; under
@@ -217,8 +226,9 @@ typedef struct cvo_fe_camera_model {
  * footprint is the set of pixel centres inside the projected cell, half-open, capped at 8 x 8 so
  * that a pixel's work is bounded; a rig that is the colour camera itself (same size and pinhole,
  * R = I, T = 0) returns the depth image byte for byte; the result does not depend on the order
- * of the writes.  Holes a forward warp leaves are not filled here; the median stage (the median contract at
- * cvo_fe_depth_median) fills the small ones if it is asked to. */
+ * of the writes.  Holes a forward warp leaves are not filled here; the infill stage (the infill contract at
+ * cvo_fe_depth_infill) bridges them by inverse depth and the median stage (the median contract at
+ * cvo_fe_depth_median) fills the small ones with a neighbour's depth, each if it is asked to. */
 typedef struct cvo_fe_depth_camera {
     int32_t width, height;               /* of the DEPTH image; may differ from the context's (colour) size */
     float depth_scale, fx, fy, cx, cy;   /* units per metre of the depth image's values; the depth camera's pinhole */
@@ -235,7 +245,8 @@ typedef struct cvo_fe_depth_camera {
  * selector, the Canny top-up and the back-projection then run unchanged on the gated plane.  The
  * results are defined by the arithmetic below, not by the device.  It is this library's own
  * definition and is NOT pinned against any SDK's filter.  (Under a median filter U is that stage's
- * output, B of the median contract at cvo_fe_depth_median.)
+ * output, B of the median contract at cvo_fe_depth_median; under the infill stage without a median
+ * filter it is F of the infill contract at cvo_fe_depth_infill.)
  *
  * `scale` is depth_scale of the colour camera in force for the frame (the cvo_fe_set_camera model,
  * else the table row of dataset_seq).  For a pixel p with U(p) != 0:
@@ -317,7 +328,8 @@ typedef struct cvo_fe_depth_gate {
  *  10. Output.  STEREO(p) is the OR of the flags; DISPARITY(p) = STEREO(p) ? 0 : q; the depth plane gets
  *      STEREO(p) ? 0 : U(q).
  * Diagonal paths are part of it where the path mask names them; hole filling and a median filter are not: they are
- * the median stage behind the matcher (the median contract at cvo_fe_depth_median); what the
+ * the infill stage (the infill contract at cvo_fe_depth_infill, linear in inverse depth and so in disparity) and the
+ * median stage (the median contract at cvo_fe_depth_median) behind the matcher; what the
  * diagonals are worth in accuracy on real pairs is not measured.  A pair that is not rectified goes in
  * with its rig (cvo_fe_set_stereo_rig, the rig contract below). */
 typedef struct cvo_fe_stereo {
@@ -347,7 +359,8 @@ typedef struct cvo_fe_stereo {
  *     DISPARITY = 0 and depth plane 0.  Every other byte of the frame's planes is what it is without the filter.
  * The gate, if one is set, and level 0 read the filtered plane.  The result does not depend on the order in which
  * the device meets the pixels: sizes are integer counts.  Not part of it: hole filling and a median filter, which are
- * the median stage behind this one (the median contract at cvo_fe_depth_median). */
+ * the infill stage (the infill contract at cvo_fe_depth_infill) and the median stage (the median contract at
+ * cvo_fe_depth_median) behind this one. */
 typedef struct cvo_fe_speckle {
     int32_t max_size;   /* components of at most this many pixels lose their disparity; 1 .. 2^26 */
     int32_t max_diff;   /* largest |Q(p) - Q(n)| that joins two neighbours, in units of the plane (1/16 pixel for
@@ -361,8 +374,10 @@ typedef struct cvo_fe_speckle {
  * THE MEDIAN CONTRACT.  While a filter is set every frame of the context, of every kind, passes its depth plane through
  * one more stage directly in front of the gate.  The results are defined by the integer arithmetic below, not by the
  * device.  It is this library's own definition and is NOT pinned against cv::medianBlur or any SDK's filter.
- * Let A be the depth plane as it stands after the rectification, the depth camera's registration, or the stereo
- * matcher and its speckle filter: w x h uint16 with 0 = none -- what the gate contract calls U without this stage.
+ * Let A be the depth plane as it stands after the rectification, the depth camera's registration, the stereo
+ * matcher and its speckle filter, or the LiDAR projection and its cull -- and, where the infill stage is set, after that
+ * stage: A is then F of the infill contract at cvo_fe_depth_infill.  It is w x h uint16 with 0 = none -- what the gate
+ * contract calls U without this stage.
  * For a pixel p:
  *   W(p) is the set of pixels q inside the image with max(|dx|, |dy|) <= radius.  Pixels outside the image are not in
  *     it: no replicated border.
@@ -430,8 +445,55 @@ typedef struct cvo_fe_depth_median {
  * P is the plane an uploaded depth image fills otherwise: the input of the median stage, the gate and level 0, all
  * unchanged.  It is CVO_FE_STAGE_RAW_DEPTH; without median or gate it is also UNGATED_DEPTH and RECT_DEPTH.
  * Not part of it: motion compensation of a spinning scan (the caller's, before the points come here); a lens in the
- * projection (the colour image is rectified instead); reflectance as a feature; densifying beyond splat and the median
- * stage's fill. */
+ * projection (the colour image is rectified instead); reflectance as a feature; densifying beyond splat, which is the
+ * infill stage behind this one (the infill contract at cvo_fe_depth_infill: between two scan lines on one surface the
+ * depth is interpolated, not copied) and the median stage's fill. */
+
+/* Bridging the gaps of a sparse depth plane.  A LiDAR scan's lines land some pixels apart in the image; on a ground
+ * plane near the horizon two neighbouring lines differ by decimetres to metres of depth, and a pixel between them that
+ * copies one line's depth (splat, the median stage's fill) becomes a point that floats above or below the road by
+ * that much.  In a pinhole image a plane's INVERSE depth is linear in the pixel coordinates, so interpolating the inverse
+ * depth between the two lines is exact on planes up to rounding; it is also what interpolating a stereo pair's
+ * disparity linearly gives.  What the stage is worth in trajectory accuracy on real scans is not measured.
+ *
+ * THE INFILL CONTRACT.  While the stage is set every frame of the context, of every kind, passes its depth plane through
+ * one more stage directly behind whatever fills it and directly in front of the median stage.  The results are defined
+ * by the integer arithmetic below, not by the device.  It is this library's own definition and is NOT pinned against
+ * any SDK's hole filling.
+ * Let S be the depth plane as it stands after the upload or the rectification, the depth camera's registration, the
+ * stereo matcher and its speckle filter, or the LiDAR projection and its cull: w x h uint16 with 0 = none
+ * (CVO_FE_STAGE_SPARSE_DEPTH).  The stage's output F is A of the median contract if a median filter is set
+ * (CVO_FE_STAGE_UNFILTERED_DEPTH), otherwise U of the gate contract (CVO_FE_STAGE_UNGATED_DEPTH), otherwise the depth
+ * plane.  CVO_FE_STAGE_RAW_DEPTH keeps its meaning.
+ * One pass along an axis has an input plane X and a limit g.  For a maximal run of L >= 1 consecutive pixels with X = 0
+ * along the axis:
+ *   The run is bounded iff the pixel in front of it and the pixel behind it both lie inside the image; both then have
+ *     a depth, A and B.  A pixel outside the image is never an end: no replicated border.
+ *   A bounded run with L <= g is a candidate.
+ *   With lo = min(A, B) and hi = max(A, B) a candidate is refused iff
+ *     jump_rel > 0 && (float)(hi - lo) > jump_rel * (float)lo
+ *     -- one float32 multiplication and one comparison, the shape of the gate's jump test and of the LiDAR cull.  At
+ *     jump_rel 0.25 a 5000 beside a 4000 is bridged and a 5001 is not.
+ *   A candidate that is not refused is bridged.  Its pixel da >= 1 pixels from the A end and db >= 1 from the B end
+ *     (da + db = L + 1) takes
+ *       N = A * B * (da + db);  Dn = A * da + B * db;  value = floor((2 * N + Dn) / (2 * Dn))
+ *     in exact integers (N reaches 65535^2 * 32: 64 bits).  That is 1 / ((db/A + da/B) / (da + db)), the interpolation
+ *     of the inverse depths, rounded half up; it lies in [lo, hi] and is at least 1.
+ *   Every other pixel of the pass keeps X.  Every pixel of a pass is a function of the pass's input alone: a pass is not
+ *   computed in place.  A pass with g = 0 is the identity.
+ * The row pass turns S into H with g = gap_x; the column pass then turns H -- not S -- into F with g = gap_y: a column
+ * may be bridged from a pixel the row pass made.
+ * INFILL(p) (CVO_FE_STAGE_INFILL) is CVO_FE_INFILL_ROW where the row pass filled p, CVO_FE_INFILL_COL where the column
+ * pass did, CVO_FE_INFILL_JUMP where F(p) = 0 and at least one pass refused p's run, and 0 elsewhere.  A pixel with
+ * S != 0 is never changed: F = S there.  65535 is a depth like any other.
+ * Under stereo CVO_FE_STAGE_DISPARITY and CVO_FE_STAGE_STEREO stay the matcher's: a filled pixel has a depth and
+ * DISPARITY 0. */
+typedef struct cvo_fe_depth_infill {
+    int32_t gap_x;     /* 0..15: the longest run of pixels without depth in a ROW that is bridged; 0: no row pass */
+    int32_t gap_y;     /* 0..31: likewise in a COLUMN; 0: no column pass */
+    float   jump_rel;  /* 0: no test; > 0: ends that differ by more than this relative step are not bridged */
+    int32_t pad_;      /* must be 0 */
+} cvo_fe_depth_infill; /* 16 bytes */
 typedef struct cvo_fe_lidar {
     int32_t max_points;          /* capacity of a scan, 1 .. 2^21; the staging a frame copies has this size */
     int32_t splat;               /* 0..3: a point writes the (2*splat+1)^2 pixels around its nearest pixel */
@@ -657,6 +719,15 @@ int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *s
 int cvo_fe_set_depth_median(cvo_fe_ctx *ctx, const cvo_fe_depth_median *m);
 /* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int *set);
+/* The infill stage (the infill contract at cvo_fe_depth_infill); f == NULL: no stage (the state of a new context).  A
+ * setting of the context, like the median filter: every kind of frame reads it and it survives every other setter.
+ * Without it a frame launches no kernel of the stage, a captured graph has no node of it, and every stage writes where
+ * it writes without.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame submitted and not
+ * collected; settings cvo_fe_check_depth_infill refuses.  The stage's two planes (S and the flags) take device memory
+ * only once it has been set and are given back when it is cleared. */
+int cvo_fe_set_depth_infill(cvo_fe_ctx *ctx, const cvo_fe_depth_infill *f);
+/* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_depth_infill(const cvo_fe_ctx *ctx, cvo_fe_depth_infill *out, int *set);
 /* A scan source (the LiDAR contract at cvo_fe_lidar); l == NULL: depth images again (the state of a new context).
  * While it is set a frame goes in through cvo_fe_submit_lidar / cvo_fe_create_pointcloud_lidar; cvo_fe_submit and
  * cvo_fe_create_pointcloud refuse, and cvo_fe_set_stereo and cvo_fe_set_depth_camera refuse settings and rigs.
@@ -821,6 +892,20 @@ int cvo_fe_check_depth_median(const cvo_fe_depth_median *m);
  * stride_bytes < width*2 and settings cvo_fe_check_depth_median refuses; CVO_HIP_ERR_NODEVICE without such a device. */
 int cvo_fe_median_plane(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
                         const cvo_fe_depth_median *m, uint8_t *flags, int *changed, int *filled);
+
+/* CVO_HIP_OK for settings cvo_fe_set_depth_infill() would accept on an idle context, CVO_HIP_ERR_INVALID otherwise:
+ * NULL; gap_x outside [0, 15]; gap_y outside [0, 31]; a jump_rel that is not finite or is below 0; pad_ != 0.  Both
+ * gaps 0 is accepted and fills nothing.  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_depth_infill(const cvo_fe_depth_infill *f);
+/* The stage of the infill contract on any uint16 plane with 0 = none -- a depth image of another pipeline, a disparity
+ * map -- by the kernel a frame runs, without a context: host arrays in and out.  `plane` is height rows of width uint16,
+ * `stride_bytes` BYTES apart; it is S on entry and F on return (the bytes between the rows stay; "in place" is the
+ * host array only, the kernel writes another plane than it reads); `flags`, if not NULL, receives INFILL (width*height
+ * uint8, dense); *row_filled and *col_filled the numbers of pixels with CVO_FE_INFILL_ROW and CVO_FE_INFILL_COL.
+ * CVO_HIP_ERR_INVALID for a null plane, `row_filled` or `col_filled`, width or height outside [1, 8192],
+ * stride_bytes < width*2 and settings cvo_fe_check_depth_infill refuses; CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_infill_plane(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
+                        const cvo_fe_depth_infill *f, uint8_t *flags, int *row_filled, int *col_filled);
 
 /* CVO_HIP_OK for settings cvo_fe_set_lidar() would accept on an idle context without stereo and depth camera,
  * CVO_HIP_ERR_INVALID otherwise: NULL; max_points outside [1, 2^21]; splat outside [0, 3]; a float that is not finite;
