@@ -61,7 +61,8 @@ registration::registration(int mode, int device, void *stream)
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
-      depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), select_mode_(CVO_FE_SELECT_IMAGE)
+      depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), select_mode_(CVO_FE_SELECT_IMAGE),
+      pixel_format_(CVO_FE_PIXEL_BGR8)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -97,6 +98,7 @@ void registration::apply_stored_settings()
         if (have_depth_median_) fe_check(cvo_fe_set_depth_median(fe_, &depth_median_), "cvo_fe_set_depth_median");
         if (have_depth_infill_) fe_check(cvo_fe_set_depth_infill(fe_, &depth_infill_), "cvo_fe_set_depth_infill");
         if (have_lidar_) fe_check(cvo_fe_set_lidar(fe_, &lidar_), "cvo_fe_set_lidar");
+        fe_check(cvo_fe_set_pixel_format(fe_, pixel_format_), "cvo_fe_set_pixel_format");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -262,6 +264,16 @@ void registration::set_select_mode(int mode)
         throw std::runtime_error("set_select_mode(): CVO_FE_SELECT_IMAGE or CVO_FE_SELECT_DEPTH");
     if (fe_) fe_check(cvo_fe_set_select_mode(fe_, mode), "cvo_fe_set_select_mode");
     select_mode_ = mode;
+}
+
+void registration::set_pixel_format(int format)
+{
+    // (before the first image there is no size yet: 2 x 2 fits every format, and a size the format does not fit throws
+    // when that image creates the front end)
+    if (!fe_ && cvo_fe_check_pixel_format(format, 2, 2) != CVO_HIP_OK)
+        throw std::runtime_error("set_pixel_format(): one of CVO_FE_PIXEL_*");
+    if (fe_) fe_check(cvo_fe_set_pixel_format(fe_, format), "cvo_fe_set_pixel_format");
+    pixel_format_ = format;
 }
 
 void registration::set_stereo(const cvo_fe_stereo &stereo)

@@ -26,6 +26,7 @@
 #include "cvo_median.h"
 #include "cvo_speckle.h"
 #include "cvo_stereo.h"
+#include "cvo_unpack.h"
 
 namespace {
 
@@ -1178,6 +1179,16 @@ struct cvo_fe_ctx {
     // qu, qv of the right one; rect_plane(np) entries each) and the validity plane (rect_plane(np) bytes)
     Dev<uint8_t> srig_raw_l, srig_raw_r, srig_valid;
     Dev<int32_t> srig_map;
+    // the pixel format of the caller's colour images (cvo_fe_set_pixel_format): a setting of the context, read by every
+    // frame; under another than BGR8 the packed bytes are what is staged and uploaded, and k_fe_unpack of cvo_unpack.hip
+    // writes where the upload lands otherwise
+    int pixfmt = CVO_FE_PIXEL_BGR8;
+    size_t pix_row = 0;        // row_bytes and rows of the packed image (cvo_fe_pixel_layout); 0 under BGR8
+    int pix_rows = 0;
+    // with such a format, and gone with it: the packed image and its pinned staging (they stand in for h_img); under
+    // stereo the right image's as well (they stand in for h_right)
+    Dev<uint8_t> packed, packed_r;
+    Pin<uint8_t> h_packed, h_packed_r;
     std::string err;
 };
 
@@ -1443,6 +1454,23 @@ void camera_in_force(const cvo_fe_ctx *ctx, int dataset_seq, float cam[5])
 // Dropping those graphs here is what keeps them from being launched again -- and what keeps the cache of 8
 // from filling with dead entries; the generation in the key is the guard behind it, should a graph ever
 // outlive such a change.
+inline bool unpacks(const cvo_fe_ctx *ctx) { return ctx->pixfmt != CVO_FE_PIXEL_BGR8; }
+
+// the staging a frame's colour image is copied to and uploaded from, its row and its rows: the packed image under a
+// pixel format; and the right image's under stereo
+inline uint8_t *img_staging(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->h_packed.get() : ctx->h_img.get(); }
+inline uint8_t *right_staging(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->h_packed_r.get() : ctx->h_right.get(); }
+inline size_t img_row(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_row : (size_t)ctx->d.w * 3; }
+inline int img_rows(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_rows : ctx->d.h; }
+
+// where the colour image lands on the device (an upload, or k_fe_unpack's output): the stereo rig's raw buffer, else the
+// raw image k_fe_rectify resamples, else the image every later stage reads; and the right image of a stereo frame
+inline uint8_t *img_landing(const cvo_fe_ctx *ctx)
+{
+    return ctx->has_srig ? ctx->srig_raw_l.get() : ctx->rectify ? ctx->raw_img.get() : ctx->img.get();
+}
+inline uint8_t *right_landing(const cvo_fe_ctx *ctx) { return ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(); }
+
 void drop_graphs(cvo_fe_ctx *ctx)
 {
     ctx->cam_gen++;
@@ -1459,6 +1487,15 @@ int gate_buffers(cvo_fe_ctx *ctx, Dev<uint16_t> &ungated, Dev<uint8_t> &flags)
     const size_t n = rect_plane(ctx->np);
     if (ctx->ungated || (dev_alloc(ungated, n) && dev_alloc(flags, n))) return CVO_HIP_OK;
     return no_memory(ctx, "device memory for the ungated depth and the gate's flags");
+}
+
+// the packed right image and its staging, for a stereo context under a pixel format; both or neither (left empty for a
+// context that has them, or one in BGR8)
+int packed_right_buffers(cvo_fe_ctx *ctx, Dev<uint8_t> &packed_r, Pin<uint8_t> &h_packed_r)
+{
+    const size_t n = ctx->pix_row * (size_t)ctx->pix_rows;
+    if (!unpacks(ctx) || ctx->packed_r || (dev_alloc(packed_r, n) && pin_alloc(h_packed_r, n))) return CVO_HIP_OK;
+    return no_memory(ctx, "device and pinned memory for the packed right image");
 }
 
 // the Canny path of a frame whose selection came out short (host loop: rare)
@@ -1520,8 +1557,9 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     const int32_t *qu = ctx->rect_map.get(), *qv = qu ? qu + rect_plane(np) : nullptr;   // (read under a distorting model)
     // a distorting camera: the images land in the raw buffers and k_fe_rectify fills img / depth
     // (a stereo rig: the pair lands in the rig's raw buffers and k_fe_stereo_rectify fills img / right_img)
-    uint8_t *img_upload = ctx->has_srig ? ctx->srig_raw_l.get() : ctx->rectify ? ctx->raw_img.get() : img;
-    FE_HIP(hipMemcpyAsync(img_upload, ctx->h_img.get(), (size_t)np * 3, hipMemcpyHostToDevice, s));
+    // (a pixel format: the packed images land in buffers of their own and k_fe_unpack fills what is named above)
+    const size_t img_bytes = img_row(ctx) * (size_t)img_rows(ctx);
+    FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed.get() : img_landing(ctx), img_staging(ctx), img_bytes, hipMemcpyHostToDevice, s));
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
@@ -1530,13 +1568,20 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     uint16_t *plane = source_plane(ctx);
     // (a scan source: the scan is uploaded in place of a depth image, its count in front, and the projection fills that plane)
     if (ctx->has_stereo)
-        FE_HIP(hipMemcpyAsync(ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(), ctx->h_right.get(), (size_t)np * 3,
+        FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), right_staging(ctx), img_bytes,
                               hipMemcpyHostToDevice, s));
     else if (ctx->has_lidar)
         FE_HIP(hipMemcpyAsync(ctx->d_scan.get(), ctx->h_scan.get(), lidar_scan_bytes(ctx->lidar.max_points), hipMemcpyHostToDevice, s));
     else
         FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
+    if (unpacks(ctx)) {   // (the unpack contract: in front of everything else in the frame, one launch for a pair)
+        FeUnpackArgs u{};
+        u.src[0] = ctx->packed.get(); u.dst[0] = img_landing(ctx);
+        u.src[1] = ctx->has_stereo ? ctx->packed_r.get() : nullptr; u.dst[1] = ctx->has_stereo ? right_landing(ctx) : nullptr;
+        u.w = w; u.h = h; u.format = ctx->pixfmt; u.images = ctx->has_stereo ? 2 : 1;
+        fe_unpack_enqueue(u, s);
+    }
     const int32_t *srig_qu = ctx->srig_map.get();   // (read under a stereo rig: qu, qv left, qu, qv right)
     if (ctx->has_srig) {
         const size_t plane = rect_plane(np);
@@ -1946,6 +1991,8 @@ int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
     Dev<uint16_t> sum, disparity, table;
     Dev<uint32_t> win;
     Pin<uint16_t> h_table;
+    Dev<uint8_t> packed_r;   // (under a pixel format: the right image arrives packed as the left one does)
+    Pin<uint8_t> h_packed_r;
     if (st) {
         // (all but the cost sums come with the first settings and stay; the table has room for the largest max_disp)
         if (!ctx->right_img &&
@@ -1955,6 +2002,7 @@ int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
             return no_memory(ctx, "set_stereo: device and pinned memory for the right image and the matcher's planes");
         if ((!ctx->sgm_sum || !ctx->has_stereo || st->max_disp != ctx->stereo.max_disp) && !dev_alloc(sum, np * (size_t)st->max_disp))
             return no_memory(ctx, "set_stereo: device memory for the cost sums");
+        if (packed_right_buffers(ctx, packed_r, h_packed_r) != CVO_HIP_OK) return CVO_HIP_ERR_NOMEM;
     }
     // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
     FE_HIP(hipStreamSynchronize(ctx->stream));
@@ -1968,6 +2016,8 @@ int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
     hand_over(ctx->depth_table, table);
     hand_over(ctx->h_depth_table, h_table);
     hand_over(ctx->sgm_sum, sum);
+    hand_over(ctx->packed_r, packed_r);
+    hand_over(ctx->h_packed_r, h_packed_r);
     if (!st) ctx->sgm_sum.reset();   // (the one large buffer: a context back on depth images does not keep it)
     ctx->has_stereo = st != nullptr;
     ctx->stereo = st ? *st : cvo_fe_stereo{};
@@ -2137,6 +2187,46 @@ int cvo_fe_get_depth_infill(const cvo_fe_ctx *ctx, cvo_fe_depth_infill *out, int
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     *out = ctx->has_infill ? ctx->infill : cvo_fe_depth_infill{};
     if (set) *set = ctx->has_infill ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_pixel_format(cvo_fe_ctx *ctx, int format)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_pixel_format: a frame is in flight");
+    size_t row = 0;
+    int rows = 0;
+    if (!fe_unpack_layout(format, ctx->d.w, ctx->d.h, &row, &rows))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_pixel_format: a CVO_FE_PIXEL_* format that fits the context's size (YUY2, UYVY: an "
+                                              "even width; NV12: an even width and height)");
+    if (format == ctx->pixfmt) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    const bool on = format != CVO_FE_PIXEL_BGR8;
+    Dev<uint8_t> packed, packed_r;
+    Pin<uint8_t> h_packed, h_packed_r;
+    // (the sizes follow the format: built anew for each, the right image's only for a context under stereo)
+    if (on && !(dev_alloc(packed, row * (size_t)rows) && pin_alloc(h_packed, row * (size_t)rows) &&
+                (!ctx->has_stereo || (dev_alloc(packed_r, row * (size_t)rows) && pin_alloc(h_packed_r, row * (size_t)rows)))))
+        return no_memory(ctx, "set_pixel_format: device and pinned memory for the packed image");
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->packed = std::move(packed);   // (all four replaced or, back in BGR8, freed)
+    ctx->packed_r = std::move(packed_r);
+    ctx->h_packed = std::move(h_packed);
+    ctx->h_packed_r = std::move(h_packed_r);
+    ctx->pixfmt = format;
+    ctx->pix_row = on ? row : 0;
+    ctx->pix_rows = on ? rows : 0;
+    drop_graphs(ctx);   // (whether a frame has the stage's launch, its instance and what is uploaded are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_pixel_format(const cvo_fe_ctx *ctx, int *format)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !format) return CVO_HIP_ERR_INVALID;
+    *format = ctx->pixfmt;
     return CVO_HIP_OK;
 }
 
@@ -2550,7 +2640,7 @@ int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **
 int cvo_fe_host_buffers(cvo_fe_ctx *ctx, uint8_t **img, uint16_t **depth)
 {
     if (!ctx || !img || !depth) return CVO_HIP_ERR_INVALID;
-    *img = ctx->h_img.get();
+    *img = img_staging(ctx);
     *depth = ctx->h_depth.get();
     return CVO_HIP_OK;
 }
@@ -2580,7 +2670,7 @@ namespace {
 int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *second, size_t second_stride,
                  int dataset_seq, int feature_type, bool stereo, bool lidar = false, int num_points = 0)
 {
-    const int w = ctx->d.w, h = ctx->d.h, np = ctx->np;
+    const int np = ctx->np;
     const int dw = ctx->dw, dh = ctx->dh;   // (the depth camera's image, if the context has one)
     if (lidar != ctx->has_lidar)
         return fail(ctx, CVO_HIP_ERR_INVALID, lidar ? "submit_lidar: no scan source (cvo_fe_set_lidar)"
@@ -2592,17 +2682,18 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
                   (!second && num_points > 0)))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit_lidar: num_points in [0, max_points], a stride of at least 12 bytes "
                                               "and a multiple of 4, points not null");
-    if (!img || (!second && !lidar) || img_stride < (size_t)w * 3 ||
-        (!lidar && second_stride < (stereo ? (size_t)w * 3 : (size_t)dw * 2)) ||
+    const size_t row = img_row(ctx);   // (of the pixel format in force: w * 3 without one)
+    if (!img || (!second && !lidar) || img_stride < row ||
+        (!lidar && second_stride < (stereo ? row : (size_t)dw * 2)) ||
         (feature_type != CVO_FE_FEATURES_HSV && feature_type != CVO_FE_FEATURES_RGB))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit: bad argument");
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the previous frame was not collected");
     FE_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // pinned staging (not when the caller decoded into the staging image itself: cvo_fe_host_buffers)
-    if (!(img == ctx->h_img.get() && img_stride == (size_t)w * 3)) copy_rows(ctx->h_img.get(), img, img_stride, (size_t)w * 3, h);
+    if (!(img == img_staging(ctx) && img_stride == row)) copy_rows(img_staging(ctx), img, img_stride, row, img_rows(ctx));
     if (stereo) {
-        copy_rows(ctx->h_right.get(), second, second_stride, (size_t)w * 3, h);
+        copy_rows(right_staging(ctx), second, second_stride, row, img_rows(ctx));
         // the table U(q) of the camera in force, if the device holds another's: in front of the frame, outside the
         // captured graph (its address is the graph's), as the mask below
         float cam[5];
@@ -2807,12 +2898,18 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_LIDAR: src = ctx->lidar_flags.get(); need = np; break;
     case CVO_FE_STAGE_SPARSE_DEPTH: src = ctx->sparse.get(); need = np * 2; break;
     case CVO_FE_STAGE_INFILL: src = ctx->infill_flags.get(); need = np; break;
+    case CVO_FE_STAGE_INPUT_BGR: src = img_landing(ctx); need = np * 3; break;
+    case CVO_FE_STAGE_INPUT_RIGHT_BGR: src = right_landing(ctx); need = np * 3; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
     if ((stage == CVO_FE_STAGE_UNFILTERED_DEPTH || stage == CVO_FE_STAGE_MEDIAN) && !ctx->has_median)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the median filter, and no filter is set");
     if ((stage == CVO_FE_STAGE_SPARSE_DEPTH || stage == CVO_FE_STAGE_INFILL) && !ctx->has_infill)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the infill stage, and the stage is not set");
+    if ((stage == CVO_FE_STAGE_INPUT_BGR || stage == CVO_FE_STAGE_INPUT_RIGHT_BGR) && !unpacks(ctx))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: an unpacked image, and the context's pixel format is BGR8");
+    if (stage == CVO_FE_STAGE_INPUT_RIGHT_BGR && !ctx->has_stereo)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the unpacked right image, and the context has no stereo");
     if ((stage == CVO_FE_STAGE_LIDAR_DEPTH || stage == CVO_FE_STAGE_LIDAR) && !ctx->has_lidar)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of a scan source, and none is set");
     if (stage >= CVO_FE_STAGE_RIGHT_GRAY && stage <= CVO_FE_STAGE_SPECKLE_SIZE && !ctx->has_stereo)

@@ -17,6 +17,11 @@ behind whatever fills the plane (the infill contract of include/cvo_frontend.h; 
 
     gen.set_depth_infill(DepthInfill(gap_x=2, gap_y=8, jump_rel=0.25))
 
+Colour images in the sensor's own pixel format -- a Bayer mosaic, YUY2 / UYVY / NV12, grey, RGB, BGRA / RGBA -- unpacked
+on the device in front of everything else (the unpack contract of include/cvo_frontend.h; frames of every kind):
+
+    gen.set_pixel_format(PIXEL_BAYER_RGGB8)     # the images are then h x w bytes of mosaic
+
 A LiDAR scan in place of the depth image, projected into the colour camera on the device (the LiDAR contract of
 include/cvo_frontend.h; KITTI: R, T from R_rect_00 * Tr_velo_to_cam):
 
@@ -58,12 +63,16 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
  STAGE_EDGES, STAGE_RECT_BGR, STAGE_RECT_DEPTH, STAGE_RAW_DEPTH, STAGE_UNGATED_DEPTH, STAGE_GATE, STAGE_RIGHT_GRAY,
  STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
  STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE, STAGE_UNFILTERED_DEPTH, STAGE_MEDIAN, STAGE_LIDAR_DEPTH,
- STAGE_LIDAR, STAGE_SPARSE_DEPTH, STAGE_INFILL) = range(30)
+ STAGE_LIDAR, STAGE_SPARSE_DEPTH, STAGE_INFILL, STAGE_INPUT_BGR, STAGE_INPUT_RIGHT_BGR) = range(32)
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 MEDIAN_CHANGED, MEDIAN_FILLED = 1, 2   # the values of STAGE_MEDIAN
 LIDAR_HIT, LIDAR_OCCLUDED = 1, 2       # the bits of STAGE_LIDAR
 INFILL_ROW, INFILL_COL, INFILL_JUMP = 1, 2, 4   # the values of STAGE_INFILL
+# pixel formats of the colour images (set_pixel_format; the unpack contract of include/cvo_frontend.h).  Bayer: the four
+# letters are the colours of pixels (0,0) (1,0) / (0,1) (1,1) -- not OpenCV's names
+(PIXEL_BGR8, PIXEL_RGB8, PIXEL_BGRA8, PIXEL_RGBA8, PIXEL_GREY8, PIXEL_YUY2, PIXEL_UYVY, PIXEL_NV12, PIXEL_BAYER_RGGB8,
+ PIXEL_BAYER_BGGR8, PIXEL_BAYER_GRBG8, PIXEL_BAYER_GBRG8) = range(12)
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
 # modes of the selector (set_select_mode): by the image alone (the reference; a new object's), or among the pixels
@@ -83,7 +92,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_get_select_mode", "cvo_fe_check_depth_median", "cvo_fe_set_depth_median", "cvo_fe_get_depth_median",
            "cvo_fe_median_plane", "cvo_fe_check_depth_infill", "cvo_fe_set_depth_infill", "cvo_fe_get_depth_infill",
            "cvo_fe_infill_plane", "cvo_fe_check_lidar", "cvo_fe_set_lidar", "cvo_fe_get_lidar", "cvo_fe_submit_lidar",
-           "cvo_fe_create_pointcloud_lidar", "cvo_fe_project_points")
+           "cvo_fe_create_pointcloud_lidar", "cvo_fe_project_points", "cvo_fe_check_pixel_format", "cvo_fe_pixel_layout",
+           "cvo_fe_set_pixel_format", "cvo_fe_get_pixel_format", "cvo_fe_unpack_image")
 
 
 class Info(C.Structure):
@@ -349,6 +359,11 @@ def lib():
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cvo_fe_median_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthMedian), u8p,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.cvo_fe_check_pixel_format.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.cvo_fe_pixel_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.cvo_fe_set_pixel_format.argtypes = [vp, C.c_int]
+        L.cvo_fe_get_pixel_format.argtypes = [vp, C.POINTER(C.c_int)]
+        L.cvo_fe_unpack_image.argtypes = [C.c_int, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p]
         L.cvo_fe_check_lidar.argtypes = [C.POINTER(Lidar)]
         L.cvo_fe_set_lidar.argtypes = [vp, C.POINTER(Lidar)]
         L.cvo_fe_get_lidar.argtypes = [vp, C.POINTER(Lidar), C.POINTER(C.c_int)]
@@ -521,6 +536,44 @@ def infill_plane(plane, infill, device=0, stride=None):
     return np.ascontiguousarray(buf[:, :w]), flags, rows.value, cols.value
 
 
+def _c_int(v, what):
+    v = int(v)
+    if not -2 ** 31 <= v < 2 ** 31:
+        raise capi.CvoHipError("%s: outside the range of a C int" % what)
+    return v
+
+
+def check_pixel_format(fmt, width, height):
+    """True for a PIXEL_* format that fits a width x height picture (cvo_fe_check_pixel_format): YUY2 and UYVY need an
+    even width, NV12 an even width and height, Bayer at least 2 x 2.  Host only."""
+    return lib().cvo_fe_check_pixel_format(_c_int(fmt, "check_pixel_format"), _c_int(width, "check_pixel_format"),
+                                           _c_int(height, "check_pixel_format")) == 0
+
+
+def pixel_layout(fmt, width, height):
+    """(rows, row_bytes) of a packed width x height image of format `fmt` (cvo_fe_pixel_layout).  Host only."""
+    row, rows = C.c_size_t(0), C.c_int(0)
+    capi.check(lib().cvo_fe_pixel_layout(_c_int(fmt, "pixel_layout"), _c_int(width, "pixel_layout"),
+                                         _c_int(height, "pixel_layout"), C.byref(row), C.byref(rows)), what="pixel_layout")
+    return rows.value, row.value
+
+
+def unpack_image(src, fmt, width, height, device=0, stride=None):
+    """The unpack contract on any packed image (cvo_fe_unpack_image: the kernel a frame runs, without a generator): `src`
+    is any uint8 array whose C-order bytes are the rows of pixel_layout(fmt, width, height), `stride` bytes apart (dense
+    without one).  Returns the height x width x 3 uint8 image, B G R; the argument is left as it is."""
+    rows, row = pixel_layout(fmt, width, height)
+    pitch = row if stride is None else int(stride)
+    src = np.ascontiguousarray(src, np.uint8)
+    if pitch < row or src.size != rows * pitch:
+        raise ValueError("expected %d rows of %d bytes, %d apart" % (rows, row, pitch))
+    out = np.empty((int(height), int(width), 3), np.uint8)
+    u8p = C.POINTER(C.c_uint8)
+    capi.check(lib().cvo_fe_unpack_image(int(device), src.ctypes.data_as(u8p), pitch, int(width), int(height), int(fmt),
+                                         out.ctypes.data_as(u8p)), what="unpack_image")
+    return out
+
+
 def check_lidar(lidar):
     """True for a Lidar set_lidar() accepts on a generator without stereo and depth camera (cvo_fe_check_lidar); None is
     refused.  Host only."""
@@ -617,6 +670,8 @@ class PcdGenerator:
         self.capacity = self.width * self.height   # (upper bound of any selection)
         self._dshape = (self.height, self.width)   # of the depth image: the depth camera's, if one is set
         self._max_disp = 0                         # of the stereo settings, if some are set
+        self._pix = PIXEL_BGR8                     # the pixel format of the colour images (set_pixel_format)
+        self._ishape = (self.height, self.width * 3)   # rows x row_bytes of a colour image in that format
         self._pos = np.empty((self.capacity, 3), np.float32)
         self._feat = np.empty((self.capacity, 5), np.float32)
 
@@ -628,11 +683,10 @@ class PcdGenerator:
 
     def _images(self, bgr, depth):
         """The two images of a frame as dense arrays of the sizes the context takes."""
-        bgr = np.ascontiguousarray(bgr, np.uint8)
+        bgr = self._image(bgr)
         depth = np.ascontiguousarray(depth, np.uint16)
-        if bgr.shape != (self.height, self.width, 3) or depth.shape != self._dshape:
-            raise ValueError("expected a %dx%dx3 uint8 image and a %dx%d uint16 depth map"
-                             % ((self.height, self.width) + self._dshape))
+        if depth.shape != self._dshape:
+            raise ValueError("expected a %dx%d uint16 depth map" % self._dshape)
         return bgr, depth
 
     def create_pointcloud(self, bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB):
@@ -641,7 +695,7 @@ class PcdGenerator:
         bgr, depth = self._images(bgr, depth)
         n = C.c_int(0)
         st = lib().cvo_fe_create_pointcloud(
-            self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3,
+            self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self._ishape[1],
             depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2, int(dataset_seq), int(feature_type),
             self._pos.ctypes.data_as(C.POINTER(C.c_float)), self._feat.ctypes.data_as(C.POINTER(C.c_float)),
             self.capacity, C.byref(n))
@@ -651,7 +705,7 @@ class PcdGenerator:
     def submit(self, bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB):
         """First half of create_pointcloud: stage the images, enqueue everything, return."""
         bgr, depth = self._images(bgr, depth)
-        self._chk(lib().cvo_fe_submit(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3,
+        self._chk(lib().cvo_fe_submit(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self._ishape[1],
                                       depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2,
                                       int(dataset_seq), int(feature_type)), "submit")
 
@@ -673,10 +727,11 @@ class PcdGenerator:
     def host_buffers(self):
         """numpy views of the context's pinned staging images (h x w x 3 uint8, h x w uint16): fill
         them in place and pass them to submit() / create_pointcloud() to save a copy.  The depth view is
-        of the depth camera's size while one is set and valid until the next set_depth_camera()."""
+        of the depth camera's size while one is set and valid until the next set_depth_camera().  Under a pixel
+        format the image view is the packed image, rows x row_bytes, valid until the next set_pixel_format()."""
         pi, pd = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint16)()
         self._chk(lib().cvo_fe_host_buffers(self._h, C.byref(pi), C.byref(pd)), "host_buffers")
-        img = np.ctypeslib.as_array(pi, shape=(self.height, self.width, 3))
+        img = np.ctypeslib.as_array(pi, shape=self._ishape if self._pix != PIXEL_BGR8 else (self.height, self.width, 3))
         dep = np.ctypeslib.as_array(pd, shape=self._dshape)
         return img, dep
 
@@ -820,10 +875,31 @@ class PcdGenerator:
         return out if isset.value else None
 
     def _image(self, bgr):
+        """A colour image as a dense array: h x w x 3 under BGR8, else any uint8 array whose C-order bytes are the
+        rows x row_bytes of the pixel format in force."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
-        if bgr.shape != (self.height, self.width, 3):
-            raise ValueError("expected a %dx%dx3 uint8 image" % (self.height, self.width))
+        if self._pix == PIXEL_BGR8:
+            if bgr.shape != (self.height, self.width, 3):
+                raise ValueError("expected a %dx%dx3 uint8 image" % (self.height, self.width))
+        elif bgr.size != self._ishape[0] * self._ishape[1]:
+            raise ValueError("expected %d rows of %d bytes (the pixel format in force)" % self._ishape)
         return bgr
+
+    def set_pixel_format(self, fmt):
+        """The PIXEL_* format of every colour image of every following frame of any kind -- both images of a stereo
+        pair (the unpack contract of include/cvo_frontend.h): the images are then handed over packed, pixel_layout()'s
+        rows x row_bytes, and unpacked on the device in front of everything else.  PIXEL_BGR8: a new object's.  A
+        setting of its own: it survives every other setter."""
+        fmt = _c_int(fmt, "set_pixel_format")
+        self._chk(lib().cvo_fe_set_pixel_format(self._h, fmt), "set_pixel_format")
+        self._pix = fmt
+        self._ishape = pixel_layout(fmt, self.width, self.height)
+
+    def pixel_format(self):
+        """The pixel format in force."""
+        out = C.c_int(0)
+        self._chk(lib().cvo_fe_get_pixel_format(self._h, C.byref(out)), "get_pixel_format")
+        return int(out.value)
 
     def create_pointcloud_lidar(self, bgr, points, dataset_seq=4, feature_type=FEATURES_RGB):
         """create_pointcloud() for a colour image and a scan: `points` is n x k float32, x y z first (KITTI's .bin read
@@ -833,7 +909,7 @@ class PcdGenerator:
         n = C.c_int(0)
         fp = C.POINTER(C.c_float)
         st = lib().cvo_fe_create_pointcloud_lidar(
-            self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3, addr, stride, npts, int(dataset_seq),
+            self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self._ishape[1], addr, stride, npts, int(dataset_seq),
             int(feature_type), self._pos.ctypes.data_as(fp), self._feat.ctypes.data_as(fp), self.capacity, C.byref(n))
         self._chk(st, "create_pointcloud_lidar")
         return self._pos[:n.value].copy(), self._feat[:n.value].copy()
@@ -843,7 +919,7 @@ class PcdGenerator:
         copied before the call returns."""
         bgr = self._image(bgr)
         pts, addr, stride, npts = _scan(points)
-        self._chk(lib().cvo_fe_submit_lidar(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self.width * 3, addr, stride,
+        self._chk(lib().cvo_fe_submit_lidar(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self._ishape[1], addr, stride,
                                             npts, int(dataset_seq), int(feature_type)), "submit_lidar")
 
     def set_select_mode(self, mode):
@@ -876,20 +952,17 @@ class PcdGenerator:
     stereo_rig_map = staticmethod(stereo_rig_map)
 
     def _pair(self, left, right):
-        left = np.ascontiguousarray(left, np.uint8)
-        right = np.ascontiguousarray(right, np.uint8)
-        if left.shape != (self.height, self.width, 3) or right.shape != left.shape:
-            raise ValueError("expected two %dx%dx3 uint8 images" % (self.height, self.width))
-        return left, right
+        return self._image(left), self._image(right)
 
     def create_pointcloud_stereo(self, left, right, dataset_seq=4, feature_type=FEATURES_RGB):
         """create_pointcloud() for a stereo pair: two h x w x 3 uint8 images (a grey right image is replicated by the
-        caller); the left one is the colour image of the frame."""
+        caller, or both are handed over as they are under set_pixel_format(PIXEL_GREY8)); the left one is the colour image
+        of the frame."""
         left, right = self._pair(left, right)
         n = C.c_int(0)
         u8p, fp = C.POINTER(C.c_uint8), C.POINTER(C.c_float)
         st = lib().cvo_fe_create_pointcloud_stereo(
-            self._h, left.ctypes.data_as(u8p), self.width * 3, right.ctypes.data_as(u8p), self.width * 3, int(dataset_seq),
+            self._h, left.ctypes.data_as(u8p), self._ishape[1], right.ctypes.data_as(u8p), self._ishape[1], int(dataset_seq),
             int(feature_type), self._pos.ctypes.data_as(fp), self._feat.ctypes.data_as(fp), self.capacity, C.byref(n))
         self._chk(st, "create_pointcloud_stereo")
         return self._pos[:n.value].copy(), self._feat[:n.value].copy()
@@ -898,8 +971,8 @@ class PcdGenerator:
         """submit() for a stereo pair; collect() / collect_device() as for any other frame."""
         left, right = self._pair(left, right)
         u8p = C.POINTER(C.c_uint8)
-        self._chk(lib().cvo_fe_submit_stereo(self._h, left.ctypes.data_as(u8p), self.width * 3, right.ctypes.data_as(u8p),
-                                             self.width * 3, int(dataset_seq), int(feature_type)), "submit_stereo")
+        self._chk(lib().cvo_fe_submit_stereo(self._h, left.ctypes.data_as(u8p), self._ishape[1], right.ctypes.data_as(u8p),
+                                             self._ishape[1], int(dataset_seq), int(feature_type)), "submit_stereo")
 
     def info(self):
         out = Info()
@@ -922,7 +995,8 @@ class PcdGenerator:
                   STAGE_STEREO_VALID: ((h, w), np.uint8), STAGE_SPECKLE_SIZE: ((h, w), np.uint32),
                   STAGE_UNFILTERED_DEPTH: ((h, w), np.uint16), STAGE_MEDIAN: ((h, w), np.uint8),
                   STAGE_LIDAR_DEPTH: ((h, w), np.uint16), STAGE_LIDAR: ((h, w), np.uint8),
-                  STAGE_SPARSE_DEPTH: ((h, w), np.uint16), STAGE_INFILL: ((h, w), np.uint8)}
+                  STAGE_SPARSE_DEPTH: ((h, w), np.uint16), STAGE_INFILL: ((h, w), np.uint8),
+                  STAGE_INPUT_BGR: ((h, w, 3), np.uint8), STAGE_INPUT_RIGHT_BGR: ((h, w, 3), np.uint8)}
         shape, dt = shapes[stage]
         out = np.empty(shape, dt)
         self._chk(lib().cvo_fe_read_stage(self._h, stage, out.ctypes.data_as(C.c_void_p), out.nbytes), "read_stage")
@@ -969,8 +1043,10 @@ def load_img(rgb_path, depth_path):
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
-               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None):
+               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None, pixel_format=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `pixel_format`: a PIXEL_* format for the generator: the colour images `frames` yields are then packed in it (both of a
+    stereo pair); None leaves the generator as it is.
     `lidar`: a Lidar for the generator: `frames` then yields (name, bgr, points), a colour image and a scan (n x k
     float32, x y z first), and the depth comes from the scan projected on the device; None leaves the generator as it is.
     `stereo`: a Stereo for the generator: `frames` then yields (name, left, right), two colour images of a rectified
@@ -1025,6 +1101,8 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_depth_median(depth_median)
     if depth_infill is not None:
         gen.set_depth_infill(depth_infill)
+    if pixel_format is not None:
+        gen.set_pixel_format(pixel_format)
     if lidar is not None:
         gen.set_lidar(lidar)
     submit = gen.submit_stereo if stereo is not None else gen.submit_lidar if lidar is not None else gen.submit

@@ -27,7 +27,7 @@ namespace cvo_hip {
 
 // Stand-in for the cv::Mat arguments of set_pcd() / run_cvo(): what cv::imread gives
 // -- rows x cols pixels, `step` bytes per row; the colour image 3 bytes per pixel in
-// file (B, G, R) order, the depth image one uint16 per pixel.
+// file (B, G, R) order (or packed in the format of set_pixel_format()), the depth image one uint16 per pixel.
 struct image_view {
     const void *data;
     int rows, cols;
@@ -139,6 +139,13 @@ class registration {
     // not compete, so the cloud holds the points asked for -- the selection contract: cvo_frontend.h).  A setting of
     // its own, before or after the first image; throws for a mode the front end refuses.
     void set_select_mode(int mode);
+    // The pixel format of every colour image of the image form of set_pcd() / run_cvo() of every kind of frame, both
+    // images of a stereo pair: cvo_fe_set_pixel_format (CVO_FE_PIXEL_BGR8, a new object's; the unpack contract:
+    // cvo_frontend.h).  An image_view's rows and cols stay the picture's, and its step is the pitch of the packed rows
+    // (cvo_fe_pixel_layout: NV12's chroma rows follow the picture's at the same pitch).  A setting of its own, before
+    // or after the first image; throws for a format the front end refuses -- one the image size does not fit included,
+    // which before the first image shows when that image arrives.
+    void set_pixel_format(int format);
     // A mask for every following frame: rows x cols bytes of the colour image's size, `step` bytes apart,
     // non-zero = no point from this pixel (cvo_fe_set_mask).  The bytes are copied.  May be called before the
     // first image: the copy is handed to the front end when it is created, and a mask of another size than that
@@ -226,6 +233,7 @@ class registration {
     cvo_fe_lidar lidar_;                 // what set_lidar() gave, likewise
     bool have_lidar_;
     int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)
+    int pixel_format_;                   // what set_pixel_format() gave, likewise (CVO_FE_PIXEL_BGR8 without a call)
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();

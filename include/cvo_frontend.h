@@ -121,7 +121,11 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        /* of a frame under the infill stage (cvo_fe_set_depth_infill; CVO_HIP_ERR_INVALID on a context without it).
           With it UNFILTERED_DEPTH (under a median filter), else UNGATED_DEPTH, is F of the infill contract. */
        CVO_FE_STAGE_SPARSE_DEPTH = 28,    /* S of the infill contract: w*h uint16 */
-       CVO_FE_STAGE_INFILL = 29 };        /* INFILL of the infill contract: w*h uint8, CVO_FE_INFILL_* */
+       CVO_FE_STAGE_INFILL = 29,          /* INFILL of the infill contract: w*h uint8, CVO_FE_INFILL_* */
+       /* of a frame under a pixel format (cvo_fe_set_pixel_format; CVO_HIP_ERR_INVALID on a context in
+          CVO_FE_PIXEL_BGR8, and the second on one without stereo as well) */
+       CVO_FE_STAGE_INPUT_BGR = 30,       /* the unpacked colour or left image, in front of any rectification: w*h*3 uint8 */
+       CVO_FE_STAGE_INPUT_RIGHT_BGR = 31 };   /* the unpacked right image: w*h*3 uint8 */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
@@ -136,6 +140,46 @@ enum { CVO_FE_MEDIAN_CHANGED = 1, CVO_FE_MEDIAN_FILLED = 2 };
 enum { CVO_FE_LIDAR_HIT = 1, CVO_FE_LIDAR_OCCLUDED = 2 };
 /* values of CVO_FE_STAGE_INFILL (the infill contract at cvo_fe_depth_infill) */
 enum { CVO_FE_INFILL_ROW = 1, CVO_FE_INFILL_COL = 2, CVO_FE_INFILL_JUMP = 4 };
+
+/* The pixel format of the colour images a caller hands over (cvo_fe_set_pixel_format), and the unpack contract.
+ *
+ * Layout.  A packed image of a w x h picture is `rows` rows of `row_bytes` bytes (cvo_fe_pixel_layout):
+ *   BGR8, RGB8: 3w.  BGRA8, RGBA8: 4w.  YUY2, UYVY: 2w.  GREY8, NV12 and the four Bayer formats: w.
+ *   rows is h, except NV12: h + h/2 (h rows of Y, then h/2 rows of U V pairs).
+ * A caller's image has one stride for every row, NV12's chroma rows included, of at least row_bytes.
+ * Sizes.  YUY2 and UYVY need an even w, NV12 an even w and an even h, Bayer w >= 2 and h >= 2.
+ *
+ * The unpacked image is w*h*3 bytes, B G R per pixel, defined by this arithmetic and not by the device -- this
+ * library's own definition, not pinned against another library's conversions:
+ *   RGB8, BGRA8, RGBA8, GREY8: byte moves; alpha is dropped; GREY8: B = G = R = the byte.
+ *   YUY2 (Y0 U Y1 V), UYVY (U Y0 V Y1), NV12: pixels 2k and 2k+1 of a row share the U and V of their pair; NV12 pixel
+ *     (x, y) takes the pair at column x >> 1 of chroma row y >> 1; no chroma is interpolated.  BT.601, limited range,
+ *     in int32 with an arithmetic shift, Y NOT clamped before the multiply:
+ *         c = Y - 16;  d = U - 128;  e = V - 128;
+ *         R = sat8((1220945*c + 1673555*e             + 524288) >> 20);
+ *         G = sat8((1220945*c -  410793*d - 852458*e  + 524288) >> 20);
+ *         B = sat8((1220945*c + 2115221*d             + 524288) >> 20);
+ *     The constants are 2^20 times 255/219, 1.402*255/224, 1.772*(0.114/0.587)*255/224, 1.402*(0.299/0.587)*255/224
+ *     and 1.772*255/224, rounded to nearest; over all 2^24 triples the largest accumulator is 560 963 210 in
+ *     magnitude.  (16, 128, 128) gives 0 0 0, (235, 128, 128) gives 255 255 255, and B = G = R along the grey axis.
+ *   Bayer, bilinear.  The four letters of a format are the colours of pixels (0,0) (1,0) / (0,1) (1,1) -- NOT OpenCV's
+ *     names.  A pixel keeps the value of its own colour.  Green at a red or blue site is (N + S + E + W + 2) >> 2; the
+ *     opposite colour there is the four diagonals, (... + 2) >> 2.  At a green site the colour of its row is
+ *     (E + W + 1) >> 1 and the other is (N + S + 1) >> 1.  A neighbour outside the image is MIRRORED about the border
+ *     pixel (-1 -> 1, w -> w - 2), which keeps the mosaic's phase.  The mosaic of a flat colour comes back exactly;
+ *     that of an integer ramp comes back exactly in the interior, not on the border.
+ *
+ * Where it sits.  Under a format other than BGR8 one kernel runs in front of everything else in the frame; its output
+ * lands where the uploaded image lands otherwise (CVO_FE_STAGE_INPUT_BGR, CVO_FE_STAGE_INPUT_RIGHT_BGR), and no
+ * later stage changes: the frame is that of a context in BGR8 fed the unpacked image.  The mask's grid ("the colour
+ * image as uploaded") is the same pixel grid. */
+enum { CVO_FE_PIXEL_BGR8 = 0,      /* a new context's: the layout cv::imread decodes to */
+       CVO_FE_PIXEL_RGB8 = 1, CVO_FE_PIXEL_BGRA8 = 2, CVO_FE_PIXEL_RGBA8 = 3, CVO_FE_PIXEL_GREY8 = 4,
+       CVO_FE_PIXEL_YUY2 = 5,      /* Y0 U Y1 V */
+       CVO_FE_PIXEL_UYVY = 6,      /* U Y0 V Y1 */
+       CVO_FE_PIXEL_NV12 = 7,      /* h rows of Y, then h/2 rows of U V pairs */
+       CVO_FE_PIXEL_BAYER_RGGB8 = 8, CVO_FE_PIXEL_BAYER_BGGR8 = 9,
+       CVO_FE_PIXEL_BAYER_GRBG8 = 10, CVO_FE_PIXEL_BAYER_GBRG8 = 11 };
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141; under
@@ -611,7 +655,9 @@ int cvo_fe_create_pointcloud(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_str
                              size_t depth_stride, int dataset_seq, int feature_type, float *positions,
                              float *features, int capacity, int *num_points);
 
-/* The context's own pinned staging images (width*3 bytes per colour row, width uint16 per
+/* The context's own pinned staging images (width*3 bytes per colour row -- under a pixel format
+ * the packed image, rows * row_bytes bytes of cvo_fe_pixel_layout, and the pointer is valid until
+ * the next cvo_fe_set_pixel_format() -- width uint16 per
  * depth row, no padding): a decoder that writes straight into them -- e.g. a cv::Mat header
  * over the pointer handed to cv::imdecode -- saves the copy that submit() / create_pointcloud()
  * otherwise make; pass these same pointers (and the dense strides) to them.  They may be
@@ -906,6 +952,28 @@ int cvo_fe_check_depth_infill(const cvo_fe_depth_infill *f);
  * stride_bytes < width*2 and settings cvo_fe_check_depth_infill refuses; CVO_HIP_ERR_NODEVICE without such a device. */
 int cvo_fe_infill_plane(int device, uint16_t *plane, size_t stride_bytes, int width, int height,
                         const cvo_fe_depth_infill *f, uint8_t *flags, int *row_filled, int *col_filled);
+
+/* CVO_HIP_OK for a format of the list above that fits a width x height picture (the sizes of the unpack contract;
+ * width and height at least 1), CVO_HIP_ERR_INVALID otherwise.  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_pixel_format(int format, int width, int height);
+/* The layout table of the unpack contract: *row_bytes and *rows of a packed width x height image.
+ * CVO_HIP_ERR_INVALID for a null pointer and for what cvo_fe_check_pixel_format refuses.  Host only. */
+int cvo_fe_pixel_layout(int format, int width, int height, size_t *row_bytes, int *rows);
+/* The format of EVERY colour image of every following frame: the image of cvo_fe_submit / cvo_fe_create_pointcloud
+ * and of cvo_fe_submit_lidar, and both images of cvo_fe_submit_stereo (one format for the pair, with or without a
+ * stereo rig).  Their strides are then at least row_bytes, and their rows are `rows`.  A setting of its own: it
+ * survives every other setter.  CVO_FE_PIXEL_BGR8: a new context's state; the buffers of the setting are freed and a
+ * frame launches what it launched before.  CVO_HIP_ERR_INVALID while a frame is pending and for a format
+ * cvo_fe_check_pixel_format refuses at the context's size; cvo_fe_last_error() says which. */
+int cvo_fe_set_pixel_format(cvo_fe_ctx *ctx, int format);
+int cvo_fe_get_pixel_format(const cvo_fe_ctx *ctx, int *format);
+/* The unpack contract on any packed image by the kernel a frame runs, without a context: host arrays in and out.
+ * `src` is `rows` rows of row_bytes bytes, `stride_bytes` apart, and is not written; `bgr` receives width*height*3
+ * bytes, dense.  Under CVO_FE_PIXEL_BGR8 it is a copy.  CVO_HIP_ERR_INVALID for a null pointer, width or height
+ * outside [1, 8192], a format cvo_fe_check_pixel_format refuses at that size and stride_bytes < row_bytes;
+ * CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_unpack_image(int device, const uint8_t *src, size_t stride_bytes, int width, int height, int format,
+                        uint8_t *bgr);
 
 /* CVO_HIP_OK for settings cvo_fe_set_lidar() would accept on an idle context without stereo and depth camera,
  * CVO_HIP_ERR_INVALID otherwise: NULL; max_points outside [1, 2^21]; splat outside [0, 3]; a float that is not finite;
