@@ -61,7 +61,7 @@ registration::registration(int mode, int device, void *stream)
       fe_points_(0), device_(device), camera_(), have_camera_(false), depth_camera_(), have_depth_camera_(false),
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
-      depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), select_mode_(CVO_FE_SELECT_IMAGE),
+      depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), lidar_sweep_(), have_lidar_sweep_(false), lidar_motion_(), select_mode_(CVO_FE_SELECT_IMAGE),
       pixel_format_(CVO_FE_PIXEL_BGR8)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
@@ -98,6 +98,10 @@ void registration::apply_stored_settings()
         if (have_depth_median_) fe_check(cvo_fe_set_depth_median(fe_, &depth_median_), "cvo_fe_set_depth_median");
         if (have_depth_infill_) fe_check(cvo_fe_set_depth_infill(fe_, &depth_infill_), "cvo_fe_set_depth_infill");
         if (have_lidar_) fe_check(cvo_fe_set_lidar(fe_, &lidar_), "cvo_fe_set_lidar");
+        if (have_lidar_sweep_) {
+            fe_check(cvo_fe_set_lidar_sweep(fe_, &lidar_sweep_), "cvo_fe_set_lidar_sweep");
+            fe_check(cvo_fe_set_lidar_motion(fe_, lidar_motion_), "cvo_fe_set_lidar_motion");
+        }
         fe_check(cvo_fe_set_pixel_format(fe_, pixel_format_), "cvo_fe_set_pixel_format");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
@@ -256,6 +260,42 @@ void registration::set_lidar(const cvo_fe_lidar &lidar)
 void registration::clear_lidar()
 {
     store<cvo_fe_lidar>(cvo_fe_set_lidar, "cvo_fe_set_lidar", nullptr, lidar_, have_lidar_);
+    have_lidar_sweep_ = false;   // (the sweep goes with the scan source)
+    for (float &t : lidar_motion_) t = 0.0f;
+}
+
+void registration::set_lidar_sweep(const cvo_fe_lidar_sweep &sweep)
+{
+    if (!fe_ && cvo_fe_check_lidar_sweep(&sweep) != CVO_HIP_OK)
+        throw std::runtime_error("set_lidar_sweep(): a mode of CVO_FE_SWEEP_*, finite members, time_offset >= 12 and a "
+                                 "multiple of 4, time_scale not 0, direction +1 or -1 under the azimuth mode and 0 "
+                                 "otherwise, phase0 in [0, 1), s_ref in [0, 1], pad_ 0");
+    if (!fe_ && !have_lidar_) throw std::runtime_error("set_lidar_sweep(): no scan source: set_lidar() first");
+    store<cvo_fe_lidar_sweep>(cvo_fe_set_lidar_sweep, "cvo_fe_set_lidar_sweep", &sweep, lidar_sweep_, have_lidar_sweep_);
+    for (float &t : lidar_motion_) t = 0.0f;
+}
+
+void registration::clear_lidar_sweep()
+{
+    store<cvo_fe_lidar_sweep>(cvo_fe_set_lidar_sweep, "cvo_fe_set_lidar_sweep", nullptr, lidar_sweep_, have_lidar_sweep_);
+    for (float &t : lidar_motion_) t = 0.0f;
+}
+
+void registration::set_lidar_motion(const float twist[6])
+{
+    if (!twist) throw std::runtime_error("set_lidar_motion(): a twist holds six numbers");
+    if (!have_lidar_sweep_) throw std::runtime_error("set_lidar_motion(): no sweep: set_lidar_sweep() first");
+    double w2 = 0.0, v2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        w2 += (double)twist[k] * twist[k];
+        v2 += (double)twist[3 + k] * twist[3 + k];
+    }
+    // (NaN fails both comparisons)
+    if (!(w2 <= (double)CVO_FE_SWEEP_MAX_ROTATION * CVO_FE_SWEEP_MAX_ROTATION) ||
+        !(v2 <= (double)CVO_FE_SWEEP_MAX_TRANSLATION * CVO_FE_SWEEP_MAX_TRANSLATION))
+        throw std::runtime_error("set_lidar_motion(): finite members, |w| <= 1 radian and |v| <= 64 metres per sweep");
+    if (fe_) fe_check(cvo_fe_set_lidar_motion(fe_, twist), "cvo_fe_set_lidar_motion");
+    for (int k = 0; k < 6; ++k) lidar_motion_[k] = twist[k];
 }
 
 void registration::set_select_mode(int mode)

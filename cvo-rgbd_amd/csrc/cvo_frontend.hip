@@ -1162,6 +1162,13 @@ struct cvo_fe_ctx {
     Dev<uint8_t> d_scan;
     Dev<uint16_t> lidar_p0;
     Dev<uint8_t> lidar_flags;
+    // the sweep of the scan source (cvo_fe_set_lidar_sweep), gone with it; the twist of the frames submitted from now
+    // on (cvo_fe_set_lidar_motion), which lidar_stage puts into the scan's header; and the bytes of one staged record,
+    // which h_scan and d_scan are sized for: 16 under a field mode, else 12
+    cvo_fe_lidar_sweep sweep{};
+    bool has_sweep = false;
+    float lidar_twist[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    size_t scan_record = 12;
     // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
     // table U(q) with its staging copy; the cost sums follow max_disp
     Dev<uint8_t> right_img, right_gray, stereo_flags;
@@ -1312,19 +1319,47 @@ bool lidar_ok(const cvo_fe_lidar &l)
 
 inline bool lidar_stride_ok(size_t stride_bytes) { return stride_bytes >= 12 && stride_bytes % 4 == 0; }
 
-inline size_t lidar_scan_bytes(int capacity) { return (size_t)FE_LIDAR_HEADER + (size_t)capacity * 12; }
+// (the staging of a scan and its packing, lidar_stage: cvo_lidar_stage.h)
 
-// `n` points of records `stride` bytes apart into a scan's staging: the count in the header, the points packed
-void lidar_stage(uint8_t *scan, const void *points, size_t stride, int n)
+inline bool sweep_field_mode(const cvo_fe_lidar_sweep &sw) { return sw.mode == CVO_FE_SWEEP_TIME_F32 || sw.mode == CVO_FE_SWEEP_TIME_U32; }
+
+// the byte offset of the time word that lidar_stage carries along, -1: none
+inline int sweep_time_offset(const cvo_fe_lidar_sweep *sw) { return sw && sweep_field_mode(*sw) ? sw->time_offset : -1; }
+
+// what cvo_fe_set_lidar_sweep accepts
+bool sweep_ok(const cvo_fe_lidar_sweep &sw)
 {
-    int32_t header[FE_LIDAR_HEADER / 4] = {n, 0, 0, 0};
-    std::memcpy(scan, header, sizeof(header));
-    uint8_t *dst = scan + FE_LIDAR_HEADER;
-    if (stride == 12) {
-        if (n) std::memcpy(dst, points, (size_t)n * 12);
-        return;
+    static_assert(sizeof(cvo_fe_lidar_sweep) == 32, "32 bytes, no padding");
+    if (!std::isfinite(sw.time_origin) || !std::isfinite(sw.time_scale) || !std::isfinite(sw.phase0) || !std::isfinite(sw.s_ref))
+        return false;
+    if (!(sw.s_ref >= 0.0f && sw.s_ref <= 1.0f) || sw.pad_ != 0) return false;
+    if (sweep_field_mode(sw)) {
+        if (sw.time_offset < 12 || sw.time_offset % 4 != 0 || sw.time_scale == 0.0f || sw.direction != 0) return false;
+        return sw.mode == CVO_FE_SWEEP_TIME_F32 || sw.time_origin == 0.0f;
     }
-    for (int i = 0; i < n; ++i) std::memcpy(dst + (size_t)i * 12, (const uint8_t *)points + (size_t)i * stride, 12);
+    if (sw.mode != CVO_FE_SWEEP_AZIMUTH) return false;
+    return (sw.direction == 1 || sw.direction == -1) && sw.phase0 >= 0.0f && sw.phase0 < 1.0f && sw.time_origin == 0.0f;
+}
+
+// what cvo_fe_set_lidar_motion accepts
+bool twist_ok(const float twist[6])
+{
+    double w2 = 0.0, v2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(twist[k]) || !std::isfinite(twist[3 + k])) return false;
+        w2 += (double)twist[k] * twist[k];
+        v2 += (double)twist[3 + k] * twist[3 + k];
+    }
+    return w2 <= (double)CVO_FE_SWEEP_MAX_ROTATION * CVO_FE_SWEEP_MAX_ROTATION &&
+           v2 <= (double)CVO_FE_SWEEP_MAX_TRANSLATION * CVO_FE_SWEEP_MAX_TRANSLATION;
+}
+
+// the sweep's part of the projection's arguments
+void sweep_args(FeLidarSweepArgs &a, const cvo_fe_lidar_sweep &sw, float *phase, float *moved)
+{
+    a.time_origin = sw.time_origin; a.time_scale = sw.time_scale; a.phase0 = sw.phase0;
+    a.direction = (float)sw.direction; a.s_ref = sw.s_ref;
+    a.phase = phase; a.moved = moved;
 }
 
 // what cvo_fe_set_depth_gate accepts
@@ -1571,7 +1606,8 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), right_staging(ctx), img_bytes,
                               hipMemcpyHostToDevice, s));
     else if (ctx->has_lidar)
-        FE_HIP(hipMemcpyAsync(ctx->d_scan.get(), ctx->h_scan.get(), lidar_scan_bytes(ctx->lidar.max_points), hipMemcpyHostToDevice, s));
+        FE_HIP(hipMemcpyAsync(ctx->d_scan.get(), ctx->h_scan.get(), lidar_scan_bytes(ctx->lidar.max_points, ctx->scan_record),
+                              hipMemcpyHostToDevice, s));
     else
         FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
@@ -1639,7 +1675,13 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         for (int q = 0; q < 9; ++q) a.R[q] = l.R[q];
         for (int q = 0; q < 3; ++q) a.T[q] = l.T[q];
         camera_in_force(ctx, dataset_seq, a.cam);
-        fe_lidar_project_enqueue(a, s);
+        if (ctx->has_sweep) {   // (the sweep contract: another instance of the same kernel; the twist is in the header)
+            FeLidarSweepArgs sa{};
+            sa.base = a;
+            sweep_args(sa, ctx->sweep, nullptr, nullptr);
+            fe_lidar_project_sweep_enqueue(ctx->sweep.mode, sa, s);
+        } else
+            fe_lidar_project_enqueue(a, s);
         const bool cull = l.occl_rel > 0.0f;   // (without the test P is P0, written where P goes)
         hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf.get(), np,
                            cull ? ctx->lidar_p0.get() : plane);
@@ -2252,7 +2294,7 @@ int cvo_fe_set_lidar(cvo_fe_ctx *ctx, const cvo_fe_lidar *l)
     Dev<uint32_t> z;
     const size_t nz = rect_plane(ctx->np);
     if (l) {
-        const size_t bytes = lidar_scan_bytes(l->max_points);
+        const size_t bytes = lidar_scan_bytes(l->max_points, ctx->scan_record);   // (a sweep stays: its record size too)
         const bool resize = !ctx->has_lidar || l->max_points != ctx->lidar.max_points;
         if (resize && !(pin_alloc(h_scan, bytes) && dev_alloc(d_scan, bytes)))
             return no_memory(ctx, "set_lidar: pinned and device memory for a scan of max_points points");
@@ -2275,10 +2317,14 @@ int cvo_fe_set_lidar(cvo_fe_ctx *ctx, const cvo_fe_lidar *l)
     hand_over(ctx->zbuf, z);
     hand_over(ctx->lidar_p0, p0);
     hand_over(ctx->lidar_flags, flags);
-    if (!l) {   // (given back: a depth camera set later makes its own z-buffer)
+    if (!l) {   // (given back: a depth camera set later makes its own z-buffer; the sweep goes with the scan source)
         ctx->h_scan.reset();
         ctx->d_scan.reset();
         ctx->zbuf.reset();
+        ctx->has_sweep = false;
+        ctx->sweep = cvo_fe_lidar_sweep{};
+        ctx->scan_record = 12;
+        for (float &t : ctx->lidar_twist) t = 0.0f;
     }
     if (!l || !(l->occl_rel > 0.0f)) {
         ctx->lidar_p0.reset();
@@ -2296,6 +2342,131 @@ int cvo_fe_get_lidar(const cvo_fe_ctx *ctx, cvo_fe_lidar *out, int *set)
     if (!ctx || !out) return CVO_HIP_ERR_INVALID;
     *out = ctx->has_lidar ? ctx->lidar : cvo_fe_lidar{};
     if (set) *set = ctx->has_lidar ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_check_lidar_sweep(const cvo_fe_lidar_sweep *sw) { return sw && sweep_ok(*sw) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
+
+int cvo_fe_set_lidar_sweep(cvo_fe_ctx *ctx, const cvo_fe_lidar_sweep *sw)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_sweep: a frame is in flight");
+    if (sw && !sweep_ok(*sw))
+        return fail(ctx, CVO_HIP_ERR_INVALID,
+                    "set_lidar_sweep: a mode of CVO_FE_SWEEP_*, finite members, time_offset >= 12 and a multiple of 4, "
+                    "time_scale not 0, direction +1 or -1 under the azimuth mode and 0 otherwise, phase0 in [0, 1), "
+                    "s_ref in [0, 1], time_origin 0 outside the float mode, pad_ 0");
+    if (sw && !ctx->has_lidar) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_sweep: no scan source (cvo_fe_set_lidar)");
+    if (!sw && !ctx->has_sweep) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Pin<uint8_t> h_scan;
+    Dev<uint8_t> d_scan;
+    const size_t record = lidar_record_bytes(sweep_time_offset(sw));
+    if (record != ctx->scan_record) {   // (a record with or without its time word: the staging and its copy follow)
+        const size_t bytes = lidar_scan_bytes(ctx->lidar.max_points, record);
+        if (!(pin_alloc(h_scan, bytes) && dev_alloc(d_scan, bytes)))
+            return no_memory(ctx, "set_lidar_sweep: pinned and device memory for a scan of max_points points");
+        std::memset(h_scan.get(), 0, FE_LIDAR_HEADER);   // (a scan of no points until the first frame)
+    }
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, CVO_HIP_ERR_HIP, "set_lidar_sweep", e);
+    }
+    hand_over(ctx->h_scan, h_scan);
+    hand_over(ctx->d_scan, d_scan);
+    ctx->scan_record = record;
+    ctx->has_sweep = sw != nullptr;
+    ctx->sweep = sw ? *sw : cvo_fe_lidar_sweep{};
+    for (float &t : ctx->lidar_twist) t = 0.0f;
+    drop_graphs(ctx);   // (the kernel's instance, the sweep's words and the size of the copy are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_lidar_sweep(const cvo_fe_ctx *ctx, cvo_fe_lidar_sweep *out, int *set)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    *out = ctx->has_sweep ? ctx->sweep : cvo_fe_lidar_sweep{};
+    if (set) *set = ctx->has_sweep ? 1 : 0;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_lidar_motion(cvo_fe_ctx *ctx, const float twist[6])
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (!twist) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_motion: bad argument");
+    if (!ctx->has_sweep) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_motion: no sweep (cvo_fe_set_lidar_sweep)");
+    if (!twist_ok(twist))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_motion: finite members, |w| <= 1 radian and |v| <= 64 metres per sweep");
+    for (int k = 0; k < 6; ++k) ctx->lidar_twist[k] = twist[k];   // (read by the next submit: no graph holds it)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_lidar_motion(const cvo_fe_ctx *ctx, float twist[6])
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !twist) return CVO_HIP_ERR_INVALID;
+    for (int k = 0; k < 6; ++k) twist[k] = ctx->lidar_twist[k];
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_lidar_twist(const float T_cam[16], const cvo_fe_lidar *l, float sweep_fraction, float twist[6])
+{
+    if (!T_cam || !l || !twist || !std::isfinite(sweep_fraction) || !(sweep_fraction > 0.0f)) return CVO_HIP_ERR_INVALID;
+    for (int q = 0; q < 16; ++q)
+        if (!std::isfinite(T_cam[q])) return CVO_HIP_ERR_INVALID;
+    cvo_fe_lidar checked = *l;
+    checked.max_points = 1;   // (not read)
+    float Rc[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Rc[3 * r + c] = T_cam[4 * r + c];
+    if (!lidar_ok(checked) || !rotation_ok(Rc)) return CVO_HIP_ERR_INVALID;
+    // M = [R | T]^-1 = [R^T | -R^T T]: the later camera's pose in the earlier camera's frame
+    double M[9], m[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) M[3 * r + c] = (double)T_cam[4 * c + r];
+        m[r] = -((double)T_cam[r] * T_cam[3] + (double)T_cam[4 + r] * T_cam[7] + (double)T_cam[8 + r] * T_cam[11]);
+    }
+    // X^-1 M X with X = [Rx | Tx]: the rotation Rx^T M Rx, the translation Rx^T (M Tx + m - Tx)
+    double Rx[9], Tx[3], MRx[9], S[9], u[3], t[3];
+    for (int q = 0; q < 9; ++q) Rx[q] = (double)l->R[q];
+    for (int q = 0; q < 3; ++q) Tx[q] = (double)l->T[q];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) MRx[3 * r + c] = M[3 * r] * Rx[c] + M[3 * r + 1] * Rx[3 + c] + M[3 * r + 2] * Rx[6 + c];
+        u[r] = (M[3 * r] * Tx[0] + M[3 * r + 1] * Tx[1] + M[3 * r + 2] * Tx[2]) + m[r] - Tx[r];
+    }
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) S[3 * r + c] = Rx[r] * MRx[c] + Rx[3 + r] * MRx[3 + c] + Rx[6 + r] * MRx[6 + c];
+        t[r] = Rx[r] * u[0] + Rx[3 + r] * u[1] + Rx[6 + r] * u[2];
+    }
+    // the logarithm: w = theta * axis from the antisymmetric part, v = V^-1 t, V^-1 = I - W/2 + k W^2
+    const double ax[3] = {0.5 * (S[7] - S[5]), 0.5 * (S[2] - S[6]), 0.5 * (S[3] - S[1])};   // sin(theta) * axis
+    const double sn = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+    const double cs = 0.5 * ((S[0] + S[4] + S[8]) - 1.0);
+    const double theta = std::atan2(sn, cs);
+    if (!(theta * (double)sweep_fraction <= (double)CVO_FE_SWEEP_MAX_ROTATION)) return CVO_HIP_ERR_INVALID;
+    if (theta > 3.0) return CVO_HIP_ERR_INVALID;   // (too near a half turn for the logarithm, whatever the fraction)
+    const double f = theta < 1e-6 ? 1.0 + theta * theta / 6.0 : theta / sn;   // theta / sin(theta)
+    const double w[3] = {f * ax[0], f * ax[1], f * ax[2]};
+    // (1 - (theta/2) cot(theta/2)) / theta^2, from the angle itself: 1 - cos from the matrix would keep the matrix's rounding
+    const double t2 = theta * theta;
+    const double k = theta < 1e-2 ? 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0
+                                  : (1.0 - 0.5 * theta * std::cos(0.5 * theta) / std::sin(0.5 * theta)) / t2;
+    const double wt[3] = {w[1] * t[2] - w[2] * t[1], w[2] * t[0] - w[0] * t[2], w[0] * t[1] - w[1] * t[0]};
+    const double wwt[3] = {w[1] * wt[2] - w[2] * wt[1], w[2] * wt[0] - w[0] * wt[2], w[0] * wt[1] - w[1] * wt[0]};
+    double out[6];
+    for (int q = 0; q < 3; ++q) {
+        out[q] = w[q] * (double)sweep_fraction;
+        out[3 + q] = ((t[q] - 0.5 * wt[q]) + k * wwt[q]) * (double)sweep_fraction;
+    }
+    float res[6];
+    for (int q = 0; q < 6; ++q) res[q] = (float)out[q];
+    if (!twist_ok(res)) return CVO_HIP_ERR_INVALID;
+    for (int q = 0; q < 6; ++q) twist[q] = res[q];
     return CVO_HIP_OK;
 }
 
@@ -2682,6 +2853,9 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
                   (!second && num_points > 0)))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit_lidar: num_points in [0, max_points], a stride of at least 12 bytes "
                                               "and a multiple of 4, points not null");
+    const int time_offset = lidar && ctx->has_sweep ? sweep_time_offset(&ctx->sweep) : -1;
+    if (time_offset >= 0 && (size_t)time_offset + 4 > second_stride)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "submit_lidar: the sweep's time_offset + 4 is beyond the stride");
     const size_t row = img_row(ctx);   // (of the pixel format in force: w * 3 without one)
     if (!img || (!second && !lidar) || img_stride < row ||
         (!lidar && second_stride < (stereo ? row : (size_t)dw * 2)) ||
@@ -2709,7 +2883,7 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
             ctx->table_scale = cam[0];
         }
     } else if (lidar)
-        lidar_stage(ctx->h_scan.get(), second, second_stride, num_points);
+        lidar_stage(ctx->h_scan.get(), second, second_stride, num_points, time_offset, ctx->lidar_twist);
     else if (!(second == ctx->h_depth.get() && second_stride == (size_t)dw * 2))
         copy_rows(ctx->h_depth.get(), second, second_stride, (size_t)dw * 2, dh);
     FeCtrl c0{};
@@ -2957,6 +3131,7 @@ namespace {
 // the device memory and the stream of one cvo_fe_project_points call
 struct ProjectCall {
     Dev<uint8_t> scan, flags;
+    Dev<float> phase;   // n phases, then 3n floats of p', where the caller asked for either
     Dev<uint32_t> z;
     Dev<uint16_t> planes;
     hipStream_t s = nullptr;
@@ -2966,13 +3141,15 @@ struct ProjectCall {
     }
 };
 
-}   // namespace
-
-extern "C" int cvo_fe_project_points(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
-                                     const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled,
-                                     uint8_t *flags, int *hits, int *occluded)
+// cvo_fe_project_points (sw NULL) and cvo_fe_project_points_sweep
+int project_points(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l, const float cam[5],
+                   int width, int height, uint16_t *plane, uint16_t *unculled, uint8_t *flags, int *hits, int *occluded,
+                   const cvo_fe_lidar_sweep *sw, const float *twist, float *phase, float *moved)
 {
     cvo_lock::Api api_guard;
+    if (sw ? (!sweep_ok(*sw) || !twist || !twist_ok(twist)) : (phase || moved)) return CVO_HIP_ERR_INVALID;
+    const int time_offset = sweep_time_offset(sw);
+    if (time_offset >= 0 && (size_t)time_offset + 4 > stride_bytes) return CVO_HIP_ERR_INVALID;
     if (!plane || !cam || !hits || !occluded || n < 0 || n > FE_LIDAR_MAX_POINTS || (!points && n > 0) ||
         !lidar_stride_ok(stride_bytes) || width < 1 || height < 1 || width > 8192 || height > 8192)
         return CVO_HIP_ERR_INVALID;
@@ -2988,13 +3165,18 @@ extern "C" int cvo_fe_project_points(int device, const void *points, size_t stri
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return CVO_HIP_ERR_NODEVICE; }
 #define LD_TRY(e) do { if ((e) != hipSuccess) { (void)hipGetLastError(); return CVO_HIP_ERR_HIP; } } while (0)
     const int np = width * height;
-    const size_t cells = rect_plane(np), scan_bytes = lidar_scan_bytes(n);
+    const size_t cells = rect_plane(np), scan_bytes = lidar_scan_bytes(n, lidar_record_bytes(time_offset));
     const bool cull = l->occl_rel > 0.0f;
     std::vector<uint8_t> scan, fl;
     std::vector<uint16_t> p0;
     try { scan.resize(scan_bytes); fl.resize((size_t)np); p0.resize((size_t)np); } catch (const std::bad_alloc &) { return CVO_HIP_ERR_NOMEM; }
-    lidar_stage(scan.data(), points, stride_bytes, n);
+    lidar_stage(scan.data(), points, stride_bytes, n, time_offset, sw ? twist : nullptr);
     ProjectCall c;
+    const bool outputs = n > 0 && (phase || moved);
+    if (outputs && !dev_alloc(c.phase, (size_t)4 * n)) {
+        (void)hipGetLastError();
+        return CVO_HIP_ERR_NOMEM;
+    }
     if (!dev_alloc(c.scan, scan_bytes) || !dev_alloc(c.z, cells) || !dev_alloc(c.planes, 2 * cells) || !dev_alloc(c.flags, cells)) {
         (void)hipGetLastError();
         return CVO_HIP_ERR_NOMEM;
@@ -3011,7 +3193,13 @@ extern "C" int cvo_fe_project_points(int device, const void *points, size_t stri
         for (int q = 0; q < 9; ++q) a.R[q] = l->R[q];
         for (int q = 0; q < 3; ++q) a.T[q] = l->T[q];
         for (int q = 0; q < 5; ++q) a.cam[q] = cam[q];
-        fe_lidar_project_enqueue(a, c.s);
+        if (sw) {
+            FeLidarSweepArgs sa{};
+            sa.base = a;
+            sweep_args(sa, *sw, phase ? c.phase.get() : nullptr, moved ? c.phase.get() + n : nullptr);
+            fe_lidar_project_sweep_enqueue(sw->mode, sa, c.s);
+        } else
+            fe_lidar_project_enqueue(a, c.s);
     }
     hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, c.s, c.z.get(), np, d_p0);
     if (cull) {
@@ -3024,6 +3212,8 @@ extern "C" int cvo_fe_project_points(int device, const void *points, size_t stri
     LD_TRY(hipMemcpyAsync(p0.data(), d_p0, (size_t)np * 2, hipMemcpyDeviceToHost, c.s));
     LD_TRY(hipMemcpyAsync(plane, cull ? d_p : d_p0, (size_t)np * 2, hipMemcpyDeviceToHost, c.s));
     if (cull) LD_TRY(hipMemcpyAsync(fl.data(), c.flags.get(), (size_t)np, hipMemcpyDeviceToHost, c.s));
+    if (outputs && phase) LD_TRY(hipMemcpyAsync(phase, c.phase.get(), (size_t)n * 4, hipMemcpyDeviceToHost, c.s));
+    if (outputs && moved) LD_TRY(hipMemcpyAsync(moved, c.phase.get() + n, (size_t)n * 12, hipMemcpyDeviceToHost, c.s));
     LD_TRY(hipStreamSynchronize(c.s));
 #undef LD_TRY
     int nh = 0, no = 0;
@@ -3037,4 +3227,23 @@ extern "C" int cvo_fe_project_points(int device, const void *points, size_t stri
     *hits = nh;
     *occluded = no;
     return CVO_HIP_OK;
+}
+
+}   // namespace
+
+extern "C" int cvo_fe_project_points(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
+                                     const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled,
+                                     uint8_t *flags, int *hits, int *occluded)
+{
+    return project_points(device, points, stride_bytes, n, l, cam, width, height, plane, unculled, flags, hits, occluded,
+                          nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int cvo_fe_project_points_sweep(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
+                                           const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled,
+                                           uint8_t *flags, int *hits, int *occluded, const cvo_fe_lidar_sweep *sw,
+                                           const float twist[6], float *phase, float *moved)
+{
+    return project_points(device, points, stride_bytes, n, l, cam, width, height, plane, unculled, flags, hits, occluded,
+                          sw, twist, phase, moved);
 }

@@ -9,7 +9,10 @@
 //   not depend on the order of the points).  Every write is bounded here: x in [0, w), y in [0, h).  The number of
 //   points is read from device memory -- the header in front of the points, copied with them -- so that a frame whose
 //   launches sit in a captured graph takes a count that changes from frame to frame: the grid covers the scan's
-//   capacity and the threads at or beyond the count return.
+//   capacity and the threads at or beyond the count return.  The kernel is a template on the sweep mode: instance 0
+//   is the above and nothing else; the instances CVO_FE_SWEEP_* put the sweep contract (at cvo_fe_lidar_sweep: the
+//   point's phase, then the scanner's motion since the image's phase, from the twist in the same header) in front of
+//   the projection, in the same pass.  The restatement tests/fe_lidar_sweep_ref.py holds them by bits.
 // k_fe_depth_final of cvo_frontend.hip, the depth camera's, then turns the z-buffer into P0 and arms it again.
 // k_fe_lidar_cull (only with occl_rel > 0), one workgroup per tile of 64 x 16 pixels: the tile of P0 with a halo of
 //   (rx, ry) goes to LDS as 16-bit keys value - 1, so that "none" (0) becomes 65535 and sorts behind every depth, 65535
@@ -29,12 +32,111 @@ constexpr int LD_S = LD_TW + 2 * LD_R + 2;   // 80 cells per LDS row of keys
 constexpr int LD_ROWS = LD_TH + 2 * LD_R;    // 30 rows at the most
 static_assert(LD_TW * LD_TH == 4 * LD_BLOCK, "four pixels of the tile per thread");
 
-__global__ void __launch_bounds__(LD_BLOCK) k_fe_lidar_project(const FeLidarProjectArgs a)
+// a1*b2 - a2*b1 by components
+__device__ __forceinline__ void ld_cross(const float a[3], const float b[3], float c[3])
 {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// a point that has no phase: NaN where the stand-alone entry asked for phase and p'
+__device__ __forceinline__ void ld_no_phase(const FeLidarSweepArgs &a, const int i)
+{
+    const float nan = __uint_as_float(0x7FC00000u);
+    if (a.phase) a.phase[i] = nan;
+    if (a.moved) a.moved[3 * (size_t)i] = a.moved[3 * (size_t)i + 1] = a.moved[3 * (size_t)i + 2] = nan;
+}
+
+// The sweep contract on point i: its phase and the move.  False: the point is skipped (step 1, or a time that is not
+// finite); else (x, y, z) is p'.  The words of the header -- the frame's twist -- and the arguments are the same for
+// every lane of a wave.  The arguments and the count arrive through scalar loads; the twist does under the azimuth
+// mode, and under the field modes as two vector loads of one address for the whole wave (one line, 24 bytes), which is
+// how the compiler orders them behind the branch that stores NaN.  The point's own words are vector loads, one
+// 16-byte load under a field mode.
+template <int MODE>
+__device__ __forceinline__ bool ld_sweep_point(const FeLidarSweepArgs &args, const int i, float &x, float &y, float &z)
+{
+    const FeLidarProjectArgs &a = args.base;
+    // (read first, in front of every store of the thread: the loads are then scalar ones, like the count's)
+    const float *header = reinterpret_cast<const float *>(a.count) + FE_LIDAR_TWIST_WORD;
+    const float twist[6] = {header[0], header[1], header[2], header[3], header[4], header[5]};
+    float p[3];
+    uint32_t word = 0u;
+    if constexpr (MODE == CVO_FE_SWEEP_AZIMUTH) {
+        p[0] = a.points[3 * (size_t)i]; p[1] = a.points[3 * (size_t)i + 1]; p[2] = a.points[3 * (size_t)i + 2];
+    } else {
+        const float4 rec = reinterpret_cast<const float4 *>(a.points)[i];
+        p[0] = rec.x; p[1] = rec.y; p[2] = rec.z;
+        word = __float_as_uint(rec.w);
+    }
+    if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) { ld_no_phase(args, i); return false; }
+    // the phase
+    float s;
+    if constexpr (MODE == CVO_FE_SWEEP_TIME_F32) {
+        const float t = __uint_as_float(word);
+        if (!isfinite(t)) { ld_no_phase(args, i); return false; }
+        s = (t - args.time_origin) * args.time_scale;
+        s = fminf(fmaxf(s, 0.0f), 1.0f);
+    } else if constexpr (MODE == CVO_FE_SWEEP_TIME_U32) {
+        s = (float)word * args.time_scale;
+        s = fminf(fmaxf(s, 0.0f), 1.0f);
+    } else {
+        const float ax = fabsf(p[0]), ay = fabsf(p[1]);
+        const float lo = fminf(ax, ay), hi = fmaxf(ax, ay);
+        const float r = hi > 0.0f ? lo / hi : 0.0f;
+        const float r2 = r * r;
+        float q = ((((CVO_FE_SWEEP_ATAN_C5 * r2 + CVO_FE_SWEEP_ATAN_C4) * r2 + CVO_FE_SWEEP_ATAN_C3) * r2 + CVO_FE_SWEEP_ATAN_C2) * r2 +
+                   CVO_FE_SWEEP_ATAN_C1) * r2 + CVO_FE_SWEEP_ATAN_C0;
+        q = q * r;
+        if (ay > ax) q = 0.25f - q;
+        if (p[0] < 0.0f) q = 0.5f - q;
+        if (p[1] < 0.0f) q = -q;
+        s = args.direction * q + args.phase0;
+        s = s - floorf(s);
+    }
+    // the move
+    const float am = s - args.s_ref;
+    float w[3], tau[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { w[k] = am * twist[k]; tau[k] = am * twist[3 + k]; }
+    const float t2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+    const float A = ((((CVO_FE_SWEEP_A5 * t2 + CVO_FE_SWEEP_A4) * t2 + CVO_FE_SWEEP_A3) * t2 + CVO_FE_SWEEP_A2) * t2 + CVO_FE_SWEEP_A1) * t2 + CVO_FE_SWEEP_A0;
+    const float B = ((((CVO_FE_SWEEP_B5 * t2 + CVO_FE_SWEEP_B4) * t2 + CVO_FE_SWEEP_B3) * t2 + CVO_FE_SWEEP_B2) * t2 + CVO_FE_SWEEP_B1) * t2 + CVO_FE_SWEEP_B0;
+    const float Cc = (((CVO_FE_SWEEP_C4 * t2 + CVO_FE_SWEEP_C3) * t2 + CVO_FE_SWEEP_C2) * t2 + CVO_FE_SWEEP_C1) * t2 + CVO_FE_SWEEP_C0;
+    float c1[3], c2[3], d1[3], d2[3], m[3];
+    ld_cross(w, p, c1);
+    ld_cross(w, c1, c2);
+    ld_cross(w, tau, d1);
+    ld_cross(w, d1, d2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = ((p[k] + A * c1[k]) + B * c2[k]) + ((tau[k] + B * d1[k]) + Cc * d2[k]);
+    if (args.phase) args.phase[i] = s;
+    if (args.moved) { args.moved[3 * (size_t)i] = m[0]; args.moved[3 * (size_t)i + 1] = m[1]; args.moved[3 * (size_t)i + 2] = m[2]; }
+    x = m[0]; y = m[1]; z = m[2];
+    return true;
+}
+
+template <int MODE> struct LdArgs { using type = FeLidarSweepArgs; };
+template <> struct LdArgs<0> { using type = FeLidarProjectArgs; };
+__device__ __forceinline__ const FeLidarProjectArgs &ld_base(const FeLidarProjectArgs &a) { return a; }
+__device__ __forceinline__ const FeLidarProjectArgs &ld_base(const FeLidarSweepArgs &a) { return a.base; }
+
+// MODE 0: the LiDAR contract alone, what a context without a sweep launches.  MODE CVO_FE_SWEEP_*: phase, move and
+// projection of the sweep contract in one pass over the points.
+template <int MODE>
+__global__ void __launch_bounds__(LD_BLOCK) k_fe_lidar_project(const typename LdArgs<MODE>::type args)
+{
+    const FeLidarProjectArgs &a = ld_base(args);
     const int i = blockIdx.x * LD_BLOCK + threadIdx.x;
     if (i >= a.capacity || i >= a.count[0]) return;
-    const float x = a.points[3 * (size_t)i], y = a.points[3 * (size_t)i + 1], z = a.points[3 * (size_t)i + 2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return;
+    float x, y, z;
+    if constexpr (MODE == 0) {
+        x = a.points[3 * (size_t)i]; y = a.points[3 * (size_t)i + 1]; z = a.points[3 * (size_t)i + 2];
+        if (!(isfinite(x) && isfinite(y) && isfinite(z))) return;
+    } else {
+        if (!ld_sweep_point<MODE>(args, i, x, y, z)) return;
+    }
     float Q[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) Q[k] = ((a.R[3 * k] * x + a.R[3 * k + 1] * y) + a.R[3 * k + 2] * z) + a.T[k];
@@ -125,7 +227,15 @@ __global__ void __launch_bounds__(LD_BLOCK) k_fe_lidar_cull(const FeLidarCullArg
 
 void fe_lidar_project_enqueue(const FeLidarProjectArgs &a, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_fe_lidar_project, dim3((a.capacity + LD_BLOCK - 1) / LD_BLOCK), dim3(LD_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(k_fe_lidar_project<0>, dim3((a.capacity + LD_BLOCK - 1) / LD_BLOCK), dim3(LD_BLOCK), 0, s, a);
+}
+
+void fe_lidar_project_sweep_enqueue(int mode, const FeLidarSweepArgs &a, hipStream_t s)
+{
+    const dim3 grid((a.base.capacity + LD_BLOCK - 1) / LD_BLOCK), block(LD_BLOCK);
+    if (mode == CVO_FE_SWEEP_TIME_F32) hipLaunchKernelGGL(k_fe_lidar_project<CVO_FE_SWEEP_TIME_F32>, grid, block, 0, s, a);
+    else if (mode == CVO_FE_SWEEP_TIME_U32) hipLaunchKernelGGL(k_fe_lidar_project<CVO_FE_SWEEP_TIME_U32>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_fe_lidar_project<CVO_FE_SWEEP_AZIMUTH>, grid, block, 0, s, a);
 }
 
 void fe_lidar_cull_enqueue(const FeLidarCullArgs &a, hipStream_t s)

@@ -68,6 +68,7 @@ GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 MEDIAN_CHANGED, MEDIAN_FILLED = 1, 2   # the values of STAGE_MEDIAN
 LIDAR_HIT, LIDAR_OCCLUDED = 1, 2       # the bits of STAGE_LIDAR
+SWEEP_TIME_F32, SWEEP_TIME_U32, SWEEP_AZIMUTH = 1, 2, 3   # the modes of a LidarSweep
 INFILL_ROW, INFILL_COL, INFILL_JUMP = 1, 2, 4   # the values of STAGE_INFILL
 # pixel formats of the colour images (set_pixel_format; the unpack contract of include/cvo_frontend.h).  Bayer: the four
 # letters are the colours of pixels (0,0) (1,0) / (0,1) (1,1) -- not OpenCV's names
@@ -93,7 +94,9 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_median_plane", "cvo_fe_check_depth_infill", "cvo_fe_set_depth_infill", "cvo_fe_get_depth_infill",
            "cvo_fe_infill_plane", "cvo_fe_check_lidar", "cvo_fe_set_lidar", "cvo_fe_get_lidar", "cvo_fe_submit_lidar",
            "cvo_fe_create_pointcloud_lidar", "cvo_fe_project_points", "cvo_fe_check_pixel_format", "cvo_fe_pixel_layout",
-           "cvo_fe_set_pixel_format", "cvo_fe_get_pixel_format", "cvo_fe_unpack_image")
+           "cvo_fe_set_pixel_format", "cvo_fe_get_pixel_format", "cvo_fe_unpack_image", "cvo_fe_check_lidar_sweep",
+           "cvo_fe_set_lidar_sweep", "cvo_fe_get_lidar_sweep", "cvo_fe_set_lidar_motion", "cvo_fe_get_lidar_motion",
+           "cvo_fe_lidar_twist", "cvo_fe_project_points_sweep")
 
 
 class Info(C.Structure):
@@ -225,6 +228,21 @@ class Lidar(_Settings):
             raise ValueError("R is 3 x 3; T holds 3 numbers")
         super().__init__(int(max_points), int(splat), (C.c_float * 9)(*R), (C.c_float * 3)(*T), min_range, max_range,
                          occl_rel, int(occl_rx), int(occl_ry), int(pad_))
+
+
+class LidarSweep(_Settings):
+    """cvo_fe_lidar_sweep: motion compensation of a spinning scan (the sweep contract of include/cvo_frontend.h).
+    `mode`: where a point's phase, the fraction of the sweep at which it was measured, comes from -- SWEEP_TIME_F32 /
+    SWEEP_TIME_U32: the float32 / uint32 at byte `time_offset` of its record (a multiple of 4, >= 12), as
+    (t - `time_origin`) * `time_scale` (`time_origin` under SWEEP_TIME_F32 only), clamped to [0, 1]; SWEEP_AZIMUTH: its
+    azimuth, `direction` (+1 or -1) * atan2(y, x) / 2 pi + `phase0` (in [0, 1)), wrapped.  `s_ref` in [0, 1]: the phase
+    at which the colour image is exposed."""
+    _fields_ = [("mode", C.c_int32), ("time_offset", C.c_int32), ("time_origin", C.c_float), ("time_scale", C.c_float),
+                ("phase0", C.c_float), ("direction", C.c_int32), ("s_ref", C.c_float), ("pad_", C.c_int32)]
+
+    def __init__(self, mode=SWEEP_AZIMUTH, time_offset=0, time_origin=0.0, time_scale=0.0, phase0=0.0, direction=0,
+                 s_ref=0.0, pad_=0):
+        super().__init__(int(mode), int(time_offset), time_origin, time_scale, phase0, int(direction), s_ref, int(pad_))
 
 
 class Lens(_Settings):
@@ -372,6 +390,15 @@ def lib():
                                                      fp, fp, C.c_int, C.POINTER(C.c_int)]
         L.cvo_fe_project_points.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Lidar), fp, C.c_int, C.c_int,
                                             u16p, u16p, u8p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.cvo_fe_check_lidar_sweep.argtypes = [C.POINTER(LidarSweep)]
+        L.cvo_fe_set_lidar_sweep.argtypes = [vp, C.POINTER(LidarSweep)]
+        L.cvo_fe_get_lidar_sweep.argtypes = [vp, C.POINTER(LidarSweep), C.POINTER(C.c_int)]
+        L.cvo_fe_set_lidar_motion.argtypes = [vp, fp]
+        L.cvo_fe_get_lidar_motion.argtypes = [vp, fp]
+        L.cvo_fe_lidar_twist.argtypes = [fp, C.POINTER(Lidar), C.c_float, fp]
+        L.cvo_fe_project_points_sweep.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Lidar), fp, C.c_int,
+                                                  C.c_int, u16p, u16p, u8p, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                  C.POINTER(LidarSweep), fp, fp, fp]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
         L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
         L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
@@ -617,6 +644,60 @@ def project_points(points, lidar, cam, width, height, device=0):
                                            p0.ctypes.data_as(u16p), flags.ctypes.data_as(C.POINTER(C.c_uint8)),
                                            C.byref(hits), C.byref(occluded)), what="project_points")
     return plane, p0, flags, hits.value, occluded.value
+
+
+def check_lidar_sweep(sweep):
+    """True for a LidarSweep set_lidar_sweep() accepts on a generator with a scan source (cvo_fe_check_lidar_sweep);
+    None is refused.  Host only."""
+    return lib().cvo_fe_check_lidar_sweep(None if sweep is None else C.byref(sweep)) == 0
+
+
+def _twist(twist, what):
+    tw = np.ascontiguousarray(twist, np.float32)
+    if tw.shape != (6,):
+        raise ValueError("%s: a twist holds w (radians per sweep) then v (metres per sweep), six numbers" % what)
+    return tw
+
+
+def lidar_twist(transform, lidar, sweep_fraction=1.0):
+    """The twist for set_lidar_motion() of a caller who assumes the velocity of the last frame interval to hold
+    (cvo_fe_lidar_twist; host only, float64): `transform` is the registration's last relative transform, 4 x 4 as
+    `registration.transform` holds it -- coordinates in the earlier camera's frame to coordinates in the later one's, so
+    the camera's motion is its inverse --, `lidar` the Lidar whose R, T mount the scanner, `sweep_fraction` the sweep
+    duration over the frame interval.  Raises for a motion over the caps of set_lidar_motion()."""
+    T = np.ascontiguousarray(transform, np.float32)
+    if T.shape != (4, 4):
+        raise ValueError("expected a 4 x 4 transform")
+    out = np.zeros(6, np.float32)
+    fp = C.POINTER(C.c_float)
+    capi.check(lib().cvo_fe_lidar_twist(T.ctypes.data_as(fp), None if lidar is None else C.byref(lidar),
+                                        float(sweep_fraction), out.ctypes.data_as(fp)), what="lidar_twist")
+    return out
+
+
+def project_points_sweep(points, lidar, cam, width, height, sweep, twist, device=0):
+    """project_points() under the sweep contract (cvo_fe_project_points_sweep): `points` n x k float32 whose records
+    hold the time word of a field mode at `sweep.time_offset` (a uint32 time: view the array as float32); `twist`: w
+    then v of the scan.  Returns project_points()'s five and (the phase of every point, p' of every point as n x 3):
+    NaN for a point skipped before it has a phase."""
+    pts, addr, stride, n = _scan(points)
+    cam = np.ascontiguousarray(cam, np.float32)
+    if cam.shape != (5,):
+        raise ValueError("cam holds depth scale, fx, fy, cx, cy")
+    w, h = int(width), int(height)
+    if not (1 <= w <= 8192 and 1 <= h <= 8192):
+        raise capi.CvoHipError("project_points_sweep: width and height in [1, 8192]")
+    tw = _twist(twist, "project_points_sweep")
+    plane, p0, flags = np.empty((h, w), np.uint16), np.empty((h, w), np.uint16), np.empty((h, w), np.uint8)
+    phase, moved = np.empty(n, np.float32), np.empty((n, 3), np.float32)
+    hits, occluded = C.c_int(0), C.c_int(0)
+    u16p, fp = C.POINTER(C.c_uint16), C.POINTER(C.c_float)
+    capi.check(lib().cvo_fe_project_points_sweep(
+        int(device), addr, stride, n, None if lidar is None else C.byref(lidar), cam.ctypes.data_as(fp), w, h,
+        plane.ctypes.data_as(u16p), p0.ctypes.data_as(u16p), flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(hits),
+        C.byref(occluded), None if sweep is None else C.byref(sweep), tw.ctypes.data_as(fp), phase.ctypes.data_as(fp),
+        moved.ctypes.data_as(fp)), what="project_points_sweep")
+    return plane, p0, flags, hits.value, occluded.value, phase, moved
 
 
 def stereo_depth_table(stereo, fx, depth_scale):
@@ -874,6 +955,31 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_get_lidar(self._h, C.byref(out), C.byref(isset)), "get_lidar")
         return out if isset.value else None
 
+    def set_lidar_sweep(self, sweep):
+        """A LidarSweep for the scan source: every point of a frame's scan is moved into the scanner's frame at the
+        instant of the colour image, by the twist of set_lidar_motion(), before it is projected (the sweep contract of
+        include/cvo_frontend.h); None: no motion compensation, as for a new object.  Needs a scan source and goes
+        with it; the twist is zero afterwards."""
+        self._chk(lib().cvo_fe_set_lidar_sweep(self._h, None if sweep is None else C.byref(sweep)), "set_lidar_sweep")
+
+    def lidar_sweep(self):
+        """The LidarSweep set, or None."""
+        out, isset = LidarSweep(), C.c_int(0)
+        self._chk(lib().cvo_fe_get_lidar_sweep(self._h, C.byref(out), C.byref(isset)), "get_lidar_sweep")
+        return out if isset.value else None
+
+    def set_lidar_motion(self, twist):
+        """The scanner's own motion over one full sweep, in its own frame, for the frames submitted from now on: w
+        (radians per sweep) then v (metres per sweep); |w| <= 1 and |v| <= 64.  Needs a sweep."""
+        tw = _twist(twist, "set_lidar_motion")
+        self._chk(lib().cvo_fe_set_lidar_motion(self._h, tw.ctypes.data_as(C.POINTER(C.c_float))), "set_lidar_motion")
+
+    def lidar_motion(self):
+        """The twist in force: six float32, zero without a sweep."""
+        out = np.zeros(6, np.float32)
+        self._chk(lib().cvo_fe_get_lidar_motion(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "get_lidar_motion")
+        return out
+
     def _image(self, bgr):
         """A colour image as a dense array: h x w x 3 under BGR8, else any uint8 array whose C-order bytes are the
         rows x row_bytes of the pixel format in force."""
@@ -1043,8 +1149,16 @@ def load_img(rgb_path, depth_path):
 
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
-               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None, pixel_format=None):
+               stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None, pixel_format=None,
+               lidar_sweep=None, lidar_motion=None, sweep_fraction=1.0):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `lidar_sweep`: a LidarSweep for the generator's scan source (motion compensation of a spinning scan); None leaves the
+    generator as it is.  `lidar_motion`: where each frame's twist comes from -- None: the generator's stays as it is
+    (zero after `lidar_sweep`); a callable name -> twist (w then v, per sweep), asked before the frame is submitted;
+    or "constant-velocity": lidar_twist() of the registration's last relative transform, the generator's Lidar and
+    `sweep_fraction` (the sweep duration over the frame interval), zero until a pair has been registered and where the
+    motion is over the caps.  With `prefetch` a frame is submitted before the frame in front of it is registered, so
+    that transform is one frame older.
     `pixel_format`: a PIXEL_* format for the generator: the colour images `frames` yields are then packed in it (both of a
     stereo pair); None leaves the generator as it is.
     `lidar`: a Lidar for the generator: `frames` then yields (name, bgr, points), a colour image and a scan (n x k
@@ -1105,9 +1219,33 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_pixel_format(pixel_format)
     if lidar is not None:
         gen.set_lidar(lidar)
+    if lidar_sweep is not None:
+        gen.set_lidar_sweep(lidar_sweep)
     submit = gen.submit_stereo if stereo is not None else gen.submit_lidar if lidar is not None else gen.submit
+    if lidar_motion is not None:
+        if lidar_motion != "constant-velocity" and not callable(lidar_motion):
+            raise ValueError('lidar_motion: None, a callable name -> twist, or "constant-velocity"')
+        mount, inner = gen.lidar(), submit
+
+        def submit(bgr, points, seq, ft, name=None):
+            if callable(lidar_motion):
+                gen.set_lidar_motion(lidar_motion(name))
+            else:
+                twist = np.zeros(6, np.float32)
+                if registration.init:
+                    try:
+                        twist = lidar_twist(registration.transform, mount, sweep_fraction)
+                    except capi.CvoHipError:
+                        pass   # (over the caps: such a frame is not compensated)
+                gen.set_lidar_motion(twist)
+            inner(bgr, points, seq, ft)
+    else:
+        inner0 = submit
+
+        def submit(bgr, points, seq, ft, name=None):
+            inner0(bgr, points, seq, ft)
     gen.set_device_output(device)
-    submit(cur[1], cur[2], dataset_seq, ftype)
+    submit(cur[1], cur[2], dataset_seq, ftype, cur[0])
     while cur is not None:
         if device:
             d_xyz, d_feat, npts = gen.collect_device()
@@ -1115,19 +1253,19 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
             first = not registration.init
             registration.set_pcd_device(d_xyz, d_feat, npts)   # (consumed: the next frame may overwrite it)
             if nxt is not None and prefetch:
-                submit(nxt[1], nxt[2], dataset_seq, ftype)
+                submit(nxt[1], nxt[2], dataset_seq, ftype, nxt[0])
             if not first:
                 registration.align()
         else:
             xyz, feat = gen.collect()
             nxt = next(it, None)
             if nxt is not None and prefetch:
-                submit(nxt[1], nxt[2], dataset_seq, ftype)
+                submit(nxt[1], nxt[2], dataset_seq, ftype, nxt[0])
             registration.run_cvo(xyz, feat)
         if writer is not None and registration.init:
             writer.append(cur[0], registration.accum_transform)
         if nxt is not None and not prefetch:
-            submit(nxt[1], nxt[2], dataset_seq, ftype)
+            submit(nxt[1], nxt[2], dataset_seq, ftype, nxt[0])
         count += 1
         cur = nxt
     return count
@@ -1191,14 +1329,18 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
 
 def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, image="image_2", scans="velodyne",
                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
-                        select_mode=None, depth_median=None, depth_infill=None):
+                        select_mode=None, depth_median=None, depth_infill=None, lidar_sweep=None, lidar_motion=None,
+                        sweep_fraction=1.0):
     """run_directory() for the KITTI odometry layout with its scans: one line of `folder`/`times` per frame (the line is
     the frame's name), the colour image in `folder`/`image`/%06d.png, decoded by PIL as load_img does (B, G, R; a grey
     image is replicated), and the scan in `folder`/`scans`/%06d.bin, records of four float32 (x y z reflectance).
     `lidar`: the Lidar for the generator, e.g. Lidar(130000, 1, R, T, occl_rel=0.25, occl_rx=7, occl_ry=1) with R, T of
     R_rect_00 * Tr_velo_to_cam and dataset_seq 4.  `camera`, `depth_gate`, `mask`, `select_mode`, `depth_median`: as in
     run_frames, e.g. SELECT_DEPTH and DepthMedian(1, 3) for a plane as sparse as a projected scan.  `depth_infill`: as in
-    run_frames, e.g. DepthInfill(2, 8, 0.25) for scan lines some five rows apart."""
+    run_frames, e.g. DepthInfill(2, 8, 0.25) for scan lines some five rows apart.  `lidar_sweep`, `lidar_motion`,
+    `sweep_fraction`: as in run_frames, e.g. LidarSweep(SWEEP_AZIMUTH, phase0=0.5, direction=1, s_ref=0.5) and
+    "constant-velocity" for records that carry no time, as KITTI's: `direction` is the scanner's sense of rotation,
+    `phase0` says at which azimuth its sweep begins and `s_ref` where in the sweep the image is taken."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1215,4 +1357,5 @@ def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, i
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, select_mode=select_mode, depth_median=depth_median, lidar=lidar,
-                      depth_infill=depth_infill)
+                      depth_infill=depth_infill, lidar_sweep=lidar_sweep, lidar_motion=lidar_motion,
+                      sweep_fraction=sweep_fraction)

@@ -187,6 +187,14 @@ class registration {
     // front end refuses, and beside stereo or a depth camera.  clear_lidar(): depth images again.
     void set_lidar(const cvo_fe_lidar &lidar);
     void clear_lidar();
+    // Motion compensation of a spinning scan: cvo_fe_set_lidar_sweep (the sweep contract: cvo_frontend.h).  Needs
+    // set_lidar() first and goes with clear_lidar().  set_lidar_motion(): the scanner's own motion over one sweep, in
+    // its own frame, w (radians per sweep) then v (metres per sweep), for the frames that follow
+    // (cvo_fe_set_lidar_motion; cvo_fe_lidar_twist makes it from `transform`); zero after set_lidar_sweep().  May be
+    // called before the first image; throw for what the front end refuses.  clear_lidar_sweep(): no compensation.
+    void set_lidar_sweep(const cvo_fe_lidar_sweep &sweep);
+    void clear_lidar_sweep();
+    void set_lidar_motion(const float twist[6]);
     void set_pcd_lidar(const int dataset_seq, const image_view &RGB_img, const void *points, size_t stride_bytes,
                        int num_points);
     void run_cvo_lidar(const int dataset_seq, const image_view &RGB_img, const void *points, size_t stride_bytes,
@@ -232,6 +240,9 @@ class registration {
     bool have_depth_infill_;
     cvo_fe_lidar lidar_;                 // what set_lidar() gave, likewise
     bool have_lidar_;
+    cvo_fe_lidar_sweep lidar_sweep_;     // what set_lidar_sweep() gave, likewise, and the twist of set_lidar_motion()
+    bool have_lidar_sweep_;
+    float lidar_motion_[6];
     int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)
     int pixel_format_;                   // what set_pixel_format() gave, likewise (CVO_FE_PIXEL_BGR8 without a call)
     void check(int status, const char *what);

@@ -55,7 +55,10 @@
  * a nearer object is culled.  The LiDAR contract is stated at cvo_fe_lidar below.  And a stage that bridges the gaps of a
  * sparse depth plane -- between scan lines, in the holes a forward warp leaves, where the stereo tests drop pixels of a
  * smooth surface -- linearly in inverse depth, for every kind of frame (cvo_fe_set_depth_infill; cvo_fe_infill_plane for
- * any uint16 plane).  The infill contract is stated at cvo_fe_depth_infill below.
+ * any uint16 plane).  The infill contract is stated at cvo_fe_depth_infill below.  And motion compensation of a spinning
+ * LiDAR scan (cvo_fe_set_lidar_sweep, cvo_fe_set_lidar_motion; cvo_fe_project_points_sweep without a context): every
+ * point is moved into the scanner's frame at the instant of the colour image, by its own time or azimuth and the
+ * scanner's motion over the sweep, in the pass that projects it.  The sweep contract is stated at cvo_fe_lidar_sweep below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -488,7 +491,8 @@ typedef struct cvo_fe_depth_median {
  * CVO_FE_STAGE_LIDAR holds CVO_FE_LIDAR_HIT where P0 != 0, and CVO_FE_LIDAR_OCCLUDED beside it where OCCLUDED.
  * P is the plane an uploaded depth image fills otherwise: the input of the median stage, the gate and level 0, all
  * unchanged.  It is CVO_FE_STAGE_RAW_DEPTH; without median or gate it is also UNGATED_DEPTH and RECT_DEPTH.
- * Not part of it: motion compensation of a spinning scan (the caller's, before the points come here); a lens in the
+ * Motion compensation of a spinning scan is the sweep contract at cvo_fe_lidar_sweep below: off unless it is set.
+ * Not part of it: a lens in the
  * projection (the colour image is rectified instead); reflectance as a feature; densifying beyond splat, which is the
  * infill stage behind this one (the infill contract at cvo_fe_depth_infill: between two scan lines on one surface the
  * depth is interpolated, not copied) and the median stage's fill. */
@@ -548,6 +552,91 @@ typedef struct cvo_fe_lidar {
     int32_t occl_rx, occl_ry;    /* 0..7 each: half-widths of the occlusion window */
     int32_t pad_;                /* must be 0 */
 } cvo_fe_lidar;                  /* 80 bytes, no padding */
+
+/* Motion compensation of a spinning scan.  A spinning scanner collects a scan over a whole sweep -- 100 ms at 10 Hz --
+ * while the colour image is exposed at one instant: at 10 m/s the first and the last point are measured from places a
+ * metre apart, and in a turn of 30 degrees/s a point 40 m out lands 2 m beside its surface.  With a sweep set every
+ * point is moved into the scanner's frame at the instant of the image before it is projected, by the scanner's motion
+ * over the sweep, which the caller hands over per frame (cvo_fe_set_lidar_motion; cvo_fe_lidar_twist makes it from the
+ * last registration).  What it is worth in trajectory accuracy on real scans is not measured: none are shipped.
+ *
+ * THE SWEEP CONTRACT.  While a sweep is set (cvo_fe_set_lidar_sweep) every point of a frame's scan that has passed
+ * step 1 of the LiDAR contract goes through the two steps below, and steps 2 to 9 and the cull run on p' in place of
+ * (x, y, z), unchanged.  All arithmetic in float32, every operation explicit in the stated order, division correctly
+ * rounded, nothing fused, no library transcendental.  It is this library's own definition.
+ * Phase s of the point, the fraction of the sweep at which it was measured:
+ *   CVO_FE_SWEEP_TIME_F32: t is the float at byte time_offset of the record.  Skip the point unless t is finite.
+ *     s = (t - time_origin) * time_scale;  s = fminf(fmaxf(s, 0), 1).
+ *   CVO_FE_SWEEP_TIME_U32: t is the uint32 at byte time_offset.  s = (float)t * time_scale (the conversion rounds to
+ *     nearest even);  s = fminf(fmaxf(s, 0), 1).
+ *   CVO_FE_SWEEP_AZIMUTH (records without a time, KITTI's): a turn fraction q of (x, y), with ax = |x|, ay = |y|:
+ *     r = min(ax, ay) / max(ax, ay), and r = 0 if max(ax, ay) is 0;  r2 = r*r;
+ *     q = (((((C5*r2 + C4)*r2 + C3)*r2 + C2)*r2 + C1)*r2 + C0) * r   with Ck = CVO_FE_SWEEP_ATAN_Ck below: atan(r)/2pi
+ *       within 3e-7 turn on [0, 1];
+ *     then, in this order:  if ay > ax: q = 0.25 - q;   if x < 0: q = 0.5 - q;   if y < 0: q = -q.
+ *     The tie ax == ay belongs to the octant of the x axis (no first fix-up: q = the polynomial at r = 1); -0 is not < 0.
+ *     s = (float)direction * q + phase0;  s = s - floorf(s).  s lies in [0, 1]; 1 itself is reached where s was just
+ *     below a whole number.
+ *     The seam of this mode is ambiguous by nature: a point on the azimuth where the sweep begins and ends may have been
+ *     measured at either end, and is moved as the end its phase names.
+ * Move, with the frame's twist (w_twist, v_twist) (cvo_fe_set_lidar_motion):
+ *   a = s - s_ref;   w.k = a * w_twist.k;   tau.k = a * v_twist.k   (k = 0, 1, 2);
+ *   t2 = (w.0*w.0 + w.1*w.1) + w.2*w.2;
+ *   A = ((((A5*t2 + A4)*t2 + A3)*t2 + A2)*t2 + A1)*t2 + A0      sin(t)/t,         Ak = (-1)^k / (2k+1)!
+ *   B = ((((B5*t2 + B4)*t2 + B3)*t2 + B2)*t2 + B1)*t2 + B0      (1 - cos t)/t^2,  Bk = (-1)^k / (2k+2)!
+ *   C =  (((C4*t2 + C3)*t2 + C2)*t2 + C1)*t2 + C0               (t - sin t)/t^3,  Ck = (-1)^k / (2k+3)!
+ *     with the coefficients CVO_FE_SWEEP_A0 .. below, each the float32 nearest to its fraction.  t2 <= 1 by the cap on
+ *     the twist; the first term left out is below 2^-26 in every series (B carries one term more than that asks for).
+ *   cross(a, b) = (a.1*b.2 - a.2*b.1,  a.2*b.0 - a.0*b.2,  a.0*b.1 - a.1*b.0);
+ *   c1 = cross(w, p);  c2 = cross(w, c1);  d1 = cross(w, tau);  d2 = cross(w, d1)      with p = (x, y, z);
+ *   p'.k = ((p.k + A*c1.k) + B*c2.k) + ((tau.k + B*d1.k) + C*d2.k).
+ * Meaning: p' is the point in the scanner's frame at phase s_ref, for a scanner whose pose over the sweep is
+ * T0 * Exp(s * xi), xi = (w_twist, v_twist): p' = Exp((s - s_ref) * xi) p.
+ * Identities: with a zero twist, or where s == s_ref, p' = p up to the sign of a zero, and with a zero twist the planes
+ * are those of a context without a sweep, byte for byte.
+ * p' may overflow for a point beyond 1e37; steps 3, 6 and 7 then skip it. */
+enum { CVO_FE_SWEEP_TIME_F32 = 1, CVO_FE_SWEEP_TIME_U32 = 2, CVO_FE_SWEEP_AZIMUTH = 3 };
+typedef struct cvo_fe_lidar_sweep {
+    int32_t mode;         /* one of the above */
+    int32_t time_offset;  /* byte offset of the time word in a record (modes 1, 2): a multiple of 4, >= 12; not read
+                             under mode 3 */
+    float   time_origin;  /* mode 1: subtracted first; must be 0 otherwise */
+    float   time_scale;   /* modes 1, 2: phase per unit of the field (1 / sweep duration); finite, != 0; not read
+                             under mode 3 */
+    float   phase0;       /* mode 3: phase of azimuth 0, in [0, 1); finite and not read otherwise */
+    int32_t direction;    /* mode 3: +1 phase grows with atan2(y, x), -1 it falls; must be 0 otherwise */
+    float   s_ref;        /* phase at which the colour image is exposed, in [0, 1] */
+    int32_t pad_;         /* must be 0 */
+} cvo_fe_lidar_sweep;     /* 32 bytes, no padding */
+/* The coefficients of the sweep contract.  ATAN: an odd polynomial of degree 11 for atan(r) / (2 pi) on [0, 1], a
+ * least-squares fit at 400 Chebyshev nodes; its largest error in float32 is 3.0e-7 turn, which at the caps on the twist
+ * moves a point 120 m out by less than 0.06 mm. */
+#define CVO_FE_SWEEP_ATAN_C0 1.591517329e-01f
+#define CVO_FE_SWEEP_ATAN_C1 -5.294376612e-02f
+#define CVO_FE_SWEEP_ATAN_C2 3.082358837e-02f
+#define CVO_FE_SWEEP_ATAN_C3 -1.856560260e-02f
+#define CVO_FE_SWEEP_ATAN_C4 8.407119662e-03f
+#define CVO_FE_SWEEP_ATAN_C5 -1.873333240e-03f
+#define CVO_FE_SWEEP_A0 1.0f
+#define CVO_FE_SWEEP_A1 (-1.0f / 6.0f)
+#define CVO_FE_SWEEP_A2 (1.0f / 120.0f)
+#define CVO_FE_SWEEP_A3 (-1.0f / 5040.0f)
+#define CVO_FE_SWEEP_A4 (1.0f / 362880.0f)
+#define CVO_FE_SWEEP_A5 (-1.0f / 39916800.0f)
+#define CVO_FE_SWEEP_B0 (1.0f / 2.0f)
+#define CVO_FE_SWEEP_B1 (-1.0f / 24.0f)
+#define CVO_FE_SWEEP_B2 (1.0f / 720.0f)
+#define CVO_FE_SWEEP_B3 (-1.0f / 40320.0f)
+#define CVO_FE_SWEEP_B4 (1.0f / 3628800.0f)
+#define CVO_FE_SWEEP_B5 (-1.0f / 479001600.0f)
+#define CVO_FE_SWEEP_C0 (1.0f / 6.0f)
+#define CVO_FE_SWEEP_C1 (-1.0f / 120.0f)
+#define CVO_FE_SWEEP_C2 (1.0f / 5040.0f)
+#define CVO_FE_SWEEP_C3 (-1.0f / 362880.0f)
+#define CVO_FE_SWEEP_C4 (1.0f / 39916800.0f)
+/* the caps on a frame's twist: |w| in radians per sweep (573 degrees/s at 10 Hz), |v| in metres per sweep */
+#define CVO_FE_SWEEP_MAX_ROTATION 1.0f
+#define CVO_FE_SWEEP_MAX_TRANSLATION 64.0f
 
 /* One camera of a stereo rig: its pinhole and its lens (k1 k2 p1 p2 k3, as cvo_fe_camera_model's dist). */
 typedef struct cvo_fe_lens {
@@ -784,10 +873,29 @@ int cvo_fe_get_depth_infill(const cvo_fe_ctx *ctx, cvo_fe_depth_infill *out, int
 int cvo_fe_set_lidar(cvo_fe_ctx *ctx, const cvo_fe_lidar *l);
 /* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
 int cvo_fe_get_lidar(const cvo_fe_ctx *ctx, cvo_fe_lidar *out, int *set);
+/* A sweep for the scan source (the sweep contract at cvo_fe_lidar_sweep); sw == NULL: none (the state of a new context
+ * and of a new scan source).  It needs a scan source and goes when the scan source goes (cvo_fe_set_lidar(ctx, NULL));
+ * other settings of the scan source leave it.  The frame's twist is zero after every call that sets a sweep.  Under a
+ * field mode a frame's staging and its copy hold 16 bytes per point instead of 12.  CVO_HIP_ERR_INVALID, the context
+ * keeping what it had: a null context; a frame submitted and not collected; no scan source; settings
+ * cvo_fe_check_lidar_sweep refuses.  Without a sweep a frame launches the kernel it launched before there was one. */
+int cvo_fe_set_lidar_sweep(cvo_fe_ctx *ctx, const cvo_fe_lidar_sweep *sw);
+/* *set = 1 and the settings, or *set = 0 and *out zeroed.  `set` may be NULL. */
+int cvo_fe_get_lidar_sweep(const cvo_fe_ctx *ctx, cvo_fe_lidar_sweep *out, int *set);
+/* The twist of the scanner's own motion over one full sweep, in its own frame: w (radians per sweep) then v (metres
+ * per sweep), so that the scanner's pose at phase s is T0 * Exp(s * twist).  It holds for the frames submitted after
+ * the call (a frame submitted and not collected keeps the one it was submitted with) and travels with the frame's
+ * points, so that a captured frame is replayed with a twist that changes.  Zero in a new context and after a sweep is
+ * set.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null argument; no sweep set; a member that is not
+ * finite; |w| > CVO_FE_SWEEP_MAX_ROTATION or |v| > CVO_FE_SWEEP_MAX_TRANSLATION (norms in float64). */
+int cvo_fe_set_lidar_motion(cvo_fe_ctx *ctx, const float twist[6]);
+/* The twist in force, zero without a sweep. */
+int cvo_fe_get_lidar_motion(const cvo_fe_ctx *ctx, float twist[6]);
 /* cvo_fe_submit / cvo_fe_create_pointcloud for a colour image and a scan: `img` as there; `points` are num_points
  * records `stride_bytes` apart whose first three floats are x, y, z.  The points are copied to the context's pinned
  * staging before the call returns.  CVO_HIP_ERR_INVALID without a scan source, for num_points outside
- * [0, max_points], a stride below 12 or not a multiple of 4, and null points with num_points > 0.  collect,
+ * [0, max_points], a stride below 12 or not a multiple of 4, under a sweep with a field mode a stride below
+ * time_offset + 4, and null points with num_points > 0.  collect,
  * collect_device, get_info, set_device_output, set_num_want, the mask, the gate, the median and the select mode work on
  * such a frame as on any other. */
 int cvo_fe_submit_lidar(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *points, size_t stride_bytes,
@@ -992,6 +1100,33 @@ int cvo_fe_check_lidar(const cvo_fe_lidar *l);
 int cvo_fe_project_points(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
                           const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled, uint8_t *flags,
                           int *hits, int *occluded);
+/* CVO_HIP_OK for a sweep cvo_fe_set_lidar_sweep() would accept on an idle context with a scan source,
+ * CVO_HIP_ERR_INVALID otherwise: NULL; a mode that is none of CVO_FE_SWEEP_*; a float that is not finite; under a field
+ * mode time_offset below 12 or not a multiple of 4, time_scale 0, direction != 0; time_origin != 0 outside
+ * CVO_FE_SWEEP_TIME_F32; under CVO_FE_SWEEP_AZIMUTH a direction that is neither +1 nor -1, phase0 outside [0, 1);
+ * s_ref outside [0, 1]; pad_ != 0.  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_lidar_sweep(const cvo_fe_lidar_sweep *sw);
+/* The twist for cvo_fe_set_lidar_motion of a caller who assumes the velocity of the last frame interval to hold.  Host
+ * only, float64.  `T_cam` is the relative camera pose of the last registration as the registration objects return it
+ * in `transform` (row-major 4 x 4): the moving cloud, the LATER frame's, is aligned to the fixed one, the earlier
+ * frame's, by y = R^T (z - T), so [R | T] takes coordinates in the earlier camera's frame to coordinates in the later
+ * one's, and the later camera's pose in the earlier one's frame -- the camera's motion over the frame interval -- is
+ * its inverse M.  With X = [l->R | l->T], the scanner's pose in the camera's frame, the scanner's own motion is
+ * X^-1 M X; the twist is its SE(3) logarithm times `sweep_fraction`, the sweep duration over the frame interval
+ * (1 for a scanner that spins once per image).  CVO_HIP_ERR_INVALID: a null argument; a member of T_cam or a
+ * sweep_fraction that is not finite; sweep_fraction <= 0; a rotation part that fails the depth camera's rotation rule;
+ * settings cvo_fe_check_lidar refuses (max_points is not read); a rotation of more than 3 radians over the frame
+ * interval; a twist over the caps of cvo_fe_set_lidar_motion. */
+int cvo_fe_lidar_twist(const float T_cam[16], const cvo_fe_lidar *l, float sweep_fraction, float twist[6]);
+/* cvo_fe_project_points under the sweep contract: its arguments, then the sweep and the scan's twist (what
+ * cvo_fe_set_lidar_sweep and cvo_fe_set_lidar_motion accept; under a field mode time_offset + 4 <= stride_bytes).
+ * `phase`, if not NULL, receives s of each of the n points and `moved`, if not NULL, p' (3n floats); a point that
+ * step 1 or a time that is not finite skipped has NaN in all four.  sw == NULL: cvo_fe_project_points itself (`twist`
+ * is not read; phase and moved must be NULL). */
+int cvo_fe_project_points_sweep(int device, const void *points, size_t stride_bytes, int n, const cvo_fe_lidar *l,
+                                const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled,
+                                uint8_t *flags, int *hits, int *occluded, const cvo_fe_lidar_sweep *sw,
+                                const float twist[6], float *phase, float *moved);
 #ifdef __cplusplus
 }
 #endif
