@@ -62,7 +62,7 @@ registration::registration(int mode, int device, void *stream)
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
       depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), lidar_sweep_(), have_lidar_sweep_(false), lidar_motion_(), select_mode_(CVO_FE_SELECT_IMAGE),
-      pixel_format_(CVO_FE_PIXEL_BGR8)
+      pixel_format_(CVO_FE_PIXEL_BGR8), depth_format_(CVO_FE_DEPTH_U16), depth_unit_(1.0f)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -103,6 +103,7 @@ void registration::apply_stored_settings()
             fe_check(cvo_fe_set_lidar_motion(fe_, lidar_motion_), "cvo_fe_set_lidar_motion");
         }
         fe_check(cvo_fe_set_pixel_format(fe_, pixel_format_), "cvo_fe_set_pixel_format");
+        fe_check(cvo_fe_set_depth_format(fe_, depth_format_, depth_unit_), "cvo_fe_set_depth_format");
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -122,8 +123,9 @@ void registration::apply_stored_settings()
 // output arrays go straight into cvo_hip_set_*_device.
 // `stereo`: `dep` is the right colour image of a rectified pair (cvo_fe_submit_stereo) and `rgb` the left one.
 // `scan`: a LiDAR frame (cvo_fe_submit_lidar); `dep` is `rgb` again and is not read.
+// `on_device`: the two views' `data` is device memory (cvo_fe_submit_device, cvo_fe_submit_stereo_device).
 void registration::cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo,
-                                     const scan_view *scan)
+                                     const scan_view *scan, bool on_device)
 {
     if (scan && !have_lidar_) throw std::runtime_error("set_pcd_lidar(): no scan source: set_lidar() first");
     if (!scan && have_lidar_)
@@ -149,6 +151,8 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
     const int ftype = params_.mode == CVO_HIP_MODE_ACVO ? CVO_FE_FEATURES_HSV : CVO_FE_FEATURES_RGB;
     int rc = scan   ? cvo_fe_submit_lidar(fe_, (const uint8_t *)rgb.data, rgb.step, scan->points, scan->stride_bytes,
                                           scan->num_points, dataset_seq, ftype)
+             : on_device ? (stereo ? cvo_fe_submit_stereo_device(fe_, rgb.data, rgb.step, dep.data, dep.step, dataset_seq, ftype)
+                                   : cvo_fe_submit_device(fe_, rgb.data, rgb.step, dep.data, dep.step, dataset_seq, ftype))
              : stereo ? cvo_fe_submit_stereo(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint8_t *)dep.data, dep.step,
                                            dataset_seq, ftype)
                     : cvo_fe_submit(fe_, (const uint8_t *)rgb.data, rgb.step, (const uint16_t *)dep.data, dep.step,
@@ -316,6 +320,16 @@ void registration::set_pixel_format(int format)
     pixel_format_ = format;
 }
 
+void registration::set_depth_format(int format, float unit)
+{
+    if (!fe_ && cvo_fe_check_depth_format(format, unit) != CVO_HIP_OK)
+        throw std::runtime_error("set_depth_format(): one of CVO_FE_DEPTH_*, a finite unit in [2^-20, 2^20], and a unit of 1 "
+                                 "under CVO_FE_DEPTH_U16");
+    if (fe_) fe_check(cvo_fe_set_depth_format(fe_, format, unit), "cvo_fe_set_depth_format");
+    depth_format_ = format;
+    depth_unit_ = unit;
+}
+
 void registration::set_stereo(const cvo_fe_stereo &stereo)
 {
     if (!fe_ && cvo_fe_check_stereo(&stereo) != CVO_HIP_OK)
@@ -436,11 +450,31 @@ void registration::run_cvo_stereo(const int dataset_seq, const image_view &left_
     run_images(dataset_seq, left_img, right_img, true);
 }
 
+void registration::set_pcd_on_device(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img)
+{
+    cloud_from_images(dataset_seq, RGB_img, dep_img, false, nullptr, true);
+}
+
+void registration::run_cvo_on_device(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img)
+{
+    run_images(dataset_seq, RGB_img, dep_img, false, nullptr, true);
+}
+
+void registration::set_pcd_stereo_on_device(const int dataset_seq, const image_view &left_img, const image_view &right_img)
+{
+    cloud_from_images(dataset_seq, left_img, right_img, true, nullptr, true);
+}
+
+void registration::run_cvo_stereo_on_device(const int dataset_seq, const image_view &left_img, const image_view &right_img)
+{
+    run_images(dataset_seq, left_img, right_img, true, nullptr, true);
+}
+
 void registration::run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo,
-                              const scan_view *scan)
+                              const scan_view *scan, bool on_device)
 {   // ref src/cvo.cpp:422-435
     const bool first = !init;
-    cloud_from_images(dataset_seq, rgb, second, stereo, scan);
+    cloud_from_images(dataset_seq, rgb, second, stereo, scan, on_device);
     if (first) return;
     align();
     std::cout << "Total iterations: " << iter << std::endl;

@@ -27,6 +27,8 @@
 #include "cvo_speckle.h"
 #include "cvo_stereo.h"
 #include "cvo_unpack.h"
+#include "cvo_depthfmt.h"
+#include "cvo_input.h"
 
 namespace {
 
@@ -1196,6 +1198,18 @@ struct cvo_fe_ctx {
     // stereo the right image's as well (they stand in for h_right)
     Dev<uint8_t> packed, packed_r;
     Pin<uint8_t> h_packed, h_packed_r;
+    // the format of the caller's depth images (cvo_fe_set_depth_format): a setting of the context, read by frames that
+    // have a depth image; under a float format the float image is what is staged and uploaded, and k_fe_depth_convert of
+    // cvo_depthfmt.hip writes where the uint16 upload lands otherwise
+    int depthfmt = CVO_FE_DEPTH_U16;
+    float depth_unit = 1.0f;
+    // with a float format, and gone with it: the float image (dw * dh values) and its pinned staging (they stand in for
+    // h_depth); both follow the depth camera's size
+    Dev<uint8_t> fdepth;
+    Pin<uint8_t> h_fdepth;
+    // the frame being submitted takes its images from the caller's device memory (cvo_fe_submit_device): they are
+    // brought to the landing buffers in front of the frame, and the frame's sequence holds no upload of them
+    bool dev_in = false;
     std::string err;
 };
 
@@ -1500,6 +1514,30 @@ inline int img_rows(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_rows
 
 // where the colour image lands on the device (an upload, or k_fe_unpack's output): the stereo rig's raw buffer, else the
 // raw image k_fe_rectify resamples, else the image every later stage reads; and the right image of a stereo frame
+// under a float depth format: the bytes of one value, and the staging a frame's depth image is copied to and uploaded from
+inline bool converts(const cvo_fe_ctx *ctx) { return ctx->depthfmt != CVO_FE_DEPTH_U16; }
+inline size_t depth_item(const cvo_fe_ctx *ctx) { return fe_depth_item(ctx->depthfmt); }
+inline void *depth_staging(const cvo_fe_ctx *ctx) { return converts(ctx) ? (void *)ctx->h_fdepth.get() : (void *)ctx->h_depth.get(); }
+
+// the `scale` of the depth-format contract: of whatever reads the uploaded depth image first
+inline float depth_format_scale(const cvo_fe_ctx *ctx, int dataset_seq)
+{
+    if (ctx->has_rig) return ctx->rig.depth_scale;
+    float cam[5];
+    camera_in_force(ctx, dataset_seq, cam);
+    return cam[0];
+}
+
+// the depth-format contract on the float image at `src`: in front of everything else that reads the depth image
+inline void enqueue_depth_convert(const cvo_fe_ctx *ctx, const void *src, size_t pitch, int dataset_seq)
+{
+    FeDepthConvertArgs a{};
+    a.src = src; a.src_pitch = pitch; a.dst = depth_upload(ctx);
+    a.w = ctx->dw; a.h = ctx->dh; a.format = ctx->depthfmt; a.unit = ctx->depth_unit;
+    a.scale = depth_format_scale(ctx, dataset_seq);
+    fe_depth_convert_enqueue(a, ctx->stream);
+}
+
 inline uint8_t *img_landing(const cvo_fe_ctx *ctx)
 {
     return ctx->has_srig ? ctx->srig_raw_l.get() : ctx->rectify ? ctx->raw_img.get() : ctx->img.get();
@@ -1594,7 +1632,11 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // (a stereo rig: the pair lands in the rig's raw buffers and k_fe_stereo_rectify fills img / right_img)
     // (a pixel format: the packed images land in buffers of their own and k_fe_unpack fills what is named above)
     const size_t img_bytes = img_row(ctx) * (size_t)img_rows(ctx);
-    FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed.get() : img_landing(ctx), img_staging(ctx), img_bytes, hipMemcpyHostToDevice, s));
+    // (a frame from device memory: its images were brought to these buffers in front of the frame, and its depth image,
+    // under a float format, converted from where it lies; this sequence then holds no copy of them)
+    const bool upload = !ctx->dev_in;
+    if (upload)
+        FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed.get() : img_landing(ctx), img_staging(ctx), img_bytes, hipMemcpyHostToDevice, s));
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
@@ -1602,15 +1644,21 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // (the infill stage: likewise in front of the median stage, and k_fe_infill fills what is named above)
     uint16_t *plane = source_plane(ctx);
     // (a scan source: the scan is uploaded in place of a depth image, its count in front, and the projection fills that plane)
-    if (ctx->has_stereo)
-        FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), right_staging(ctx), img_bytes,
-                              hipMemcpyHostToDevice, s));
-    else if (ctx->has_lidar)
+    // (a float depth format: the float image lands in a buffer of its own and k_fe_depth_convert fills what is named above)
+    if (ctx->has_stereo) {
+        if (upload)
+            FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), right_staging(ctx), img_bytes,
+                                  hipMemcpyHostToDevice, s));
+    } else if (ctx->has_lidar)
         FE_HIP(hipMemcpyAsync(ctx->d_scan.get(), ctx->h_scan.get(), lidar_scan_bytes(ctx->lidar.max_points, ctx->scan_record),
                               hipMemcpyHostToDevice, s));
-    else
+    else if (upload && converts(ctx))
+        FE_HIP(hipMemcpyAsync(ctx->fdepth.get(), ctx->h_fdepth.get(), (size_t)ctx->dw * ctx->dh * depth_item(ctx), hipMemcpyHostToDevice, s));
+    else if (upload)
         FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
+    if (upload && converts(ctx) && !ctx->has_stereo && !ctx->has_lidar)   // (the depth-format contract)
+        enqueue_depth_convert(ctx, ctx->fdepth.get(), (size_t)ctx->dw * depth_item(ctx), dataset_seq);
     if (unpacks(ctx)) {   // (the unpack contract: in front of everything else in the frame, one launch for a pair)
         FeUnpackArgs u{};
         u.src[0] = ctx->packed.get(); u.dst[0] = img_landing(ctx);
@@ -1899,8 +1947,12 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
     Pin<uint16_t> new_host;
     Dev<float2> new_rays;
     Dev<uint32_t> new_z;
+    Dev<uint8_t> new_fdepth;   // (under a float depth format: the float image and its staging follow the size as well)
+    Pin<uint8_t> new_fhost;
     const bool resize = dw != ctx->dw || dh != ctx->dh;   // the pinned staging image follows the depth size
     if (resize && !pin_alloc(new_host, dnp)) return no_memory(ctx, "set_depth_camera: pinned memory for the depth image");
+    if (resize && converts(ctx) && !(dev_alloc(new_fdepth, dnp * depth_item(ctx)) && pin_alloc(new_fhost, dnp * depth_item(ctx))))
+        return no_memory(ctx, "set_depth_camera: device and pinned memory for the float depth image");
     if (rig) {
         const size_t nr = (size_t)(dw + 1) * (dh + 1), nz = rect_plane(ctx->np);
         std::vector<float> t;
@@ -1932,6 +1984,8 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
     ctx->rays = std::move(new_rays);
     hand_over(ctx->zbuf, new_z);
     hand_over(ctx->h_depth, new_host);
+    hand_over(ctx->fdepth, new_fdepth);
+    hand_over(ctx->h_fdepth, new_fhost);
     ctx->has_rig = rig != nullptr;
     ctx->rig = rig ? *rig : cvo_fe_depth_camera{};
     ctx->dw = dw;
@@ -2269,6 +2323,43 @@ int cvo_fe_get_pixel_format(const cvo_fe_ctx *ctx, int *format)
     cvo_lock::Api api_guard;
     if (!ctx || !format) return CVO_HIP_ERR_INVALID;
     *format = ctx->pixfmt;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_depth_format(cvo_fe_ctx *ctx, int format, float unit)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_format: a frame is in flight");
+    if (!fe_depth_format_ok(format, unit))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_format: a CVO_FE_DEPTH_* format, a finite unit in [2^-20, 2^20], "
+                                              "and a unit of 1 under CVO_FE_DEPTH_U16");
+    if (format == ctx->depthfmt && unit == ctx->depth_unit) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint8_t> fdepth;
+    Pin<uint8_t> h_fdepth;
+    const size_t bytes = (size_t)ctx->dw * ctx->dh * fe_depth_item(format);
+    const bool on = format != CVO_FE_DEPTH_U16, sized = on && fe_depth_item(format) == depth_item(ctx) && converts(ctx);
+    if (on && !sized && !(dev_alloc(fdepth, bytes) && pin_alloc(h_fdepth, bytes)))
+        return no_memory(ctx, "set_depth_format: device and pinned memory for the float depth image");
+    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
+    FE_HIP(hipStreamSynchronize(ctx->stream));
+    if (!sized) {   // (both replaced or, back in U16, freed)
+        ctx->fdepth = std::move(fdepth);
+        ctx->h_fdepth = std::move(h_fdepth);
+    }
+    ctx->depthfmt = format;
+    ctx->depth_unit = unit;
+    drop_graphs(ctx);   // (the format, the unit and the float image are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_depth_format(const cvo_fe_ctx *ctx, int *format, float *unit)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !format || !unit) return CVO_HIP_ERR_INVALID;
+    *format = ctx->depthfmt;
+    *unit = ctx->depth_unit;
     return CVO_HIP_OK;
 }
 
@@ -2812,7 +2903,7 @@ int cvo_fe_host_buffers(cvo_fe_ctx *ctx, uint8_t **img, uint16_t **depth)
 {
     if (!ctx || !img || !depth) return CVO_HIP_ERR_INVALID;
     *img = img_staging(ctx);
-    *depth = ctx->h_depth.get();
+    *depth = (uint16_t *)depth_staging(ctx);
     return CVO_HIP_OK;
 }
 
@@ -2838,8 +2929,30 @@ namespace {
 // submit() of any kind of frame: `second` is the depth image (uint16 rows) of a depth frame, the right colour image of
 // a stereo frame (`stereo`), and the `num_points` records of a scan, second_stride bytes apart, of a LiDAR frame
 // (`lidar`); the kind must be the one the context is set up for
+// An image a caller hands over in device memory (the device-input contract of cvo_frontend.h): device memory of the
+// context's device, and, where the runtime knows the allocation's range, inside it.  Nothing is enqueued before every
+// image of the frame has passed.
+int device_image_ok(cvo_fe_ctx *ctx, const void *p, size_t stride, size_t row, int rows, const char *refused)
+{
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device) {
+        (void)hipGetLastError();   // (an unknown pointer is an error of the runtime's: taken, so that the next frame does not find it)
+        return fail(ctx, CVO_HIP_ERR_INVALID, refused);
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return CVO_HIP_OK;   // (no answer: the image is taken at the caller's word)
+    }
+    if ((uintptr_t)p < (uintptr_t)base || !input_fits((uintptr_t)p - (uintptr_t)base, size, (size_t)rows, stride, row))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "submit_device: an image ends past the end of its allocation");
+    return CVO_HIP_OK;
+}
+
+// `device`: img and second are device memory (cvo_fe_submit_device, cvo_fe_submit_stereo_device)
 int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *second, size_t second_stride,
-                 int dataset_seq, int feature_type, bool stereo, bool lidar = false, int num_points = 0)
+                 int dataset_seq, int feature_type, bool stereo, bool lidar = false, int num_points = 0, bool device = false)
 {
     const int np = ctx->np;
     const int dw = ctx->dw, dh = ctx->dh;   // (the depth camera's image, if the context has one)
@@ -2857,17 +2970,31 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
     if (time_offset >= 0 && (size_t)time_offset + 4 > second_stride)
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit_lidar: the sweep's time_offset + 4 is beyond the stride");
     const size_t row = img_row(ctx);   // (of the pixel format in force: w * 3 without one)
+    const size_t ditem = depth_item(ctx), drow = (size_t)dw * ditem;   // (of the depth format in force: dw * 2 without one)
     if (!img || (!second && !lidar) || img_stride < row ||
-        (!lidar && second_stride < (stereo ? row : (size_t)dw * 2)) ||
+        (!lidar && second_stride < (stereo ? row : drow)) ||
         (feature_type != CVO_FE_FEATURES_HSV && feature_type != CVO_FE_FEATURES_RGB))
         return fail(ctx, CVO_HIP_ERR_INVALID, "submit: bad argument");
+    if (!lidar && !stereo && (converts(ctx) || device) && second_stride % ditem != 0)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the depth stride is not a multiple of the size of a depth value");
     if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "submit: the previous frame was not collected");
     FE_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    if (device) {   // (every image is checked before anything is enqueued)
+        if (!stereo && (uintptr_t)second % ditem != 0)
+            return fail(ctx, CVO_HIP_ERR_INVALID, "submit_device: the depth image is not aligned to the size of a depth value");
+        int rc = device_image_ok(ctx, img, img_stride, row, img_rows(ctx),
+                                 "submit_device: the colour image is not device memory of the context's device");
+        if (!rc)
+            rc = device_image_ok(ctx, second, second_stride, stereo ? row : drow, stereo ? img_rows(ctx) : dh,
+                                 stereo ? "submit_stereo_device: the right image is not device memory of the context's device"
+                                        : "submit_device: the depth image is not device memory of the context's device");
+        if (rc) return rc;
+    }
     // pinned staging (not when the caller decoded into the staging image itself: cvo_fe_host_buffers)
-    if (!(img == img_staging(ctx) && img_stride == row)) copy_rows(img_staging(ctx), img, img_stride, row, img_rows(ctx));
+    if (!device && !(img == img_staging(ctx) && img_stride == row)) copy_rows(img_staging(ctx), img, img_stride, row, img_rows(ctx));
     if (stereo) {
-        copy_rows(right_staging(ctx), second, second_stride, row, img_rows(ctx));
+        if (!device) copy_rows(right_staging(ctx), second, second_stride, row, img_rows(ctx));
         // the table U(q) of the camera in force, if the device holds another's: in front of the frame, outside the
         // captured graph (its address is the graph's), as the mask below
         float cam[5];
@@ -2884,8 +3011,25 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
         }
     } else if (lidar)
         lidar_stage(ctx->h_scan.get(), second, second_stride, num_points, time_offset, ctx->lidar_twist);
-    else if (!(second == ctx->h_depth.get() && second_stride == (size_t)dw * 2))
-        copy_rows(ctx->h_depth.get(), second, second_stride, (size_t)dw * 2, dh);
+    else if (!device && !(second == depth_staging(ctx) && second_stride == drow))
+        copy_rows(depth_staging(ctx), second, second_stride, drow, dh);
+    if (device) {
+        // The caller's images: in front of the frame, outside the captured graph (a graph must not hold a caller's
+        // pointer), as the mask below.  One pitched copy per image into the buffer its upload lands in; a float depth
+        // image is not copied: the conversion reads it where it lies.
+        const size_t rows = (size_t)img_rows(ctx);
+        FE_HIP(hipMemcpy2DAsync(unpacks(ctx) ? ctx->packed.get() : img_landing(ctx), row, img, img_stride, row, rows,
+                                hipMemcpyDeviceToDevice, s));
+        if (stereo)
+            FE_HIP(hipMemcpy2DAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), row, second, second_stride, row, rows,
+                                    hipMemcpyDeviceToDevice, s));
+        else if (converts(ctx)) {
+            enqueue_depth_convert(ctx, second, second_stride, ctx->custom || ctx->has_srig ? 0 : dataset_seq);
+            FE_HIP(hipGetLastError());
+        } else
+            FE_HIP(hipMemcpy2DAsync(depth_upload(ctx), drow, second, second_stride, drow, (size_t)dh, hipMemcpyDeviceToDevice, s));
+    }
+    ctx->dev_in = device;   // (read by enqueue_frame: such a frame's sequence holds no upload of the images)
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
     *ctx->h_ctrl = c0;
@@ -2901,7 +3045,7 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
     const int seq_given = dataset_seq;
     if (ctx->custom || ctx->has_srig) dataset_seq = 0;   // (ignored: one key whatever the caller passed)
     const uint64_t key = ((uint64_t)(uint32_t)dataset_seq << 40) ^ ((uint64_t)feature_type << 36) ^
-                         ((uint64_t)ctx->device_output << 32) ^ (uint64_t)(uint32_t)ctx->num_want;
+                         ((uint64_t)ctx->device_output << 32) ^ ((uint64_t)device << 33) ^ (uint64_t)(uint32_t)ctx->num_want;
     int rc = CVO_HIP_OK;
     FeGraph *g = nullptr;
     for (auto &e : ctx->graphs)
@@ -2956,6 +3100,26 @@ int cvo_fe_submit_stereo(cvo_fe_ctx *ctx, const uint8_t *left, size_t left_strid
     cvo_lock::Api api_guard;
     if (!ctx) return CVO_HIP_ERR_INVALID;
     return submit_frame(ctx, left, left_stride, right, right_stride, dataset_seq, feature_type, true);
+}
+
+int cvo_fe_submit_device(cvo_fe_ctx *ctx, const void *d_img, size_t img_stride, const void *d_depth, size_t depth_stride,
+                         int dataset_seq, int feature_type)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (ctx->has_lidar)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "submit_device: a scan source is set; a scan is staged by the host (cvo_fe_submit_lidar)");
+    return submit_frame(ctx, (const uint8_t *)d_img, img_stride, d_depth, depth_stride, dataset_seq, feature_type, false, false, 0,
+                        true);
+}
+
+int cvo_fe_submit_stereo_device(cvo_fe_ctx *ctx, const void *d_left, size_t left_stride, const void *d_right,
+                                size_t right_stride, int dataset_seq, int feature_type)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    return submit_frame(ctx, (const uint8_t *)d_left, left_stride, d_right, right_stride, dataset_seq, feature_type, true, false, 0,
+                        true);
 }
 
 int cvo_fe_submit_lidar(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const void *points, size_t stride_bytes,

@@ -22,6 +22,14 @@ on the device in front of everything else (the unpack contract of include/cvo_fr
 
     gen.set_pixel_format(PIXEL_BAYER_RGGB8)     # the images are then h x w bytes of mosaic
 
+Depth as float32 / float16 in metres, as a network or a simulator produces it (the depth-format contract of
+include/cvo_frontend.h), and frames whose images lie in device memory already (the device-input contract; any object with
+`__cuda_array_interface__`, a torch tensor on ROCm among them -- the producer synchronised, or the generator on its stream):
+
+    gen.set_depth_format(DEPTH_F32, unit=1.0)
+    gen.submit_device(bgr_on_device, metres_on_device, dataset_seq=1)
+    d_xyz, d_feat, n = gen.collect_device()     # from a tensor to the registration without touching host memory
+
 A LiDAR scan in place of the depth image, projected into the colour camera on the device (the LiDAR contract of
 include/cvo_frontend.h; KITTI: R, T from R_rect_00 * Tr_velo_to_cam):
 
@@ -74,6 +82,10 @@ INFILL_ROW, INFILL_COL, INFILL_JUMP = 1, 2, 4   # the values of STAGE_INFILL
 # letters are the colours of pixels (0,0) (1,0) / (0,1) (1,1) -- not OpenCV's names
 (PIXEL_BGR8, PIXEL_RGB8, PIXEL_BGRA8, PIXEL_RGBA8, PIXEL_GREY8, PIXEL_YUY2, PIXEL_UYVY, PIXEL_NV12, PIXEL_BAYER_RGGB8,
  PIXEL_BAYER_BGGR8, PIXEL_BAYER_GRBG8, PIXEL_BAYER_GBRG8) = range(12)
+# formats of the depth images (set_depth_format; the depth-format contract of include/cvo_frontend.h): uint16 in the
+# camera's own units (a new object's), or float32 / float16 in `unit` metres
+DEPTH_U16, DEPTH_F32, DEPTH_F16 = 0, 1, 2
+_DEPTH_DTYPES = {DEPTH_U16: np.uint16, DEPTH_F32: np.float32, DEPTH_F16: np.float16}
 # path masks of the stereo matcher (set_stereo_paths): bits 0-3 rows and columns, bits 4-7 the diagonals
 PATHS_4, PATHS_8 = 0x0F, 0xFF
 # modes of the selector (set_select_mode): by the image alone (the reference; a new object's), or among the pixels
@@ -96,7 +108,8 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_create_pointcloud_lidar", "cvo_fe_project_points", "cvo_fe_check_pixel_format", "cvo_fe_pixel_layout",
            "cvo_fe_set_pixel_format", "cvo_fe_get_pixel_format", "cvo_fe_unpack_image", "cvo_fe_check_lidar_sweep",
            "cvo_fe_set_lidar_sweep", "cvo_fe_get_lidar_sweep", "cvo_fe_set_lidar_motion", "cvo_fe_get_lidar_motion",
-           "cvo_fe_lidar_twist", "cvo_fe_project_points_sweep")
+           "cvo_fe_lidar_twist", "cvo_fe_project_points_sweep", "cvo_fe_check_depth_format", "cvo_fe_set_depth_format",
+           "cvo_fe_get_depth_format", "cvo_fe_convert_depth", "cvo_fe_submit_device", "cvo_fe_submit_stereo_device")
 
 
 class Info(C.Structure):
@@ -406,6 +419,12 @@ def lib():
         L.cvo_fe_stereo_rectify.argtypes = [C.POINTER(StereoCalib), C.c_int, C.c_int, C.POINTER(StereoRig), C.c_float]
         L.cvo_fe_stereo_rig_map.argtypes = [C.POINTER(StereoRig), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32)]
+        L.cvo_fe_check_depth_format.argtypes = [C.c_int, C.c_float]
+        L.cvo_fe_set_depth_format.argtypes = [vp, C.c_int, C.c_float]
+        L.cvo_fe_get_depth_format.argtypes = [vp, C.POINTER(C.c_int), fp]
+        L.cvo_fe_convert_depth.argtypes = [C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, u16p]
+        L.cvo_fe_submit_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]
+        L.cvo_fe_submit_stereo_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -601,6 +620,72 @@ def unpack_image(src, fmt, width, height, device=0, stride=None):
     return out
 
 
+def check_depth_format(fmt, unit=1.0):
+    """True for what set_depth_format() accepts (cvo_fe_check_depth_format): a DEPTH_* format, a finite unit in
+    [2^-20, 2^20], and a unit of 1 under DEPTH_U16.  Host only."""
+    return lib().cvo_fe_check_depth_format(_c_int(fmt, "check_depth_format"), float(unit)) == 0
+
+
+def convert_depth(src, fmt, width, height, unit=1.0, scale=1000.0, device=0, stride=None):
+    """The depth-format contract on any plane (cvo_fe_convert_depth: the kernel a frame runs, without a generator): `src`
+    is any array whose C-order bytes are `height` rows of `width` values of the format (uint16, float32, float16),
+    `stride` bytes apart (dense without one; the last row may end with its last value).  `scale` is the depth_scale of
+    what reads the plane.  Returns the height x width uint16 plane; the argument is left as it is."""
+    fmt, w, h = _c_int(fmt, "convert_depth"), _c_int(width, "convert_depth"), _c_int(height, "convert_depth")
+    if fmt not in _DEPTH_DTYPES:
+        raise capi.CvoHipError("convert_depth: an unknown depth format")
+    item = np.dtype(_DEPTH_DTYPES[fmt]).itemsize
+    pitch = w * item if stride is None else int(stride)
+    src = np.ascontiguousarray(src)
+    if h < 1 or w < 1 or pitch < w * item or src.nbytes < (h - 1) * pitch + w * item:
+        raise ValueError("expected %d rows of %d values of %d bytes, %d bytes apart" % (h, w, item, pitch))
+    out = np.empty((h, w), np.uint16)
+    capi.check(lib().cvo_fe_convert_depth(int(device), src.ctypes.data, pitch, w, h, fmt, float(unit), float(scale),
+                                          out.ctypes.data_as(C.POINTER(C.c_uint16))), what="convert_depth")
+    return out
+
+
+_DEVICE_TYPES = {1: ("u1",), 2: ("u2", "f2"), 4: ("f4",)}
+
+
+def device_image(obj, rows, row_bytes, itemsize, what):
+    """(pointer, pitch in bytes) of an image in device memory: `obj` is any object with `__cuda_array_interface__` (a
+    torch tensor on ROCm, a cupy array) that holds `rows` rows of `row_bytes` bytes in items of `itemsize` bytes -- shape
+    (rows, ...) with the dimensions behind the first dense, as a slice of a wider array is.  ValueError for another dtype
+    or shape, a last dimension that is not dense, a row stride below the row or not a multiple of the item size, and
+    negative strides.  It needs no device: nothing is read through the pointer."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise ValueError("%s: an object with __cuda_array_interface__ is expected (a device array)" % what)
+    typestr, shape, strides = str(cai["typestr"]), tuple(int(v) for v in cai["shape"]), cai.get("strides")
+    if typestr[:1] not in "<|" or typestr[1:] not in _DEVICE_TYPES.get(int(itemsize), ()):
+        raise ValueError("%s: dtype %s, and items of %d bytes are expected" % (what, typestr, itemsize))
+    inner = 1
+    for v in shape[1:]:
+        inner *= v
+    if len(shape) < 2 or shape[0] != rows or inner * itemsize != row_bytes:
+        raise ValueError("%s: shape %s, and %d rows of %d bytes are expected" % (what, shape, rows, row_bytes))
+    pitch = row_bytes
+    if strides is not None:
+        strides = tuple(int(v) for v in strides)
+        if len(strides) != len(shape) or any(v < 0 for v in strides):
+            raise ValueError("%s: strides %s (negative strides are not taken)" % (what, strides))
+        dense = itemsize
+        for k in range(len(shape) - 1, 0, -1):
+            if strides[k] != dense:
+                raise ValueError("%s: strides %s: every dimension behind the first must be dense" % (what, strides))
+            dense *= shape[k]
+        if rows > 1:
+            pitch = strides[0]
+        if pitch < row_bytes or pitch % itemsize != 0:
+            raise ValueError("%s: a row stride of %d bytes, below the row of %d or no multiple of the item size %d"
+                             % (what, pitch, row_bytes, itemsize))
+    ptr = cai["data"][0]
+    if not ptr:
+        raise ValueError("%s: a null device pointer" % what)
+    return int(ptr), int(pitch)
+
+
 def check_lidar(lidar):
     """True for a Lidar set_lidar() accepts on a generator without stereo and depth camera (cvo_fe_check_lidar); None is
     refused.  Host only."""
@@ -753,6 +838,8 @@ class PcdGenerator:
         self._max_disp = 0                         # of the stereo settings, if some are set
         self._pix = PIXEL_BGR8                     # the pixel format of the colour images (set_pixel_format)
         self._ishape = (self.height, self.width * 3)   # rows x row_bytes of a colour image in that format
+        self._dfmt = DEPTH_U16                     # the format of the depth images (set_depth_format)
+        self._held = None                          # the device images of a frame in flight (submit_device)
         self._pos = np.empty((self.capacity, 3), np.float32)
         self._feat = np.empty((self.capacity, 5), np.float32)
 
@@ -765,9 +852,10 @@ class PcdGenerator:
     def _images(self, bgr, depth):
         """The two images of a frame as dense arrays of the sizes the context takes."""
         bgr = self._image(bgr)
-        depth = np.ascontiguousarray(depth, np.uint16)
+        dtype = np.dtype(_DEPTH_DTYPES[self._dfmt])
+        depth = np.ascontiguousarray(depth, dtype)
         if depth.shape != self._dshape:
-            raise ValueError("expected a %dx%d uint16 depth map" % self._dshape)
+            raise ValueError("expected a %dx%d %s depth map" % (self._dshape + (dtype.name,)))
         return bgr, depth
 
     def create_pointcloud(self, bgr, depth, dataset_seq=1, feature_type=FEATURES_RGB):
@@ -777,7 +865,7 @@ class PcdGenerator:
         n = C.c_int(0)
         st = lib().cvo_fe_create_pointcloud(
             self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self._ishape[1],
-            depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2, int(dataset_seq), int(feature_type),
+            depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * depth.itemsize, int(dataset_seq), int(feature_type),
             self._pos.ctypes.data_as(C.POINTER(C.c_float)), self._feat.ctypes.data_as(C.POINTER(C.c_float)),
             self.capacity, C.byref(n))
         self._chk(st, "create_pointcloud")
@@ -787,8 +875,36 @@ class PcdGenerator:
         """First half of create_pointcloud: stage the images, enqueue everything, return."""
         bgr, depth = self._images(bgr, depth)
         self._chk(lib().cvo_fe_submit(self._h, bgr.ctypes.data_as(C.POINTER(C.c_uint8)), self._ishape[1],
-                                      depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * 2,
+                                      depth.ctypes.data_as(C.POINTER(C.c_uint16)), self._dshape[1] * depth.itemsize,
                                       int(dataset_seq), int(feature_type)), "submit")
+
+    def submit_device(self, img, depth, dataset_seq=1, feature_type=FEATURES_RGB):
+        """submit() for images that lie in device memory already (cvo_fe_submit_device; the device-input contract of
+        include/cvo_frontend.h): `img` and `depth` are any objects with `__cuda_array_interface__` -- torch tensors on
+        ROCm have it -- of the layout the host forms take: uint8 rows of the pixel format in force (h x w x 3 under BGR8),
+        and an h x w plane of the depth format's dtype of the depth camera's size.  A slice of a wider array is taken with
+        its pitch; nothing is copied to the host.  collect() / collect_device() as for any other frame.
+        Streams: the images are read by work on this generator's stream.  What wrote them must have completed -- the
+        caller synchronises the producer (torch.cuda.synchronize()) -- or the generator must have been created on the
+        producer's stream (PcdGenerator(stream=...)).  They must stay alive and unwritten until the frame is collected;
+        the generator keeps a reference until then."""
+        pi, si = device_image(img, self._ishape[0], self._ishape[1], 1, "submit_device: the colour image")
+        item = np.dtype(_DEPTH_DTYPES[self._dfmt]).itemsize
+        pd, sd = device_image(depth, self._dshape[0], self._dshape[1] * item, item, "submit_device: the depth image")
+        want = np.dtype(_DEPTH_DTYPES[self._dfmt]).str[1:]
+        if str(depth.__cuda_array_interface__["typestr"])[1:] != want:
+            raise ValueError("submit_device: the depth image: dtype %s is expected (the depth format in force)" % want)
+        self._chk(lib().cvo_fe_submit_device(self._h, pi, si, pd, sd, int(dataset_seq), int(feature_type)), "submit_device")
+        self._held = (img, depth)
+
+    def submit_stereo_device(self, left, right, dataset_seq=4, feature_type=FEATURES_RGB):
+        """submit_stereo() for a pair that lies in device memory already (cvo_fe_submit_stereo_device): two objects with
+        `__cuda_array_interface__`, uint8 rows of the pixel format in force.  Streams and lifetime as submit_device()."""
+        pl, sl = device_image(left, self._ishape[0], self._ishape[1], 1, "submit_stereo_device: the left image")
+        pr, sr = device_image(right, self._ishape[0], self._ishape[1], 1, "submit_stereo_device: the right image")
+        self._chk(lib().cvo_fe_submit_stereo_device(self._h, pl, sl, pr, sr, int(dataset_seq), int(feature_type)),
+                  "submit_stereo_device")
+        self._held = (left, right)
 
     def collect(self):
         """Second half: wait for the submitted frame and return its cloud."""
@@ -796,6 +912,7 @@ class PcdGenerator:
         self._chk(lib().cvo_fe_collect(self._h, self._pos.ctypes.data_as(C.POINTER(C.c_float)),
                                        self._feat.ctypes.data_as(C.POINTER(C.c_float)), self.capacity, C.byref(n)),
                   "collect")
+        self._held = None
         return self._pos[:n.value].copy(), self._feat[:n.value].copy()
 
     def collect_device(self):
@@ -803,17 +920,24 @@ class PcdGenerator:
         features, number of points); valid until the next submit on this object."""
         dp, df, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
         self._chk(lib().cvo_fe_collect_device(self._h, C.byref(dp), C.byref(df), C.byref(n)), "collect_device")
+        self._held = None
         return dp.value, df.value, n.value
 
     def host_buffers(self):
         """numpy views of the context's pinned staging images (h x w x 3 uint8, h x w uint16): fill
         them in place and pass them to submit() / create_pointcloud() to save a copy.  The depth view is
         of the depth camera's size while one is set and valid until the next set_depth_camera().  Under a pixel
-        format the image view is the packed image, rows x row_bytes, valid until the next set_pixel_format()."""
+        format the image view is the packed image, rows x row_bytes, valid until the next set_pixel_format().  Under a
+        float depth format the depth view is the float staging image (float32 or float16), valid until the next
+        set_depth_format() / set_depth_camera()."""
         pi, pd = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint16)()
         self._chk(lib().cvo_fe_host_buffers(self._h, C.byref(pi), C.byref(pd)), "host_buffers")
         img = np.ctypeslib.as_array(pi, shape=self._ishape if self._pix != PIXEL_BGR8 else (self.height, self.width, 3))
         dep = np.ctypeslib.as_array(pd, shape=self._dshape)
+        if self._dfmt != DEPTH_U16:   # (the same memory, seen as the format's values)
+            dtype = np.dtype(_DEPTH_DTYPES[self._dfmt])
+            raw = np.ctypeslib.as_array(C.cast(pd, C.POINTER(C.c_uint8)), shape=(self._dshape[0] * self._dshape[1] * dtype.itemsize,))
+            dep = raw.view(dtype).reshape(self._dshape)
         return img, dep
 
     def set_device_output(self, on=True):
@@ -1001,6 +1125,21 @@ class PcdGenerator:
         self._pix = fmt
         self._ishape = pixel_layout(fmt, self.width, self.height)
 
+    def set_depth_format(self, fmt, unit=1.0):
+        """The DEPTH_* format of the depth image of every following frame that has one (the depth-format contract of
+        include/cvo_frontend.h): under DEPTH_F32 / DEPTH_F16 the depth images are float32 / float16 planes in `unit`
+        metres per value (1: metres, 0.001: millimetres) and are converted on the device in front of everything else.
+        DEPTH_U16 with unit 1: a new object's.  A setting of its own: it survives every other setter."""
+        fmt = _c_int(fmt, "set_depth_format")
+        self._chk(lib().cvo_fe_set_depth_format(self._h, fmt, float(unit)), "set_depth_format")
+        self._dfmt = fmt
+
+    def depth_format(self):
+        """(format, unit) in force."""
+        fmt, unit = C.c_int(0), C.c_float(0.0)
+        self._chk(lib().cvo_fe_get_depth_format(self._h, C.byref(fmt), C.byref(unit)), "get_depth_format")
+        return int(fmt.value), float(unit.value)
+
     def pixel_format(self):
         """The pixel format in force."""
         out = C.c_int(0)
@@ -1150,8 +1289,13 @@ def load_img(rgb_path, depth_path):
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
                stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None, pixel_format=None,
-               lidar_sweep=None, lidar_motion=None, sweep_fraction=1.0):
+               lidar_sweep=None, lidar_motion=None, sweep_fraction=1.0, depth_format=None, device_input=False):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `depth_format`: a DEPTH_* format, or (format, unit), for the generator: the depth images `frames` yields are then of
+    that format; None leaves the generator as it is.
+    `device_input`: `frames` yields device arrays (objects with `__cuda_array_interface__`), which go in through
+    submit_device() / submit_stereo_device() and never touch host memory; not for LiDAR frames.  The producer of the
+    arrays must be synchronised, or the generator created on its stream (see submit_device()).
     `lidar_sweep`: a LidarSweep for the generator's scan source (motion compensation of a spinning scan); None leaves the
     generator as it is.  `lidar_motion`: where each frame's twist comes from -- None: the generator's stays as it is
     (zero after `lidar_sweep`); a callable name -> twist (w then v, per sweep), asked before the frame is submitted;
@@ -1217,11 +1361,17 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_depth_infill(depth_infill)
     if pixel_format is not None:
         gen.set_pixel_format(pixel_format)
+    if depth_format is not None:
+        gen.set_depth_format(*(depth_format if isinstance(depth_format, (tuple, list)) else (depth_format,)))
     if lidar is not None:
         gen.set_lidar(lidar)
     if lidar_sweep is not None:
         gen.set_lidar_sweep(lidar_sweep)
+    if device_input and lidar is not None:
+        raise ValueError("device_input: not for LiDAR frames (a scan is staged by the host)")
     submit = gen.submit_stereo if stereo is not None else gen.submit_lidar if lidar is not None else gen.submit
+    if device_input:
+        submit = gen.submit_stereo_device if stereo is not None else gen.submit_device
     if lidar_motion is not None:
         if lidar_motion != "constant-velocity" and not callable(lidar_motion):
             raise ValueError('lidar_motion: None, a callable name -> twist, or "constant-velocity"')

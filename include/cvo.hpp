@@ -146,6 +146,19 @@ class registration {
     // or after the first image; throws for a format the front end refuses -- one the image size does not fit included,
     // which before the first image shows when that image arrives.
     void set_pixel_format(int format);
+    // The format of the depth image of the image form of set_pcd() / run_cvo(): cvo_fe_set_depth_format
+    // (CVO_FE_DEPTH_U16 with unit 1, a new object's; CVO_FE_DEPTH_F32 / CVO_FE_DEPTH_F16: the depth image_view's data is
+    // float32 / float16 in `unit` metres per value and its step the pitch of those rows -- the depth-format contract:
+    // cvo_frontend.h).  A setting of its own, before or after the first image; throws for what the front end refuses.
+    void set_depth_format(int format, float unit = 1.0f);
+    // set_pcd() / run_cvo() and the stereo pair for images that lie in DEVICE memory already: the views' `data` is
+    // device memory of this object's device, in the layout of the host forms (the pixel and depth formats in force), and
+    // never touches host memory: cvo_fe_submit_device / cvo_fe_submit_stereo_device (the device-input contract:
+    // cvo_frontend.h).  What wrote the images must have completed before the call; they are read before it returns.
+    void set_pcd_on_device(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img);
+    void run_cvo_on_device(const int dataset_seq, const image_view &RGB_img, const image_view &dep_img);
+    void set_pcd_stereo_on_device(const int dataset_seq, const image_view &left_img, const image_view &right_img);
+    void run_cvo_stereo_on_device(const int dataset_seq, const image_view &left_img, const image_view &right_img);
     // A mask for every following frame: rows x cols bytes of the colour image's size, `step` bytes apart,
     // non-zero = no point from this pixel (cvo_fe_set_mask).  The bytes are copied.  May be called before the
     // first image: the copy is handed to the front end when it is created, and a mask of another size than that
@@ -245,6 +258,8 @@ class registration {
     float lidar_motion_[6];
     int select_mode_;                    // what set_select_mode() gave, likewise (CVO_FE_SELECT_IMAGE without a call)
     int pixel_format_;                   // what set_pixel_format() gave, likewise (CVO_FE_PIXEL_BGR8 without a call)
+    int depth_format_;                   // what set_depth_format() gave, likewise (CVO_FE_DEPTH_U16, unit 1 without a call)
+    float depth_unit_;
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();
@@ -258,9 +273,9 @@ class registration {
         int num_points;
     };
     void cloud_from_images(int dataset_seq, const image_view &rgb, const image_view &dep, bool stereo,
-                           const scan_view *scan = nullptr);
+                           const scan_view *scan = nullptr, bool on_device = false);
     void run_images(int dataset_seq, const image_view &rgb, const image_view &second, bool stereo,
-                    const scan_view *scan = nullptr);
+                    const scan_view *scan = nullptr, bool on_device = false);
 };
 
 }   // namespace cvo_hip

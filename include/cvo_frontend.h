@@ -21,8 +21,11 @@
  * (w/32)*(h/32) cells that exist (any w % 32 > 5 or h % 32 > 3, 1280x720 among them)
  * takes the last cell's threshold; the reference reads memory it never wrote.
  *
- * Every stage runs as HIP kernels on the context's stream; the images are
- * copied in, the cloud is copied out.  There is no CPU path: without a gfx950
+ * Every stage runs as HIP kernels on the context's stream.  The images come from
+ * host memory (cvo_fe_submit) or lie in device memory already (cvo_fe_submit_device),
+ * and the cloud goes to host memory (cvo_fe_collect) or stays in device memory
+ * (cvo_fe_collect_device): a frame can go from a device image to a pose without
+ * touching host memory.  There is no CPU path: without a gfx950
  * device cvo_fe_create() fails with CVO_HIP_ERR_NODEVICE.
  *
  * Beyond the reference: a caller's own camera (cvo_fe_set_camera) in place of the
@@ -59,6 +62,10 @@
  * LiDAR scan (cvo_fe_set_lidar_sweep, cvo_fe_set_lidar_motion; cvo_fe_project_points_sweep without a context): every
  * point is moved into the scanner's frame at the instant of the colour image, by its own time or azimuth and the
  * scanner's motion over the sweep, in the pass that projects it.  The sweep contract is stated at cvo_fe_lidar_sweep below.
+ * And a format for the depth image (cvo_fe_set_depth_format; cvo_fe_convert_depth for any plane): float32 or float16 in a
+ * unit the caller names, converted on the device in front of everything that reads it.  The depth-format contract is stated
+ * at CVO_FE_DEPTH_* below.  And frames whose images lie in device memory already (cvo_fe_submit_device,
+ * cvo_fe_submit_stereo_device).  The device-input contract is stated at cvo_fe_submit_device below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -183,6 +190,37 @@ enum { CVO_FE_PIXEL_BGR8 = 0,      /* a new context's: the layout cv::imread dec
        CVO_FE_PIXEL_NV12 = 7,      /* h rows of Y, then h/2 rows of U V pairs */
        CVO_FE_PIXEL_BAYER_RGGB8 = 8, CVO_FE_PIXEL_BAYER_BGGR8 = 9,
        CVO_FE_PIXEL_BAYER_GRBG8 = 10, CVO_FE_PIXEL_BAYER_GBRG8 = 11 };
+
+/* The format of the depth images a caller hands over (cvo_fe_set_depth_format), and the depth-format contract: depth
+ * that comes out of a network or a simulator is a float32 or float16 plane in metres (or another unit), not uint16.
+ *
+ * THE DEPTH-FORMAT CONTRACT.  Under CVO_FE_DEPTH_F32 or CVO_FE_DEPTH_F16 the depth image of a frame is w x h values of
+ * 4 or 2 bytes (the depth camera's size while one is set), and one kernel turns it into the uint16 image that
+ * CVO_FE_DEPTH_U16 takes as it is.  The results are defined by the arithmetic below, not by the device; it is this
+ * library's own definition.
+ * `unit` is metres per input unit: 1 for metres, 0.001 for float millimetres.  `scale` is the depth_scale of whatever
+ * reads the uploaded depth image first: the depth camera's (rig.depth_scale) while one is set, otherwise the colour
+ * camera's in force for the frame (the cvo_fe_set_camera model, else the table row of dataset_seq).
+ * For every input value, in float32, every operation rounded on its own, in this order and no other:
+ *     v = the value (a float16 is widened exactly)
+ *     no depth (0) unless v is finite and v >= 2^-126     (drops NaN, both infinities, +-0, negatives, subnormals)
+ *     t = v * unit;          no depth unless t >= 2^-126
+ *     q = rintf(t * scale)   (ties to even)
+ *     out = (1 <= q && q <= 65535) ? (uint16)q : 0        (too near and too far are no depth, never clamped)
+ * The two subnormal rules make the result independent of whether the device flushes denormals.  The order of the two
+ * multiplications is observable and part of the contract: at unit 0.001 and scale 5000 the value 2947.099853515625
+ * gives 14736, and v * (unit * scale) would give 14735.  At scale 5000 and unit 1, 0.8 gives 4000 and 0.7998 gives
+ * 3999; at scale 1024, 62.5/1024 gives 62, 63.5/1024 gives 64, 0.5/1024 gives 0, 1.5/1024 gives 2, 65534.5/1024 gives
+ * 65534 and 65535.5/1024 gives 0.
+ *
+ * Where it sits.  Under a float format one kernel runs in front of everything else that reads the depth image
+ * (rectification, the depth camera's warp, infill, median, gate); it writes where the uint16 upload lands otherwise, and
+ * no later stage changes: the frame is that of a context in CVO_FE_DEPTH_U16 fed the converted plane, and
+ * CVO_FE_STAGE_RAW_DEPTH is the converted plane.  Stereo and LiDAR frames have no depth image and do not read the
+ * format; it may be set beside them and is kept. */
+enum { CVO_FE_DEPTH_U16 = 0,       /* a new context's: uint16 in the camera's own depth units */
+       CVO_FE_DEPTH_F32 = 1,       /* float32 in `unit` metres */
+       CVO_FE_DEPTH_F16 = 2 };     /* float16 (IEEE binary16) in `unit` metres */
 
 typedef struct cvo_fe_info {
     int32_t num_selected;   /* pixels the selector kept (before the depth test), ref pcd_generator.cpp:141; under
@@ -751,7 +789,8 @@ int cvo_fe_create_pointcloud(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_str
  * over the pointer handed to cv::imdecode -- saves the copy that submit() / create_pointcloud()
  * otherwise make; pass these same pointers (and the dense strides) to them.  They may be
  * refilled once the frame has been collected.  While a depth camera is set the depth image is
- * of its size; the depth pointer is valid until the next cvo_fe_set_depth_camera(). */
+ * of its size; the depth pointer is valid until the next cvo_fe_set_depth_camera().  Under a float
+ * depth format (cvo_fe_set_depth_format) *depth points at the float staging image instead. */
 int cvo_fe_host_buffers(cvo_fe_ctx *ctx, uint8_t **img, uint16_t **depth);
 
 /* The same in two halves, for callers that have other work while the GPU is busy (the
@@ -1082,6 +1121,61 @@ int cvo_fe_get_pixel_format(const cvo_fe_ctx *ctx, int *format);
  * CVO_HIP_ERR_NODEVICE without such a device. */
 int cvo_fe_unpack_image(int device, const uint8_t *src, size_t stride_bytes, int width, int height, int format,
                         uint8_t *bgr);
+
+/* CVO_HIP_OK for what cvo_fe_set_depth_format() would accept on an idle context, CVO_HIP_ERR_INVALID otherwise: a format
+ * that is none of CVO_FE_DEPTH_*; a unit that is not finite or lies outside [2^-20, 2^20]; under CVO_FE_DEPTH_U16 a unit
+ * other than 1.  The one statement of what is accepted.  Host only; it asks for no device. */
+int cvo_fe_check_depth_format(int format, float unit);
+/* The format of the depth image of every following frame that has one (cvo_fe_submit / cvo_fe_create_pointcloud and
+ * cvo_fe_submit_device): those take the image through their `depth` pointer, cast; depth_stride is in bytes, at least
+ * the depth image's width times the bytes of a value, and a multiple of the bytes of a value.  A setting of its own: it
+ * survives every other setter, cvo_fe_set_depth_camera in either order included (the float staging follows the rig's
+ * size).  CVO_FE_DEPTH_U16 with unit 1: a new context's state; the buffers of the setting are freed and a frame launches
+ * what it launched before.  Under a float format cvo_fe_host_buffers' *depth points at the float staging image (dw*dh
+ * values of 4 or 2 bytes, valid until the next cvo_fe_set_depth_format / cvo_fe_set_depth_camera).
+ * CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame submitted and not collected; what
+ * cvo_fe_check_depth_format refuses. */
+int cvo_fe_set_depth_format(cvo_fe_ctx *ctx, int format, float unit);
+int cvo_fe_get_depth_format(const cvo_fe_ctx *ctx, int *format, float *unit);
+/* The depth-format contract on any plane by the kernel a frame runs, without a context: host arrays in and out.  `src`
+ * is height rows of width values, `stride_bytes` apart, and is not written; `out` receives width*height uint16, dense.
+ * `scale` is the contract's.  Under CVO_FE_DEPTH_U16 it is a copy on the host and no device is asked for.
+ * CVO_HIP_ERR_INVALID, before a device is asked for: a null pointer; width or height outside [1, 8192]; what
+ * cvo_fe_check_depth_format refuses; a scale that is not finite and positive; stride_bytes below the row or not a
+ * multiple of the bytes of a value.  CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_convert_depth(int device, const void *src, size_t stride_bytes, int width, int height, int format, float unit,
+                         float scale, uint16_t *out);
+
+/* FRAMES WHOSE IMAGES ARE IN DEVICE MEMORY: a decoder or a camera pipeline that delivers into device memory, a depth
+ * network in the same process.  cvo_fe_submit_device / cvo_fe_submit_stereo_device are cvo_fe_submit /
+ * cvo_fe_submit_stereo for such images and are followed by cvo_fe_collect or cvo_fe_collect_device like them.  The
+ * images have the layout of the host forms: the pixel format in force (packed rows at one pitch, NV12's chroma rows
+ * included), the depth format in force, the depth camera's size while one is set.  Host and device submits may
+ * alternate on one context, frame by frame.
+ *
+ * THE DEVICE-INPUT CONTRACT.
+ * What is accepted.  A pointer is accepted only if hipPointerGetAttributes reports device memory (hipMemoryTypeDevice)
+ *   of the context's device.  Pinned host memory, managed memory, another device's memory and pointers the runtime
+ *   does not know are refused with CVO_HIP_ERR_INVALID and a message (cvo_fe_last_error).
+ * Checks before anything is enqueued.  A stride below the row, and a depth stride or a depth pointer that is not a
+ *   multiple of the bytes of a depth value, are refused (nothing more is asked of a pointer's alignment).  If hipMemGetAddressRange answers for a pointer, an image whose last byte -- at
+ *   (rows - 1) * stride + row_bytes from its first -- lies past the end of the allocation is refused too.  The runtime's
+ *   range is the ALLOCATION's, which may be larger than the caller's array (an allocator that cuts arrays out of larger
+ *   blocks): the check catches an image that leaves the block, not one that leaves the array.
+ * Ordering.  The images are read by work enqueued on the context's stream during the call.  What wrote them must have
+ *   completed, or have been enqueued on that same stream, before the call; they must stay valid and unwritten until the
+ *   frame's collect has returned.  The library never writes them.
+ * Results.  The cloud, cvo_fe_info and every cvo_fe_read_stage plane of a device frame are, by bits, those of the same
+ *   images submitted from the host.
+ * A captured frame graph holds no pointer of the caller's: the images are brought to the buffers an upload lands in by one
+ *   pitched device-to-device copy each, in front of the frame and outside its graph (a float depth image is not copied:
+ *   the conversion kernel reads it in place), and the frame's graph is a variant without the uploads.
+ * LiDAR frames are out of scope: a scan's header and time words are packed by host code, and a device-side packer is a
+ *   piece of work of its own; cvo_fe_submit_device refuses on a context with a scan source. */
+int cvo_fe_submit_device(cvo_fe_ctx *ctx, const void *d_img, size_t img_stride, const void *d_depth,
+                         size_t depth_stride, int dataset_seq, int feature_type);
+int cvo_fe_submit_stereo_device(cvo_fe_ctx *ctx, const void *d_left, size_t left_stride, const void *d_right,
+                                size_t right_stride, int dataset_seq, int feature_type);
 
 /* CVO_HIP_OK for settings cvo_fe_set_lidar() would accept on an idle context without stereo and depth camera,
  * CVO_HIP_ERR_INVALID otherwise: NULL; max_points outside [1, 2^21]; splat outside [0, 3]; a float that is not finite;
