@@ -56,6 +56,7 @@ const OptDef kOptions[] = {
     {"engine_crowd", "CVO_HIP_ENGINE_CROWD", 2, 0.0},     {"engine_merge_max", "CVO_HIP_ENGINE_MERGE_MAX", 2, 0.0},
     {"matches_combine", nullptr, 0, 0.0},                 {"scan_chunk", nullptr, 0, 0.0},
     {"record_narrow", "CVO_HIP_NO_RECORD_NARROW", 1, 0.0}, {"list_stale_max", "CVO_HIP_LIST_STALE_MAX", 2, 0.0},
+    {"tiles_from_record", "CVO_HIP_NO_TILES_FROM_RECORD", 1, 0.0}, {"tiles_from_record_cap", nullptr, 0, 0.0},
 };
 void env_defaults(cvo_hip_ctx *ctx)
 {
@@ -110,6 +111,8 @@ int apply_option(cvo_hip_ctx *ctx, const char *key, double v)
     else if (is("scan_chunk")) { if (v < 0.0 || v > (double)SCAN_CHUNK) return CVO_HIP_ERR_INVALID; o.scan_chunk = (int)v; }
     else if (is("list_margin")) { if (v > 4.0) return CVO_HIP_ERR_INVALID; o.list_margin = v < 0.0 ? -1.0f : (float)v; }
     else if (is("record_narrow")) o.record_narrow = on;
+    else if (is("tiles_from_record")) o.tiles_from_record = on;
+    else if (is("tiles_from_record_cap")) { if (v < 0.0 || v > 1.0e9) return CVO_HIP_ERR_INVALID; o.tiles_from_record_cap = (int)v; }
     else if (is("list_stale_max")) { if (!(v >= 1.0 && v <= 64.0)) return CVO_HIP_ERR_INVALID; o.list_stale_max = (float)v; }
     else if (is("final_mirror")) o.no_final_mirror = !on;
     else if (is("twist_on_shared_gpu")) o.twist_on_shared_gpu = on;
@@ -897,6 +900,8 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     else if (is("scan_chunk")) *value = o.scan_chunk;
     else if (is("list_margin")) *value = o.list_margin;
     else if (is("record_narrow")) *value = o.record_narrow;
+    else if (is("tiles_from_record")) *value = o.tiles_from_record;
+    else if (is("tiles_from_record_cap")) *value = o.tiles_from_record_cap;
     else if (is("list_stale_max")) *value = o.list_stale_max;
     else if (is("final_mirror")) *value = !o.no_final_mirror;
     else if (is("twist_on_shared_gpu")) *value = o.twist_on_shared_gpu;
@@ -913,6 +918,7 @@ int cvo_hip_get_option(const cvo_hip_ctx *ctx, const char *key, double *value)
     // read-only counters
     else if (is("run_timeouts")) *value = (double)ctx->run_timeouts;
     else if (is("list_grows")) *value = (double)ctx->list_grows;
+    else if (is("tile_rebuilds")) *value = (double)ctx->tile_rebuilds;
     else if (is("async_builds_named")) *value = (double)ctx->async_stats[0];
     else if (is("async_stalls")) *value = (double)ctx->async_stats[1];
     else if (is("run_aborts")) *value = (double)ctx->run_aborts;

@@ -59,6 +59,21 @@ constexpr int MAX_CSEG = 32;        // column segments of a filter block (jt <= 
 
 // x = first row of the tile, y = first column | r << 30, z/w = the 64-bit mask
 typedef uint4 TileEntry;
+// The pair <-> (entry, bit) map of a tile list whose tiles begin at multiples of 16 in both clouds (k_filter: a wave's rows begin at
+// row_lo + a multiple of ROWS_PER_WAVE, a block's columns at a multiple of its chunk, itself a multiple of SEG; row_lo is 0 unless the
+// fixed cloud is sharded over ranks).  tile_pair: what expand_lists makes of bit `bit` of an entry (x, y); tile_key: the entry and the
+// bit pair (i, j) lives in -- what k_tiles_from_record rebuilds a list from.  tests/cpp/tile_key_host.cpp holds the two to each other.
+CVO_HD void tile_pair(const unsigned x, const unsigned y, const unsigned bit, unsigned &i, unsigned &j)
+{
+    i = x + (bit >> 4) * 4u + (y >> 30);
+    j = (y & 0x3fffffffu) + (bit & 15u);
+}
+CVO_HD void tile_key(const unsigned i, const unsigned j, unsigned &x, unsigned &y, unsigned &bit)
+{
+    x = i & ~15u;
+    y = (j & ~15u) | ((i & 3u) << 30);
+    bit = (((i >> 2) & 3u) << 4) | (j & 15u);
+}
 
 enum ProcMode { PROC_FLOW = 0, PROC_STEP = 1, PROC_SELF = 2 };
 // lists: three tile lists + the kept list
@@ -197,6 +212,8 @@ struct DevParams {
     float run_cand_cap;  // > 0: the plan has resident runs (kt_run) that hold this many candidates in registers
     int32_t record_narrow;   // the synchronous plan narrows the xy record when the length scale drops instead of building anew (plan_lists)
     float list_stale_max;    // ... and lets the tile list behind a narrowed record get this many times wider than a fresh one would be
+    float list_stale_engine; // > 0: this bound in its place -- the slots of an engine, whose tile list is rebuilt from its record when the
+                             // launch geometry changes (k_tiles_from_record), narrow at every drop (loop_params sets it for them alone)
     double s2_d, cs2_d, dl_step;
 };
 
@@ -236,7 +253,7 @@ struct alignas(16) DevHead {
     int32_t list_stat[3];       // since align() began: all-pairs xy builds named, narrowings named, re-expansions seen (cvo_hip_get_list_stats)
     int32_t async_stat[2];      // ... and of the asynchronous plans: xy builds plan_xy_async named, stall slots (a slot that only builds: no buffer of the
                                 // xy list or of a self list was valid) -- cvo_hip_get_option "async_builds_named", "async_stalls"
-    int32_t rec_pad_;
+    int32_t tile_rebuilds;      // ... tile lists rebuilt from their record (k_tiles_from_record; cvo_hip_get_option "tile_rebuilds")
     // Asynchronous xy builds (DevParams::async_xy): two buffers; FLOW consumes `xy_active`; the
     // k_filter blocks of the launch that READS this state build `xy_target` (-1: none) at the
     // transform recorded for it (xy_Rt / xy_t[target]); `xy_fresh`: the buffer whose build ran in
@@ -635,21 +652,37 @@ constexpr float LIST_LOOSE = 1.3f;
 // list stays the old, wide one.  The flow pass expands it again when the launch geometry changes (process_body), so it must
 // stay a superset by its own radius and pose as well, and an expansion of a bounded record keeps only d2 < rec_r^2 (the post
 // kernel then moves the record's pose to that iteration's, head_plan).  An expansion over a list many times too wide costs
-// more than a build: beyond list_stale_max x the width of a fresh list the plan builds.
+// more than a build: beyond list_stale_max x the width of a fresh list the plan builds.  (The slots of an engine have their tile list
+// rebuilt from the record when the geometry changes, k_tiles_from_record: they narrow at every drop, DevParams::list_stale_engine.)
 // (travel of y = Rt y0 + t since the pose [Rt0 | t0])
-CVO_HD float pose_travel(const DevHead *s, const float *Rt0, const float *t0, const float ymax)
+CVO_HD float pose_travel_between(const float *Rt1, const float *t1, const float *Rt0, const float *t0, const float *center, const float ymax)
 {
     float f2 = 0.0f, c2 = 0.0f;
     for (int r = 0; r < 3; ++r) {
-        float dc = s->t[r] - t0[r];
+        float dc = t1[r] - t0[r];
         for (int q = 0; q < 3; ++q) {
-            const float d = s->Rt[3 * r + q] - Rt0[3 * r + q];
+            const float d = Rt1[3 * r + q] - Rt0[3 * r + q];
             f2 += d * d;
-            dc += d * s->center[q];
+            dc += d * center[q];
         }
         c2 += dc * dc;
     }
     return sqrtf(0.5f * f2) * 1.001f * ymax + sqrtf(c2);
+}
+CVO_HD float pose_travel(const DevHead *s, const float *Rt0, const float *t0, const float ymax)
+{
+    return pose_travel_between(s->Rt, s->t, Rt0, t0, s->center, ymax);
+}
+// A tile list rebuilt from its candidate record (k_tiles_from_record) is the record's pair set.  By construction a record holds every pair
+// OF ITS TILE LIST closer than rec_r at the record's pose (a fresh record: all of the list; a bounded expansion: exactly those; a narrowing
+// from radius rr to rb over the travel tr: rb + tr <= rr).  The tile list holds every pair closer than list_r at the list's pose, so the
+// record holds EVERY pair closer than rec_r at its pose -- and may stand in for the tile list with that radius and pose -- if
+//     rec_r + (travel from the list's pose to the record's) <= list_r
+// with the rounding slack of the re-use bounds.  Where that fails (no narrowing yet: rec_r = list_r) the list stays as it is.
+CVO_HD bool record_covers_its_radius(const DevHead *s)
+{
+    const float tr = pose_travel_between(s->rec_Rt, s->rec_t, s->list_Rt, s->list_t, s->center, s->y0max);
+    return (s->rec_r + tr) * 1.0001f + reuse_slack(s->rec_t, s->center, s->xmax, s->y0max, 1.0f) <= s->list_r[LIST_XY];
 }
 // (`bulk`: where the transform records and the kernel constants are stored -- the state itself; the post
 // kernels run the plan on a private copy in registers, every lane of a wave the same, and send these few
@@ -681,7 +714,8 @@ CVO_HD void plan_lists(DevHead *s, DevHead *bulk, const bool store, const DevPar
             // a record exists: it is judged by its own radius and pose, the tile list behind it by the staleness bound
             const float tr = pose_travel(s, s->rec_Rt, s->rec_t, ymax);
             const float rr = s->rec_r;
-            keep = (r_now + tr) * 1.0001f + slack <= rr && lr <= fmaxf(p.list_stale_max, LIST_LOOSE) * (1.0f + margin) * r0;
+            const float stale = p.list_stale_engine > 0.0f ? p.list_stale_engine : p.list_stale_max;
+            keep = (r_now + tr) * 1.0001f + slack <= rr && lr <= fmaxf(stale, LIST_LOOSE) * (1.0f + margin) * r0;
             s->narrow &= REC_BOUNDED;
             if (keep && !(rr <= LIST_LOOSE * (1.0f + margin) * r0)) {   // valid, but too wide: narrow it if it has the room
                 keep = (rb + tr) * 1.0001f + slack <= rr;
@@ -1259,6 +1293,10 @@ void launch_prepare(DevState *st, const DevParams &prm, hipStream_t s, uint32_t 
 // n registrations that begin (or resume) in one table: ceil(n / MAXG) launches, a block per registration; the first block of
 // every launch sets the table's build masks
 void launch_prepare_many(const PrepareEntry *e, int n, hipStream_t s, uint32_t *build_masks);
+// The xy tile lists of the first `gz` slots of a table rebuilt from their candidate records (op[q] = the flow pass that recorded them), then
+// the slots' heads brought up to date: two launches, blockIdx.z = slot (cvo_kernels.hip kt_tiles_from_record).  slot_mask: bit z = slot z
+// takes part (the others are left as they are); cap_limit > 0: the sub-lists count as no longer than this (test switch)
+void launch_tiles_from_record(const Slot *tab, int q, unsigned gz, unsigned slot_mask, unsigned cap_limit, hipStream_t s);
 void launch_filter(const FilterArgs &a, dim3 grid, hipStream_t s, hipEvent_t ev_start = nullptr,
                    hipEvent_t ev_stop = nullptr);
 void launch_process(int mode, const ProcessArgs &a, hipStream_t s, hipEvent_t ev_start = nullptr,

@@ -104,7 +104,7 @@ struct Engine {
     struct FlowEv { hipEvent_t a, b; int live; };
     std::vector<FlowEv> flow_ev;           // engine profiling: one pair per flow-pass launch
     // diagnostics (CVO_HIP_ENGINE_DEBUG)
-    long long n_batches[5] = {}, n_replans = 0, n_inserts = 0, n_sends = 0, n_prepares = 0, n_mirrored = 0, n_copied = 0;
+    long long n_batches[5] = {}, n_replans = 0, n_inserts = 0, n_sends = 0, n_prepares = 0, n_mirrored = 0, n_copied = 0, n_rebuilds = 0;
     double t_replan = 0, t_insert = 0, t_launch = 0, t_finish = 0, t_wait = 0, t_collect = 0, t_idle_at = 0;
     static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -238,6 +238,27 @@ struct Engine {
         int zd = 1;
         while (zd < n) zd *= 2;
         if (n > 16 && n <= 24) zd = 24;   // (three engines sharing 64 registrations hold 21 or 22 each)
+        // The geometry changes: every member that stays will expand its xy tile list again (process_body: the record is of another
+        // geometry) -- behind a narrowed record that is the old, wide list.  The lists are rebuilt from the records first
+        // (kt_tiles_from_record), on this stream behind the batches already queued and in front of the new table: the table on the device
+        // is still the old geometry's, whose flow op names each slot's record, and the members sit in the slots it knows them in (a slot
+        // with recorded ops has been sent; the others began since and have nothing to rebuild).
+        if (zd != zdim && zdim > 0 && n > 0) {
+            unsigned mask = 0u, cap_limit = 0u;
+            for (int z = 0; z < std::min(zdim, (int)ENGINE_SLOTS); ++z)
+                if (member[z] && !ops[z].empty() && tiles_from_record_slot(member[z]->ctx)) {
+                    mask |= 1u << z;
+                    cap_limit = (unsigned)member[z]->ctx->opt.tiles_from_record_cap;
+                }
+            int q_flow = -1;
+            for (const TLaunch &l : plan)
+                if (l.kernel == TK_FLOW || l.kernel == TK_FLOW_D2) q_flow = l.q;
+            if (mask != 0u && q_flow >= 0) {
+                launch_tiles_from_record(tab.dev, q_flow, (unsigned)zdim, mask, cap_limit, s);
+                if (hipGetLastError() != hipSuccess) return CVO_HIP_ERR_HIP;
+                ++n_rebuilds;
+            }
+        }
         for (int z = ENGINE_SLOTS - 1, hole = 0; z >= zd; --z) {
             if (!member[z]) continue;
             while (member[hole]) ++hole;
@@ -533,13 +554,13 @@ void engine_release(Engine *e)
     std::lock_guard<std::mutex> lock(*engine_mutex());
     if (engine_debug_on())
         fprintf(stderr, "[cvo_hip] engine %p: batches at zdim 1/2/4/8/16: %lld %lld %lld %lld %lld, replans %lld, "
-                "prepare launches %lld, final states mirrored %lld copied %lld, graph captures %lld hits %lld; host ms: insert %.2f replan %.2f launch %.2f collect %.2f finish %.2f wait %.2f\n",
+                "prepare launches %lld, tile-list rebuild launches %lld, final states mirrored %lld copied %lld, graph captures %lld hits %lld; host ms: insert %.2f replan %.2f launch %.2f collect %.2f finish %.2f wait %.2f\n",
                 (void *)e, e->n_batches[0], e->n_batches[1], e->n_batches[2],
-                e->n_batches[3], e->n_batches[4], e->n_replans, e->n_prepares, e->n_mirrored, e->n_copied, e->plans.captures, e->plans.hits,
+                e->n_batches[3], e->n_batches[4], e->n_replans, e->n_prepares, e->n_rebuilds, e->n_mirrored, e->n_copied, e->plans.captures, e->plans.hits,
                 e->t_insert, e->t_replan, e->t_launch, e->t_collect, e->t_finish, e->t_wait);
     e->t_insert = e->t_replan = e->t_launch = e->t_collect = e->t_finish = e->t_wait = 0;
     for (long long &v : e->n_batches) v = 0;
-    e->n_replans = e->n_prepares = e->n_mirrored = e->n_copied = 0;
+    e->n_replans = e->n_prepares = e->n_mirrored = e->n_copied = e->n_rebuilds = 0;
     e->launched = e->checked = 0;
     e->in_use = false;
 }

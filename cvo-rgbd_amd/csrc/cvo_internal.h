@@ -278,6 +278,10 @@ struct CtxOptions {
     float list_margin = -1.0f;        // "list_margin": width of the tile lists (< 0: by the clouds)
     bool record_narrow = true;        // "record_narrow" = 0: a record too wide for the length scale is thrown away with its tile list (cvo_device.h plan_lists)
     float list_stale_max = 3.0f;      // "list_stale_max": how many times wider than a fresh one the tile list behind a narrowed record may get
+    bool tiles_from_record = true;    // "tiles_from_record" = 0: an engine's slots keep their tile list across a change of launch geometry and plan by
+                                      // list_stale_max like everybody else (1: the list is rebuilt from the record and they narrow at every drop)
+    int tiles_from_record_cap = 0;    // "tiles_from_record_cap" (test switch): a rebuild takes the sub-lists for this many entries long (0: as they are),
+                                      // so that it overflows: the list is void, the loop parks, the host grows the list, an all-pairs build follows
     int run_cand = 0;                 // "run_candidates_max" (0: what the runs hold)
     double mailbox_timeout_s = 5.0;   // "mailbox_timeout_s": read by the next cvo_hip_mailbox_connect
     double run_timeout_ms = 0.0;      // "run_timeout_ms": a resident run's exchange gives up after this long (0: 1 s)
@@ -296,6 +300,7 @@ struct cvo_hip_ctx {
     long long engine_final_copied = 0;   // state in stream order ("engine_final_mirrored", "engine_final_copied")
     long long run_aborts = 0;            // resident runs of this context that gave up at their entry hand-shake ("run_aborts")
     int list_stats[3] = {0, 0, 0};       // the last registration's all-pairs xy builds, narrowings, re-expansions (cvo_hip_get_list_stats)
+    int tile_rebuilds = 0;               // ... its tile lists rebuilt from their record (cvo_hip_get_option "tile_rebuilds")
     int async_stats[2] = {0, 0};         // ... and the asynchronous plans' xy builds named and stall slots (cvo_hip_get_option "async_builds_named", "async_stalls")
     long long list_grows = 0;            // tile / kept lists of this context grown after a pass overflowed one (cvo_hip_get_option "list_grows")
     long long run_timeouts = 0;          // resident runs of this context that gave up on an exchange (cvo_hip_get_option "run_timeouts")
@@ -462,6 +467,7 @@ int mailboxes_usable(cvo_hip_ctx *ctx);
 bool host_reduce(const cvo_hip_ctx *ctx);
 bool multi_rank(const cvo_hip_ctx *ctx);
 DevParams loop_params(const cvo_hip_ctx *ctx);
+bool tiles_from_record_slot(const cvo_hip_ctx *ctx);
 hipStream_t loop_stream(const cvo_hip_ctx *ctx);
 int enqueue_filter(cvo_hip_ctx *ctx, int list, const Cloud &ca, int row_lo, int row_hi, int tf_a, const Cloud &cb, int tf_b, int check_done);
 int kept_format(const cvo_hip_ctx *ctx, unsigned *ebase);

@@ -264,6 +264,7 @@ int job_finish(AlignJob &j)
         return fail(ctx, CVO_HIP_ERR_INVALID, "align loop ended without a verdict");
     const int executed = f.n_exec;
     for (int q = 0; q < 3; ++q) ctx->list_stats[q] = f.list_stat[q];
+    ctx->tile_rebuilds = f.tile_rebuilds;
     for (int q = 0; q < 2; ++q) ctx->async_stats[q] = f.async_stat[q];
     if (j.trace_cap > 0 && executed > 0)
         HIP_TRY(ctx, hipMemcpy(j.trace, ctx->trace_dev,

@@ -991,12 +991,12 @@ __device__ __forceinline__ bool expand_lists(const ProcessArgs &a, const ProcHea
                 const unsigned long long m =
                     (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)mine.z, k) |
                     ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)mine.w, k) << 32);
-                const unsigned r = ty >> 30, tcol = ty & 0x3fffffffu;
                 if (__builtin_amdgcn_inverse_ballot_w64(m)) {   // the mask IS the set of lanes that act: no per-lane test
                     const unsigned below = __builtin_amdgcn_mbcnt_hi(
                         (unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                    pairq[qn + below] =
-                        make_uint2(tx + (unsigned)(lane >> 4) * 4u + r, tcol + (unsigned)(lane & 15));
+                    unsigned pi, pj;
+                    tile_pair(tx, ty, (unsigned)lane, pi, pj);   // (cvo_device.h: the map k_tiles_from_record inverts)
+                    pairq[qn + below] = make_uint2(pi, pj);
                 }
                 qn += __popcll(m);
                 if (qn >= 64) {
@@ -2415,6 +2415,145 @@ __global__ void __launch_bounds__(BLOCK) kt_post_step(const Slot *__restrict__ t
     CVO_SLOT(tab);
     const PostStepArgs a = CVO_ARG(PostStepArgs, op[q].ps);
     post_step_body(a);
+}
+
+// ---------------------------------------------------------------------------
+// The xy tile list of a slot rebuilt from its candidate record (engines, in front of a change of launch geometry: cvo_engine.cpp
+// Engine::replan).  The flow pass of the new geometry expands the tile list again; behind a narrowed record that list is the old, wide
+// one -- up to 25 x the pairs the record holds.  The record IS the pair set a list of its radius needs (record_covers_its_radius), so the
+// list is written anew from it: candidate (i | j << 16, ck) sets bit tile_key(i, j) of its entry, the maximal runs of adjacent candidates
+// with one entry in a wave's slice become one TileEntry each (a segmented OR over the wave; the last run of a round is carried into the
+// next).  A recording wave met its pairs entry by entry but evaluated them in batches of 64 taken from the END of its queue, so the
+// candidates of one entry may lie in two or three runs: they come back as that many entries with disjoint masks, the same pairs.
+// Layout, fixed by the geometry alone (no atomics, no order among blocks): wave w of block b owns destination sub-list d = 4 b + w and
+// walks, in order, the slices of the recording waves that read sub-list d -- with nblk >= NSUB recording blocks d, d + NSUB, ..., four
+// waves each; with fewer, block d % nblk took sub-lists d % nblk, d % nblk + nblk, ... through its four waves, and its waves
+// d / nblk, d / nblk + NSUB / nblk, ... go to d.  Either way d = the recording block's index mod 8: the XCD class of k_filter's dealing.
+// The kernel reads the record and the head and writes the list and its counters, in place; the head is brought up to date by the launch
+// behind it (kt_tiles_from_record_head), so that every block of this one decides by the same words.
+// (slot_mask: the slots of the table whose registration is still its engine's member; cap_limit: the test switch "tiles_from_record_cap" --
+// the sub-lists count as no longer than this, so that the overflow path runs; else UINT_MAX)
+__device__ __forceinline__ bool tiles_from_record_wanted(const ProcessArgs &a, const DevState *st)
+{
+    if (!a.cand || !a.cand_cnt || a.async_xy || a.list != LIST_XY || a.kept_packed != 1 || a.weight != 0 || a.kept_wcap == 0u) return false;
+    if (st->done != RUNNING || !st->list_ok[LIST_XY]) return false;
+    const int ck = st->ck_nblk[LIST_XY];
+    if (ck == 0 || ck != a.nblk || ck < 64 || ck > PROC_BLOCKS || (ck & (ck - 1)) != 0) return false;   // (the record is of the geometry the table holds)
+    unsigned ovf = 0u;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) ovf |= st->ovf[0][l];
+    if (ovf != 0u) return false;   // (the loop is about to park: the host needs the lists as they are)
+    return record_covers_its_radius(st);
+}
+
+__global__ void __launch_bounds__(BLOCK) kt_tiles_from_record(const Slot *__restrict__ tab, const int q, const unsigned slot_mask, const unsigned cap_limit)
+{
+    if (((slot_mask >> blockIdx.z) & 1u) == 0u) return;
+    CVO_SLOT(tab);
+    const ProcessArgs &a = CVO_ARG(ProcessArgs, op[q].p);
+    DevState *st = a.st;
+    if (!tiles_from_record_wanted(a, st)) return;
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned d = blockIdx.x * 4u + (unsigned)wid;   // destination sub-list (the launch has NSUB / 4 blocks per slot)
+    if (d >= (unsigned)NSUB) return;
+    const unsigned nblk = (unsigned)a.nblk, wcap = a.kept_wcap, subcap = min(a.subcap, cap_limit);
+    const unsigned nsrc = nblk / (NSUB / 4);   // slices per destination: 4 nblk recording waves over NSUB sub-lists
+    TileEntry *out_tl = const_cast<TileEntry *>(a.tiles) + (size_t)d * subcap;
+    unsigned out = 0;                                  // wave-uniform: entries of the destination so far (may pass subcap: nothing is written there)
+    unsigned cx = 0u, cy = 0u;                         // the run carried from the last round: its entry ...
+    unsigned long long cm = 0ull;                      // ... and its mask so far (0: none)
+    for (unsigned k = 0; k < nsrc; ++k) {
+        const unsigned slice = nblk >= (unsigned)NSUB ? (d + (unsigned)NSUB * (k >> 2)) * 4u + (k & 3u)
+                                                      : (d % nblk) * 4u + d / nblk + ((unsigned)NSUB / nblk) * k;
+        unsigned n = a.cand_cnt[slice];
+        if (n > wcap) n = wcap;
+        const uint2 *src = a.cand + (size_t)slice * wcap;
+        for (unsigned b0 = 0; b0 < n; b0 += 64u) {
+            const bool live = b0 + (unsigned)lane < n;
+            const unsigned last = min(n - b0, 64u) - 1u;   // the round's last live lane
+            unsigned x = 0xffffffffu - (unsigned)lane, y = 0u, bit = 0u;   // (a dead lane: a run of its own)
+            if (live) {
+                const uint2 e = src[b0 + (unsigned)lane];
+                tile_key(e.x & 0xffffu, e.x >> 16, x, y, bit);
+            }
+            unsigned long long m = live ? 1ull << bit : 0ull;
+            const unsigned x_dn = (unsigned)__shfl_up((int)x, 1, 64), y_dn = (unsigned)__shfl_up((int)y, 1, 64);
+            const unsigned x_up = (unsigned)__shfl_down((int)x, 1, 64), y_up = (unsigned)__shfl_down((int)y, 1, 64);
+            int head = (lane == 0 || x_dn != x || y_dn != y) ? 1 : 0;
+            const bool tail = lane == 63 || x_up != x || y_up != y;
+            const unsigned long long heads = __ballot(head != 0);
+            const bool first_run = (heads & ((2ull << lane) - 1ull)) == 1ull;   // no run begins in lanes 1 .. lane
+            // segmented inclusive OR over the wave (the scan of cvo_matches.hip)
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const unsigned lo = (unsigned)__shfl_up((int)(unsigned)m, s, 64), hi = (unsigned)__shfl_up((int)(unsigned)(m >> 32), s, 64);
+                const int head_o = __shfl_up(head, s, 64);
+                if (lane >= s) {
+                    if (!head) m |= ((unsigned long long)hi << 32) | lo;
+                    head |= head_o;
+                }
+            }
+            // the carried run: continued by the round's first run, or an entry of its own in front of the round's
+            const unsigned x0 = (unsigned)__builtin_amdgcn_readfirstlane((int)x), y0 = (unsigned)__builtin_amdgcn_readfirstlane((int)y);
+            const bool joins = cm != 0ull && x0 == cx && y0 == cy;
+            if (joins && first_run) m |= cm;
+            if (cm != 0ull && !joins) {
+                if (lane == 0 && out < subcap) out_tl[out] = make_uint4(cx, cy, (unsigned)cm, (unsigned)(cm >> 32));
+                out += 1u;
+            }
+            // every run that ends in front of the round's last live lane is an entry; the run of that lane is carried on
+            const bool emit = live && tail && (unsigned)lane < last;
+            const unsigned long long em = __ballot(emit);
+            if (emit) {
+                const unsigned pos = out + __builtin_amdgcn_mbcnt_hi((unsigned)(em >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)em, 0u));
+                if (pos < subcap) out_tl[pos] = make_uint4(x, y, (unsigned)m, (unsigned)(m >> 32));
+            }
+            out += (unsigned)__popcll(em);
+            cx = (unsigned)__builtin_amdgcn_readlane((int)x, (int)last);
+            cy = (unsigned)__builtin_amdgcn_readlane((int)y, (int)last);
+            cm = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)m, (int)last) |
+                 ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(m >> 32), (int)last) << 32);
+        }
+    }
+    if (cm != 0ull) {
+        if (lane == 0 && out < subcap) out_tl[out] = make_uint4(cx, cy, (unsigned)cm, (unsigned)(cm >> 32));
+        out += 1u;
+    }
+    if (lane == 0) st->sub[LIST_XY][d] = out;   // (what the sub-list wanted, as k_filter leaves it: past subcap = it overflowed)
+}
+
+// ... and the slot's head: the rebuilt list is the record's pair set, so its radius and pose are the record's (the record's own stay).
+// A destination that wanted more than subcap entries: the list is void, and the overflow flag goes up as it does behind a build that
+// did not fit -- the plan of the iteration that begins was made with the list in place, so that iteration parks, the host grows the list
+// and the registration resumes with an all-pairs build.  One block per slot.
+__global__ void __launch_bounds__(BLOCK) kt_tiles_from_record_head(const Slot *__restrict__ tab, const int q, const unsigned slot_mask, const unsigned cap_limit)
+{
+    if (((slot_mask >> blockIdx.z) & 1u) == 0u) return;
+    CVO_SLOT(tab);
+    const ProcessArgs &a = CVO_ARG(ProcessArgs, op[q].p);
+    DevState *st = a.st;
+    if (!tiles_from_record_wanted(a, st)) return;
+    static_assert(BLOCK == NSUB, "a thread per sub-list");
+    const int over = __syncthreads_or(st->sub[LIST_XY][threadIdx.x] > min(a.subcap, cap_limit) ? 1 : 0);
+    if (threadIdx.x != 0) return;
+    if (over) {
+        st->list_ok[LIST_XY] = 0;
+        st->ck_nblk[LIST_XY] = 0;
+        st->ovf[0][LIST_XY] = 1u;
+        return;
+    }
+    st->list_r[LIST_XY] = st->rec_r;
+    for (int k = 0; k < 9; ++k) st->list_Rt[k] = st->rec_Rt[k];
+    for (int k = 0; k < 3; ++k) st->list_t[k] = st->rec_t[k];
+    st->tile_rebuilds += 1;
+}
+
+void launch_tiles_from_record(const Slot *tab, int q, unsigned gz, unsigned slot_mask, unsigned cap_limit, hipStream_t s)
+{
+    if (cap_limit == 0u) cap_limit = 0xffffffffu;
+    hipLaunchKernelGGL(kt_tiles_from_record, dim3(NSUB / 4, 1, gz), dim3(BLOCK), 0, s, tab, q, slot_mask, cap_limit);
+    hipLaunchKernelGGL(kt_tiles_from_record_head, dim3(1, 1, gz), dim3(BLOCK), 0, s, tab, q, slot_mask, cap_limit);
 }
 
 // The merged launches of a registration with its launches to itself (asynchronous list builds,

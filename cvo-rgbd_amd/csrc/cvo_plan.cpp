@@ -461,6 +461,15 @@ int drain_events(cvo_hip_ctx *ctx, int n_exec, const DevState *fin)
 bool host_reduce(const cvo_hip_ctx *ctx) { return !ctx->comm_table && (ctx->comm || ctx->user_allreduce); }
 bool multi_rank(const cvo_hip_ctx *ctx) { return ctx->comm_table || ctx->comm || ctx->user_allreduce; }
 
+// An engine's slot whose xy tile list Engine::replan rebuilds from its candidate record when the launch geometry changes
+// (kt_tiles_from_record): the synchronous list of a single rank, clouds that keep 8-byte records.  Such a slot narrows at every drop
+// of the length scale (DevParams::list_stale_engine): the wide list behind its record does not outlive the geometry it was built in.
+bool tiles_from_record_slot(const cvo_hip_ctx *ctx)
+{
+    return ctx->opt.tiles_from_record && ctx->opt.record_narrow && !ctx->lone && !ctx->use_async && !multi_rank(ctx) && !ctx->opt.no_cand &&
+           !(ctx->prm.color_scale > 0.0f) && ctx->fixed.np <= 65536 && ctx->moving.np <= 65536;
+}
+
 // the parameter block of the kernels of align(): the context's, plus the mode of this run
 DevParams loop_params(const cvo_hip_ctx *ctx)
 {
@@ -492,6 +501,7 @@ DevParams loop_params(const cvo_hip_ctx *ctx)
     // (narrowing: the synchronous xy plan -- engines, large and sharded registrations; cvo_device.h plan_lists)
     dp.record_narrow = ctx->opt.record_narrow ? 1 : 0;
     dp.list_stale_max = ctx->opt.list_stale_max;
+    dp.list_stale_engine = tiles_from_record_slot(ctx) ? 1.0e6f : 0.0f;   // (any width: every drop narrows)
     return dp;
 }
 

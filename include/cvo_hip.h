@@ -578,8 +578,10 @@ int cvo_hip_set_graph_capture(cvo_hip_ctx *ctx, int enable);
  *   "async_builds_named", "async_stalls"   read-only, of the context's last registration: the builds of the xy list the asynchronous
  *                        plan named and the slots that only built (no valid buffer), counted on the device since the registration began --
  *                        what cvo_hip_get_list_stats counts for the synchronous plan
+ *   "tile_rebuilds"      read-only, of the context's last registration: how many times its xy tile list was rebuilt from its candidate
+ *                        record while it was a member of a cvo_hip_align_many engine ("tiles_from_record"), counted on the device
  * and the test switches of tests/ ("head_mode", "merged_launches", "async_builds", "candidate_records", "kept_pack",
- * "list_init", "list_margin", "record_narrow", "list_stale_max", "final_mirror", "one_launch_hand_over", "small_calls_alone", "fused_groups", "engines",
+ * "list_init", "list_margin", "record_narrow", "list_stale_max", "tiles_from_record", "tiles_from_record_cap", "final_mirror", "one_launch_hand_over", "small_calls_alone", "fused_groups", "engines",
  * "run_candidates_max", "run_fault", "sync_upload", "no_graph", "twist_on_shared_gpu", "comm_debug", "engine_debug"; the
  * measured probes "engine_crowd", "engine_merge_max", "narrow_merge", "narrow_blocks", all off: profiles/r06_ab.txt 16).
  * The environment variables of the same switches only set the DEFAULTS, read once when a context is
