@@ -1,5 +1,6 @@
 // cvo_class.cpp -- C++ registration objects over the C-ABI (see include/cvo.hpp).
 #include "cvo.hpp"
+#include "cvo_fe_rules.h"
 
 #include <cmath>
 #include <cstring>
@@ -186,11 +187,19 @@ void registration::store(int (*set)(cvo_fe_ctx *, const S *), const char *what, 
 
 // (Without a front end yet, the host-only checks below refuse what its setters refuse: the answer does not wait
 // for the first image.)
+// "set_x(): " in front of the sentence the setter puts "set_x: " in front of (cvo_fe_rules.h)
+namespace rules = cvo_fe_rules;
+
+static std::runtime_error refused(const char *name, const char *rule)
+{
+    return std::runtime_error(std::string(name) + "(): " + rule);
+}
+
 void registration::set_camera(const cvo_fe_camera_model &model)
 {
     int32_t qu = 0, qv = 0;
     if (cvo_fe_rectify_map(&model, 1, 1, &qu, &qv) != CVO_HIP_OK)
-        throw std::runtime_error("set_camera(): members must be finite and fx, fy, depth_scale positive");
+        throw refused("set_camera", rules::camera);
     if (!fe_ && have_stereo_rig_) throw std::runtime_error("set_camera(): a stereo rig is set: clear the rig first");
     store<cvo_fe_camera_model>(cvo_fe_set_camera, "cvo_fe_set_camera", &model, camera_, have_camera_);
 }
@@ -203,8 +212,7 @@ void registration::clear_camera()
 void registration::set_depth_camera(const cvo_fe_depth_camera &rig)
 {
     if (!fe_ && cvo_fe_check_depth_camera(&rig) != CVO_HIP_OK)
-        throw std::runtime_error("set_depth_camera(): size in [8, 8192], finite members, fx, fy, depth_scale "
-                                 "positive, max_range above min_range, R a rotation");
+        throw refused("set_depth_camera", rules::depth_camera);
     if (!fe_ && have_lidar_) throw std::runtime_error("set_depth_camera(): a scan source is set");
     store<cvo_fe_depth_camera>(cvo_fe_set_depth_camera, "cvo_fe_set_depth_camera", &rig, depth_camera_, have_depth_camera_);
 }
@@ -217,8 +225,7 @@ void registration::clear_depth_camera()
 void registration::set_depth_gate(const cvo_fe_depth_gate &gate)
 {
     if (!fe_ && cvo_fe_check_depth_gate(&gate) != CVO_HIP_OK)
-        throw std::runtime_error("set_depth_gate(): finite members, jump_rel >= 0, max_range above min_range, "
-                                 "grow in [0, 3], hole_border 0 or 1, pad_ 0");
+        throw refused("set_depth_gate", rules::depth_gate);
     store<cvo_fe_depth_gate>(cvo_fe_set_depth_gate, "cvo_fe_set_depth_gate", &gate, depth_gate_, have_depth_gate_);
 }
 
@@ -230,7 +237,7 @@ void registration::clear_depth_gate()
 void registration::set_depth_median(const cvo_fe_depth_median &median)
 {
     if (!fe_ && cvo_fe_check_depth_median(&median) != CVO_HIP_OK)
-        throw std::runtime_error("set_depth_median(): radius 1 or 2, fill_min in [0, (2*radius+1)^2 - 1], pad_ 0");
+        throw refused("set_depth_median", rules::depth_median);
     store<cvo_fe_depth_median>(cvo_fe_set_depth_median, "cvo_fe_set_depth_median", &median, depth_median_, have_depth_median_);
 }
 
@@ -242,7 +249,7 @@ void registration::clear_depth_median()
 void registration::set_depth_infill(const cvo_fe_depth_infill &infill)
 {
     if (!fe_ && cvo_fe_check_depth_infill(&infill) != CVO_HIP_OK)
-        throw std::runtime_error("set_depth_infill(): gap_x in [0, 15], gap_y in [0, 31], jump_rel finite and >= 0, pad_ 0");
+        throw refused("set_depth_infill", rules::depth_infill);
     store<cvo_fe_depth_infill>(cvo_fe_set_depth_infill, "cvo_fe_set_depth_infill", &infill, depth_infill_, have_depth_infill_);
 }
 
@@ -254,8 +261,7 @@ void registration::clear_depth_infill()
 void registration::set_lidar(const cvo_fe_lidar &lidar)
 {
     if (!fe_ && cvo_fe_check_lidar(&lidar) != CVO_HIP_OK)
-        throw std::runtime_error("set_lidar(): max_points in [1, 2^21], splat in [0, 3], finite members, occl_rel >= 0, "
-                                 "occl_rx and occl_ry in [0, 7], max_range above min_range, R a rotation, pad_ 0");
+        throw refused("set_lidar", rules::lidar);
     if (!fe_ && (have_stereo_ || have_depth_camera_))
         throw std::runtime_error("set_lidar(): stereo or a depth camera is set");
     store<cvo_fe_lidar>(cvo_fe_set_lidar, "cvo_fe_set_lidar", &lidar, lidar_, have_lidar_);
@@ -297,7 +303,7 @@ void registration::set_lidar_motion(const float twist[6])
     // (NaN fails both comparisons)
     if (!(w2 <= (double)CVO_FE_SWEEP_MAX_ROTATION * CVO_FE_SWEEP_MAX_ROTATION) ||
         !(v2 <= (double)CVO_FE_SWEEP_MAX_TRANSLATION * CVO_FE_SWEEP_MAX_TRANSLATION))
-        throw std::runtime_error("set_lidar_motion(): finite members, |w| <= 1 radian and |v| <= 64 metres per sweep");
+        throw refused("set_lidar_motion", rules::lidar_motion);
     if (fe_) fe_check(cvo_fe_set_lidar_motion(fe_, twist), "cvo_fe_set_lidar_motion");
     for (int k = 0; k < 6; ++k) lidar_motion_[k] = twist[k];
 }
@@ -305,7 +311,7 @@ void registration::set_lidar_motion(const float twist[6])
 void registration::set_select_mode(int mode)
 {
     if (!fe_ && cvo_fe_check_select_mode(mode) != CVO_HIP_OK)
-        throw std::runtime_error("set_select_mode(): CVO_FE_SELECT_IMAGE or CVO_FE_SELECT_DEPTH");
+        throw refused("set_select_mode", rules::select_mode);
     if (fe_) fe_check(cvo_fe_set_select_mode(fe_, mode), "cvo_fe_set_select_mode");
     select_mode_ = mode;
 }
@@ -333,8 +339,7 @@ void registration::set_depth_format(int format, float unit)
 void registration::set_stereo(const cvo_fe_stereo &stereo)
 {
     if (!fe_ && cvo_fe_check_stereo(&stereo) != CVO_HIP_OK)
-        throw std::runtime_error("set_stereo(): baseline positive and finite, max_disp a multiple of 8 in [8, 128], "
-                                 "min_disp >= 1, 1 <= p1 <= p2 <= 255, uniqueness in [0, 99], lr_max in [-1, 8], pad_ 0");
+        throw refused("set_stereo", rules::stereo);
     if (!fe_ && have_lidar_) throw std::runtime_error("set_stereo(): a scan source is set");
     store<cvo_fe_stereo>(cvo_fe_set_stereo, "cvo_fe_set_stereo", &stereo, stereo_, have_stereo_);
 }
@@ -348,7 +353,7 @@ void registration::clear_stereo()
 void registration::set_stereo_paths(unsigned mask)
 {
     if (!fe_ && cvo_fe_check_stereo_paths(mask) != CVO_HIP_OK)
-        throw std::runtime_error("set_stereo_paths(): a non-empty subset of the eight bits, 1 <= mask <= 0xFF");
+        throw refused("set_stereo_paths", rules::stereo_paths);
     if (fe_) fe_check(cvo_fe_set_stereo_paths(fe_, mask), "cvo_fe_set_stereo_paths");
     stereo_paths_ = mask;
 }
@@ -356,7 +361,7 @@ void registration::set_stereo_paths(unsigned mask)
 void registration::set_stereo_speckle(const cvo_fe_speckle &speckle)
 {
     if (!fe_ && cvo_fe_check_speckle(&speckle) != CVO_HIP_OK)
-        throw std::runtime_error("set_stereo_speckle(): max_size in [1, 2^26], max_diff in [0, 65535]");
+        throw refused("set_stereo_speckle", rules::stereo_speckle);
     store<cvo_fe_speckle>(cvo_fe_set_stereo_speckle, "cvo_fe_set_stereo_speckle", &speckle, stereo_speckle_, have_stereo_speckle_);
 }
 
@@ -368,8 +373,7 @@ void registration::clear_stereo_speckle()
 void registration::set_stereo_rig(const cvo_fe_stereo_rig &rig)
 {
     if (!fe_ && cvo_fe_check_stereo_rig(&rig) != CVO_HIP_OK)
-        throw std::runtime_error("set_stereo_rig(): finite members, every fx, fy, depth_scale and baseline positive, "
-                                 "R_left and R_right rotations");
+        throw refused("set_stereo_rig", rules::stereo_rig);
     if (!fe_ && (!have_stereo_ || have_camera_))
         throw std::runtime_error("set_stereo_rig(): after set_stereo(), and without a camera model");
     store<cvo_fe_stereo_rig>(cvo_fe_set_stereo_rig, "cvo_fe_set_stereo_rig", &rig, stereo_rig_, have_stereo_rig_);

@@ -8,18 +8,20 @@
 //
 // What each kernel restates is cited at the kernel.  The arithmetic contract of the
 // library holds here too (-ffp-contract=off, correctly rounded sqrt / divide).
+//
+// This file holds every kernel and everything that launches one: a frame's sequence, submit and collect, the stage
+// reader, the stand-alone projection, and the context's creation and end.  The context itself is cvo_fe_ctx.h's, the
+// settings are cvo_fe_settings.cpp's and the host-only calibration helpers cvo_fe_calib.cpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <memory>
 #include <new>
-#include <string>
 #include <vector>
 
-#include "cvo_frontend.h"
+#include "cvo_fe_ctx.h"
+#include "cvo_fe_rules.h"
 #include "cvo_infill.h"
 #include "cvo_lidar.h"
 #include "cvo_lock.h"
@@ -27,35 +29,17 @@
 #include "cvo_speckle.h"
 #include "cvo_stereo.h"
 #include "cvo_unpack.h"
-#include "cvo_depthfmt.h"
 #include "cvo_input.h"
+
+using namespace cvo_fe;
+using cvo_fe_rules::lidar_ok;
+using cvo_fe_rules::sweep_ok;
+using cvo_fe_rules::twist_ok;
 
 namespace {
 
-constexpr int FE_LEVELS = 3;
 constexpr int FE_BLOCK = 256;
 constexpr int FE_CHUNK = 4 * FE_BLOCK;   // pixels per block of the ordered (scan) kernels
-
-// device-resident control words of one frame
-struct FeCtrl {
-    int n[2][3];        // pixels chosen at level 0 / 1 / 2 by selection pass 0 / 1
-    int pot[2];         // potential of pass 0 / 1
-    int redo;           // pass 1 runs
-    int do_sub;         // the map is sub-sampled
-    int char_th;        // ... with this threshold on the random bytes
-    int num_have;       // pixels chosen by the pass that counts
-    int in_map;         // pixels in the map when the cloud was emitted
-    int pad2_[2];
-    int num_points;     // selected pixels with depth
-    int changed;        // hysteresis sweep flag
-    int pad_;
-};
-
-struct FeDims {
-    int w, h;
-    int wl[FE_LEVELS], hl[FE_LEVELS];
-    int w32, h32;
-};
 
 __device__ __forceinline__ int wave_sum(int v)
 {
@@ -357,7 +341,7 @@ __global__ void __launch_bounds__(FE_BLOCK) k_fe_depth_final(uint32_t *z, int np
 // dword.  A group of four that is cut by the right border, or whose first pixel is no multiple of four in
 // the plane (a width that is none), goes pixel by pixel.
 constexpr int FG_TW = 64, FG_TH = 16;            // the tile; FG_TW / 4 * FG_TH == FE_BLOCK
-constexpr int FG_HALO = 4;                       // the largest grow + 1
+constexpr int FG_HALO = FE_GATE_MAX_GROW + 1;    // the largest grow + 1
 constexpr int FG_UW = FG_TW + 2 * FG_HALO, FG_UH = FG_TH + 2 * FG_HALO;               // 72 x 24 cells of U
 constexpr int FG_JW = FG_TW + 2 * (FG_HALO - 1), FG_JH = FG_TH + 2 * (FG_HALO - 1);   // 70 x 22 cells of J
 constexpr int FG_JS = 72;                        // ... in rows of this many bytes
@@ -1054,428 +1038,32 @@ const float kCameras[6][5] = {{1000.0f, 616.368f, 616.745f, 319.935f, 243.639f},
                               {2000.0f, 718.856f, 718.856f, 607.1928f, 185.2157f},  // kitti 15 :271-277
                               {2000.0f, 707.0912f, 707.0912f, 601.8873f, 183.1104f}};   // kitti 05 :279-285
 
-}   // namespace
-
-struct FeGraph {
-    uint64_t key = 0;
-    uint64_t cam_gen = 0;   // the context's camera generation the graph was captured at
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-};
-
-// A buffer and its release.  Every buffer of the context is held by one of these, and so is every buffer a
-// setter builds: whatever is not handed on frees itself.  Launch sites take the raw pointer (get()).
-struct DevFree { void operator()(void *p) const { (void)hipFree(p); } };
-struct PinFree { void operator()(void *p) const { (void)hipHostFree(p); } };
-template <class T> using Dev = std::unique_ptr<T, DevFree>;   // device memory
-template <class T> using Pin = std::unique_ptr<T, PinFree>;   // pinned host memory
-
-struct cvo_fe_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    FeDims d{};
-    int np = 0, nblk = 0, nchunks = 0;
-    int num_want = 3000;
-    int cap = 0;
-    // device
-    Dev<uint8_t> img, gray, pattern, tmp8, st8, edges;
-    Dev<uint16_t> depth;
-    Dev<uint32_t> hsv;
-    Dev<float> I[FE_LEVELS], ag[FE_LEVELS], dx0, dy0, map;
-    Dev<float> ths, ths_s, pos, feat;
-    Dev<int> sdiv, hdiv, cnt, mag, blk_cnt;
-    Dev<short2> grad;
-    Dev<FeCtrl> ctrl;
-    // pinned host
-    Pin<uint8_t> h_img;
-    Pin<uint16_t> h_depth;
-    Pin<FeCtrl> h_ctrl;
-    Pin<float> h_pos, h_feat;
-    cvo_fe_info info{};
-    std::vector<FeGraph> graphs;   // one frame's device work, captured per (camera, features, ...)
-    int copied = 0;            // points of the cloud already on their way to h_pos / h_feat
-    bool pending = false;      // a frame was submitted and not collected yet
-    bool device_output = false;   // collect_device() will be used: no copy of the cloud to the host
-    int p_seq = 0, p_ftype = 0;
-    // the caller's camera (cvo_fe_set_camera); without one the table row of dataset_seq
-    cvo_fe_camera_model cam{};
-    bool custom = false;
-    bool rectify = false;      // ... and its dist is not all zero: frames start with k_fe_rectify
-    uint64_t cam_gen = 0;      // counts the changes of camera: part of a captured graph's key
-    // with the first distorting model: the upload targets of such frames and the map (qu, then qv)
-    Dev<uint8_t> raw_img;
-    Dev<uint16_t> raw_depth;
-    Dev<int32_t> rect_map;     // 2 planes of rect_plane(np) entries
-    // the caller's depth camera (cvo_fe_set_depth_camera); without one depth is registered to colour
-    cvo_fe_depth_camera rig{};
-    bool has_rig = false;      // frames start with k_fe_depth_warp / k_fe_depth_final
-    int dw = 0, dh = 0;        // the size of the depth image a frame takes: the rig's, or the context's
-    // with the first rig: the upload target of the depth image, the ray table and the z-buffer
-    Dev<uint16_t> rig_depth;
-    Dev<float2> rays;          // (dh + 1) * (dw + 1)
-    Dev<uint32_t> zbuf;        // rect_plane(np) entries, FE_Z_EMPTY between frames
-    // the caller's gate and mask (cvo_fe_set_depth_gate, cvo_fe_set_mask); with either, frames pass k_fe_depth_gate
-    cvo_fe_depth_gate gate{};
-    bool has_gate = false, has_mask = false;
-    bool mask_dirty = false;       // h_mask holds bytes the device has not seen yet: the next submit() uploads them
-    // with the first gate or mask: the plane the stages in front of the gate write, and the flags
-    Dev<uint16_t> ungated;     // rect_plane(np) entries
-    Dev<uint8_t> gate_flags;
-    // with the first mask: its device plane and its pinned staging image
-    Dev<uint8_t> d_mask;
-    Pin<uint8_t> h_mask;
-    // the caller's stereo settings (cvo_fe_set_stereo); with them a frame is a stereo pair and the matcher of
-    // cvo_stereo.hip fills the depth plane
-    cvo_fe_stereo stereo{};
-    bool has_stereo = false;
-    // the path mask (cvo_fe_set_stereo_paths): a setting of the context beside `stereo`, read by stereo frames only
-    uint32_t stereo_paths = CVO_FE_PATHS_4;
-    // the selector's mode (cvo_fe_set_select_mode): a setting of the context likewise, read by every frame
-    int select_mode = CVO_FE_SELECT_IMAGE;
-    // the speckle filter (cvo_fe_set_stereo_speckle): a setting of the context likewise; with it a stereo frame passes
-    // the kernels of cvo_speckle.hip behind k_fe_stereo_final
-    cvo_fe_speckle speckle{};
-    bool has_speckle = false;
-    // with the filter, and gone with it: parents, sums and sizes (np words each) and the count of removed pixels
-    Dev<uint32_t> speckle_words;
-    // the median stage (cvo_fe_set_depth_median): a setting of the context likewise, read by every frame; with it
-    // whatever fills the depth plane fills `unfiltered`, and k_fe_median of cvo_median.hip writes that plane
-    cvo_fe_depth_median median{};
-    bool has_median = false;
-    // with the filter, and gone with it: A of the median contract (rect_plane(np) entries) and the flags
-    Dev<uint16_t> unfiltered;
-    Dev<uint8_t> median_flags;
-    // the infill stage (cvo_fe_set_depth_infill): a setting of the context likewise, read by every frame; with it
-    // whatever fills the depth plane fills `sparse`, and k_fe_infill of cvo_infill.hip writes the plane they filled before
-    cvo_fe_depth_infill infill{};
-    bool has_infill = false;
-    // with the stage, and gone with it: S of the infill contract (rect_plane(np) entries) and the flags
-    Dev<uint16_t> sparse;
-    Dev<uint8_t> infill_flags;
-    // the caller's scan source (cvo_fe_set_lidar); with it a frame is a colour image and a scan, and the kernels of
-    // cvo_lidar.hip with k_fe_depth_final between them fill the plane an uploaded depth image fills otherwise
-    cvo_fe_lidar lidar{};
-    bool has_lidar = false;
-    // with a scan source, and gone with it: the scan's staging, pinned and on the device (a header of FE_LIDAR_HEADER
-    // bytes whose first word is the frame's number of points, then max_points packed points), the z-buffer above, and,
-    // with an occlusion test, P0 (rect_plane(np) entries) and the flags
-    Pin<uint8_t> h_scan;
-    Dev<uint8_t> d_scan;
-    Dev<uint16_t> lidar_p0;
-    Dev<uint8_t> lidar_flags;
-    // the sweep of the scan source (cvo_fe_set_lidar_sweep), gone with it; the twist of the frames submitted from now
-    // on (cvo_fe_set_lidar_motion), which lidar_stage puts into the scan's header; and the bytes of one staged record,
-    // which h_scan and d_scan are sized for: 16 under a field mode, else 12
-    cvo_fe_lidar_sweep sweep{};
-    bool has_sweep = false;
-    float lidar_twist[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    size_t scan_record = 12;
-    // with the first settings: the right image and its pinned staging image, the planes of the matcher, and the
-    // table U(q) with its staging copy; the cost sums follow max_disp
-    Dev<uint8_t> right_img, right_gray, stereo_flags;
-    Pin<uint8_t> h_right;
-    Dev<uint64_t> census;      // 2 planes of np entries: left, right
-    Dev<uint16_t> sgm_sum;     // np * stereo.max_disp
-    Dev<uint32_t> stereo_win;
-    Dev<uint16_t> disparity, depth_table;
-    Pin<uint16_t> h_depth_table;
-    float table_fx = 0.0f, table_scale = 0.0f;   // the camera the device's table was made for; 0: none yet
-    // the caller's stereo rig (cvo_fe_set_stereo_rig); with it a frame is a RAW pair and starts with k_fe_stereo_rectify
-    cvo_fe_stereo_rig srig{};
-    bool has_srig = false;
-    // with a rig, and gone with it: the upload targets of the raw pair, the four map planes (qu, qv of the left camera,
-    // qu, qv of the right one; rect_plane(np) entries each) and the validity plane (rect_plane(np) bytes)
-    Dev<uint8_t> srig_raw_l, srig_raw_r, srig_valid;
-    Dev<int32_t> srig_map;
-    // the pixel format of the caller's colour images (cvo_fe_set_pixel_format): a setting of the context, read by every
-    // frame; under another than BGR8 the packed bytes are what is staged and uploaded, and k_fe_unpack of cvo_unpack.hip
-    // writes where the upload lands otherwise
-    int pixfmt = CVO_FE_PIXEL_BGR8;
-    size_t pix_row = 0;        // row_bytes and rows of the packed image (cvo_fe_pixel_layout); 0 under BGR8
-    int pix_rows = 0;
-    // with such a format, and gone with it: the packed image and its pinned staging (they stand in for h_img); under
-    // stereo the right image's as well (they stand in for h_right)
-    Dev<uint8_t> packed, packed_r;
-    Pin<uint8_t> h_packed, h_packed_r;
-    // the format of the caller's depth images (cvo_fe_set_depth_format): a setting of the context, read by frames that
-    // have a depth image; under a float format the float image is what is staged and uploaded, and k_fe_depth_convert of
-    // cvo_depthfmt.hip writes where the uint16 upload lands otherwise
-    int depthfmt = CVO_FE_DEPTH_U16;
-    float depth_unit = 1.0f;
-    // with a float format, and gone with it: the float image (dw * dh values) and its pinned staging (they stand in for
-    // h_depth); both follow the depth camera's size
-    Dev<uint8_t> fdepth;
-    Pin<uint8_t> h_fdepth;
-    // the frame being submitted takes its images from the caller's device memory (cvo_fe_submit_device): they are
-    // brought to the landing buffers in front of the frame, and the frame's sequence holds no upload of them
-    bool dev_in = false;
-    std::string err;
-};
-
-namespace {
-
-int fail(cvo_fe_ctx *c, int code, const char *what, hipError_t e = hipSuccess)
-{
-    if (c) {
-        c->err = what;
-        if (e != hipSuccess) { c->err += ": "; c->err += hipGetErrorString(e); }
-    }
-    return code;
-}
-
-#define FE_HIP(call)                                                            \
-    do {                                                                        \
-        const hipError_t e_ = (call);                                           \
-        if (e_ != hipSuccess) return fail(ctx, CVO_HIP_ERR_HIP, #call, e_);     \
-    } while (0)
-
-template <class T> bool dev_alloc(Dev<T> &b, size_t n)
-{
-    T *p = nullptr;
-    if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) return false;
-    b.reset(p);
-    return true;
-}
-
-template <class T> bool pin_alloc(Pin<T> &b, size_t n)
-{
-    T *p = nullptr;
-    if (hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) return false;
-    b.reset(p);
-    return true;
-}
-
-// a setter whose allocation failed: the runtime's error is taken, so that the next frame does not find it
-int no_memory(cvo_fe_ctx *ctx, const char *what)
-{
-    (void)hipGetLastError();
-    return fail(ctx, CVO_HIP_ERR_NOMEM, what);
-}
-
-// The setters replace only when whole: they build what they need in locals, and after the last step that can
-// fail the context takes what was built.  A local left empty (the context has that buffer already) changes nothing.
-template <class B> void hand_over(B &to, B &built)
-{
-    if (built) to = std::move(built);
-}
-
 inline int blocks(int n) { return (n + FE_BLOCK - 1) / FE_BLOCK; }
 
-// the two planes of the device map lie this many entries apart: k_fe_rectify's 16-byte loads stay aligned
-inline size_t rect_plane(int np) { return ((size_t)np + 3) & ~(size_t)3; }
-
-// what cvo_fe_set_camera accepts
-bool model_ok(const cvo_fe_camera_model &m)
+// The projection of a staged scan (a header whose first word is the number of points, then `capacity` records) into
+// `z`, for a frame and for cvo_fe_project_points alike: the arguments from the scan source and the camera, and with a
+// sweep (the sweep contract: another instance of the same kernel; the twist is in the scan's header) its words and
+// the two optional outputs.
+void enqueue_lidar_project(const cvo_fe_lidar &l, const float cam[5], const uint8_t *scan, int capacity, uint32_t *z, int w,
+                           int h, const cvo_fe_lidar_sweep *sw, float *phase, float *moved, hipStream_t s)
 {
-    const float v[10] = {m.depth_scale, m.fx, m.fy, m.cx, m.cy, m.dist[0], m.dist[1], m.dist[2], m.dist[3], m.dist[4]};
-    for (float x : v)
-        if (!std::isfinite(x)) return false;
-    return m.depth_scale > 0.0f && m.fx > 0.0f && m.fy > 0.0f;
-}
-
-// a rotation, as a depth camera's and a stereo rig's must be: within 1e-3 (largest absolute entry of R R^T - I) of
-// orthonormal, with a positive determinant
-bool rotation_ok(const float Rf[9])
-{
-    double R[9];
-    for (int q = 0; q < 9; ++q) R[q] = (double)Rf[q];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const double e = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2];
-            if (!(std::fabs(e - (i == j ? 1.0 : 0.0)) <= 1e-3)) return false;
-        }
-    const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) +
-                       R[2] * (R[3] * R[7] - R[4] * R[6]);
-    return det > 0.0;
-}
-
-// what cvo_fe_set_depth_camera accepts
-bool rig_ok(const cvo_fe_depth_camera &r)
-{
-    if (r.width < 8 || r.width > 8192 || r.height < 8 || r.height > 8192) return false;
-    const float *f = &r.depth_scale;   // the 24 floats after the two sizes
-    static_assert(sizeof(cvo_fe_depth_camera) == 2 * sizeof(int32_t) + 24 * sizeof(float), "no padding");
-    for (int q = 0; q < 24; ++q)
-        if (!std::isfinite(f[q])) return false;
-    if (!(r.depth_scale > 0.0f && r.fx > 0.0f && r.fy > 0.0f)) return false;
-    if (r.max_range > 0.0f && r.max_range <= r.min_range) return false;
-    return rotation_ok(r.R);
-}
-
-// what cvo_fe_set_stereo_rig accepts
-bool srig_ok(const cvo_fe_stereo_rig &r)
-{
-    static_assert(sizeof(cvo_fe_lens) == 9 * sizeof(float), "36 bytes, no padding");
-    static_assert(sizeof(cvo_fe_stereo_rig) == 42 * sizeof(float), "168 bytes, no padding");
-    const float *f = &r.left.fx;   // floats only
-    for (int q = 0; q < 42; ++q)
-        if (!std::isfinite(f[q])) return false;
-    if (!(r.left.fx > 0.0f && r.left.fy > 0.0f && r.right.fx > 0.0f && r.right.fy > 0.0f && r.fx > 0.0f && r.fy > 0.0f))
-        return false;
-    if (!(r.depth_scale > 0.0f && r.baseline > 0.0f)) return false;
-    return rotation_ok(r.R_left) && rotation_ok(r.R_right);
-}
-
-// what cvo_fe_set_lidar accepts
-bool lidar_ok(const cvo_fe_lidar &l)
-{
-    static_assert(sizeof(cvo_fe_lidar) == 5 * sizeof(int32_t) + 15 * sizeof(float), "80 bytes, no padding");
-    if (l.max_points < 1 || l.max_points > FE_LIDAR_MAX_POINTS || l.splat < 0 || l.splat > 3) return false;
-    const float *f = l.R;   // the 15 floats after the two sizes
-    for (int q = 0; q < 15; ++q)
-        if (!std::isfinite(f[q])) return false;
-    if (l.occl_rel < 0.0f) return false;
-    if (l.occl_rx < 0 || l.occl_rx > FE_LIDAR_RMAX || l.occl_ry < 0 || l.occl_ry > FE_LIDAR_RMAX) return false;
-    if (l.max_range > 0.0f && l.max_range <= l.min_range) return false;
-    return rotation_ok(l.R) && l.pad_ == 0;
-}
-
-inline bool lidar_stride_ok(size_t stride_bytes) { return stride_bytes >= 12 && stride_bytes % 4 == 0; }
-
-// (the staging of a scan and its packing, lidar_stage: cvo_lidar_stage.h)
-
-inline bool sweep_field_mode(const cvo_fe_lidar_sweep &sw) { return sw.mode == CVO_FE_SWEEP_TIME_F32 || sw.mode == CVO_FE_SWEEP_TIME_U32; }
-
-// the byte offset of the time word that lidar_stage carries along, -1: none
-inline int sweep_time_offset(const cvo_fe_lidar_sweep *sw) { return sw && sweep_field_mode(*sw) ? sw->time_offset : -1; }
-
-// what cvo_fe_set_lidar_sweep accepts
-bool sweep_ok(const cvo_fe_lidar_sweep &sw)
-{
-    static_assert(sizeof(cvo_fe_lidar_sweep) == 32, "32 bytes, no padding");
-    if (!std::isfinite(sw.time_origin) || !std::isfinite(sw.time_scale) || !std::isfinite(sw.phase0) || !std::isfinite(sw.s_ref))
-        return false;
-    if (!(sw.s_ref >= 0.0f && sw.s_ref <= 1.0f) || sw.pad_ != 0) return false;
-    if (sweep_field_mode(sw)) {
-        if (sw.time_offset < 12 || sw.time_offset % 4 != 0 || sw.time_scale == 0.0f || sw.direction != 0) return false;
-        return sw.mode == CVO_FE_SWEEP_TIME_F32 || sw.time_origin == 0.0f;
-    }
-    if (sw.mode != CVO_FE_SWEEP_AZIMUTH) return false;
-    return (sw.direction == 1 || sw.direction == -1) && sw.phase0 >= 0.0f && sw.phase0 < 1.0f && sw.time_origin == 0.0f;
-}
-
-// what cvo_fe_set_lidar_motion accepts
-bool twist_ok(const float twist[6])
-{
-    double w2 = 0.0, v2 = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        if (!std::isfinite(twist[k]) || !std::isfinite(twist[3 + k])) return false;
-        w2 += (double)twist[k] * twist[k];
-        v2 += (double)twist[3 + k] * twist[3 + k];
-    }
-    return w2 <= (double)CVO_FE_SWEEP_MAX_ROTATION * CVO_FE_SWEEP_MAX_ROTATION &&
-           v2 <= (double)CVO_FE_SWEEP_MAX_TRANSLATION * CVO_FE_SWEEP_MAX_TRANSLATION;
-}
-
-// the sweep's part of the projection's arguments
-void sweep_args(FeLidarSweepArgs &a, const cvo_fe_lidar_sweep &sw, float *phase, float *moved)
-{
-    a.time_origin = sw.time_origin; a.time_scale = sw.time_scale; a.phase0 = sw.phase0;
-    a.direction = (float)sw.direction; a.s_ref = sw.s_ref;
-    a.phase = phase; a.moved = moved;
-}
-
-// what cvo_fe_set_depth_gate accepts
-bool gate_ok(const cvo_fe_depth_gate &g)
-{
-    static_assert(sizeof(cvo_fe_depth_gate) == 3 * sizeof(float) + 3 * sizeof(int32_t), "24 bytes, no padding");
-    if (!std::isfinite(g.min_range) || !std::isfinite(g.max_range) || !std::isfinite(g.jump_rel)) return false;
-    if (g.jump_rel < 0.0f) return false;
-    if (g.max_range > 0.0f && g.max_range <= g.min_range) return false;
-    if (g.grow < 0 || g.grow > FG_HALO - 1) return false;
-    return (g.hole_border == 0 || g.hole_border == 1) && g.pad_ == 0;
-}
-
-// what cvo_fe_set_stereo accepts
-bool stereo_ok(const cvo_fe_stereo &s)
-{
-    static_assert(sizeof(cvo_fe_stereo) == sizeof(float) + 7 * sizeof(int32_t), "32 bytes, no padding");
-    if (!std::isfinite(s.baseline) || !(s.baseline > 0.0f)) return false;
-    if (s.max_disp < 8 || s.max_disp > 128 || s.max_disp % 8 != 0) return false;
-    if (s.min_disp < 1) return false;
-    if (!(1 <= s.p1 && s.p1 <= s.p2 && s.p2 <= 255)) return false;
-    if (s.uniqueness < 0 || s.uniqueness > 99) return false;
-    return s.lr_max >= -1 && s.lr_max <= 8 && s.pad_ == 0;
-}
-
-// The lens model of include/cvo_frontend.h for a colour or a depth camera, operation by operation (float64,
-// nothing contracted).  The tables made from it are held to their numpy restatements by bytes, so every
-// parenthesis here is part of the contract.
-struct Lens {
-    double fx, fy, cx, cy, k1, k2, p1, p2, k3;
-    template <class M>
-    explicit Lens(const M &m)
-        : fx(m.fx), fy(m.fy), cx(m.cx), cy(m.cy), k1(m.dist[0]), k2(m.dist[1]), p1(m.dist[2]), p2(m.dist[3]), k3(m.dist[4])
-    {
-    }
-    // the radial factor and the tangential shift at the ideal point (x, y)
-    void terms(double x, double y, double &rad, double &dx, double &dy) const
-    {
-        const double r2 = x * x + y * y;
-        rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-        dx = (2.0 * p1) * x * y + p2 * (r2 + (2.0 * x) * x);
-        dy = p1 * (r2 + (2.0 * y) * y) + (2.0 * p2) * x * y;
-    }
-    // the pixel at which the camera sees the ideal point (x, y)
-    void project(double x, double y, double &us, double &vs) const
-    {
-        double rad, dx, dy;
-        terms(x, y, rad, dx, dy);
-        const double xd = x * rad + dx, yd = y * rad + dy;
-        us = fx * xd + cx;
-        vs = fy * yd + cy;
-    }
-};
-
-// a source position as the entry of a map: clamped to [-1, w] x [-1, h] and in 1/32 pixel (the rectification contract)
-inline void map_entry(double us, double vs, double wmax, double hmax, int32_t &qu, int32_t &qv)
-{
-    if (!(us >= -1.0)) us = -1.0;   // (also what is not a number)
-    if (us > wmax) us = wmax;
-    if (!(vs >= -1.0)) vs = -1.0;
-    if (vs > hmax) vs = hmax;
-    qu = (int32_t)std::nearbyint(32.0 * us);   // ties to even (the default rounding mode)
-    qv = (int32_t)std::nearbyint(32.0 * vs);
-}
-
-inline bool distorts(const float dist[5])
-{
-    bool any = false;
-    for (int q = 0; q < 5; ++q) any = any || dist[q] != 0.0f;
-    return any;
-}
-
-// `rows` rows of `row` bytes from an image of any stride into a dense one; in one call when the stride is dense
-void copy_rows(void *dst, const void *src, size_t stride, size_t row, int rows)
-{
-    if (stride == row) {
-        std::memcpy(dst, src, row * (size_t)rows);
+    FeLidarProjectArgs a{};
+    a.count = (const int32_t *)scan; a.points = (const float *)(scan + FE_LIDAR_HEADER);
+    a.z = z; a.capacity = capacity; a.w = w; a.h = h; a.splat = l.splat;
+    a.min_range = l.min_range; a.max_range = l.max_range;
+    for (int q = 0; q < 9; ++q) a.R[q] = l.R[q];
+    for (int q = 0; q < 3; ++q) a.T[q] = l.T[q];
+    for (int q = 0; q < 5; ++q) a.cam[q] = cam[q];
+    if (!sw) {
+        fe_lidar_project_enqueue(a, s);
         return;
     }
-    for (int y = 0; y < rows; ++y) std::memcpy((uint8_t *)dst + (size_t)y * row, (const uint8_t *)src + (size_t)y * stride, row);
-}
-
-inline bool gate_active(const cvo_fe_ctx *ctx) { return ctx->has_gate || ctx->has_mask; }
-
-// the depth plane the stages in front of level 0 write: the gate's input while it runs
-inline uint16_t *depth_plane(const cvo_fe_ctx *ctx) { return gate_active(ctx) ? ctx->ungated.get() : ctx->depth.get(); }
-
-// the plane in front of the median stage: its input while it runs, else the depth plane itself.  The infill stage
-// writes it; without that stage the producers of depth do
-inline uint16_t *filled_plane(const cvo_fe_ctx *ctx) { return ctx->has_median ? ctx->unfiltered.get() : depth_plane(ctx); }
-
-// the plane the producers of depth write (an upload, k_fe_rectify, the depth camera's warp, the stereo matcher and its
-// speckle filter, the LiDAR projection and its cull): the infill stage's input while it runs, else the plane above
-inline uint16_t *source_plane(const cvo_fe_ctx *ctx) { return ctx->has_infill ? ctx->sparse.get() : filled_plane(ctx); }
-
-// where the uploaded depth image lands: the raw buffer of a depth camera's size, else the raw depth that
-// k_fe_rectify resamples, else the plane the producers write (a scan source: no image is uploaded, and the plane the
-// projected scan fills stands in its place)
-inline uint16_t *depth_upload(const cvo_fe_ctx *ctx)
-{
-    if (ctx->has_lidar) return source_plane(ctx);
-    return ctx->has_rig ? ctx->rig_depth.get() : ctx->rectify ? ctx->raw_depth.get() : source_plane(ctx);
+    FeLidarSweepArgs sa{};
+    sa.base = a;
+    sa.time_origin = sw->time_origin; sa.time_scale = sw->time_scale; sa.phase0 = sw->phase0;
+    sa.direction = (float)sw->direction; sa.s_ref = sw->s_ref;
+    sa.phase = phase; sa.moved = moved;
+    fe_lidar_project_sweep_enqueue(sw->mode, sa, s);
 }
 
 // the points of the cloud that follow the control block to the host before their number is known: enough for
@@ -1484,40 +1072,6 @@ inline int optimistic_copy(const cvo_fe_ctx *ctx)
 {
     return ctx->device_output ? 0 : std::min(ctx->cap, std::max(4096, 2 * ctx->num_want));
 }
-
-// the colour camera in force for a frame: a stereo rig's rectified pinhole, else the caller's model (a distorting
-// one: its rectified pinhole), else the table row of dataset_seq (never fails: an index outside the table means row 0)
-void camera_in_force(const cvo_fe_ctx *ctx, int dataset_seq, float cam[5])
-{
-    if (ctx->has_srig) {
-        const cvo_fe_stereo_rig &r = ctx->srig;
-        cam[0] = r.depth_scale; cam[1] = r.fx; cam[2] = r.fy; cam[3] = r.cx; cam[4] = r.cy;
-    } else if (ctx->custom) {
-        const cvo_fe_camera_model &m = ctx->cam;
-        cam[0] = m.depth_scale; cam[1] = m.fx; cam[2] = m.fy; cam[3] = m.cx; cam[4] = m.cy;
-    } else cvo_fe_camera(dataset_seq, cam);
-}
-
-// After a change of what a frame's sequence is -- and the only place that destroys a graph.  A graph captured
-// before the change holds the old numbers, the old buffers (the map's address too) and the old first node.
-// Dropping those graphs here is what keeps them from being launched again -- and what keeps the cache of 8
-// from filling with dead entries; the generation in the key is the guard behind it, should a graph ever
-// outlive such a change.
-inline bool unpacks(const cvo_fe_ctx *ctx) { return ctx->pixfmt != CVO_FE_PIXEL_BGR8; }
-
-// the staging a frame's colour image is copied to and uploaded from, its row and its rows: the packed image under a
-// pixel format; and the right image's under stereo
-inline uint8_t *img_staging(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->h_packed.get() : ctx->h_img.get(); }
-inline uint8_t *right_staging(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->h_packed_r.get() : ctx->h_right.get(); }
-inline size_t img_row(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_row : (size_t)ctx->d.w * 3; }
-inline int img_rows(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_rows : ctx->d.h; }
-
-// where the colour image lands on the device (an upload, or k_fe_unpack's output): the stereo rig's raw buffer, else the
-// raw image k_fe_rectify resamples, else the image every later stage reads; and the right image of a stereo frame
-// under a float depth format: the bytes of one value, and the staging a frame's depth image is copied to and uploaded from
-inline bool converts(const cvo_fe_ctx *ctx) { return ctx->depthfmt != CVO_FE_DEPTH_U16; }
-inline size_t depth_item(const cvo_fe_ctx *ctx) { return fe_depth_item(ctx->depthfmt); }
-inline void *depth_staging(const cvo_fe_ctx *ctx) { return converts(ctx) ? (void *)ctx->h_fdepth.get() : (void *)ctx->h_depth.get(); }
 
 // the `scale` of the depth-format contract: of whatever reads the uploaded depth image first
 inline float depth_format_scale(const cvo_fe_ctx *ctx, int dataset_seq)
@@ -1536,39 +1090,6 @@ inline void enqueue_depth_convert(const cvo_fe_ctx *ctx, const void *src, size_t
     a.w = ctx->dw; a.h = ctx->dh; a.format = ctx->depthfmt; a.unit = ctx->depth_unit;
     a.scale = depth_format_scale(ctx, dataset_seq);
     fe_depth_convert_enqueue(a, ctx->stream);
-}
-
-inline uint8_t *img_landing(const cvo_fe_ctx *ctx)
-{
-    return ctx->has_srig ? ctx->srig_raw_l.get() : ctx->rectify ? ctx->raw_img.get() : ctx->img.get();
-}
-inline uint8_t *right_landing(const cvo_fe_ctx *ctx) { return ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(); }
-
-void drop_graphs(cvo_fe_ctx *ctx)
-{
-    ctx->cam_gen++;
-    for (auto &g : ctx->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    ctx->graphs.clear();
-}
-
-// the ungated plane and the flags, with the first gate or mask; both or neither (left empty for a context that has them)
-int gate_buffers(cvo_fe_ctx *ctx, Dev<uint16_t> &ungated, Dev<uint8_t> &flags)
-{
-    const size_t n = rect_plane(ctx->np);
-    if (ctx->ungated || (dev_alloc(ungated, n) && dev_alloc(flags, n))) return CVO_HIP_OK;
-    return no_memory(ctx, "device memory for the ungated depth and the gate's flags");
-}
-
-// the packed right image and its staging, for a stereo context under a pixel format; both or neither (left empty for a
-// context that has them, or one in BGR8)
-int packed_right_buffers(cvo_fe_ctx *ctx, Dev<uint8_t> &packed_r, Pin<uint8_t> &h_packed_r)
-{
-    const size_t n = ctx->pix_row * (size_t)ctx->pix_rows;
-    if (!unpacks(ctx) || ctx->packed_r || (dev_alloc(packed_r, n) && pin_alloc(h_packed_r, n))) return CVO_HIP_OK;
-    return no_memory(ctx, "device and pinned memory for the packed right image");
 }
 
 // the Canny path of a frame whose selection came out short (host loop: rare)
@@ -1716,20 +1237,10 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     }
     if (ctx->has_lidar) {   // (the LiDAR contract; neither stereo nor a depth camera beside it: cvo_fe_set_lidar)
         const cvo_fe_lidar &l = ctx->lidar;
-        FeLidarProjectArgs a{};
-        a.count = (const int32_t *)ctx->d_scan.get(); a.points = (const float *)(ctx->d_scan.get() + FE_LIDAR_HEADER);
-        a.z = ctx->zbuf.get(); a.capacity = l.max_points; a.w = w; a.h = h; a.splat = l.splat;
-        a.min_range = l.min_range; a.max_range = l.max_range;
-        for (int q = 0; q < 9; ++q) a.R[q] = l.R[q];
-        for (int q = 0; q < 3; ++q) a.T[q] = l.T[q];
-        camera_in_force(ctx, dataset_seq, a.cam);
-        if (ctx->has_sweep) {   // (the sweep contract: another instance of the same kernel; the twist is in the header)
-            FeLidarSweepArgs sa{};
-            sa.base = a;
-            sweep_args(sa, ctx->sweep, nullptr, nullptr);
-            fe_lidar_project_sweep_enqueue(ctx->sweep.mode, sa, s);
-        } else
-            fe_lidar_project_enqueue(a, s);
+        float cam[5];
+        camera_in_force(ctx, dataset_seq, cam);
+        enqueue_lidar_project(l, cam, ctx->d_scan.get(), l.max_points, ctx->zbuf.get(), w, h,
+                              ctx->has_sweep ? &ctx->sweep : nullptr, nullptr, nullptr, s);
         const bool cull = l.occl_rel > 0.0f;   // (without the test P is P0, written where P goes)
         hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, s, ctx->zbuf.get(), np,
                            cull ? ctx->lidar_p0.get() : plane);
@@ -1872,947 +1383,6 @@ int cvo_fe_camera(int dataset_seq, float cam[5])
     return CVO_HIP_OK;
 }
 
-int cvo_fe_rectify_map(const cvo_fe_camera_model *model, int width, int height, int32_t *qu, int32_t *qv)
-{
-    if (!model || !qu || !qv || width < 1 || height < 1 || !model_ok(*model)) return CVO_HIP_ERR_INVALID;
-    const Lens lens(*model);
-    const double wmax = (double)width, hmax = (double)height;
-    for (int v = 0; v < height; ++v) {
-        const double y = ((double)v - lens.cy) / lens.fy;
-        for (int u = 0; u < width; ++u) {
-            const double x = ((double)u - lens.cx) / lens.fx;
-            double us, vs;
-            lens.project(x, y, us, vs);
-            const size_t i = (size_t)v * width + u;
-            map_entry(us, vs, wmax, hmax, qu[i], qv[i]);
-        }
-    }
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_depth_camera(const cvo_fe_depth_camera *rig)
-{
-    return rig && rig_ok(*rig) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID;
-}
-
-int cvo_fe_depth_rays(const cvo_fe_depth_camera *rig, float *xn, float *yn)
-{
-    if (!rig || !xn || !yn || !rig_ok(*rig)) return CVO_HIP_ERR_INVALID;
-    const Lens lens(*rig);
-    const bool bent = distorts(rig->dist);
-    const double nan = std::nan("");
-    for (int j = 0; j <= rig->height; ++j) {
-        const double py = (double)j - 0.5, yd = (py - lens.cy) / lens.fy;
-        for (int i = 0; i <= rig->width; ++i) {
-            const double px = (double)i - 0.5, xd = (px - lens.cx) / lens.fx;
-            double x = xd, y = yd;
-            if (bent) {
-                for (int it = 0; it < 20; ++it) {   // the fixed-point step
-                    double rad, dx, dy;
-                    lens.terms(x, y, rad, dx, dy);
-                    x = (xd - dx) / rad;
-                    y = (yd - dy) / rad;
-                }
-                double us, vs;   // the forward check
-                lens.project(x, y, us, vs);
-                if (!(std::fabs(us - px) <= 1.0 / 32.0 && std::fabs(vs - py) <= 1.0 / 32.0)) x = y = nan;
-            }
-            const size_t c = (size_t)j * ((size_t)rig->width + 1) + i;
-            xn[c] = (float)x;
-            yn[c] = (float)y;
-        }
-    }
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: a frame is in flight");
-    if (rig && !rig_ok(*rig))
-        return fail(ctx, CVO_HIP_ERR_INVALID,
-                    "set_depth_camera: size in [8, 8192], finite members, fx, fy, depth_scale positive, "
-                    "max_range above min_range, R a rotation");
-    if (rig && ctx->has_stereo)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: stereo is set, there is no depth image");
-    if (rig && ctx->has_lidar)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: a scan source is set, there is no depth image");
-    if (!rig && !ctx->has_rig) return CVO_HIP_OK;
-    if (rig && ctx->has_rig && std::memcmp(rig, &ctx->rig, sizeof(*rig)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    const int dw = rig ? rig->width : ctx->d.w, dh = rig ? rig->height : ctx->d.h;
-    const size_t dnp = (size_t)dw * dh;
-    Dev<uint16_t> new_depth;
-    Pin<uint16_t> new_host;
-    Dev<float2> new_rays;
-    Dev<uint32_t> new_z;
-    Dev<uint8_t> new_fdepth;   // (under a float depth format: the float image and its staging follow the size as well)
-    Pin<uint8_t> new_fhost;
-    const bool resize = dw != ctx->dw || dh != ctx->dh;   // the pinned staging image follows the depth size
-    if (resize && !pin_alloc(new_host, dnp)) return no_memory(ctx, "set_depth_camera: pinned memory for the depth image");
-    if (resize && converts(ctx) && !(dev_alloc(new_fdepth, dnp * depth_item(ctx)) && pin_alloc(new_fhost, dnp * depth_item(ctx))))
-        return no_memory(ctx, "set_depth_camera: device and pinned memory for the float depth image");
-    if (rig) {
-        const size_t nr = (size_t)(dw + 1) * (dh + 1), nz = rect_plane(ctx->np);
-        std::vector<float> t;
-        std::vector<float2> inter;
-        try { t.resize(2 * nr); inter.resize(nr); } catch (const std::bad_alloc &) {
-            return fail(ctx, CVO_HIP_ERR_NOMEM, "set_depth_camera");
-        }
-        if (cvo_fe_depth_rays(rig, t.data(), t.data() + nr) != CVO_HIP_OK)
-            return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: depth_rays");
-        for (size_t q = 0; q < nr; ++q) inter[q] = make_float2(t[q], t[nr + q]);
-        if (!dev_alloc(new_depth, dnp) || !dev_alloc(new_rays, nr) || (!ctx->zbuf && !dev_alloc(new_z, nz)))
-            return no_memory(ctx, "set_depth_camera: device memory for the raw depth, the rays and the z-buffer");
-        // (no frame is in flight: once the stream is idle nothing reads the old buffers any more)
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(new_rays.get(), inter.data(), nr * sizeof(float2), hipMemcpyHostToDevice);
-        // the z-buffer is armed here and by every frame's k_fe_depth_final after it
-        if (e == hipSuccess) e = hipMemset(new_z ? new_z.get() : ctx->zbuf.get(), 0xFF, nz * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera: upload of the rays", e);
-        }
-    } else {
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, CVO_HIP_ERR_HIP, "set_depth_camera", e);
-    }
-    // whole: the old raw depth and rays go, with or without new ones
-    ctx->rig_depth = std::move(new_depth);
-    ctx->rays = std::move(new_rays);
-    hand_over(ctx->zbuf, new_z);
-    hand_over(ctx->h_depth, new_host);
-    hand_over(ctx->fdepth, new_fdepth);
-    hand_over(ctx->h_fdepth, new_fhost);
-    ctx->has_rig = rig != nullptr;
-    ctx->rig = rig ? *rig : cvo_fe_depth_camera{};
-    ctx->dw = dw;
-    ctx->dh = dh;
-    drop_graphs(ctx);
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_depth_camera(const cvo_fe_ctx *ctx, cvo_fe_depth_camera *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_rig ? ctx->rig : cvo_fe_depth_camera{};
-    if (set) *set = ctx->has_rig ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_depth_gate(const cvo_fe_depth_gate *gate)
-{
-    return gate && gate_ok(*gate) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID;
-}
-
-int cvo_fe_set_depth_gate(cvo_fe_ctx *ctx, const cvo_fe_depth_gate *gate)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_gate: a frame is in flight");
-    if (gate && !gate_ok(*gate))
-        return fail(ctx, CVO_HIP_ERR_INVALID,
-                    "set_depth_gate: finite members, jump_rel >= 0, max_range above min_range, grow in [0, 3], "
-                    "hole_border 0 or 1, pad_ 0");
-    if (!gate && !ctx->has_gate) return CVO_HIP_OK;
-    if (gate && ctx->has_gate && std::memcmp(gate, &ctx->gate, sizeof(*gate)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint16_t> ungated;
-    Dev<uint8_t> flags;
-    if (gate) {
-        const int rc = gate_buffers(ctx, ungated, flags);
-        if (rc) return rc;
-    }
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->ungated, ungated);
-    hand_over(ctx->gate_flags, flags);
-    ctx->has_gate = gate != nullptr;
-    ctx->gate = gate ? *gate : cvo_fe_depth_gate{};
-    drop_graphs(ctx);   // (the gate's numbers and the planes of a frame are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_depth_gate(const cvo_fe_ctx *ctx, cvo_fe_depth_gate *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_gate ? ctx->gate : cvo_fe_depth_gate{};
-    if (set) *set = ctx->has_gate ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_stereo(const cvo_fe_stereo *st) { return st && stereo_ok(*st) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
-
-int cvo_fe_stereo_depth_table(const cvo_fe_stereo *st, float fx, float depth_scale, uint16_t *out)
-{
-    if (!st || !out || !stereo_ok(*st) || !std::isfinite(fx) || !std::isfinite(depth_scale) || !(fx > 0.0f) ||
-        !(depth_scale > 0.0f))
-        return CVO_HIP_ERR_INVALID;
-    // contract 9, operation by operation in float64 (nothing can be contracted: there is no addition)
-    const double num = (((double)fx * (double)st->baseline) * (double)depth_scale) * 16.0;
-    const int n = 16 * st->max_disp, q0 = 16 * st->min_disp;
-    for (int q = 0; q < n; ++q) {
-        double u = 0.0;
-        if (q >= q0) u = std::nearbyint(num / (double)q);   // (ties to even: the default rounding mode)
-        out[q] = (u >= 1.0 && u <= 65535.0) ? (uint16_t)u : (uint16_t)0;
-    }
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a frame is in flight");
-    if (st && !stereo_ok(*st))
-        return fail(ctx, CVO_HIP_ERR_INVALID,
-                    "set_stereo: baseline positive and finite, max_disp a multiple of 8 in [8, 128], min_disp >= 1, "
-                    "1 <= p1 <= p2 <= 255, uniqueness in [0, 99], lr_max in [-1, 8], pad_ 0");
-    if (st && ctx->has_rig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a depth camera is set");
-    if (st && ctx->has_lidar) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a scan source is set");
-    if (st && ctx->rectify)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: the camera model has a lens distortion; the pair must be rectified");
-    if (!st && ctx->has_srig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo: a stereo rig is set: clear the rig first");
-    if (!st && !ctx->has_stereo) return CVO_HIP_OK;
-    if (st && ctx->has_stereo && std::memcmp(st, &ctx->stereo, sizeof(*st)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    const size_t np = (size_t)ctx->np;
-    Dev<uint8_t> right_img, right_gray, flags;
-    Pin<uint8_t> h_right;
-    Dev<uint64_t> census;
-    Dev<uint16_t> sum, disparity, table;
-    Dev<uint32_t> win;
-    Pin<uint16_t> h_table;
-    Dev<uint8_t> packed_r;   // (under a pixel format: the right image arrives packed as the left one does)
-    Pin<uint8_t> h_packed_r;
-    if (st) {
-        // (all but the cost sums come with the first settings and stay; the table has room for the largest max_disp)
-        if (!ctx->right_img &&
-            !(dev_alloc(right_img, np * 3) && dev_alloc(right_gray, np) && dev_alloc(flags, np) && pin_alloc(h_right, np * 3) &&
-              dev_alloc(census, 2 * np) && dev_alloc(disparity, np) && dev_alloc(win, np) && dev_alloc(table, 16 * 128) &&
-              pin_alloc(h_table, 16 * 128)))
-            return no_memory(ctx, "set_stereo: device and pinned memory for the right image and the matcher's planes");
-        if ((!ctx->sgm_sum || !ctx->has_stereo || st->max_disp != ctx->stereo.max_disp) && !dev_alloc(sum, np * (size_t)st->max_disp))
-            return no_memory(ctx, "set_stereo: device memory for the cost sums");
-        if (packed_right_buffers(ctx, packed_r, h_packed_r) != CVO_HIP_OK) return CVO_HIP_ERR_NOMEM;
-    }
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->right_img, right_img);
-    hand_over(ctx->right_gray, right_gray);
-    hand_over(ctx->stereo_flags, flags);
-    hand_over(ctx->h_right, h_right);
-    hand_over(ctx->census, census);
-    hand_over(ctx->disparity, disparity);
-    hand_over(ctx->stereo_win, win);
-    hand_over(ctx->depth_table, table);
-    hand_over(ctx->h_depth_table, h_table);
-    hand_over(ctx->sgm_sum, sum);
-    hand_over(ctx->packed_r, packed_r);
-    hand_over(ctx->h_packed_r, h_packed_r);
-    if (!st) ctx->sgm_sum.reset();   // (the one large buffer: a context back on depth images does not keep it)
-    ctx->has_stereo = st != nullptr;
-    ctx->stereo = st ? *st : cvo_fe_stereo{};
-    ctx->table_fx = ctx->table_scale = 0.0f;   // (the table depends on baseline, min_disp and max_disp: made again)
-    drop_graphs(ctx);   // (the settings and the planes of a frame are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_stereo(const cvo_fe_ctx *ctx, cvo_fe_stereo *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_stereo ? ctx->stereo : cvo_fe_stereo{};
-    if (set) *set = ctx->has_stereo ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_stereo_paths(uint32_t mask) { return mask >= 1u && mask <= (uint32_t)CVO_FE_PATHS_8 ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
-
-int cvo_fe_set_stereo_paths(cvo_fe_ctx *ctx, uint32_t mask)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_paths: a frame is in flight");
-    if (cvo_fe_check_stereo_paths(mask) != CVO_HIP_OK)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_paths: a non-empty subset of the eight bits, 1 <= mask <= 0xFF");
-    if (mask == ctx->stereo_paths) return CVO_HIP_OK;
-    ctx->stereo_paths = mask;
-    drop_graphs(ctx);   // (which path launches a frame has is part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_stereo_paths(const cvo_fe_ctx *ctx, uint32_t *mask)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !mask) return CVO_HIP_ERR_INVALID;
-    *mask = ctx->stereo_paths;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_select_mode(int mode)
-{
-    return mode == CVO_FE_SELECT_IMAGE || mode == CVO_FE_SELECT_DEPTH ? CVO_HIP_OK : CVO_HIP_ERR_INVALID;
-}
-
-int cvo_fe_set_select_mode(cvo_fe_ctx *ctx, int mode)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_select_mode: a frame is in flight");
-    if (cvo_fe_check_select_mode(mode) != CVO_HIP_OK)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_select_mode: CVO_FE_SELECT_IMAGE or CVO_FE_SELECT_DEPTH");
-    if (mode == ctx->select_mode) return CVO_HIP_OK;
-    ctx->select_mode = mode;
-    drop_graphs(ctx);   // (which instance of the selector a frame launches is part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_select_mode(const cvo_fe_ctx *ctx, int *mode)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !mode) return CVO_HIP_ERR_INVALID;
-    *mode = ctx->select_mode;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_stereo_speckle(cvo_fe_ctx *ctx, const cvo_fe_speckle *sp)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_speckle: a frame is in flight");
-    if (sp && cvo_fe_check_speckle(sp) != CVO_HIP_OK)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_speckle: max_size in [1, 2^26], max_diff in [0, 65535]");
-    if (!sp && !ctx->has_speckle) return CVO_HIP_OK;
-    if (sp && ctx->has_speckle && std::memcmp(sp, &ctx->speckle, sizeof(*sp)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint32_t> words;
-    if (sp && !ctx->speckle_words && !dev_alloc(words, 3 * (size_t)ctx->np + 1))
-        return no_memory(ctx, "set_stereo_speckle: device memory for the parents, the sums and the sizes");
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->speckle_words, words);
-    if (!sp) ctx->speckle_words.reset();
-    ctx->has_speckle = sp != nullptr;
-    ctx->speckle = sp ? *sp : cvo_fe_speckle{};
-    drop_graphs(ctx);   // (whether a frame has the filter's launches, their numbers and planes are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_stereo_speckle(const cvo_fe_ctx *ctx, cvo_fe_speckle *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_speckle ? ctx->speckle : cvo_fe_speckle{};
-    if (set) *set = ctx->has_speckle ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_depth_median(cvo_fe_ctx *ctx, const cvo_fe_depth_median *m)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_median: a frame is in flight");
-    if (m && cvo_fe_check_depth_median(m) != CVO_HIP_OK)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_median: radius 1 or 2, fill_min in [0, (2*radius+1)^2 - 1], pad_ 0");
-    if (!m && !ctx->has_median) return CVO_HIP_OK;
-    if (m && ctx->has_median && std::memcmp(m, &ctx->median, sizeof(*m)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint16_t> unfiltered;
-    Dev<uint8_t> flags;
-    if (m && !ctx->unfiltered && !(dev_alloc(unfiltered, rect_plane(ctx->np)) && dev_alloc(flags, rect_plane(ctx->np))))
-        return no_memory(ctx, "set_depth_median: device memory for the unfiltered depth and the stage's flags");
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->unfiltered, unfiltered);
-    hand_over(ctx->median_flags, flags);
-    if (!m) {
-        ctx->unfiltered.reset();
-        ctx->median_flags.reset();
-    }
-    ctx->has_median = m != nullptr;
-    ctx->median = m ? *m : cvo_fe_depth_median{};
-    drop_graphs(ctx);   // (whether a frame has the stage's launch, its numbers and where the producers write are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_depth_median(const cvo_fe_ctx *ctx, cvo_fe_depth_median *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_median ? ctx->median : cvo_fe_depth_median{};
-    if (set) *set = ctx->has_median ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_depth_infill(cvo_fe_ctx *ctx, const cvo_fe_depth_infill *f)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_infill: a frame is in flight");
-    if (f && cvo_fe_check_depth_infill(f) != CVO_HIP_OK)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_infill: gap_x in [0, 15], gap_y in [0, 31], jump_rel finite and >= 0, pad_ 0");
-    if (!f && !ctx->has_infill) return CVO_HIP_OK;
-    if (f && ctx->has_infill && std::memcmp(f, &ctx->infill, sizeof(*f)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint16_t> sparse;
-    Dev<uint8_t> flags;
-    if (f && !ctx->sparse && !(dev_alloc(sparse, rect_plane(ctx->np)) && dev_alloc(flags, rect_plane(ctx->np))))
-        return no_memory(ctx, "set_depth_infill: device memory for the sparse depth and the stage's flags");
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->sparse, sparse);
-    hand_over(ctx->infill_flags, flags);
-    if (!f) {
-        ctx->sparse.reset();
-        ctx->infill_flags.reset();
-    }
-    ctx->has_infill = f != nullptr;
-    ctx->infill = f ? *f : cvo_fe_depth_infill{};
-    drop_graphs(ctx);   // (whether a frame has the stage's launch, its numbers and where the producers write are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_depth_infill(const cvo_fe_ctx *ctx, cvo_fe_depth_infill *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_infill ? ctx->infill : cvo_fe_depth_infill{};
-    if (set) *set = ctx->has_infill ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_pixel_format(cvo_fe_ctx *ctx, int format)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_pixel_format: a frame is in flight");
-    size_t row = 0;
-    int rows = 0;
-    if (!fe_unpack_layout(format, ctx->d.w, ctx->d.h, &row, &rows))
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_pixel_format: a CVO_FE_PIXEL_* format that fits the context's size (YUY2, UYVY: an "
-                                              "even width; NV12: an even width and height)");
-    if (format == ctx->pixfmt) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    const bool on = format != CVO_FE_PIXEL_BGR8;
-    Dev<uint8_t> packed, packed_r;
-    Pin<uint8_t> h_packed, h_packed_r;
-    // (the sizes follow the format: built anew for each, the right image's only for a context under stereo)
-    if (on && !(dev_alloc(packed, row * (size_t)rows) && pin_alloc(h_packed, row * (size_t)rows) &&
-                (!ctx->has_stereo || (dev_alloc(packed_r, row * (size_t)rows) && pin_alloc(h_packed_r, row * (size_t)rows)))))
-        return no_memory(ctx, "set_pixel_format: device and pinned memory for the packed image");
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->packed = std::move(packed);   // (all four replaced or, back in BGR8, freed)
-    ctx->packed_r = std::move(packed_r);
-    ctx->h_packed = std::move(h_packed);
-    ctx->h_packed_r = std::move(h_packed_r);
-    ctx->pixfmt = format;
-    ctx->pix_row = on ? row : 0;
-    ctx->pix_rows = on ? rows : 0;
-    drop_graphs(ctx);   // (whether a frame has the stage's launch, its instance and what is uploaded are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_pixel_format(const cvo_fe_ctx *ctx, int *format)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !format) return CVO_HIP_ERR_INVALID;
-    *format = ctx->pixfmt;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_depth_format(cvo_fe_ctx *ctx, int format, float unit)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_format: a frame is in flight");
-    if (!fe_depth_format_ok(format, unit))
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_format: a CVO_FE_DEPTH_* format, a finite unit in [2^-20, 2^20], "
-                                              "and a unit of 1 under CVO_FE_DEPTH_U16");
-    if (format == ctx->depthfmt && unit == ctx->depth_unit) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint8_t> fdepth;
-    Pin<uint8_t> h_fdepth;
-    const size_t bytes = (size_t)ctx->dw * ctx->dh * fe_depth_item(format);
-    const bool on = format != CVO_FE_DEPTH_U16, sized = on && fe_depth_item(format) == depth_item(ctx) && converts(ctx);
-    if (on && !sized && !(dev_alloc(fdepth, bytes) && pin_alloc(h_fdepth, bytes)))
-        return no_memory(ctx, "set_depth_format: device and pinned memory for the float depth image");
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    if (!sized) {   // (both replaced or, back in U16, freed)
-        ctx->fdepth = std::move(fdepth);
-        ctx->h_fdepth = std::move(h_fdepth);
-    }
-    ctx->depthfmt = format;
-    ctx->depth_unit = unit;
-    drop_graphs(ctx);   // (the format, the unit and the float image are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_depth_format(const cvo_fe_ctx *ctx, int *format, float *unit)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !format || !unit) return CVO_HIP_ERR_INVALID;
-    *format = ctx->depthfmt;
-    *unit = ctx->depth_unit;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_lidar(const cvo_fe_lidar *l) { return l && lidar_ok(*l) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
-
-int cvo_fe_set_lidar(cvo_fe_ctx *ctx, const cvo_fe_lidar *l)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar: a frame is in flight");
-    if (l && !lidar_ok(*l))
-        return fail(ctx, CVO_HIP_ERR_INVALID,
-                    "set_lidar: max_points in [1, 2^21], splat in [0, 3], finite members, occl_rel >= 0, occl_rx and occl_ry "
-                    "in [0, 7], max_range above min_range, R a rotation, pad_ 0");
-    if (l && ctx->has_stereo) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar: stereo is set");
-    if (l && ctx->has_rig) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar: a depth camera is set");
-    if (!l && !ctx->has_lidar) return CVO_HIP_OK;
-    if (l && ctx->has_lidar && std::memcmp(l, &ctx->lidar, sizeof(*l)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Pin<uint8_t> h_scan;
-    Dev<uint8_t> d_scan, flags;
-    Dev<uint16_t> p0;
-    Dev<uint32_t> z;
-    const size_t nz = rect_plane(ctx->np);
-    if (l) {
-        const size_t bytes = lidar_scan_bytes(l->max_points, ctx->scan_record);   // (a sweep stays: its record size too)
-        const bool resize = !ctx->has_lidar || l->max_points != ctx->lidar.max_points;
-        if (resize && !(pin_alloc(h_scan, bytes) && dev_alloc(d_scan, bytes)))
-            return no_memory(ctx, "set_lidar: pinned and device memory for a scan of max_points points");
-        if (!ctx->zbuf && !dev_alloc(z, nz)) return no_memory(ctx, "set_lidar: device memory for the z-buffer");
-        if (l->occl_rel > 0.0f && !ctx->lidar_p0 && !(dev_alloc(p0, nz) && dev_alloc(flags, nz)))
-            return no_memory(ctx, "set_lidar: device memory for the plane before culling and the flags");
-        if (h_scan) std::memset(h_scan.get(), 0, FE_LIDAR_HEADER);   // (a scan of no points until the first frame)
-    }
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    // a new z-buffer is armed here; every frame's k_fe_depth_final arms it after that
-    if (e == hipSuccess && z) e = hipMemset(z.get(), 0xFF, nz * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, CVO_HIP_ERR_HIP, "set_lidar", e);
-    }
-    hand_over(ctx->h_scan, h_scan);
-    hand_over(ctx->d_scan, d_scan);
-    hand_over(ctx->zbuf, z);
-    hand_over(ctx->lidar_p0, p0);
-    hand_over(ctx->lidar_flags, flags);
-    if (!l) {   // (given back: a depth camera set later makes its own z-buffer; the sweep goes with the scan source)
-        ctx->h_scan.reset();
-        ctx->d_scan.reset();
-        ctx->zbuf.reset();
-        ctx->has_sweep = false;
-        ctx->sweep = cvo_fe_lidar_sweep{};
-        ctx->scan_record = 12;
-        for (float &t : ctx->lidar_twist) t = 0.0f;
-    }
-    if (!l || !(l->occl_rel > 0.0f)) {
-        ctx->lidar_p0.reset();
-        ctx->lidar_flags.reset();
-    }
-    ctx->has_lidar = l != nullptr;
-    ctx->lidar = l ? *l : cvo_fe_lidar{};
-    drop_graphs(ctx);   // (the kind of a frame, the settings, the scan's capacity and the planes are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_lidar(const cvo_fe_ctx *ctx, cvo_fe_lidar *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_lidar ? ctx->lidar : cvo_fe_lidar{};
-    if (set) *set = ctx->has_lidar ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_lidar_sweep(const cvo_fe_lidar_sweep *sw) { return sw && sweep_ok(*sw) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
-
-int cvo_fe_set_lidar_sweep(cvo_fe_ctx *ctx, const cvo_fe_lidar_sweep *sw)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_sweep: a frame is in flight");
-    if (sw && !sweep_ok(*sw))
-        return fail(ctx, CVO_HIP_ERR_INVALID,
-                    "set_lidar_sweep: a mode of CVO_FE_SWEEP_*, finite members, time_offset >= 12 and a multiple of 4, "
-                    "time_scale not 0, direction +1 or -1 under the azimuth mode and 0 otherwise, phase0 in [0, 1), "
-                    "s_ref in [0, 1], time_origin 0 outside the float mode, pad_ 0");
-    if (sw && !ctx->has_lidar) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_sweep: no scan source (cvo_fe_set_lidar)");
-    if (!sw && !ctx->has_sweep) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Pin<uint8_t> h_scan;
-    Dev<uint8_t> d_scan;
-    const size_t record = lidar_record_bytes(sweep_time_offset(sw));
-    if (record != ctx->scan_record) {   // (a record with or without its time word: the staging and its copy follow)
-        const size_t bytes = lidar_scan_bytes(ctx->lidar.max_points, record);
-        if (!(pin_alloc(h_scan, bytes) && dev_alloc(d_scan, bytes)))
-            return no_memory(ctx, "set_lidar_sweep: pinned and device memory for a scan of max_points points");
-        std::memset(h_scan.get(), 0, FE_LIDAR_HEADER);   // (a scan of no points until the first frame)
-    }
-    // (no frame is in flight: once the stream is idle nothing reads what the old graphs read)
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, CVO_HIP_ERR_HIP, "set_lidar_sweep", e);
-    }
-    hand_over(ctx->h_scan, h_scan);
-    hand_over(ctx->d_scan, d_scan);
-    ctx->scan_record = record;
-    ctx->has_sweep = sw != nullptr;
-    ctx->sweep = sw ? *sw : cvo_fe_lidar_sweep{};
-    for (float &t : ctx->lidar_twist) t = 0.0f;
-    drop_graphs(ctx);   // (the kernel's instance, the sweep's words and the size of the copy are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_lidar_sweep(const cvo_fe_ctx *ctx, cvo_fe_lidar_sweep *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_sweep ? ctx->sweep : cvo_fe_lidar_sweep{};
-    if (set) *set = ctx->has_sweep ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_lidar_motion(cvo_fe_ctx *ctx, const float twist[6])
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (!twist) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_motion: bad argument");
-    if (!ctx->has_sweep) return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_motion: no sweep (cvo_fe_set_lidar_sweep)");
-    if (!twist_ok(twist))
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_lidar_motion: finite members, |w| <= 1 radian and |v| <= 64 metres per sweep");
-    for (int k = 0; k < 6; ++k) ctx->lidar_twist[k] = twist[k];   // (read by the next submit: no graph holds it)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_lidar_motion(const cvo_fe_ctx *ctx, float twist[6])
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !twist) return CVO_HIP_ERR_INVALID;
-    for (int k = 0; k < 6; ++k) twist[k] = ctx->lidar_twist[k];
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_lidar_twist(const float T_cam[16], const cvo_fe_lidar *l, float sweep_fraction, float twist[6])
-{
-    if (!T_cam || !l || !twist || !std::isfinite(sweep_fraction) || !(sweep_fraction > 0.0f)) return CVO_HIP_ERR_INVALID;
-    for (int q = 0; q < 16; ++q)
-        if (!std::isfinite(T_cam[q])) return CVO_HIP_ERR_INVALID;
-    cvo_fe_lidar checked = *l;
-    checked.max_points = 1;   // (not read)
-    float Rc[9];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Rc[3 * r + c] = T_cam[4 * r + c];
-    if (!lidar_ok(checked) || !rotation_ok(Rc)) return CVO_HIP_ERR_INVALID;
-    // M = [R | T]^-1 = [R^T | -R^T T]: the later camera's pose in the earlier camera's frame
-    double M[9], m[3];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) M[3 * r + c] = (double)T_cam[4 * c + r];
-        m[r] = -((double)T_cam[r] * T_cam[3] + (double)T_cam[4 + r] * T_cam[7] + (double)T_cam[8 + r] * T_cam[11]);
-    }
-    // X^-1 M X with X = [Rx | Tx]: the rotation Rx^T M Rx, the translation Rx^T (M Tx + m - Tx)
-    double Rx[9], Tx[3], MRx[9], S[9], u[3], t[3];
-    for (int q = 0; q < 9; ++q) Rx[q] = (double)l->R[q];
-    for (int q = 0; q < 3; ++q) Tx[q] = (double)l->T[q];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) MRx[3 * r + c] = M[3 * r] * Rx[c] + M[3 * r + 1] * Rx[3 + c] + M[3 * r + 2] * Rx[6 + c];
-        u[r] = (M[3 * r] * Tx[0] + M[3 * r + 1] * Tx[1] + M[3 * r + 2] * Tx[2]) + m[r] - Tx[r];
-    }
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) S[3 * r + c] = Rx[r] * MRx[c] + Rx[3 + r] * MRx[3 + c] + Rx[6 + r] * MRx[6 + c];
-        t[r] = Rx[r] * u[0] + Rx[3 + r] * u[1] + Rx[6 + r] * u[2];
-    }
-    // the logarithm: w = theta * axis from the antisymmetric part, v = V^-1 t, V^-1 = I - W/2 + k W^2
-    const double ax[3] = {0.5 * (S[7] - S[5]), 0.5 * (S[2] - S[6]), 0.5 * (S[3] - S[1])};   // sin(theta) * axis
-    const double sn = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-    const double cs = 0.5 * ((S[0] + S[4] + S[8]) - 1.0);
-    const double theta = std::atan2(sn, cs);
-    if (!(theta * (double)sweep_fraction <= (double)CVO_FE_SWEEP_MAX_ROTATION)) return CVO_HIP_ERR_INVALID;
-    if (theta > 3.0) return CVO_HIP_ERR_INVALID;   // (too near a half turn for the logarithm, whatever the fraction)
-    const double f = theta < 1e-6 ? 1.0 + theta * theta / 6.0 : theta / sn;   // theta / sin(theta)
-    const double w[3] = {f * ax[0], f * ax[1], f * ax[2]};
-    // (1 - (theta/2) cot(theta/2)) / theta^2, from the angle itself: 1 - cos from the matrix would keep the matrix's rounding
-    const double t2 = theta * theta;
-    const double k = theta < 1e-2 ? 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0
-                                  : (1.0 - 0.5 * theta * std::cos(0.5 * theta) / std::sin(0.5 * theta)) / t2;
-    const double wt[3] = {w[1] * t[2] - w[2] * t[1], w[2] * t[0] - w[0] * t[2], w[0] * t[1] - w[1] * t[0]};
-    const double wwt[3] = {w[1] * wt[2] - w[2] * wt[1], w[2] * wt[0] - w[0] * wt[2], w[0] * wt[1] - w[1] * wt[0]};
-    double out[6];
-    for (int q = 0; q < 3; ++q) {
-        out[q] = w[q] * (double)sweep_fraction;
-        out[3 + q] = ((t[q] - 0.5 * wt[q]) + k * wwt[q]) * (double)sweep_fraction;
-    }
-    float res[6];
-    for (int q = 0; q < 6; ++q) res[q] = (float)out[q];
-    if (!twist_ok(res)) return CVO_HIP_ERR_INVALID;
-    for (int q = 0; q < 6; ++q) twist[q] = res[q];
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_check_stereo_rig(const cvo_fe_stereo_rig *rig) { return rig && srig_ok(*rig) ? CVO_HIP_OK : CVO_HIP_ERR_INVALID; }
-
-int cvo_fe_stereo_rectify(const cvo_fe_stereo_calib *calib, int width, int height, cvo_fe_stereo_rig *out, float depth_scale)
-{
-    static_assert(sizeof(cvo_fe_stereo_calib) == 30 * sizeof(float), "120 bytes, no padding");
-    if (!calib || !out || width < 1 || height < 1) return CVO_HIP_ERR_INVALID;
-    const float *cf = &calib->left.fx;   // floats only
-    for (int q = 0; q < 30; ++q)
-        if (!std::isfinite(cf[q])) return CVO_HIP_ERR_INVALID;
-    if (!std::isfinite(depth_scale) || !(depth_scale > 0.0f)) return CVO_HIP_ERR_INVALID;
-    if (!(calib->left.fx > 0.0f && calib->left.fy > 0.0f && calib->right.fx > 0.0f && calib->right.fy > 0.0f))
-        return CVO_HIP_ERR_INVALID;
-    if (!rotation_ok(calib->R)) return CVO_HIP_ERR_INVALID;
-    // the helper of the rig contract, step by step in float64
-    double R[9], T[3];
-    for (int q = 0; q < 9; ++q) R[q] = (double)calib->R[q];
-    for (int q = 0; q < 3; ++q) T[q] = (double)calib->T[q];
-    // 1: the axis-angle of R
-    const double c = (((R[0] + R[4]) + R[8]) - 1.0) / 2.0;
-    const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-    const double n = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    const double angle = std::atan2(n / 2.0, c);
-    if (!(angle <= 0.5)) return CVO_HIP_ERR_INVALID;
-    double k[3] = {0.0, 0.0, 0.0};
-    if (n > 0.0)
-        for (int q = 0; q < 3; ++q) k[q] = v[q] / n;
-    // 2: half the way each, by Rodrigues' formula
-    const double K[9] = {0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0};
-    double KK[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) KK[3 * i + j] = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
-    double Rl0[9], Rr0[9];
-    const double sl = std::sin(angle / 2.0), cl = 1.0 - std::cos(angle / 2.0);
-    for (int q = 0; q < 9; ++q) {
-        const double eye = (q % 4 == 0) ? 1.0 : 0.0;
-        Rl0[q] = (eye + sl * K[q]) + cl * KK[q];
-        Rr0[q] = (eye - sl * K[q]) + cl * KK[q];
-    }
-    // 3: the direction from the left centre to the right one
-    double t[3];
-    for (int i = 0; i < 3; ++i) t[i] = (Rr0[3 * i] * T[0] + Rr0[3 * i + 1] * T[1]) + Rr0[3 * i + 2] * T[2];
-    const double b = std::sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
-    if (!(b > 0.0)) return CVO_HIP_ERR_INVALID;
-    const double e1[3] = {-t[0] / b, -t[1] / b, -t[2] / b};
-    if (!(e1[0] > 0.0 && e1[0] >= std::fabs(e1[1]) && e1[0] >= std::fabs(e1[2]))) return CVO_HIP_ERR_INVALID;
-    // 4: (0, 0, 1) x e1 = (-e1.y, e1.x, 0)
-    const double n2 = std::sqrt(e1[1] * e1[1] + e1[0] * e1[0]);
-    const double e2[3] = {-e1[1] / n2, e1[0] / n2, 0.0};
-    const double e3[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-    const double W[9] = {e1[0], e1[1], e1[2], e2[0], e2[1], e2[2], e3[0], e3[1], e3[2]};
-    double Rk[2][9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            Rk[0][3 * i + j] = (W[3 * i] * Rl0[j] + W[3 * i + 1] * Rl0[3 + j]) + W[3 * i + 2] * Rl0[6 + j];
-            Rk[1][3 * i + j] = (W[3 * i] * Rr0[j] + W[3 * i + 1] * Rr0[3 + j]) + W[3 * i + 2] * Rr0[6 + j];
-        }
-    // 5, 6: one focal length, and the centre that puts the mean of the two optical axes in the middle of the image
-    const double f = ((double)calib->left.fy + (double)calib->right.fy) / 2.0;
-    const double mx = (f * Rk[0][2] / Rk[0][8] + f * Rk[1][2] / Rk[1][8]) / 2.0;
-    const double my = (f * Rk[0][5] / Rk[0][8] + f * Rk[1][5] / Rk[1][8]) / 2.0;
-    // 7
-    cvo_fe_stereo_rig r{};
-    r.left = calib->left;
-    r.right = calib->right;
-    for (int q = 0; q < 9; ++q) { r.R_left[q] = (float)Rk[0][q]; r.R_right[q] = (float)Rk[1][q]; }
-    r.fx = r.fy = (float)f;
-    r.cx = (float)(((double)width - 1.0) / 2.0 - mx);
-    r.cy = (float)(((double)height - 1.0) / 2.0 - my);
-    r.baseline = (float)b;
-    r.depth_scale = depth_scale;
-    if (!srig_ok(r)) return CVO_HIP_ERR_INVALID;   // (a baseline that rounds to 0, a centre that overflows)
-    *out = r;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_stereo_rig_map(const cvo_fe_stereo_rig *rig, int which, int width, int height, int32_t *qu, int32_t *qv)
-{
-    if (!rig || !qu || !qv || width < 1 || height < 1 || (which != 0 && which != 1) || !srig_ok(*rig)) return CVO_HIP_ERR_INVALID;
-    const Lens lens(which ? rig->right : rig->left);
-    double R[9];
-    for (int q = 0; q < 9; ++q) R[q] = (double)(which ? rig->R_right : rig->R_left)[q];
-    const double fx = (double)rig->fx, fy = (double)rig->fy, cx = (double)rig->cx, cy = (double)rig->cy;
-    const double wmax = (double)width, hmax = (double)height;
-    for (int v = 0; v < height; ++v) {
-        const double yr = ((double)v - cy) / fy;
-        for (int u = 0; u < width; ++u) {
-            const double xr = ((double)u - cx) / fx;
-            // R^T applied to (xr, yr, 1): from the rectified frame back into the camera's
-            const double X = (R[0] * xr + R[3] * yr) + R[6];
-            const double Y = (R[1] * xr + R[4] * yr) + R[7];
-            const double Z = (R[2] * xr + R[5] * yr) + R[8];
-            double us = -1.0, vs = -1.0;
-            if (Z > 0.0) lens.project(X / Z, Y / Z, us, vs);
-            const size_t i = (size_t)v * width + u;
-            map_entry(us, vs, wmax, hmax, qu[i], qv[i]);
-        }
-    }
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_stereo_rig(cvo_fe_ctx *ctx, const cvo_fe_stereo_rig *rig)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: a frame is in flight");
-    if (rig && !srig_ok(*rig))
-        return fail(ctx, CVO_HIP_ERR_INVALID,
-                    "set_stereo_rig: finite members, every fx, fy, depth_scale and baseline positive, R_left and R_right rotations");
-    if (rig && !ctx->has_stereo) return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: stereo is not set (cvo_fe_set_stereo)");
-    if (rig && ctx->custom)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: a camera model is set; the rig is the camera: clear the model first");
-    if (!rig && !ctx->has_srig) return CVO_HIP_OK;
-    if (rig && ctx->has_srig && std::memcmp(rig, &ctx->srig, sizeof(*rig)) == 0) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint8_t> raw_l, raw_r, valid;
-    Dev<int32_t> new_map;
-    if (rig) {
-        const size_t np = (size_t)ctx->np, plane = rect_plane(ctx->np);
-        std::vector<int32_t> map;
-        try { map.resize(4 * plane); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "set_stereo_rig"); }
-        for (int k = 0; k < 2; ++k)
-            if (cvo_fe_stereo_rig_map(rig, k, ctx->d.w, ctx->d.h, map.data() + 2 * k * plane, map.data() + (2 * k + 1) * plane) !=
-                CVO_HIP_OK)
-                return fail(ctx, CVO_HIP_ERR_INVALID, "set_stereo_rig: stereo_rig_map");
-        // (the raw images and the validity plane come with the first rig and stay until it is cleared; the map is new)
-        if ((!ctx->srig_raw_l && !(dev_alloc(raw_l, np * 3) && dev_alloc(raw_r, np * 3) && dev_alloc(valid, plane))) ||
-            !dev_alloc(new_map, 4 * plane))
-            return no_memory(ctx, "set_stereo_rig: device memory for the raw pair, the maps and the validity plane");
-        hipError_t e = hipMemcpy(new_map.get(), map.data(), 4 * plane * sizeof(int32_t), hipMemcpyHostToDevice);
-        // (no frame is in flight: once the stream is idle nothing reads the old maps any more)
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, CVO_HIP_ERR_HIP, "set_stereo_rig: upload of the maps", e);
-        }
-    } else FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->srig_raw_l, raw_l);
-    hand_over(ctx->srig_raw_r, raw_r);
-    hand_over(ctx->srig_valid, valid);
-    ctx->srig_map = std::move(new_map);
-    if (!rig) {   // (given back with the rig)
-        ctx->srig_raw_l.reset();
-        ctx->srig_raw_r.reset();
-        ctx->srig_valid.reset();
-    }
-    ctx->has_srig = rig != nullptr;
-    ctx->srig = rig ? *rig : cvo_fe_stereo_rig{};
-    ctx->table_fx = ctx->table_scale = 0.0f;   // (the table follows the rig's baseline: made again)
-    drop_graphs(ctx);   // (the rig's buffers and numbers are part of a captured graph)
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_stereo_rig(const cvo_fe_ctx *ctx, cvo_fe_stereo_rig *out, int *set)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    *out = ctx->has_srig ? ctx->srig : cvo_fe_stereo_rig{};
-    if (set) *set = ctx->has_srig ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_mask: a frame is in flight");
-    const int w = ctx->d.w, h = ctx->d.h;
-    if (mask && stride < (size_t)w) return fail(ctx, CVO_HIP_ERR_INVALID, "set_mask: stride below the width");
-    if (!mask && !ctx->has_mask) return CVO_HIP_OK;
-    FE_HIP(hipSetDevice(ctx->device));
-    Dev<uint16_t> ungated;
-    Dev<uint8_t> flags, d_mask;
-    Pin<uint8_t> h_mask;
-    if (mask) {
-        const int rc = gate_buffers(ctx, ungated, flags);
-        if (rc) return rc;
-        // (the mask's device plane and its staging image come and go together)
-        if (!ctx->d_mask && !(dev_alloc(d_mask, rect_plane(ctx->np)) && pin_alloc(h_mask, (size_t)ctx->np)))
-            return no_memory(ctx, "set_mask: device and pinned memory for the mask");
-    }
-    // (no frame is in flight: once the stream is idle no upload reads the staging image any more)
-    FE_HIP(hipStreamSynchronize(ctx->stream));
-    hand_over(ctx->ungated, ungated);
-    hand_over(ctx->gate_flags, flags);
-    hand_over(ctx->d_mask, d_mask);
-    hand_over(ctx->h_mask, h_mask);
-    if (mask) {
-        copy_rows(ctx->h_mask.get(), mask, stride, (size_t)w, h);
-        ctx->mask_dirty = true;
-    }
-    // new contents go to the same address: only a mask that appears or disappears changes a frame's sequence
-    if ((mask != nullptr) != ctx->has_mask) {
-        ctx->has_mask = mask != nullptr;
-        drop_graphs(ctx);
-    }
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_camera(cvo_fe_ctx *ctx, const cvo_fe_camera_model *model)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: a frame is in flight");
-    if (model && !model_ok(*model))
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: members must be finite and fx, fy, depth_scale positive");
-    if (model && ctx->has_srig)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: a stereo rig is set and is the camera: clear the rig first");
-    if (!model && !ctx->custom) return CVO_HIP_OK;
-    if (model && ctx->custom && std::memcmp(model, &ctx->cam, sizeof(*model)) == 0) return CVO_HIP_OK;
-    const bool bent = model && distorts(model->dist);
-    if (bent && ctx->has_stereo)
-        return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: stereo is set and takes a rectified pair: dist must be zero");
-    if (bent) {
-        const size_t np = (size_t)ctx->np, plane = rect_plane(ctx->np);
-        std::vector<int32_t> map;
-        try { map.resize(2 * plane); } catch (const std::bad_alloc &) { return fail(ctx, CVO_HIP_ERR_NOMEM, "set_camera"); }
-        if (cvo_fe_rectify_map(model, ctx->d.w, ctx->d.h, map.data(), map.data() + plane) != CVO_HIP_OK)
-            return fail(ctx, CVO_HIP_ERR_INVALID, "set_camera: rectify_map");
-        FE_HIP(hipSetDevice(ctx->device));
-        Dev<uint8_t> raw_img;
-        Dev<uint16_t> raw_depth;
-        Dev<int32_t> new_map;
-        const bool first = !ctx->raw_img;   // (the two raw buffers come and go together)
-        if ((first && !(dev_alloc(raw_img, np * 3) && dev_alloc(raw_depth, np))) || !dev_alloc(new_map, 2 * plane))
-            return no_memory(ctx, "set_camera: device memory for the raw images and the map");
-        hipError_t e = hipMemcpy(new_map.get(), map.data(), 2 * plane * sizeof(int32_t), hipMemcpyHostToDevice);
-        // (no frame is in flight: once the stream is idle nothing reads the old map any more)
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, CVO_HIP_ERR_HIP, "set_camera: upload of the map", e);
-        hand_over(ctx->raw_img, raw_img);
-        hand_over(ctx->raw_depth, raw_depth);
-        ctx->rect_map = std::move(new_map);
-    }
-    ctx->custom = model != nullptr;
-    ctx->cam = model ? *model : cvo_fe_camera_model{};
-    ctx->rectify = bent;
-    drop_graphs(ctx);
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_get_camera(const cvo_fe_ctx *ctx, cvo_fe_camera_model *out, int *custom)
-{
-    cvo_lock::Api api_guard;
-    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
-    float cam[5];
-    camera_in_force(ctx, ctx->p_seq, cam);
-    const float *dist = ctx->cam.dist;   // (all zero without a caller's model, and under a stereo rig: it has none)
-    *out = cvo_fe_camera_model{cam[0], cam[1], cam[2], cam[3], cam[4], {dist[0], dist[1], dist[2], dist[3], dist[4]}};
-    if (custom) *custom = ctx->custom || ctx->has_srig ? 1 : 0;
-    return CVO_HIP_OK;
-}
-
 const char *cvo_fe_last_error(const cvo_fe_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int cvo_fe_destroy(cvo_fe_ctx *ctx)
@@ -2904,21 +1474,6 @@ int cvo_fe_host_buffers(cvo_fe_ctx *ctx, uint8_t **img, uint16_t **depth)
     if (!ctx || !img || !depth) return CVO_HIP_ERR_INVALID;
     *img = img_staging(ctx);
     *depth = (uint16_t *)depth_staging(ctx);
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_device_output(cvo_fe_ctx *ctx, int on)
-{
-    if (!ctx) return CVO_HIP_ERR_INVALID;
-    if (ctx->pending) return fail(ctx, CVO_HIP_ERR_INVALID, "set_device_output: a frame is in flight");
-    ctx->device_output = on != 0;
-    return CVO_HIP_OK;
-}
-
-int cvo_fe_set_num_want(cvo_fe_ctx *ctx, int num_want)
-{
-    if (!ctx || num_want < 1) return CVO_HIP_ERR_INVALID;
-    ctx->num_want = num_want;
     return CVO_HIP_OK;
 }
 
@@ -3349,22 +1904,9 @@ int project_points(int device, const void *points, size_t stride_bytes, int n, c
     LD_TRY(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
     LD_TRY(hipMemcpyAsync(c.scan.get(), scan.data(), scan_bytes, hipMemcpyHostToDevice, c.s));
     LD_TRY(hipMemsetAsync(c.z.get(), 0xFF, cells * sizeof(uint32_t), c.s));
-    if (n > 0) {
-        FeLidarProjectArgs a{};
-        a.count = (const int32_t *)c.scan.get(); a.points = (const float *)(c.scan.get() + FE_LIDAR_HEADER);
-        a.z = c.z.get(); a.capacity = n; a.w = width; a.h = height; a.splat = l->splat;
-        a.min_range = l->min_range; a.max_range = l->max_range;
-        for (int q = 0; q < 9; ++q) a.R[q] = l->R[q];
-        for (int q = 0; q < 3; ++q) a.T[q] = l->T[q];
-        for (int q = 0; q < 5; ++q) a.cam[q] = cam[q];
-        if (sw) {
-            FeLidarSweepArgs sa{};
-            sa.base = a;
-            sweep_args(sa, *sw, phase ? c.phase.get() : nullptr, moved ? c.phase.get() + n : nullptr);
-            fe_lidar_project_sweep_enqueue(sw->mode, sa, c.s);
-        } else
-            fe_lidar_project_enqueue(a, c.s);
-    }
+    if (n > 0)
+        enqueue_lidar_project(*l, cam, c.scan.get(), n, c.z.get(), width, height, sw, phase ? c.phase.get() : nullptr,
+                              moved ? c.phase.get() + n : nullptr, c.s);
     hipLaunchKernelGGL(k_fe_depth_final, dim3(blocks((np + 3) / 4)), dim3(FE_BLOCK), 0, c.s, c.z.get(), np, d_p0);
     if (cull) {
         FeLidarCullArgs g{};

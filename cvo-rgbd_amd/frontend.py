@@ -351,21 +351,20 @@ def lib():
         L.cvo_fe_read_stage.argtypes = [vp, C.c_int, vp, C.c_size_t]
         L.cvo_fe_random_pattern.argtypes = [C.c_int, u8p]
         L.cvo_fe_camera.argtypes = [C.c_int, fp]
-        L.cvo_fe_set_camera.argtypes = [vp, C.POINTER(CameraModel)]
-        L.cvo_fe_get_camera.argtypes = [vp, C.POINTER(CameraModel), C.POINTER(C.c_int)]
+        # the settings that are structures: cvo_fe_set_<name>, cvo_fe_get_<name> and, but for the camera, cvo_fe_check_<check>
+        for name, cls, check in (("camera", CameraModel, None), ("depth_camera", DepthCamera, "depth_camera"),
+                                 ("depth_gate", DepthGate, "depth_gate"), ("stereo", Stereo, "stereo"),
+                                 ("stereo_speckle", Speckle, "speckle"), ("depth_median", DepthMedian, "depth_median"),
+                                 ("depth_infill", DepthInfill, "depth_infill"), ("lidar", Lidar, "lidar"),
+                                 ("lidar_sweep", LidarSweep, "lidar_sweep"), ("stereo_rig", StereoRig, "stereo_rig")):
+            getattr(L, "cvo_fe_set_" + name).argtypes = [vp, C.POINTER(cls)]
+            getattr(L, "cvo_fe_get_" + name).argtypes = [vp, C.POINTER(cls), C.POINTER(C.c_int)]
+            if check:
+                getattr(L, "cvo_fe_check_" + check).argtypes = [C.POINTER(cls)]
         L.cvo_fe_rectify_map.argtypes = [C.POINTER(CameraModel), C.c_int, C.c_int, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32)]
-        L.cvo_fe_set_depth_camera.argtypes = [vp, C.POINTER(DepthCamera)]
-        L.cvo_fe_get_depth_camera.argtypes = [vp, C.POINTER(DepthCamera), C.POINTER(C.c_int)]
         L.cvo_fe_depth_rays.argtypes = [C.POINTER(DepthCamera), fp, fp]
-        L.cvo_fe_check_depth_camera.argtypes = [C.POINTER(DepthCamera)]
-        L.cvo_fe_set_depth_gate.argtypes = [vp, C.POINTER(DepthGate)]
-        L.cvo_fe_get_depth_gate.argtypes = [vp, C.POINTER(DepthGate), C.POINTER(C.c_int)]
-        L.cvo_fe_check_depth_gate.argtypes = [C.POINTER(DepthGate)]
         L.cvo_fe_set_mask.argtypes = [vp, u8p, C.c_size_t]
-        L.cvo_fe_check_stereo.argtypes = [C.POINTER(Stereo)]
-        L.cvo_fe_set_stereo.argtypes = [vp, C.POINTER(Stereo)]
-        L.cvo_fe_get_stereo.argtypes = [vp, C.POINTER(Stereo), C.POINTER(C.c_int)]
         L.cvo_fe_submit_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int]
         L.cvo_fe_create_pointcloud_stereo.argtypes = [vp, u8p, C.c_size_t, u8p, C.c_size_t, C.c_int, C.c_int, fp, fp,
                                                       C.c_int, C.POINTER(C.c_int)]
@@ -375,17 +374,8 @@ def lib():
         L.cvo_fe_check_select_mode.argtypes = [C.c_int]
         L.cvo_fe_set_select_mode.argtypes = [vp, C.c_int]
         L.cvo_fe_get_select_mode.argtypes = [vp, C.POINTER(C.c_int)]
-        L.cvo_fe_check_speckle.argtypes = [C.POINTER(Speckle)]
-        L.cvo_fe_set_stereo_speckle.argtypes = [vp, C.POINTER(Speckle)]
-        L.cvo_fe_get_stereo_speckle.argtypes = [vp, C.POINTER(Speckle), C.POINTER(C.c_int)]
         L.cvo_fe_filter_speckles.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Speckle),
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
-        L.cvo_fe_check_depth_median.argtypes = [C.POINTER(DepthMedian)]
-        L.cvo_fe_set_depth_median.argtypes = [vp, C.POINTER(DepthMedian)]
-        L.cvo_fe_get_depth_median.argtypes = [vp, C.POINTER(DepthMedian), C.POINTER(C.c_int)]
-        L.cvo_fe_check_depth_infill.argtypes = [C.POINTER(DepthInfill)]
-        L.cvo_fe_set_depth_infill.argtypes = [vp, C.POINTER(DepthInfill)]
-        L.cvo_fe_get_depth_infill.argtypes = [vp, C.POINTER(DepthInfill), C.POINTER(C.c_int)]
         L.cvo_fe_infill_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthInfill), u8p,
                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.cvo_fe_median_plane.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(DepthMedian), u8p,
@@ -395,17 +385,11 @@ def lib():
         L.cvo_fe_set_pixel_format.argtypes = [vp, C.c_int]
         L.cvo_fe_get_pixel_format.argtypes = [vp, C.POINTER(C.c_int)]
         L.cvo_fe_unpack_image.argtypes = [C.c_int, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p]
-        L.cvo_fe_check_lidar.argtypes = [C.POINTER(Lidar)]
-        L.cvo_fe_set_lidar.argtypes = [vp, C.POINTER(Lidar)]
-        L.cvo_fe_get_lidar.argtypes = [vp, C.POINTER(Lidar), C.POINTER(C.c_int)]
         L.cvo_fe_submit_lidar.argtypes = [vp, u8p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]
         L.cvo_fe_create_pointcloud_lidar.argtypes = [vp, u8p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                                      fp, fp, C.c_int, C.POINTER(C.c_int)]
         L.cvo_fe_project_points.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Lidar), fp, C.c_int, C.c_int,
                                             u16p, u16p, u8p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.cvo_fe_check_lidar_sweep.argtypes = [C.POINTER(LidarSweep)]
-        L.cvo_fe_set_lidar_sweep.argtypes = [vp, C.POINTER(LidarSweep)]
-        L.cvo_fe_get_lidar_sweep.argtypes = [vp, C.POINTER(LidarSweep), C.POINTER(C.c_int)]
         L.cvo_fe_set_lidar_motion.argtypes = [vp, fp]
         L.cvo_fe_get_lidar_motion.argtypes = [vp, fp]
         L.cvo_fe_lidar_twist.argtypes = [fp, C.POINTER(Lidar), C.c_float, fp]
@@ -413,9 +397,6 @@ def lib():
                                                   C.c_int, u16p, u16p, u8p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                   C.POINTER(LidarSweep), fp, fp, fp]
         L.cvo_fe_stereo_depth_table.argtypes = [C.POINTER(Stereo), C.c_float, C.c_float, u16p]
-        L.cvo_fe_set_stereo_rig.argtypes = [vp, C.POINTER(StereoRig)]
-        L.cvo_fe_get_stereo_rig.argtypes = [vp, C.POINTER(StereoRig), C.POINTER(C.c_int)]
-        L.cvo_fe_check_stereo_rig.argtypes = [C.POINTER(StereoRig)]
         L.cvo_fe_stereo_rectify.argtypes = [C.POINTER(StereoCalib), C.c_int, C.c_int, C.POINTER(StereoRig), C.c_float]
         L.cvo_fe_stereo_rig_map.argtypes = [C.POINTER(StereoRig), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32)]
@@ -849,6 +830,21 @@ class PcdGenerator:
             raise capi.CvoHipError("%s: %s (%s)" % (what, capi.lib().cvo_hip_error_string(st).decode(),
                                                      msg.decode() if msg else ""))
 
+    def _set_struct(self, name, obj):
+        """cvo_fe_set_<name> with a settings structure, or None: the setting cleared."""
+        self._chk(getattr(lib(), "cvo_fe_set_" + name)(self._h, None if obj is None else C.byref(obj)), "set_" + name)
+
+    def _get_struct(self, name, cls):
+        """cvo_fe_get_<name>: the structure in force, or None where the library says "not set"."""
+        out, isset = cls(), C.c_int(0)
+        self._chk(getattr(lib(), "cvo_fe_get_" + name)(self._h, C.byref(out), C.byref(isset)), "get_" + name)
+        return out if isset.value else None
+
+    def _get_int(self, name, ctype):
+        out = ctype(0)
+        self._chk(getattr(lib(), "cvo_fe_get_" + name)(self._h, C.byref(out)), "get_" + name)
+        return int(out.value)
+
     def _images(self, bgr, depth):
         """The two images of a frame as dense arrays of the sizes the context takes."""
         bgr = self._image(bgr)
@@ -948,13 +944,11 @@ class PcdGenerator:
         """A CameraModel for every following frame (their `dataset_seq` is then ignored); None: back
         to the reference's table.  A model with distortion makes each frame start with the
         rectification of both images on the device."""
-        self._chk(lib().cvo_fe_set_camera(self._h, None if model is None else C.byref(model)), "set_camera")
+        self._set_struct("camera", model)
 
     def camera(self):
         """The CameraModel set, or None while the table is in use."""
-        out, custom = CameraModel(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_camera(self._h, C.byref(out), C.byref(custom)), "get_camera")
-        return out if custom.value else None
+        return self._get_struct("camera", CameraModel)
 
     rectify_map = staticmethod(rectify_map)
 
@@ -962,14 +956,12 @@ class PcdGenerator:
         """A DepthCamera for every following frame: their `depth` is then rig.height x rig.width and is
         registered into the colour camera's frame on the device (the registration contract of
         include/cvo_frontend.h); None: depth is registered to colour already, as for a new object."""
-        self._chk(lib().cvo_fe_set_depth_camera(self._h, None if rig is None else C.byref(rig)), "set_depth_camera")
+        self._set_struct("depth_camera", rig)
         self._dshape = (self.height, self.width) if rig is None else (int(rig.height), int(rig.width))
 
     def depth_camera(self):
         """The DepthCamera set, or None."""
-        out, isset = DepthCamera(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_depth_camera(self._h, C.byref(out), C.byref(isset)), "get_depth_camera")
-        return out if isset.value else None
+        return self._get_struct("depth_camera", DepthCamera)
 
     depth_rays = staticmethod(depth_rays)
 
@@ -977,13 +969,11 @@ class PcdGenerator:
         """A DepthGate for every following frame: pixels out of range or on / within `grow` of a depth
         discontinuity give no point (the gate contract of include/cvo_frontend.h); None: no gate, as for a
         new object."""
-        self._chk(lib().cvo_fe_set_depth_gate(self._h, None if gate is None else C.byref(gate)), "set_depth_gate")
+        self._set_struct("depth_gate", gate)
 
     def depth_gate(self):
         """The DepthGate set, or None."""
-        out, isset = DepthGate(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_depth_gate(self._h, C.byref(out), C.byref(isset)), "get_depth_gate")
-        return out if isset.value else None
+        return self._get_struct("depth_gate", DepthGate)
 
     def set_mask(self, mask):
         """A mask for every following frame: h x w uint8 or bool on the grid of the colour image as uploaded
@@ -1005,14 +995,12 @@ class PcdGenerator:
         """A Stereo for every following frame: a frame is then a rectified stereo pair (submit_stereo /
         create_pointcloud_stereo) and a semi-global matcher on the device fills the depth plane (the stereo contract
         of include/cvo_frontend.h); None: back to depth images, as for a new object."""
-        self._chk(lib().cvo_fe_set_stereo(self._h, None if stereo is None else C.byref(stereo)), "set_stereo")
+        self._set_struct("stereo", stereo)
         self._max_disp = 0 if stereo is None else int(stereo.max_disp)
 
     def stereo(self):
         """The Stereo set, or None."""
-        out, isset = Stereo(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_stereo(self._h, C.byref(out), C.byref(isset)), "get_stereo")
-        return out if isset.value else None
+        return self._get_struct("stereo", Stereo)
 
     def set_stereo_paths(self, mask):
         """The path mask of the matcher for every following stereo frame (step 4 of the stereo contract): PATHS_4 (a new
@@ -1025,72 +1013,59 @@ class PcdGenerator:
 
     def stereo_paths(self):
         """The path mask in force."""
-        out = C.c_uint32(0)
-        self._chk(lib().cvo_fe_get_stereo_paths(self._h, C.byref(out)), "get_stereo_paths")
-        return int(out.value)
+        return self._get_int("stereo_paths", C.c_uint32)
 
     def set_stereo_speckle(self, speckle):
         """A Speckle for every following stereo frame: components of the disparity plane of `max_size` pixels at the
         most lose their disparity and their depth (the speckle contract of include/cvo_frontend.h); None: no filter, as
         for a new object.  A setting of its own: it may be made with or without stereo set and survives set_stereo()."""
-        self._chk(lib().cvo_fe_set_stereo_speckle(self._h, None if speckle is None else C.byref(speckle)),
-                  "set_stereo_speckle")
+        self._set_struct("stereo_speckle", speckle)
 
     def stereo_speckle(self):
         """The Speckle set, or None."""
-        out, isset = Speckle(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_stereo_speckle(self._h, C.byref(out), C.byref(isset)), "get_stereo_speckle")
-        return out if isset.value else None
+        return self._get_struct("stereo_speckle", Speckle)
 
     def set_depth_median(self, median):
         """A DepthMedian for every following frame of any kind: the depth plane passes the median stage in front of the
         gate (the median contract of include/cvo_frontend.h); None: no filter, as for a new object.  A setting of its
         own: it survives every other setter."""
-        self._chk(lib().cvo_fe_set_depth_median(self._h, None if median is None else C.byref(median)), "set_depth_median")
+        self._set_struct("depth_median", median)
 
     def depth_median(self):
         """The DepthMedian set, or None."""
-        out, isset = DepthMedian(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_depth_median(self._h, C.byref(out), C.byref(isset)), "get_depth_median")
-        return out if isset.value else None
+        return self._get_struct("depth_median", DepthMedian)
 
     def set_depth_infill(self, infill):
         """A DepthInfill for every following frame of any kind: the depth plane passes the infill stage directly behind
         whatever fills it (the infill contract of include/cvo_frontend.h); None: no stage, as for a new object.  A setting
         of its own: it survives every other setter."""
-        self._chk(lib().cvo_fe_set_depth_infill(self._h, None if infill is None else C.byref(infill)), "set_depth_infill")
+        self._set_struct("depth_infill", infill)
 
     def depth_infill(self):
         """The DepthInfill set, or None."""
-        out, isset = DepthInfill(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_depth_infill(self._h, C.byref(out), C.byref(isset)), "get_depth_infill")
-        return out if isset.value else None
+        return self._get_struct("depth_infill", DepthInfill)
 
     def set_lidar(self, lidar):
         """A Lidar for every following frame: a frame is then a colour image and a scan (submit_lidar /
         create_pointcloud_lidar), projected into the colour camera on the device (the LiDAR contract of
         include/cvo_frontend.h); None: back to depth images, as for a new object.  Refused beside stereo and a depth
         camera, and they beside it."""
-        self._chk(lib().cvo_fe_set_lidar(self._h, None if lidar is None else C.byref(lidar)), "set_lidar")
+        self._set_struct("lidar", lidar)
 
     def lidar(self):
         """The Lidar set, or None."""
-        out, isset = Lidar(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_lidar(self._h, C.byref(out), C.byref(isset)), "get_lidar")
-        return out if isset.value else None
+        return self._get_struct("lidar", Lidar)
 
     def set_lidar_sweep(self, sweep):
         """A LidarSweep for the scan source: every point of a frame's scan is moved into the scanner's frame at the
         instant of the colour image, by the twist of set_lidar_motion(), before it is projected (the sweep contract of
         include/cvo_frontend.h); None: no motion compensation, as for a new object.  Needs a scan source and goes
         with it; the twist is zero afterwards."""
-        self._chk(lib().cvo_fe_set_lidar_sweep(self._h, None if sweep is None else C.byref(sweep)), "set_lidar_sweep")
+        self._set_struct("lidar_sweep", sweep)
 
     def lidar_sweep(self):
         """The LidarSweep set, or None."""
-        out, isset = LidarSweep(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_lidar_sweep(self._h, C.byref(out), C.byref(isset)), "get_lidar_sweep")
-        return out if isset.value else None
+        return self._get_struct("lidar_sweep", LidarSweep)
 
     def set_lidar_motion(self, twist):
         """The scanner's own motion over one full sweep, in its own frame, for the frames submitted from now on: w
@@ -1142,9 +1117,7 @@ class PcdGenerator:
 
     def pixel_format(self):
         """The pixel format in force."""
-        out = C.c_int(0)
-        self._chk(lib().cvo_fe_get_pixel_format(self._h, C.byref(out)), "get_pixel_format")
-        return int(out.value)
+        return self._get_int("pixel_format", C.c_int)
 
     def create_pointcloud_lidar(self, bgr, points, dataset_seq=4, feature_type=FEATURES_RGB):
         """create_pointcloud() for a colour image and a scan: `points` is n x k float32, x y z first (KITTI's .bin read
@@ -1178,21 +1151,17 @@ class PcdGenerator:
 
     def select_mode(self):
         """The selector's mode in force."""
-        out = C.c_int(0)
-        self._chk(lib().cvo_fe_get_select_mode(self._h, C.byref(out)), "get_select_mode")
-        return int(out.value)
+        return self._get_int("select_mode", C.c_int)
 
     def set_stereo_rig(self, rig):
         """A StereoRig for every following frame: submit_stereo / create_pointcloud_stereo then take the RAW pair and
         both images are rectified on the device in front of the matcher (the rig contract of include/cvo_frontend.h);
         the rig is the camera of the frame.  Stereo must be set and no camera model; None: rectified pairs again."""
-        self._chk(lib().cvo_fe_set_stereo_rig(self._h, None if rig is None else C.byref(rig)), "set_stereo_rig")
+        self._set_struct("stereo_rig", rig)
 
     def stereo_rig(self):
         """The StereoRig set, or None."""
-        out, isset = StereoRig(), C.c_int(0)
-        self._chk(lib().cvo_fe_get_stereo_rig(self._h, C.byref(out), C.byref(isset)), "get_stereo_rig")
-        return out if isset.value else None
+        return self._get_struct("stereo_rig", StereoRig)
 
     stereo_rig_map = staticmethod(stereo_rig_map)
 

@@ -1,8 +1,8 @@
 """A numpy restatement of the front end's registration contract (include/cvo_frontend.h, at
 cvo_fe_depth_camera): the ray table in float64 and the forward warp with its z-buffer in
 float32 (numpy never contracts into an FMA; its float32 division and np.rint are IEEE's).  The
-order of operations below is the contract; csrc/cvo_frontend.hip repeats it line by line in
-cvo_fe_depth_rays and k_fe_depth_warp.
+order of operations below is the contract; csrc/cvo_fe_calib.cpp repeats it line by line in
+cvo_fe_depth_rays and csrc/cvo_frontend.hip in k_fe_depth_warp.
 
 A rig here is a dict with the members of cvo_fe_depth_camera (R as nine numbers, row-major);
 a colour camera is (depth_scale, fx, fy, cx, cy).  Their numbers count as float32, as the

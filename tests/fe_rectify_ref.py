@@ -1,7 +1,7 @@
 """A numpy restatement of the front end's rectification contract (include/cvo_frontend.h,
 at cvo_fe_camera_model): the map, the colour taps and the depth tap.  float64 for the map
 (numpy never contracts into an FMA), integers after it.  The order of operations below is
-the contract; csrc/cvo_frontend.hip repeats it line by line in cvo_fe_rectify_map.
+the contract; csrc/cvo_fe_calib.cpp repeats it line by line in cvo_fe_rectify_map.
 
 A model here is (depth_scale, fx, fy, cx, cy, (k1, k2, p1, p2, k3)); its numbers count as
 float32, as the library's struct holds them."""
