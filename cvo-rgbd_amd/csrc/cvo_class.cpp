@@ -63,7 +63,7 @@ registration::registration(int mode, int device, void *stream)
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
       depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), lidar_sweep_(), have_lidar_sweep_(false), lidar_motion_(), select_mode_(CVO_FE_SELECT_IMAGE),
-      pixel_format_(CVO_FE_PIXEL_BGR8), depth_format_(CVO_FE_DEPTH_U16), depth_unit_(1.0f)
+      pixel_format_(CVO_FE_PIXEL_BGR8), depth_format_(CVO_FE_DEPTH_U16), depth_unit_(1.0f), binning_(), have_binning_(false)
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -88,6 +88,8 @@ void registration::fe_check(int rc, const char *what, const char *why)
 void registration::apply_stored_settings()
 {
     try {
+        // (in front of the pixel format, which is then checked at the input size)
+        if (have_binning_) fe_check(cvo_fe_set_input_binning(fe_, &binning_), "cvo_fe_set_input_binning");
         if (have_camera_) fe_check(cvo_fe_set_camera(fe_, &camera_), "cvo_fe_set_camera");
         if (have_depth_camera_) fe_check(cvo_fe_set_depth_camera(fe_, &depth_camera_), "cvo_fe_set_depth_camera");
         if (have_depth_gate_) fe_check(cvo_fe_set_depth_gate(fe_, &depth_gate_), "cvo_fe_set_depth_gate");
@@ -140,14 +142,18 @@ void registration::cloud_from_images(int dataset_seq, const image_view &rgb, con
                                         : "set_pcd(): colour and depth image must have the same size");
     if (own_size && (dep.rows != depth_camera_.height || dep.cols != depth_camera_.width))
         throw std::runtime_error("set_pcd(): the depth image must have the depth camera's size");
+    // (input binning: the images are factor times the front end's size each way)
+    const int bin = have_binning_ ? binning_.factor : 1;
     if (!fe_) {
-        const int rc = cvo_fe_create(device_, nullptr, rgb.cols, rgb.rows, &fe_);
+        if (rgb.cols % bin != 0 || rgb.rows % bin != 0)
+            throw std::runtime_error("set_pcd(): the image size is no multiple of the input binning's factor");
+        const int rc = cvo_fe_create(device_, nullptr, rgb.cols / bin, rgb.rows / bin, &fe_);
         if (rc != CVO_HIP_OK) throw std::runtime_error(std::string("cvo_fe_create: ") + cvo_hip_error_string(rc));
-        fe_w_ = rgb.cols; fe_h_ = rgb.rows;
+        fe_w_ = rgb.cols / bin; fe_h_ = rgb.rows / bin;
         cvo_fe_set_device_output(fe_, 1);
         apply_stored_settings();
     }
-    if (rgb.cols != fe_w_ || rgb.rows != fe_h_)
+    if (rgb.cols != bin * fe_w_ || rgb.rows != bin * fe_h_)
         throw std::runtime_error("set_pcd(): the image size changed within a sequence");
     const int ftype = params_.mode == CVO_HIP_MODE_ACVO ? CVO_FE_FEATURES_HSV : CVO_FE_FEATURES_RGB;
     int rc = scan   ? cvo_fe_submit_lidar(fe_, (const uint8_t *)rgb.data, rgb.step, scan->points, scan->stride_bytes,
@@ -324,6 +330,19 @@ void registration::set_pixel_format(int format)
         throw std::runtime_error("set_pixel_format(): one of CVO_FE_PIXEL_*");
     if (fe_) fe_check(cvo_fe_set_pixel_format(fe_, format), "cvo_fe_set_pixel_format");
     pixel_format_ = format;
+}
+
+void registration::set_input_binning(const cvo_fe_binning &binning)
+{
+    // (before the first image there is no size yet: 1 x 1 fits every factor, and a size over the limit throws when that
+    // image creates the front end)
+    if (!fe_ && cvo_fe_check_binning(&binning, 1, 1) != CVO_HIP_OK) throw refused("set_input_binning", rules::binning);
+    store<cvo_fe_binning>(cvo_fe_set_input_binning, "cvo_fe_set_input_binning", &binning, binning_, have_binning_);
+}
+
+void registration::clear_input_binning()
+{
+    store<cvo_fe_binning>(cvo_fe_set_input_binning, "cvo_fe_set_input_binning", nullptr, binning_, have_binning_);
 }
 
 void registration::set_depth_format(int format, float unit)

@@ -100,7 +100,7 @@ struct cvo_fe_ctx {
     // the caller's depth camera (cvo_fe_set_depth_camera); without one depth is registered to colour
     cvo_fe_depth_camera rig{};
     bool has_rig = false;      // frames start with k_fe_depth_warp / k_fe_depth_final
-    int dw = 0, dh = 0;        // the size of the depth image a frame takes: the rig's, or the context's
+    int dw = 0, dh = 0;        // the size of the depth image a frame takes: the rig's, or the colour image's (iw x ih below)
     // with the first rig: the upload target of the depth image, the ray table and the z-buffer
     Dev<uint16_t> rig_depth;
     Dev<float2> rays;          // (dh + 1) * (dw + 1)
@@ -200,6 +200,16 @@ struct cvo_fe_ctx {
     // the frame being submitted takes its images from the caller's device memory (cvo_fe_submit_device): they are
     // brought to the landing buffers in front of the frame, and the frame's sequence holds no upload of them
     bool dev_in = false;
+    // input binning (cvo_fe_set_input_binning): a setting of the context, read by every frame; with it the caller's
+    // images are iw x ih = f * (w x h), the upload and the two kernels in front of the bin (k_fe_unpack,
+    // k_fe_depth_convert) fill the input-size buffers below, and k_fe_bin of cvo_bin.hip writes where they land otherwise
+    cvo_fe_binning bin{};
+    bool has_bin = false;
+    int iw = 0, ih = 0;        // the size of the colour image a frame takes: f * the context's, or the context's
+    // with the setting, and gone with it: the input-size colour image, the right one's (a context that has had stereo
+    // set) and the depth image
+    Dev<uint8_t> full_img, full_right;
+    Dev<uint16_t> full_depth;
     std::string err;
 };
 
@@ -312,8 +322,9 @@ inline bool unpacks(const cvo_fe_ctx *ctx) { return ctx->pixfmt != CVO_FE_PIXEL_
 // pixel format; and the right image's under stereo
 inline uint8_t *img_staging(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->h_packed.get() : ctx->h_img.get(); }
 inline uint8_t *right_staging(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->h_packed_r.get() : ctx->h_right.get(); }
-inline size_t img_row(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_row : (size_t)ctx->d.w * 3; }
-inline int img_rows(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_rows : ctx->d.h; }
+// (under input binning the image is iw x ih, and the packed layout is that size's)
+inline size_t img_row(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_row : (size_t)ctx->iw * 3; }
+inline int img_rows(const cvo_fe_ctx *ctx) { return unpacks(ctx) ? ctx->pix_rows : ctx->ih; }
 
 // where the colour image lands on the device (an upload, or k_fe_unpack's output): the stereo rig's raw buffer, else the
 // raw image k_fe_rectify resamples, else the image every later stage reads; and the right image of a stereo frame
@@ -322,6 +333,15 @@ inline uint8_t *img_landing(const cvo_fe_ctx *ctx)
     return ctx->has_srig ? ctx->srig_raw_l.get() : ctx->rectify ? ctx->raw_img.get() : ctx->img.get();
 }
 inline uint8_t *right_landing(const cvo_fe_ctx *ctx) { return ctx->has_srig ? ctx->srig_raw_r.get() : ctx->right_img.get(); }
+
+// Input binning: the bin's inputs.  A depth image is binned where the frame has one of the context's own size: not
+// under a depth camera (its image keeps the rig's size), stereo or a scan source (no depth image).  The buffer an
+// upload, a device frame's copy, k_fe_unpack or k_fe_depth_convert fills: the input-size one under binning, else the
+// landing buffer itself
+inline bool bins_depth(const cvo_fe_ctx *ctx) { return ctx->has_bin && !ctx->has_rig && !ctx->has_stereo && !ctx->has_lidar; }
+inline uint8_t *img_input(const cvo_fe_ctx *ctx) { return ctx->has_bin ? ctx->full_img.get() : img_landing(ctx); }
+inline uint8_t *right_input(const cvo_fe_ctx *ctx) { return ctx->has_bin ? ctx->full_right.get() : right_landing(ctx); }
+inline uint16_t *depth_input(const cvo_fe_ctx *ctx) { return bins_depth(ctx) ? ctx->full_depth.get() : depth_upload(ctx); }
 
 // under a float depth format: the bytes of one value, and the staging a frame's depth image is copied to and uploaded from
 inline bool converts(const cvo_fe_ctx *ctx) { return ctx->depthfmt != CVO_FE_DEPTH_U16; }

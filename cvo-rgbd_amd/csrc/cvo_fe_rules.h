@@ -29,6 +29,8 @@ constexpr const char *lidar =
 constexpr const char *lidar_motion = "finite members, |w| <= 1 radian and |v| <= 64 metres per sweep";
 constexpr const char *stereo_rig =
     "finite members, every fx, fy, depth_scale and baseline positive, R_left and R_right rotations";
+constexpr const char *binning =
+    "factor 2, 3 or 4, depth_min in [1, factor^2], pad_ 0, factor times the context's width and height at most 8192";
 // The predicates (cvo_fe_settings.cpp), for the setters and for the host-only helpers that take the same structures.
 bool model_ok(const cvo_fe_camera_model &m);
 bool rotation_ok(const float R[9]);

@@ -288,7 +288,7 @@ int cvo_fe_set_depth_camera(cvo_fe_ctx *ctx, const cvo_fe_depth_camera *rig)
         return fail(ctx, CVO_HIP_ERR_INVALID, "set_depth_camera: a scan source is set, there is no depth image");
     if (same_setting(rig, ctx->has_rig, ctx->rig)) return CVO_HIP_OK;
     FE_HIP(hipSetDevice(ctx->device));
-    const int dw = rig ? rig->width : ctx->d.w, dh = rig ? rig->height : ctx->d.h;
+    const int dw = rig ? rig->width : ctx->iw, dh = rig ? rig->height : ctx->ih;   // (without a rig: the input size)
     const size_t dnp = (size_t)dw * dh;
     Dev<uint16_t> new_depth;
     Pin<uint16_t> new_host;
@@ -375,18 +375,23 @@ int cvo_fe_set_stereo(cvo_fe_ctx *ctx, const cvo_fe_stereo *st)
     Pin<uint16_t> h_table;
     Dev<uint8_t> packed_r;   // (under a pixel format: the right image arrives packed as the left one does)
     Pin<uint8_t> h_packed_r;
+    Dev<uint8_t> full_right;
     if (st) {
         // (all but the cost sums come with the first settings and stay; the table has room for the largest max_disp)
         if (!ctx->right_img &&
-            !(dev_alloc(right_img, np * 3) && dev_alloc(right_gray, np) && dev_alloc(flags, np) && pin_alloc(h_right, np * 3) &&
+            !(dev_alloc(right_img, np * 3) && dev_alloc(right_gray, np) && dev_alloc(flags, np) && pin_alloc(h_right, (size_t)ctx->iw * ctx->ih * 3) &&
               dev_alloc(census, 2 * np) && dev_alloc(disparity, np) && dev_alloc(win, np) && dev_alloc(table, 16 * 128) &&
               pin_alloc(h_table, 16 * 128)))
             return no_memory(ctx, "set_stereo: device and pinned memory for the right image and the matcher's planes");
         if ((!ctx->sgm_sum || !ctx->has_stereo || st->max_disp != ctx->stereo.max_disp) && !dev_alloc(sum, np * (size_t)st->max_disp))
             return no_memory(ctx, "set_stereo: device memory for the cost sums");
         if (packed_right_buffers(ctx, packed_r, h_packed_r) != CVO_HIP_OK) return CVO_HIP_ERR_NOMEM;
+        // (under input binning: the right image arrives at the input size as the left one does)
+        if (ctx->has_bin && !ctx->full_right && !dev_alloc(full_right, (size_t)ctx->iw * ctx->ih * 3))
+            return no_memory(ctx, "set_stereo: device memory for the input-size right image");
     }
     if (const int rc = settle(ctx, "set_stereo")) return rc;
+    hand_over(ctx->full_right, full_right);
     hand_over(ctx->right_img, right_img);
     hand_over(ctx->right_gray, right_gray);
     hand_over(ctx->stereo_flags, flags);
@@ -488,7 +493,7 @@ int cvo_fe_set_pixel_format(cvo_fe_ctx *ctx, int format)
     if (const int rc = setter_begin(ctx, "set_pixel_format")) return rc;
     size_t row = 0;
     int rows = 0;
-    if (!fe_unpack_layout(format, ctx->d.w, ctx->d.h, &row, &rows))
+    if (!fe_unpack_layout(format, ctx->iw, ctx->ih, &row, &rows))   // (under input binning: the input size)
         return refuse(ctx, "set_pixel_format", "a CVO_FE_PIXEL_* format that fits the context's size (YUY2, UYVY: an even width; "
                                                "NV12: an even width and height)");
     if (format == ctx->pixfmt) return CVO_HIP_OK;
@@ -509,6 +514,94 @@ int cvo_fe_set_pixel_format(cvo_fe_ctx *ctx, int format)
     ctx->pix_row = on ? row : 0;
     ctx->pix_rows = on ? rows : 0;
     drop_graphs(ctx);   // (whether a frame has the stage's launch, its instance and what is uploaded are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_input_binning(const Ctx *c, cvo_fe_binning *out, int *set) { return get_setting(c, &Ctx::has_bin, &Ctx::bin, out, set); }
+
+int cvo_fe_set_input_binning(cvo_fe_ctx *ctx, const cvo_fe_binning *b)
+{
+    cvo_lock::Api api_guard;
+    if (const int rc = setter_begin(ctx, "set_input_binning")) return rc;
+    if (b && cvo_fe_check_binning(b, ctx->d.w, ctx->d.h) != CVO_HIP_OK) return refuse(ctx, "set_input_binning", rules::binning);
+    const int iw = (b ? b->factor : 1) * ctx->d.w, ih = (b ? b->factor : 1) * ctx->d.h;
+    size_t row = 0;
+    int rows = 0;
+    if (unpacks(ctx) && !fe_unpack_layout(ctx->pixfmt, iw, ih, &row, &rows))
+        return refuse(ctx, "set_input_binning", "the pixel format in force does not fit the input size, factor times the context's");
+    if (same_setting(b, ctx->has_bin, ctx->bin)) return CVO_HIP_OK;
+    FE_HIP(hipSetDevice(ctx->device));
+    // Everything that holds a caller's image follows the input size: the staging of the colour image, of the right one
+    // (a context that has had stereo set), of the depth image (unless a depth camera sizes it), the float and the
+    // packed images.  A change of depth_min alone builds nothing.
+    const bool resize = iw != ctx->iw || ih != ctx->ih;
+    const size_t inp = (size_t)iw * ih, ditem = depth_item(ctx), packed_bytes = row * (size_t)rows;
+    Dev<uint8_t> full_img, full_right, packed, packed_r, fdepth;
+    Dev<uint16_t> full_depth;
+    Pin<uint8_t> h_img, h_right, h_packed, h_packed_r, h_fdepth;
+    Pin<uint16_t> h_depth;
+    if (resize) {
+        bool ok = pin_alloc(h_img, inp * 3) && (!b || (dev_alloc(full_img, inp * 3) && dev_alloc(full_depth, inp)));
+        if (ctx->h_right) ok = ok && pin_alloc(h_right, inp * 3) && (!b || dev_alloc(full_right, inp * 3));
+        if (!ctx->has_rig) ok = ok && pin_alloc(h_depth, inp);
+        if (!ctx->has_rig && converts(ctx)) ok = ok && dev_alloc(fdepth, inp * ditem) && pin_alloc(h_fdepth, inp * ditem);
+        if (unpacks(ctx)) ok = ok && dev_alloc(packed, packed_bytes) && pin_alloc(h_packed, packed_bytes);
+        if (unpacks(ctx) && ctx->packed_r) ok = ok && dev_alloc(packed_r, packed_bytes) && pin_alloc(h_packed_r, packed_bytes);
+        if (!ok) return no_memory(ctx, "set_input_binning: device and pinned memory for the images of the input size");
+    }
+    if (const int rc = settle(ctx, "set_input_binning")) return rc;
+    if (resize) {
+        ctx->full_img = std::move(full_img);   // (the three replaced or, at off, freed)
+        ctx->full_right = std::move(full_right);
+        ctx->full_depth = std::move(full_depth);
+        ctx->h_img = std::move(h_img);
+        hand_over(ctx->h_right, h_right);
+        hand_over(ctx->h_depth, h_depth);
+        hand_over(ctx->fdepth, fdepth);
+        hand_over(ctx->h_fdepth, h_fdepth);
+        hand_over(ctx->packed, packed);
+        hand_over(ctx->h_packed, h_packed);
+        hand_over(ctx->packed_r, packed_r);
+        hand_over(ctx->h_packed_r, h_packed_r);
+        ctx->iw = iw;
+        ctx->ih = ih;
+        if (!ctx->has_rig) { ctx->dw = iw; ctx->dh = ih; }
+        if (unpacks(ctx)) { ctx->pix_row = row; ctx->pix_rows = rows; }
+    }
+    store_setting(ctx->has_bin, ctx->bin, b);
+    drop_graphs(ctx);   // (whether a frame has the bin's launch, its numbers and where the uploads land are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_bin_camera(const cvo_fe_camera_model *in, int factor, cvo_fe_camera_model *out)
+{
+    if (!in || !out || factor < 2 || factor > 4 || !model_ok(*in)) return CVO_HIP_ERR_INVALID;
+    const float f = (float)factor, c = 0.5f * (float)(factor - 1);
+    cvo_fe_camera_model m = *in;   // (depth_scale and dist unchanged)
+    m.fx = in->fx / f;
+    m.fy = in->fy / f;
+    m.cx = (in->cx - c) / f;
+    m.cy = (in->cy - c) / f;
+    *out = m;
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_bin_stereo_rig(const cvo_fe_stereo_rig *in, int factor, cvo_fe_stereo_rig *out)
+{
+    if (!in || !out || factor < 2 || factor > 4 || !srig_ok(*in)) return CVO_HIP_ERR_INVALID;
+    const float f = (float)factor, c = 0.5f * (float)(factor - 1);
+    cvo_fe_stereo_rig r = *in;   // (the rotations, the baseline and depth_scale unchanged)
+    for (cvo_fe_lens *l : {&r.left, &r.right}) {
+        l->fx = l->fx / f;
+        l->fy = l->fy / f;
+        l->cx = (l->cx - c) / f;
+        l->cy = (l->cy - c) / f;
+    }
+    r.fx = r.fx / f;
+    r.fy = r.fy / f;
+    r.cx = (r.cx - c) / f;
+    r.cy = (r.cy - c) / f;
+    *out = r;
     return CVO_HIP_OK;
 }
 

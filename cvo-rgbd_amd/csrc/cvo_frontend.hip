@@ -20,6 +20,7 @@
 #include <new>
 #include <vector>
 
+#include "cvo_bin.h"
 #include "cvo_fe_ctx.h"
 #include "cvo_fe_rules.h"
 #include "cvo_infill.h"
@@ -1086,7 +1087,7 @@ inline float depth_format_scale(const cvo_fe_ctx *ctx, int dataset_seq)
 inline void enqueue_depth_convert(const cvo_fe_ctx *ctx, const void *src, size_t pitch, int dataset_seq)
 {
     FeDepthConvertArgs a{};
-    a.src = src; a.src_pitch = pitch; a.dst = depth_upload(ctx);
+    a.src = src; a.src_pitch = pitch; a.dst = depth_input(ctx);
     a.w = ctx->dw; a.h = ctx->dh; a.format = ctx->depthfmt; a.unit = ctx->depth_unit;
     a.scale = depth_format_scale(ctx, dataset_seq);
     fe_depth_convert_enqueue(a, ctx->stream);
@@ -1157,7 +1158,7 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // under a float format, converted from where it lies; this sequence then holds no copy of them)
     const bool upload = !ctx->dev_in;
     if (upload)
-        FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed.get() : img_landing(ctx), img_staging(ctx), img_bytes, hipMemcpyHostToDevice, s));
+        FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed.get() : img_input(ctx), img_staging(ctx), img_bytes, hipMemcpyHostToDevice, s));
     // a depth camera: the depth image lands in a raw buffer of its size and the warp fills depth
     // (a gate or a mask: whatever fills the depth plane fills the gate's input, and k_fe_depth_gate fills depth)
     // (stereo: the right image is uploaded in place of a depth image, and the matcher fills that plane)
@@ -1168,7 +1169,7 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     // (a float depth format: the float image lands in a buffer of its own and k_fe_depth_convert fills what is named above)
     if (ctx->has_stereo) {
         if (upload)
-            FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), right_staging(ctx), img_bytes,
+            FE_HIP(hipMemcpyAsync(unpacks(ctx) ? ctx->packed_r.get() : right_input(ctx), right_staging(ctx), img_bytes,
                                   hipMemcpyHostToDevice, s));
     } else if (ctx->has_lidar)
         FE_HIP(hipMemcpyAsync(ctx->d_scan.get(), ctx->h_scan.get(), lidar_scan_bytes(ctx->lidar.max_points, ctx->scan_record),
@@ -1176,16 +1177,27 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
     else if (upload && converts(ctx))
         FE_HIP(hipMemcpyAsync(ctx->fdepth.get(), ctx->h_fdepth.get(), (size_t)ctx->dw * ctx->dh * depth_item(ctx), hipMemcpyHostToDevice, s));
     else if (upload)
-        FE_HIP(hipMemcpyAsync(depth_upload(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
+        FE_HIP(hipMemcpyAsync(depth_input(ctx), ctx->h_depth.get(), (size_t)ctx->dw * ctx->dh * 2, hipMemcpyHostToDevice, s));
     FE_HIP(hipMemcpyAsync(ctx->ctrl.get(), ctx->h_ctrl.get(), sizeof(FeCtrl), hipMemcpyHostToDevice, s));
     if (upload && converts(ctx) && !ctx->has_stereo && !ctx->has_lidar)   // (the depth-format contract)
         enqueue_depth_convert(ctx, ctx->fdepth.get(), (size_t)ctx->dw * depth_item(ctx), dataset_seq);
     if (unpacks(ctx)) {   // (the unpack contract: in front of everything else in the frame, one launch for a pair)
         FeUnpackArgs u{};
-        u.src[0] = ctx->packed.get(); u.dst[0] = img_landing(ctx);
-        u.src[1] = ctx->has_stereo ? ctx->packed_r.get() : nullptr; u.dst[1] = ctx->has_stereo ? right_landing(ctx) : nullptr;
-        u.w = w; u.h = h; u.format = ctx->pixfmt; u.images = ctx->has_stereo ? 2 : 1;
+        u.src[0] = ctx->packed.get(); u.dst[0] = img_input(ctx);
+        u.src[1] = ctx->has_stereo ? ctx->packed_r.get() : nullptr; u.dst[1] = ctx->has_stereo ? right_input(ctx) : nullptr;
+        u.w = ctx->iw; u.h = ctx->ih; u.format = ctx->pixfmt; u.images = ctx->has_stereo ? 2 : 1;
         fe_unpack_enqueue(u, s);
+    }
+    if (ctx->has_bin) {   // (the binning contract: behind those two, in front of everything else, one launch for all planes)
+        FeBinArgs b{};
+        b.src[0] = ctx->full_img.get(); b.dst[0] = img_landing(ctx);
+        if (ctx->has_stereo) {
+            b.src[1] = ctx->full_right.get(); b.dst[1] = right_landing(ctx);
+        } else if (bins_depth(ctx)) {
+            b.src[1] = ctx->full_depth.get(); b.dst[1] = depth_upload(ctx); b.is_depth[1] = 1;
+        }
+        b.w = w; b.h = h; b.factor = ctx->bin.factor; b.depth_min = ctx->bin.depth_min; b.planes = b.src[1] ? 2 : 1;
+        fe_bin_enqueue(b, s);
     }
     const int32_t *srig_qu = ctx->srig_map.get();   // (read under a stereo rig: qu, qv left, qu, qv right)
     if (ctx->has_srig) {
@@ -1427,6 +1439,7 @@ int cvo_fe_create(int device, void *stream, int width, int height, cvo_fe_ctx **
     FeDims &d = ctx->d;
     d.w = width; d.h = height; d.w32 = width / 32; d.h32 = height / 32;
     ctx->dw = width; ctx->dh = height;
+    ctx->iw = width; ctx->ih = height;
     int wl = width, hl = height;
     for (int l = 0; l < FE_LEVELS; ++l) { d.wl[l] = wl; d.hl[l] = hl; wl /= 2; hl /= 2; }
     const size_t np = (size_t)width * height;
@@ -1573,16 +1586,16 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
         // pointer), as the mask below.  One pitched copy per image into the buffer its upload lands in; a float depth
         // image is not copied: the conversion reads it where it lies.
         const size_t rows = (size_t)img_rows(ctx);
-        FE_HIP(hipMemcpy2DAsync(unpacks(ctx) ? ctx->packed.get() : img_landing(ctx), row, img, img_stride, row, rows,
+        FE_HIP(hipMemcpy2DAsync(unpacks(ctx) ? ctx->packed.get() : img_input(ctx), row, img, img_stride, row, rows,
                                 hipMemcpyDeviceToDevice, s));
         if (stereo)
-            FE_HIP(hipMemcpy2DAsync(unpacks(ctx) ? ctx->packed_r.get() : right_landing(ctx), row, second, second_stride, row, rows,
+            FE_HIP(hipMemcpy2DAsync(unpacks(ctx) ? ctx->packed_r.get() : right_input(ctx), row, second, second_stride, row, rows,
                                     hipMemcpyDeviceToDevice, s));
         else if (converts(ctx)) {
             enqueue_depth_convert(ctx, second, second_stride, ctx->custom || ctx->has_srig ? 0 : dataset_seq);
             FE_HIP(hipGetLastError());
         } else
-            FE_HIP(hipMemcpy2DAsync(depth_upload(ctx), drow, second, second_stride, drow, (size_t)dh, hipMemcpyDeviceToDevice, s));
+            FE_HIP(hipMemcpy2DAsync(depth_input(ctx), drow, second, second_stride, drow, (size_t)dh, hipMemcpyDeviceToDevice, s));
     }
     ctx->dev_in = device;   // (read by enqueue_frame: such a frame's sequence holds no upload of the images)
     FeCtrl c0{};
@@ -1772,7 +1785,8 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_EDGES: src = ctx->edges.get(); need = np; break;
     case CVO_FE_STAGE_RECT_BGR: src = ctx->img.get(); need = np * 3; break;
     case CVO_FE_STAGE_RECT_DEPTH: src = ctx->depth.get(); need = np * 2; break;
-    case CVO_FE_STAGE_RAW_DEPTH: src = depth_upload(ctx); need = (size_t)ctx->dw * ctx->dh * 2; break;
+    // (under binning without a depth camera dw x dh is the input size, and the plane the bin wrote is the context's)
+    case CVO_FE_STAGE_RAW_DEPTH: src = depth_upload(ctx); need = ctx->has_rig ? (size_t)ctx->dw * ctx->dh * 2 : np * 2; break;
     case CVO_FE_STAGE_UNGATED_DEPTH: src = depth_plane(ctx); need = np * 2; break;
     case CVO_FE_STAGE_GATE: src = gate_active(ctx) ? ctx->gate_flags.get() : nullptr; need = np; break;
     case CVO_FE_STAGE_RIGHT_GRAY: src = ctx->right_gray.get(); need = np; break;
@@ -1793,13 +1807,22 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
     case CVO_FE_STAGE_INFILL: src = ctx->infill_flags.get(); need = np; break;
     case CVO_FE_STAGE_INPUT_BGR: src = img_landing(ctx); need = np * 3; break;
     case CVO_FE_STAGE_INPUT_RIGHT_BGR: src = right_landing(ctx); need = np * 3; break;
+    case CVO_FE_STAGE_FULL_BGR: src = ctx->full_img.get(); need = (size_t)ctx->iw * ctx->ih * 3; break;
+    case CVO_FE_STAGE_FULL_RIGHT_BGR: src = ctx->full_right.get(); need = (size_t)ctx->iw * ctx->ih * 3; break;
+    case CVO_FE_STAGE_FULL_DEPTH: src = ctx->full_depth.get(); need = (size_t)ctx->iw * ctx->ih * 2; break;
     default: return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: unknown stage");
     }
+    if (stage >= CVO_FE_STAGE_FULL_BGR && stage <= CVO_FE_STAGE_FULL_DEPTH && !ctx->has_bin)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: an input-size plane, and input binning is not set");
+    if (stage == CVO_FE_STAGE_FULL_RIGHT_BGR && !ctx->has_stereo)
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the input-size right image, and the context has no stereo");
+    if (stage == CVO_FE_STAGE_FULL_DEPTH && !bins_depth(ctx))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the input-size depth image, and a depth camera, stereo or a scan source is set");
     if ((stage == CVO_FE_STAGE_UNFILTERED_DEPTH || stage == CVO_FE_STAGE_MEDIAN) && !ctx->has_median)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the median filter, and no filter is set");
     if ((stage == CVO_FE_STAGE_SPARSE_DEPTH || stage == CVO_FE_STAGE_INFILL) && !ctx->has_infill)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the infill stage, and the stage is not set");
-    if ((stage == CVO_FE_STAGE_INPUT_BGR || stage == CVO_FE_STAGE_INPUT_RIGHT_BGR) && !unpacks(ctx))
+    if ((stage == CVO_FE_STAGE_INPUT_BGR || stage == CVO_FE_STAGE_INPUT_RIGHT_BGR) && !unpacks(ctx) && !ctx->has_bin)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: an unpacked image, and the context's pixel format is BGR8");
     if (stage == CVO_FE_STAGE_INPUT_RIGHT_BGR && !ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the unpacked right image, and the context has no stereo");

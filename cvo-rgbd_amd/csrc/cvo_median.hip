@@ -16,7 +16,8 @@
 // 65535 (key 65534) included; no 16-bit sentinel.  With n valid cells the lower median is the sorted key of index
 // (n - 1) >> 1, at most (2R+1)^2 / 2, picked by a chain of selects; for n == 0 that chain leaves key 0xFFFFFFFF, value 0.
 // The network is Batcher's odd-even merge sort for any n, made at compile time; the comparators that only order the
-// upper half never reach an output and the compiler drops them.
+// upper half never reach an output and the compiler drops them.  (The network and the pick are cvo_sortnet.h's: the
+// input bin of cvo_bin.hip sorts its blocks by them as well.)
 // FILL (fill_min > 0) is a template argument: without it a pixel without depth is done when its own cell is read, and
 // the test against fill_min does not exist.
 // LDS rows are 36 dwords apart: the sixteen threads of a row read consecutive 8-byte groups, the next row's start four
@@ -28,6 +29,7 @@
 
 #include "cvo_frontend.h"
 #include "cvo_lock.h"
+#include "cvo_sortnet.h"
 
 namespace {
 
@@ -37,69 +39,6 @@ constexpr int MD_OFF = 4;                        // the LDS column of the tile's
 constexpr int MD_S = MD_OFF + MD_TW + 4;         // 72 cells per LDS row
 static_assert((MD_TW / 4) * MD_TH == MD_BLOCK, "one thread per four pixels of the tile");
 static_assert(MD_TW % 4 == 0 && MD_S % 4 == 0 && MD_OFF % 4 == 0, "groups of four cells are 8-byte aligned in LDS");
-
-// Batcher's odd-even merge sort on N keys, N any number: the comparators (a < b: the smaller key goes to a) in order
-template <int N> struct MdNet {
-    int a[N * N], b[N * N];
-    int n;
-};
-
-template <int N> constexpr MdNet<N> md_make_net()
-{
-    MdNet<N> t{};
-    for (int p = 1; p < N; p *= 2)
-        for (int k = p; k >= 1; k /= 2)
-            for (int j = k % p; j <= N - 1 - k; j += 2 * k)
-                for (int i = 0; i <= (k - 1 < N - j - k - 1 ? k - 1 : N - j - k - 1); ++i)
-                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
-                        t.a[t.n] = i + j;
-                        t.b[t.n] = i + j + k;
-                        ++t.n;
-                    }
-    return t;
-}
-
-template <int N> struct MdNetOf {
-    static constexpr MdNet<N> net = md_make_net<N>();
-};
-
-template <int N, int I> __host__ __device__ __forceinline__ void md_exchange(uint32_t (&v)[N])
-{
-    constexpr int ia = MdNetOf<N>::net.a[I], ib = MdNetOf<N>::net.b[I];
-    static_assert(ia >= 0 && ia < ib && ib < N, "a comparator of the network");
-    const uint32_t lo = v[ia] < v[ib] ? v[ia] : v[ib], hi = v[ia] < v[ib] ? v[ib] : v[ia];
-    v[ia] = lo;
-    v[ib] = hi;
-}
-
-template <int N, int... I> __host__ __device__ __forceinline__ void md_sort_seq(uint32_t (&v)[N], std::integer_sequence<int, I...>)
-{
-    (md_exchange<N, I>(v), ...);
-}
-
-template <int N> __host__ __device__ __forceinline__ void md_sort(uint32_t (&v)[N])
-{
-    md_sort_seq<N>(v, std::make_integer_sequence<int, MdNetOf<N>::net.n>{});
-}
-
-// the lower median of the valid cells among N (0 = none), and 0 where there is none; *count = n
-template <int N> __host__ __device__ __forceinline__ uint32_t md_lower_median(const uint32_t (&cells)[N], int *count)
-{
-    uint32_t key[N];
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        key[i] = cells[i] - 1u;   // (none: 0xFFFFFFFF, behind every depth)
-        n += cells[i] != 0u ? 1 : 0;
-    }
-    md_sort<N>(key);
-    const int pick = (n - 1) >> 1;   // (n == 0: -1, and the chain below keeps key[0], which is "none" then)
-    uint32_t m = key[0];
-#pragma unroll
-    for (int j = 1; j <= (N - 1) / 2; ++j) m = pick == j ? key[j] : m;
-    *count = n;
-    return m + 1u;
-}
 
 template <int R, bool FILL>
 __global__ void __launch_bounds__(MD_BLOCK) k_fe_median(const FeMedianArgs a)

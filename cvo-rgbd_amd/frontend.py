@@ -72,6 +72,8 @@ FEATURES_HSV, FEATURES_RGB = 0, 1
  STAGE_CENSUS_L, STAGE_CENSUS_R, STAGE_SGM_SUM, STAGE_DISPARITY, STAGE_STEREO, STAGE_RIGHT_BGR,
  STAGE_STEREO_VALID, STAGE_SPECKLE_SIZE, STAGE_UNFILTERED_DEPTH, STAGE_MEDIAN, STAGE_LIDAR_DEPTH,
  STAGE_LIDAR, STAGE_SPARSE_DEPTH, STAGE_INFILL, STAGE_INPUT_BGR, STAGE_INPUT_RIGHT_BGR) = range(32)
+# of a frame under input binning (set_input_binning): the input-size images the bin read
+STAGE_FULL_BGR, STAGE_FULL_RIGHT_BGR, STAGE_FULL_DEPTH = 32, 33, 34
 GATE_MASKED, GATE_RANGE, GATE_JUMP = 1, 2, 4   # the flags of STAGE_GATE
 STEREO_UNIQUE, STEREO_LR, STEREO_MIN, STEREO_DEPTH, STEREO_OUTSIDE, STEREO_SPECKLE = 1, 2, 4, 8, 16, 32   # the flags of STAGE_STEREO
 MEDIAN_CHANGED, MEDIAN_FILLED = 1, 2   # the values of STAGE_MEDIAN
@@ -109,7 +111,9 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_set_pixel_format", "cvo_fe_get_pixel_format", "cvo_fe_unpack_image", "cvo_fe_check_lidar_sweep",
            "cvo_fe_set_lidar_sweep", "cvo_fe_get_lidar_sweep", "cvo_fe_set_lidar_motion", "cvo_fe_get_lidar_motion",
            "cvo_fe_lidar_twist", "cvo_fe_project_points_sweep", "cvo_fe_check_depth_format", "cvo_fe_set_depth_format",
-           "cvo_fe_get_depth_format", "cvo_fe_convert_depth", "cvo_fe_submit_device", "cvo_fe_submit_stereo_device")
+           "cvo_fe_get_depth_format", "cvo_fe_convert_depth", "cvo_fe_submit_device", "cvo_fe_submit_stereo_device",
+           "cvo_fe_check_binning", "cvo_fe_set_input_binning", "cvo_fe_get_input_binning", "cvo_fe_bin_camera",
+           "cvo_fe_bin_stereo_rig", "cvo_fe_bin_image", "cvo_fe_bin_depth")
 
 
 class Info(C.Structure):
@@ -209,6 +213,18 @@ class DepthMedian(_Settings):
 
     def __init__(self, radius=1, fill_min=0, pad_=0):
         super().__init__(int(radius), int(fill_min), int(pad_))
+
+
+class Binning(_Settings):
+    """cvo_fe_binning: input binning (the binning contract of include/cvo_frontend.h).  The images a frame takes are
+    `factor` (2, 3 or 4) times the generator's size each way and are binned to it on the device in front of everything
+    else: box means of the colour bytes, and the lower median of a block's depths where at least `depth_min` (1 ..
+    factor^2) of its pixels have one.  EVERY CAMERA OF THE GENERATOR THEN DESCRIBES THE BINNED IMAGE: bin_camera(),
+    bin_stereo_rig()."""
+    _fields_ = [("factor", C.c_int32), ("depth_min", C.c_int32), ("pad_", C.c_int32)]
+
+    def __init__(self, factor=2, depth_min=1, pad_=0):
+        super().__init__(int(factor), int(depth_min), int(pad_))
 
 
 class DepthInfill(_Settings):
@@ -406,6 +422,14 @@ def lib():
         L.cvo_fe_convert_depth.argtypes = [C.c_int, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, u16p]
         L.cvo_fe_submit_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]
         L.cvo_fe_submit_stereo_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]
+        L.cvo_fe_check_binning.argtypes = [C.POINTER(Binning), C.c_int, C.c_int]
+        L.cvo_fe_set_input_binning.argtypes = [vp, C.POINTER(Binning)]
+        L.cvo_fe_get_input_binning.argtypes = [vp, C.POINTER(Binning), C.POINTER(C.c_int)]
+        L.cvo_fe_bin_camera.argtypes = [C.POINTER(CameraModel), C.c_int, C.POINTER(CameraModel)]
+        L.cvo_fe_bin_stereo_rig.argtypes = [C.POINTER(StereoRig), C.c_int, C.POINTER(StereoRig)]
+        L.cvo_fe_bin_image.argtypes = [C.c_int, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p]
+        L.cvo_fe_bin_depth.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Binning), u16p,
+                                       C.POINTER(C.c_int)]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -426,6 +450,9 @@ def camera(dataset_seq):
     cam = np.zeros(5, np.float32)
     capi.check(lib().cvo_fe_camera(int(dataset_seq), cam.ctypes.data_as(C.POINTER(C.c_float))), what="camera")
     return dict(zip(("scaling_factor", "fx", "fy", "cx", "cy"), (float(v) for v in cam)))
+
+
+_table_row = camera   # (run_frames has an argument of that name)
 
 
 def rectify_map(model, width, height):
@@ -599,6 +626,80 @@ def unpack_image(src, fmt, width, height, device=0, stride=None):
     capi.check(lib().cvo_fe_unpack_image(int(device), src.ctypes.data_as(u8p), pitch, int(width), int(height), int(fmt),
                                          out.ctypes.data_as(u8p)), what="unpack_image")
     return out
+
+
+def check_binning(binning, width, height):
+    """True for a Binning set_input_binning() accepts on a generator of width x height (cvo_fe_check_binning): factor 2,
+    3 or 4, depth_min in [1, factor^2], pad_ 0, factor times the size at most 8192 each way; None is refused.  Host only."""
+    return lib().cvo_fe_check_binning(None if binning is None else C.byref(binning), _c_int(width, "check_binning"),
+                                      _c_int(height, "check_binning")) == 0
+
+
+def bin_camera(model, factor):
+    """The CameraModel of the binned image from the input image's (cvo_fe_bin_camera): fx / f, fy / f,
+    (cx - (f - 1) / 2) / f, (cy - (f - 1) / 2) / f in float32; depth_scale and dist unchanged.  Host only."""
+    out = CameraModel()
+    capi.check(lib().cvo_fe_bin_camera(C.byref(model), _c_int(factor, "bin_camera"), C.byref(out)), what="bin_camera")
+    return out
+
+
+def bin_stereo_rig(rig, factor):
+    """bin_camera()'s rule on the two lenses and the rectified pinhole of a StereoRig (cvo_fe_bin_stereo_rig); the
+    rotations, the baseline and depth_scale unchanged.  Host only."""
+    out = StereoRig()
+    capi.check(lib().cvo_fe_bin_stereo_rig(C.byref(rig), _c_int(factor, "bin_stereo_rig"), C.byref(out)),
+               what="bin_stereo_rig")
+    return out
+
+
+def _strided(src, row_items, stride, fill):
+    """`src` (rows x row_items ...) in rows `stride` items apart, the cells between them holding `fill`."""
+    pitch = row_items if stride is None else int(stride)
+    if pitch < row_items:
+        raise ValueError("stride below the row")
+    buf = np.full((src.shape[0], pitch), fill, src.dtype)
+    buf[:, :row_items] = src.reshape(src.shape[0], row_items)
+    return buf, pitch
+
+
+def bin_image(bgr, factor, device=0, stride=None):
+    """The binning contract on any fh x fw x 3 uint8 image (cvo_fe_bin_image: the kernel a frame runs, without a
+    generator).  Returns the h x w x 3 image; the argument is left as it is.  `stride`: the image is handed over in rows
+    that many bytes apart (at least fw * 3)."""
+    f = _c_int(factor, "bin_image")
+    src = np.ascontiguousarray(bgr, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3 or f < 1 or src.shape[0] % f or src.shape[1] % f:
+        raise ValueError("expected an fh x fw x 3 uint8 image, fh and fw multiples of the factor")
+    h, w = src.shape[0] // f, src.shape[1] // f
+    buf, pitch = _strided(src, src.shape[1] * 3, stride, 0xA5)
+    keep = buf.copy()
+    out = np.empty((h, w, 3), np.uint8)
+    u8p = C.POINTER(C.c_uint8)
+    capi.check(lib().cvo_fe_bin_image(int(device), buf.ctypes.data_as(u8p), pitch, w, h, f, out.ctypes.data_as(u8p)),
+               what="bin_image")
+    if not (buf == keep).all():
+        raise RuntimeError("bin_image: the source was written")
+    return out
+
+
+def bin_depth(plane, binning, device=0, stride=None):
+    """The binning contract on any fh x fw uint16 plane with 0 = none (cvo_fe_bin_depth).  Returns (the h x w plane, the
+    number of its pixels with a depth); the argument is left as it is.  `stride`: rows that many uint16 apart."""
+    f = int(binning.factor) if binning is not None else 0
+    src = np.ascontiguousarray(plane, np.uint16)
+    if src.ndim != 2 or f < 1 or src.shape[0] % f or src.shape[1] % f:
+        raise ValueError("expected an fh x fw uint16 plane, fh and fw multiples of the factor")
+    h, w = src.shape[0] // f, src.shape[1] // f
+    buf, pitch = _strided(src, src.shape[1], stride, 0xA5A5)
+    keep = buf.copy()
+    out = np.empty((h, w), np.uint16)
+    valid = C.c_int(0)
+    u16p = C.POINTER(C.c_uint16)
+    capi.check(lib().cvo_fe_bin_depth(int(device), buf.ctypes.data_as(u16p), pitch * 2, w, h, C.byref(binning),
+                                      out.ctypes.data_as(u16p), C.byref(valid)), what="bin_depth")
+    if not (buf == keep).all():
+        raise RuntimeError("bin_depth: the source was written")
+    return out, valid.value
 
 
 def check_depth_format(fmt, unit=1.0):
@@ -815,7 +916,9 @@ class PcdGenerator:
         self.num_want = int(num_want)
         self._chk(lib().cvo_fe_set_num_want(self._h, self.num_want), "set_num_want")
         self.capacity = self.width * self.height   # (upper bound of any selection)
+        self._iw, self._ih = self.width, self.height   # of the colour images a frame takes: f times the size under set_input_binning
         self._dshape = (self.height, self.width)   # of the depth image: the depth camera's, if one is set
+        self._has_rig = False
         self._max_disp = 0                         # of the stereo settings, if some are set
         self._pix = PIXEL_BGR8                     # the pixel format of the colour images (set_pixel_format)
         self._ishape = (self.height, self.width * 3)   # rows x row_bytes of a colour image in that format
@@ -925,10 +1028,11 @@ class PcdGenerator:
         of the depth camera's size while one is set and valid until the next set_depth_camera().  Under a pixel
         format the image view is the packed image, rows x row_bytes, valid until the next set_pixel_format().  Under a
         float depth format the depth view is the float staging image (float32 or float16), valid until the next
-        set_depth_format() / set_depth_camera()."""
+        set_depth_format() / set_depth_camera().  Under input binning both views are of the input size, factor times the
+        generator's each way (the depth view unless a depth camera is set), valid until the next set_input_binning()."""
         pi, pd = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint16)()
         self._chk(lib().cvo_fe_host_buffers(self._h, C.byref(pi), C.byref(pd)), "host_buffers")
-        img = np.ctypeslib.as_array(pi, shape=self._ishape if self._pix != PIXEL_BGR8 else (self.height, self.width, 3))
+        img = np.ctypeslib.as_array(pi, shape=self._ishape if self._pix != PIXEL_BGR8 else (self._ih, self._iw, 3))
         dep = np.ctypeslib.as_array(pd, shape=self._dshape)
         if self._dfmt != DEPTH_U16:   # (the same memory, seen as the format's values)
             dtype = np.dtype(_DEPTH_DTYPES[self._dfmt])
@@ -957,7 +1061,8 @@ class PcdGenerator:
         registered into the colour camera's frame on the device (the registration contract of
         include/cvo_frontend.h); None: depth is registered to colour already, as for a new object."""
         self._set_struct("depth_camera", rig)
-        self._dshape = (self.height, self.width) if rig is None else (int(rig.height), int(rig.width))
+        self._has_rig = rig is not None
+        self._dshape = (self._ih, self._iw) if rig is None else (int(rig.height), int(rig.width))
 
     def depth_camera(self):
         """The DepthCamera set, or None."""
@@ -1084,8 +1189,8 @@ class PcdGenerator:
         rows x row_bytes of the pixel format in force."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
         if self._pix == PIXEL_BGR8:
-            if bgr.shape != (self.height, self.width, 3):
-                raise ValueError("expected a %dx%dx3 uint8 image" % (self.height, self.width))
+            if bgr.shape != (self._ih, self._iw, 3):
+                raise ValueError("expected a %dx%dx3 uint8 image" % (self._ih, self._iw))
         elif bgr.size != self._ishape[0] * self._ishape[1]:
             raise ValueError("expected %d rows of %d bytes (the pixel format in force)" % self._ishape)
         return bgr
@@ -1098,7 +1203,26 @@ class PcdGenerator:
         fmt = _c_int(fmt, "set_pixel_format")
         self._chk(lib().cvo_fe_set_pixel_format(self._h, fmt), "set_pixel_format")
         self._pix = fmt
-        self._ishape = pixel_layout(fmt, self.width, self.height)
+        self._ishape = pixel_layout(fmt, self._iw, self._ih)
+
+    def set_input_binning(self, binning):
+        """A Binning for every following frame of any kind (the binning contract of include/cvo_frontend.h): every image
+        handed over -- host or device, both of a stereo pair, the depth image unless a depth camera is set -- is then
+        factor times the generator's size each way and is binned on the device in front of everything else.  THE
+        CAMERAS AND THE MASK OF THE GENERATOR DESCRIBE THE BINNED IMAGE: hand set_camera() bin_camera()'s model and
+        set_stereo_rig() bin_stereo_rig()'s rig, or the cloud comes out factor times too large.  None: off, a new
+        object's.  A setting of its own: it survives every other setter.  Views of host_buffers() are valid until the
+        next call."""
+        self._set_struct("input_binning", binning)
+        f = 1 if binning is None else int(binning.factor)
+        self._iw, self._ih = f * self.width, f * self.height
+        self._ishape = pixel_layout(self._pix, self._iw, self._ih)
+        if not self._has_rig:
+            self._dshape = (self._ih, self._iw)
+
+    def input_binning(self):
+        """The Binning in force, or None."""
+        return self._get_struct("input_binning", Binning)
 
     def set_depth_format(self, fmt, unit=1.0):
         """The DEPTH_* format of the depth image of every following frame that has one (the depth-format contract of
@@ -1196,12 +1320,15 @@ class PcdGenerator:
     def read_stage(self, stage):
         """An intermediate image of the last create_pointcloud (parity checks)."""
         w, h = self.width, self.height
-        shapes = {STAGE_GRAY: ((h, w), np.uint8), STAGE_HSV: ((h, w, 3), np.uint8), STAGE_MAP: ((h, w), np.float32),
+        fw, fh = self._iw, self._ih
+        shapes = {STAGE_FULL_BGR: ((fh, fw, 3), np.uint8), STAGE_FULL_RIGHT_BGR: ((fh, fw, 3), np.uint8),
+                  STAGE_FULL_DEPTH: ((fh, fw), np.uint16),
+                  STAGE_GRAY: ((h, w), np.uint8), STAGE_HSV: ((h, w, 3), np.uint8), STAGE_MAP: ((h, w), np.float32),
                   STAGE_AG0: ((h, w), np.float32), STAGE_AG1: ((h // 2, w // 2), np.float32),
                   STAGE_AG2: ((h // 4, w // 4), np.float32), STAGE_THS: ((h // 32, w // 32), np.float32),
                   STAGE_DX0: ((h, w), np.float32), STAGE_DY0: ((h, w), np.float32), STAGE_EDGES: ((h, w), np.uint8),
                   STAGE_RECT_BGR: ((h, w, 3), np.uint8), STAGE_RECT_DEPTH: ((h, w), np.uint16),
-                  STAGE_RAW_DEPTH: (self._dshape, np.uint16), STAGE_UNGATED_DEPTH: ((h, w), np.uint16),
+                  STAGE_RAW_DEPTH: (self._dshape if self._has_rig else (h, w), np.uint16), STAGE_UNGATED_DEPTH: ((h, w), np.uint16),
                   STAGE_GATE: ((h, w), np.uint8), STAGE_RIGHT_GRAY: ((h, w), np.uint8),
                   STAGE_CENSUS_L: ((h, w), np.uint64), STAGE_CENSUS_R: ((h, w), np.uint64),
                   STAGE_SGM_SUM: ((h, w, self._max_disp), np.uint16), STAGE_DISPARITY: ((h, w), np.uint16),
@@ -1258,8 +1385,15 @@ def load_img(rgb_path, depth_path):
 def run_frames(registration, frames, dataset_seq, writer=None, generator=None, prefetch=False, device=True,
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
                stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None, pixel_format=None,
-               lidar_sweep=None, lidar_motion=None, sweep_fraction=1.0, depth_format=None, device_input=False):
+               lidar_sweep=None, lidar_motion=None, sweep_fraction=1.0, depth_format=None, device_input=False,
+               input_binning=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `input_binning`: a Binning for the generator: `frames` then yields images of the INPUT size, factor times the
+    generator's each way (a first frame decides a new generator's size as shape // factor; a shape that is no multiple
+    of the factor is a ValueError), and `camera`, `stereo_rig` and, where `camera` is None, the table row of
+    `dataset_seq` describe those INPUT images: they go through bin_camera() / bin_stereo_rig() and the result is set, so
+    the geometry is right without knowing the rule.  A `depth_camera` is passed as it is (its colour side is the
+    generator's camera).  None leaves the generator as it is.
     `depth_format`: a DEPTH_* format, or (format, unit), for the generator: the depth images `frames` yields are then of
     that format; None leaves the generator as it is.
     `device_input`: `frames` yields device arrays (objects with `__cuda_array_interface__`), which go in through
@@ -1304,6 +1438,20 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
     cur = next(it, None)
     if cur is None:
         return 0
+    if input_binning is not None:
+        f = int(input_binning.factor)
+        if gen is None:
+            if f < 1 or cur[1].shape[0] % f or cur[1].shape[1] % f:
+                raise ValueError("input_binning: the first frame's shape %r is no multiple of the factor" % (cur[1].shape[:2],))
+            gen = PcdGenerator(cur[1].shape[1] // f, cur[1].shape[0] // f)
+        gen.set_input_binning(input_binning)
+        if stereo_rig is not None:
+            stereo_rig = bin_stereo_rig(stereo_rig, f)
+        elif camera is not None:
+            camera = bin_camera(camera, f)
+        else:   # (the table row, as a model of the input images)
+            row = _table_row(dataset_seq)
+            camera = bin_camera(CameraModel(row["scaling_factor"], row["fx"], row["fy"], row["cx"], row["cy"]), f)
     if gen is None:
         gen = PcdGenerator(cur[1].shape[1], cur[1].shape[0])
     if camera is not None:
@@ -1392,7 +1540,7 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
                   generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None, select_mode=None,
-                  depth_median=None, depth_infill=None):
+                  depth_median=None, depth_infill=None, input_binning=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
@@ -1402,7 +1550,8 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
     `depth_gate`, `mask`: as in run_frames, e.g. DepthGate(0.8, 4.0, 0.05, 1) for a Kinect-class sensor.
     `select_mode`: as in run_frames, e.g. SELECT_DEPTH beside a gate, which removes the pixels the selector likes best.
     `depth_median`: as in run_frames, e.g. DepthMedian(1, 5) for a sensor with salt and pinholes.
-    `depth_infill`: as in run_frames, e.g. DepthInfill(2, 2, 0.05) for the holes a depth camera's registration leaves."""
+    `depth_infill`: as in run_frames, e.g. DepthInfill(2, 2, 0.05) for the holes a depth camera's registration leaves.
+    `input_binning`: as in run_frames, e.g. Binning(2, 2) for a 1280 x 720 recording worked on at 640 x 360."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -1414,19 +1563,19 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_camera=depth_camera, depth_gate=depth_gate, mask=mask, select_mode=select_mode,
-                      depth_median=depth_median, depth_infill=depth_infill)
+                      depth_median=depth_median, depth_infill=depth_infill, input_binning=input_binning)
 
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
                          stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None, depth_median=None,
-                         depth_infill=None):
+                         depth_infill=None, input_binning=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
     image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`, `depth_median`,
-    `depth_infill`: as in run_frames."""
+    `depth_infill`, `input_binning`: as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1443,13 +1592,13 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
                       stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode,
-                      depth_median=depth_median, depth_infill=depth_infill)
+                      depth_median=depth_median, depth_infill=depth_infill, input_binning=input_binning)
 
 
 def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, image="image_2", scans="velodyne",
                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
                         select_mode=None, depth_median=None, depth_infill=None, lidar_sweep=None, lidar_motion=None,
-                        sweep_fraction=1.0):
+                        sweep_fraction=1.0, input_binning=None):
     """run_directory() for the KITTI odometry layout with its scans: one line of `folder`/`times` per frame (the line is
     the frame's name), the colour image in `folder`/`image`/%06d.png, decoded by PIL as load_img does (B, G, R; a grey
     image is replicated), and the scan in `folder`/`scans`/%06d.bin, records of four float32 (x y z reflectance).
@@ -1459,7 +1608,8 @@ def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, i
     run_frames, e.g. DepthInfill(2, 8, 0.25) for scan lines some five rows apart.  `lidar_sweep`, `lidar_motion`,
     `sweep_fraction`: as in run_frames, e.g. LidarSweep(SWEEP_AZIMUTH, phase0=0.5, direction=1, s_ref=0.5) and
     "constant-velocity" for records that carry no time, as KITTI's: `direction` is the scanner's sense of rotation,
-    `phase0` says at which azimuth its sweep begins and `s_ref` where in the sweep the image is taken."""
+    `phase0` says at which azimuth its sweep begins and `s_ref` where in the sweep the image is taken.
+    `input_binning`: as in run_frames (the colour image only; the scan is projected into the binned camera)."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1477,4 +1627,4 @@ def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, i
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, select_mode=select_mode, depth_median=depth_median, lidar=lidar,
                       depth_infill=depth_infill, lidar_sweep=lidar_sweep, lidar_motion=lidar_motion,
-                      sweep_fraction=sweep_fraction)
+                      sweep_fraction=sweep_fraction, input_binning=input_binning)

@@ -146,6 +146,16 @@ class registration {
     // or after the first image; throws for a format the front end refuses -- one the image size does not fit included,
     // which before the first image shows when that image arrives.
     void set_pixel_format(int format);
+    // Input binning for the image form of set_pcd() / run_cvo() of every kind of frame: cvo_fe_set_input_binning (the
+    // binning contract: cvo_frontend.h).  Every image handed over -- both of a stereo pair, the depth image unless a
+    // depth camera is set -- is then `factor` (2, 3 or 4) times the front end's size each way and is binned on the device
+    // in front of everything else.  Before the first image: that image's size over the factor is the front end's size.
+    // With a front end: its size stays, and the images are factor times it from then on.  THE CAMERAS AND THE MASK OF
+    // THE OBJECT DESCRIBE THE BINNED IMAGE: hand set_camera() cvo_fe_bin_camera's model and set_stereo_rig()
+    // cvo_fe_bin_stereo_rig's rig, or the cloud comes out factor times too large.  Throws for what the front end
+    // refuses.  clear_input_binning(): off, a new object's state.
+    void set_input_binning(const cvo_fe_binning &binning);
+    void clear_input_binning();
     // The format of the depth image of the image form of set_pcd() / run_cvo(): cvo_fe_set_depth_format
     // (CVO_FE_DEPTH_U16 with unit 1, a new object's; CVO_FE_DEPTH_F32 / CVO_FE_DEPTH_F16: the depth image_view's data is
     // float32 / float16 in `unit` metres per value and its step the pitch of those rows -- the depth-format contract:
@@ -260,6 +270,8 @@ class registration {
     int pixel_format_;                   // what set_pixel_format() gave, likewise (CVO_FE_PIXEL_BGR8 without a call)
     int depth_format_;                   // what set_depth_format() gave, likewise (CVO_FE_DEPTH_U16, unit 1 without a call)
     float depth_unit_;
+    cvo_fe_binning binning_;             // what set_input_binning() gave, likewise
+    bool have_binning_;
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();

@@ -65,7 +65,10 @@
  * And a format for the depth image (cvo_fe_set_depth_format; cvo_fe_convert_depth for any plane): float32 or float16 in a
  * unit the caller names, converted on the device in front of everything that reads it.  The depth-format contract is stated
  * at CVO_FE_DEPTH_* below.  And frames whose images lie in device memory already (cvo_fe_submit_device,
- * cvo_fe_submit_stereo_device).  The device-input contract is stated at cvo_fe_submit_device below.
+ * cvo_fe_submit_stereo_device).  The device-input contract is stated at cvo_fe_submit_device below.  And frames in the
+ * sensor's own resolution (cvo_fe_set_input_binning; cvo_fe_bin_image and cvo_fe_bin_depth for any image): the caller's
+ * images are f times the context's size each way, and the first kernel of the frame bins them down to the working size.
+ * The binning contract is stated at cvo_fe_binning below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -135,7 +138,14 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        /* of a frame under a pixel format (cvo_fe_set_pixel_format; CVO_HIP_ERR_INVALID on a context in
           CVO_FE_PIXEL_BGR8, and the second on one without stereo as well) */
        CVO_FE_STAGE_INPUT_BGR = 30,       /* the unpacked colour or left image, in front of any rectification: w*h*3 uint8 */
-       CVO_FE_STAGE_INPUT_RIGHT_BGR = 31 };   /* the unpacked right image: w*h*3 uint8 */
+       CVO_FE_STAGE_INPUT_RIGHT_BGR = 31,     /* the unpacked right image: w*h*3 uint8 */
+       /* of a frame under input binning (the binning contract at cvo_fe_binning; CVO_HIP_ERR_INVALID without it).  Under
+        * binning the two ids above and CVO_FE_STAGE_RAW_DEPTH are what the bin wrote, with or without a pixel format;
+        * every id above names a plane of the working size. */
+       CVO_FE_STAGE_FULL_BGR = 32,        /* the colour or left image the bin read: fw*fh*3 uint8 */
+       CVO_FE_STAGE_FULL_RIGHT_BGR = 33,  /* the right image the bin read: fw*fh*3 uint8; INVALID without stereo */
+       CVO_FE_STAGE_FULL_DEPTH = 34 };    /* the depth plane the bin read: fw*fh uint16; INVALID under a depth camera,
+                                           * stereo or a scan source */
 
 /* flags of CVO_FE_STAGE_GATE (the gate contract at cvo_fe_depth_gate) */
 enum { CVO_FE_GATE_MASKED = 1, CVO_FE_GATE_RANGE = 2, CVO_FE_GATE_JUMP = 4 };
@@ -850,7 +860,9 @@ int cvo_fe_get_depth_gate(const cvo_fe_ctx *ctx, cvo_fe_depth_gate *out, int *se
  * per frame calls this before every submit().  Mask and gate are independent: either alone makes
  * the gate stage run.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a
  * frame submitted and not collected; stride < width.  The device and the pinned mask take memory
- * only once a mask has been set. */
+ * only once a mask has been set.
+ * UNDER INPUT BINNING (cvo_fe_set_input_binning) THE MASK IS width x height OF THE CONTEXT, ON THE WORKING GRID, not
+ * the size of the images a frame takes: working pixel (x, y) is block (x, y) of the input image. */
 int cvo_fe_set_mask(cvo_fe_ctx *ctx, const uint8_t *mask, size_t stride);
 
 /* While stereo is set a frame is a rectified stereo pair (the stereo contract at cvo_fe_stereo) and goes
@@ -1176,6 +1188,83 @@ int cvo_fe_submit_device(cvo_fe_ctx *ctx, const void *d_img, size_t img_stride, 
                          size_t depth_stride, int dataset_seq, int feature_type);
 int cvo_fe_submit_stereo_device(cvo_fe_ctx *ctx, const void *d_left, size_t left_stride, const void *d_right,
                                 size_t right_stride, int dataset_seq, int feature_type);
+
+/*
+ * THE BINNING CONTRACT.  The results are defined by the integer arithmetic below, not by the device; it is this
+ * library's own definition and is NOT pinned against cv::resize(INTER_AREA) or any SDK.  While binning is set the
+ * context's width x height (w x h) is the WORKING SIZE, and every image that is uploaded or read from the caller's
+ * device memory is fw x fh.  Block (x, y) of an input plane is the f x f input pixels (fx + i, fy + j), 0 <= i, j < f;
+ * n = f*f.
+ *   Colour (the unpacked B G R image, and both images of a stereo pair).  Per channel, S = the sum of the n bytes of
+ *     the block, out = (S + (n >> 1)) / n, floor division.  For f = 2 and f = 4 that is round half up; for f = 3 a half
+ *     cannot occur.  A flat block comes back exactly.
+ *   Depth (the uint16 depth image of a frame that has one and no depth camera).  k = the number of non-zero values of
+ *     the block, v_0 <= ... <= v_(k-1) those values in ascending order.  out = v_((k-1) >> 1) if k >= depth_min, else
+ *     0: the lower median of the median contract, always a value some pixel of the block holds and never an average
+ *     across an occlusion edge.  65535 is a depth like any other.  With depth_min = n a block with any hole has no depth.
+ *   Every output pixel is a function of its own block alone.
+ * Where it sits.  One launch, behind k_fe_unpack (which under a pixel format runs at the input size; the format must
+ * pass cvo_fe_check_pixel_format at fw x fh) and behind k_fe_depth_convert (which under a float depth format runs at
+ * the input size), and in front of everything else: rectification of either kind, the depth camera's warp, the LiDAR
+ * projection, infill, median, gate and level 0.  It writes the buffers an upload or those two kernels fill without
+ * binning; they fill input-size buffers instead.  No later stage changes or learns of it: by bits, the frame is that
+ * of a context of the working size, without binning, fed the binned images.
+ *   a depth camera set: only the colour image is binned; the depth image keeps the rig's own size
+ *   a scan source:      only the colour image
+ *   stereo:             both colour images, in the same launch
+ * EVERY CAMERA OF THE CONTEXT DESCRIBES THE WORKING IMAGE: the model of cvo_fe_set_camera, a stereo rig's two lenses
+ * and its rectified pinhole, the colour side of a depth camera's registration and of the LiDAR projection, the table
+ * rows of dataset_seq.  The mask of cvo_fe_set_mask is w x h, on the working grid.  A caller who bins and keeps the
+ * input image's pinhole gets a cloud f times too large: cvo_fe_bin_camera / cvo_fe_bin_stereo_rig make the working
+ * camera.  Pixel centres lie at integer coordinates, so working pixel X is centred at input f X + (f - 1) / 2 and the
+ * binned principal point is (cx - (f - 1) / 2) / f, not cx / f.
+ * Everything that names "the size of the caller's image" speaks of fw x fh (for depth: unless a depth camera is set):
+ * cvo_fe_host_buffers, the stride checks of the submits, the pointer and extent checks of the device submits.
+ * Stage ids.  No existing id changes its meaning; each names a working-size plane.  CVO_FE_STAGE_RAW_DEPTH and, under
+ * a pixel format or binning, CVO_FE_STAGE_INPUT_BGR / _INPUT_RIGHT_BGR are what the bin wrote.  CVO_FE_STAGE_FULL_*
+ * are what it read.
+ * Not part of it: factors above 4, and different factors in x and y; binning the Bayer mosaic before the demosaic;
+ * binning a depth camera's image or a LiDAR plane; any filter other than the box; cropping an input that is no
+ * multiple of f (the caller's pointer and stride do that); fusing the bin into k_fe_unpack or level 0.
+ */
+typedef struct cvo_fe_binning {
+    int32_t factor;      /* f: 2, 3 or 4 */
+    int32_t depth_min;   /* 1 .. f*f: a working pixel gets a depth when at least this many pixels of its block have one */
+    int32_t pad_;        /* must be 0 */
+} cvo_fe_binning;        /* 12 bytes */
+
+/* CVO_HIP_OK for what cvo_fe_set_input_binning() would accept on an idle BGR8 context of the working size
+ * width x height, CVO_HIP_ERR_INVALID otherwise: NULL; a factor outside {2, 3, 4}; depth_min outside [1, f*f];
+ * pad_ != 0; width or height below 1; f*width or f*height above 8192.  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_binning(const cvo_fe_binning *b, int width, int height);
+/* Input binning for every following frame.  THE CAMERAS AND THE MASK OF THE CONTEXT DESCRIBE THE WORKING IMAGE (the
+ * binning contract above): bin the input image's camera with cvo_fe_bin_camera / cvo_fe_bin_stereo_rig.  A setting of
+ * its own: it survives every other setter, in either order with cvo_fe_set_pixel_format, cvo_fe_set_depth_format,
+ * cvo_fe_set_depth_camera, cvo_fe_set_stereo, cvo_fe_set_stereo_rig, cvo_fe_set_lidar and cvo_fe_set_camera; the packed
+ * staging, the float staging and the right image's staging follow the input size.  Pointers of cvo_fe_host_buffers
+ * are valid until the next call.  NULL: off, a new context's state; the buffers of the setting are freed and a frame
+ * launches what it launched before.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame
+ * submitted and not collected; what cvo_fe_check_binning refuses at the context's size; a pixel format in force that
+ * cvo_fe_check_pixel_format refuses at fw x fh.  (In turn cvo_fe_set_pixel_format checks at the input size.) */
+int cvo_fe_set_input_binning(cvo_fe_ctx *ctx, const cvo_fe_binning *b);
+int cvo_fe_get_input_binning(const cvo_fe_ctx *ctx, cvo_fe_binning *out, int *set);
+/* The working camera of an input image's camera.  In float32, each operation rounded on its own:
+ *   c = 0.5f * (float)(f - 1)   (exact: 0.5, 1, 1.5)
+ *   fx' = fx / (float)f;  fy' = fy / (float)f;  cx' = (cx - c) / (float)f;  cy' = (cy - c) / (float)f
+ * depth_scale and dist[5] are unchanged (the distortion acts on normalised coordinates).  `out` may be `in`.
+ * CVO_HIP_ERR_INVALID for a null pointer, a factor outside {2, 3, 4} and a model cvo_fe_set_camera refuses.  Host only. */
+int cvo_fe_bin_camera(const cvo_fe_camera_model *in, int factor, cvo_fe_camera_model *out);
+/* The same rule on `left`, `right` and the rectified fx fy cx cy of a rig; the rotations, the baseline and depth_scale
+ * are unchanged.  CVO_HIP_ERR_INVALID for a null pointer, such a factor and a rig cvo_fe_check_stereo_rig refuses. */
+int cvo_fe_bin_stereo_rig(const cvo_fe_stereo_rig *in, int factor, cvo_fe_stereo_rig *out);
+/* The binning contract on any image / plane by the kernel a frame runs, without a context: host arrays in and out.
+ * width x height is the OUTPUT size; the source is factor*width x factor*height, `stride_bytes` apart, and is not
+ * written; `out` is dense.  *valid: the number of output pixels with a depth.  CVO_HIP_ERR_INVALID for a null pointer,
+ * width or height below 1, what cvo_fe_check_binning refuses (cvo_fe_bin_image reads the factor only) and a stride
+ * below the source's row; CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_bin_image(int device, const uint8_t *bgr, size_t stride_bytes, int width, int height, int factor, uint8_t *out);
+int cvo_fe_bin_depth(int device, const uint16_t *plane, size_t stride_bytes, int width, int height,
+                     const cvo_fe_binning *b, uint16_t *out, int *valid);
 
 /* CVO_HIP_OK for settings cvo_fe_set_lidar() would accept on an idle context without stereo and depth camera,
  * CVO_HIP_ERR_INVALID otherwise: NULL; max_points outside [1, 2^21]; splat outside [0, 3]; a float that is not finite;
