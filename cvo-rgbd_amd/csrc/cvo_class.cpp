@@ -63,7 +63,8 @@ registration::registration(int mode, int device, void *stream)
       depth_gate_(), have_depth_gate_(false), mask_rows_(0), mask_cols_(0), have_mask_(false), stereo_(), have_stereo_(false),
       stereo_rig_(), have_stereo_rig_(false), stereo_paths_(CVO_FE_PATHS_4), stereo_speckle_(), have_stereo_speckle_(false),
       depth_median_(), have_depth_median_(false), depth_infill_(), have_depth_infill_(false), lidar_(), have_lidar_(false), lidar_sweep_(), have_lidar_sweep_(false), lidar_motion_(), select_mode_(CVO_FE_SELECT_IMAGE),
-      pixel_format_(CVO_FE_PIXEL_BGR8), depth_format_(CVO_FE_DEPTH_U16), depth_unit_(1.0f), binning_(), have_binning_(false)
+      pixel_format_(CVO_FE_PIXEL_BGR8), depth_format_(CVO_FE_DEPTH_U16), depth_unit_(1.0f), binning_(), have_binning_(false),
+      photometric_(), have_photometric_(false), photo_rows_(0), photo_cols_(0), photo_gain_{1.0f, 1.0f, 1.0f}
 {
     check(cvo_hip_default_params(mode, &params_), "cvo_hip_default_params");
     check(cvo_hip_init_state(&params_, &state_), "cvo_hip_init_state");
@@ -107,6 +108,7 @@ void registration::apply_stored_settings()
         }
         fe_check(cvo_fe_set_pixel_format(fe_, pixel_format_), "cvo_fe_set_pixel_format");
         fe_check(cvo_fe_set_depth_format(fe_, depth_format_, depth_unit_), "cvo_fe_set_depth_format");
+        if (have_photometric_) apply_photometric();   // (behind the binning: the vignette is of the input size)
         if (have_mask_) {
             const bool fits = mask_rows_ == fe_h_ && mask_cols_ == fe_w_;
             fe_check(fits ? cvo_fe_set_mask(fe_, mask_.data(), (size_t)mask_cols_) : CVO_HIP_ERR_INVALID, "cvo_fe_set_mask",
@@ -343,6 +345,74 @@ void registration::set_input_binning(const cvo_fe_binning &binning)
 void registration::clear_input_binning()
 {
     store<cvo_fe_binning>(cvo_fe_set_input_binning, "cvo_fe_set_input_binning", nullptr, binning_, have_binning_);
+}
+
+// the stored photometric setting to the front end: its tables, then the gains
+void registration::apply_photometric()
+{
+    const uint16_t *vig = photo_vignette_.empty() ? nullptr : photo_vignette_.data();
+    const int bin = have_binning_ ? binning_.factor : 1;
+    const bool fits = !vig || (photo_rows_ == bin * fe_h_ && photo_cols_ == bin * fe_w_);
+    fe_check(fits ? cvo_fe_set_photometric(fe_, &photometric_, photo_response_.empty() ? nullptr : photo_response_.data(), vig,
+                                           (size_t)photo_cols_ * 2)
+                  : CVO_HIP_ERR_INVALID,
+             "cvo_fe_set_photometric", fits ? nullptr : "the vignette must have the size of the images handed over");
+    if (photometric_.flags & CVO_FE_PHOTO_GAIN) fe_check(cvo_fe_set_photometric_gain(fe_, photo_gain_), "cvo_fe_set_photometric_gain");
+}
+
+void registration::set_photometric(const cvo_fe_photometric &photometric, const uint16_t *response, const uint16_t *vignette,
+                                   int vignette_rows, int vignette_cols, size_t vignette_step)
+{
+    if (cvo_fe_check_photometric(&photometric, response != nullptr, vignette != nullptr) != CVO_HIP_OK)
+        throw refused("set_photometric", rules::photometric);
+    if (vignette && (vignette_rows < 1 || vignette_cols < 1 || vignette_step < (size_t)vignette_cols * 2 || vignette_step % 2 != 0))
+        throw std::runtime_error("set_photometric(): a vignette of rows x cols uint16, rows an even number of bytes, at least the row's, apart");
+    // kept first (the front end takes the dense copy); a refusal by the front end puts back what was kept before
+    const cvo_fe_photometric old = photometric_;
+    const bool had = have_photometric_;
+    std::vector<uint16_t> old_r = photo_response_, old_v = photo_vignette_;
+    const int old_rows = photo_rows_, old_cols = photo_cols_;
+    const float old_gain[3] = {photo_gain_[0], photo_gain_[1], photo_gain_[2]};
+    photometric_ = photometric;
+    have_photometric_ = true;
+    photo_response_.assign(response, response ? response + 768 : response);
+    photo_vignette_.clear();
+    for (int y = 0; vignette && y < vignette_rows; ++y) {
+        const uint16_t *row = (const uint16_t *)((const uint8_t *)vignette + (size_t)y * vignette_step);
+        photo_vignette_.insert(photo_vignette_.end(), row, row + vignette_cols);
+    }
+    photo_rows_ = vignette ? vignette_rows : 0;
+    photo_cols_ = vignette ? vignette_cols : 0;
+    for (float &g : photo_gain_) g = 1.0f;
+    if (!fe_) return;
+    try {
+        apply_photometric();
+    } catch (...) {
+        photometric_ = old; have_photometric_ = had;
+        photo_response_ = old_r; photo_vignette_ = old_v;
+        photo_rows_ = old_rows; photo_cols_ = old_cols;
+        for (int c = 0; c < 3; ++c) photo_gain_[c] = old_gain[c];
+        throw;
+    }
+}
+
+void registration::clear_photometric()
+{
+    if (fe_) fe_check(cvo_fe_set_photometric(fe_, nullptr, nullptr, nullptr, 0), "cvo_fe_set_photometric");
+    have_photometric_ = false;
+    photo_response_.clear();
+    photo_vignette_.clear();
+    photo_rows_ = photo_cols_ = 0;
+}
+
+void registration::set_photometric_gain(const float gain[3])
+{
+    if (!gain || !have_photometric_ || !(photometric_.flags & CVO_FE_PHOTO_GAIN))
+        throw std::runtime_error("set_photometric_gain(): set_photometric() with CVO_FE_PHOTO_GAIN first");
+    for (int c = 0; c < 3; ++c)
+        if (!(gain[c] >= 0.0625f && gain[c] <= 15.99f)) throw refused("set_photometric_gain", rules::photometric_gain);
+    if (fe_) fe_check(cvo_fe_set_photometric_gain(fe_, gain), "cvo_fe_set_photometric_gain");
+    for (int c = 0; c < 3; ++c) photo_gain_[c] = gain[c];
 }
 
 void registration::set_depth_format(int format, float unit)

@@ -14,6 +14,7 @@
 
 #include "cvo_frontend.h"
 #include "cvo_depthfmt.h"
+#include "cvo_photo.h"
 
 constexpr int FE_LEVELS = 3;
 constexpr int FE_GATE_MAX_GROW = 3;   // the largest `grow` k_fe_depth_gate is built for
@@ -210,6 +211,20 @@ struct cvo_fe_ctx {
     // set) and the depth image
     Dev<uint8_t> full_img, full_right;
     Dev<uint16_t> full_depth;
+    // the photometric stage (cvo_fe_set_photometric): a setting of the context, read by every frame; with it
+    // k_fe_photo_apply of cvo_photo.hip corrects img_input / right_input in place behind the unpack and in front of the bin
+    cvo_fe_photometric photo{};
+    bool has_photo = false;
+    // with the setting, and gone with it: the tables (the vignette dense at iw x ih), the header a frame's sequence
+    // copies from its pinned twin, and under AUTO the state with the frame's record and the record's pinned landing
+    Dev<uint16_t> photo_response, photo_vignette;
+    Dev<FePhotoHeader> photo_hdr;
+    Pin<FePhotoHeader> h_photo_hdr;
+    Dev<FePhotoState> photo_state;
+    Pin<cvo_fe_photometric_frame> h_photo_rec;
+    uint32_t photo_gain[3] = {4096u, 4096u, 4096u};   // of the frames submitted from now on (cvo_fe_set_photometric_gain)
+    bool photo_rearm = false;                          // the next frame opens the lock (cvo_fe_photometric_rearm)
+    cvo_fe_photometric_frame photo_frame{};            // the last collected frame's record
     std::string err;
 };
 

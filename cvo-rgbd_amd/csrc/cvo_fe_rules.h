@@ -31,6 +31,11 @@ constexpr const char *stereo_rig =
     "finite members, every fx, fy, depth_scale and baseline positive, R_left and R_right rotations";
 constexpr const char *binning =
     "factor 2, 3 or 4, depth_min in [1, factor^2], pad_ 0, factor times the context's width and height at most 8192";
+constexpr const char *photometric =
+    "flags a non-empty OR of CVO_FE_PHOTO_* without both GAIN and AUTO, 0 <= lo <= hi <= 255, min_count >= 1, per_channel 0 "
+    "or 1, every target at most 65535, 1 <= gain_min <= gain_max <= 65535, pad_ 0, a response table exactly with "
+    "CVO_FE_PHOTO_RESPONSE and a vignette exactly with CVO_FE_PHOTO_VIGNETTE";
+constexpr const char *photometric_gain = "three finite gains in [1/16, 15.99]";
 // The predicates (cvo_fe_settings.cpp), for the setters and for the host-only helpers that take the same structures.
 bool model_ok(const cvo_fe_camera_model &m);
 bool rotation_ok(const float R[9]);

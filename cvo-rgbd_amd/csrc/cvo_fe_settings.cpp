@@ -530,6 +530,12 @@ int cvo_fe_set_input_binning(cvo_fe_ctx *ctx, const cvo_fe_binning *b)
     if (unpacks(ctx) && !fe_unpack_layout(ctx->pixfmt, iw, ih, &row, &rows))
         return refuse(ctx, "set_input_binning", "the pixel format in force does not fit the input size, factor times the context's");
     if (same_setting(b, ctx->has_bin, ctx->bin)) return CVO_HIP_OK;
+    // (a vignette belongs to the sensor's pixels: it does not follow a change of the input size)
+    if (ctx->photo_vignette && (iw != ctx->iw || ih != ctx->ih))
+        return refuse(ctx, "set_input_binning", ("a vignette of " + std::to_string(ctx->iw) + " x " + std::to_string(ctx->ih) +
+                                                 " is set and the input size would become " + std::to_string(iw) + " x " +
+                                                 std::to_string(ih) + ": set the photometric stage off first, and again with a "
+                                                 "vignette of that size").c_str());
     FE_HIP(hipSetDevice(ctx->device));
     // Everything that holds a caller's image follows the input size: the staging of the colour image, of the right one
     // (a context that has had stereo set), of the depth image (unless a depth camera sizes it), the float and the
@@ -570,6 +576,98 @@ int cvo_fe_set_input_binning(cvo_fe_ctx *ctx, const cvo_fe_binning *b)
     }
     store_setting(ctx->has_bin, ctx->bin, b);
     drop_graphs(ctx);   // (whether a frame has the bin's launch, its numbers and where the uploads land are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_photometric(const Ctx *c, cvo_fe_photometric *out, int *set) { return get_setting(c, &Ctx::has_photo, &Ctx::photo, out, set); }
+
+int cvo_fe_set_photometric(cvo_fe_ctx *ctx, const cvo_fe_photometric *p, const uint16_t *response, const uint16_t *vignette,
+                           size_t vignette_stride)
+{
+    cvo_lock::Api api_guard;
+    if (const int rc = setter_begin(ctx, "set_photometric")) return rc;
+    if (p && p->flags == 0u && !response && !vignette) p = nullptr;   // (the other spelling of "off")
+    if (p && cvo_fe_check_photometric(p, response != nullptr, vignette != nullptr) != CVO_HIP_OK)
+        return refuse(ctx, "set_photometric", rules::photometric);
+    const size_t vrow = (size_t)ctx->iw * 2;
+    if (p && vignette && (vignette_stride < vrow || vignette_stride % 2 != 0))
+        return refuse(ctx, "set_photometric", ("a vignette of " + std::to_string(ctx->iw) + " x " + std::to_string(ctx->ih) +
+                                               " uint16, the size of the images a frame takes, in rows an even number of "
+                                               "bytes, at least the row's, apart").c_str());
+    if (!p && !ctx->has_photo) return CVO_HIP_OK;   // (tables cannot be compared: a setting given again is made again)
+    FE_HIP(hipSetDevice(ctx->device));
+    Dev<uint16_t> resp, vig;
+    Dev<FePhotoHeader> hdr;
+    Pin<FePhotoHeader> h_hdr;
+    Dev<FePhotoState> state;
+    Pin<cvo_fe_photometric_frame> h_rec;
+    if (p) {
+        const size_t inp = (size_t)ctx->iw * ctx->ih;
+        const bool automatic = (p->flags & CVO_FE_PHOTO_AUTO) != 0;
+        if (!(dev_alloc(hdr, 1) && pin_alloc(h_hdr, 1) && (!response || dev_alloc(resp, 768)) && (!vignette || dev_alloc(vig, inp)) &&
+              (!automatic || (dev_alloc(state, 1) && pin_alloc(h_rec, 1)))))
+            return no_memory(ctx, "set_photometric: device and pinned memory for the tables, the header and the state");
+        hipError_t e = hipSuccess;
+        if (response) e = hipMemcpy(resp.get(), response, 768 * sizeof(uint16_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess && vignette)
+            e = hipMemcpy2D(vig.get(), vrow, vignette, vignette_stride, vrow, (size_t)ctx->ih, hipMemcpyHostToDevice);
+        // the state starts at zero: the sums, and the lock open
+        if (e == hipSuccess && automatic) e = hipMemset(state.get(), 0, sizeof(FePhotoState));
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (settle(), behind the uploads under one message)
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, CVO_HIP_ERR_HIP, "set_photometric: upload of the tables", e);
+        }
+    } else if (const int rc = settle(ctx, "set_photometric")) return rc;
+    // whole: everything of the old setting goes, with or without a new one
+    ctx->photo_response = std::move(resp);
+    ctx->photo_vignette = std::move(vig);
+    ctx->photo_hdr = std::move(hdr);
+    ctx->h_photo_hdr = std::move(h_hdr);
+    ctx->photo_state = std::move(state);
+    ctx->h_photo_rec = std::move(h_rec);
+    store_setting(ctx->has_photo, ctx->photo, p);
+    for (uint32_t &g : ctx->photo_gain) g = 4096u;
+    ctx->photo_rearm = false;   // (the new state's lock is open)
+    ctx->photo_frame = cvo_fe_photometric_frame{};
+    drop_graphs(ctx);   // (whether a frame has the stage's launches, their instances, numbers and tables are part of a captured graph)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_set_photometric_gain(cvo_fe_ctx *ctx, const float gain[3])
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (!gain) return fail(ctx, CVO_HIP_ERR_INVALID, "set_photometric_gain: bad argument");
+    if (!ctx->has_photo || !(ctx->photo.flags & CVO_FE_PHOTO_GAIN))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "set_photometric_gain: the stage is not set with CVO_FE_PHOTO_GAIN (cvo_fe_set_photometric)");
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(gain[c]) || gain[c] < 0.0625f || gain[c] > 15.99f)
+            return refuse(ctx, "set_photometric_gain", rules::photometric_gain);
+    for (int c = 0; c < 3; ++c) {   // (read by the next submit: no graph holds it)
+        const float scaled = gain[c] * 4096.0f;
+        ctx->photo_gain[c] = (uint32_t)(scaled + 0.5f);
+    }
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_photometric_rearm(cvo_fe_ctx *ctx)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx) return CVO_HIP_ERR_INVALID;
+    if (!ctx->has_photo || !(ctx->photo.flags & CVO_FE_PHOTO_AUTO))
+        return fail(ctx, CVO_HIP_ERR_INVALID, "photometric_rearm: the stage is not set with CVO_FE_PHOTO_AUTO (cvo_fe_set_photometric)");
+    ctx->photo_rearm = true;   // (travels in the next frame's header)
+    return CVO_HIP_OK;
+}
+
+int cvo_fe_get_photometric_frame(const cvo_fe_ctx *ctx, cvo_fe_photometric_frame *out)
+{
+    cvo_lock::Api api_guard;
+    if (!ctx || !out) return CVO_HIP_ERR_INVALID;
+    if (!ctx->has_photo) return CVO_HIP_ERR_INVALID;
+    *out = ctx->photo_frame;
     return CVO_HIP_OK;
 }
 

@@ -1188,6 +1188,18 @@ int enqueue_frame(cvo_fe_ctx *ctx, int dataset_seq, int feature_type)
         u.w = ctx->iw; u.h = ctx->ih; u.format = ctx->pixfmt; u.images = ctx->has_stereo ? 2 : 1;
         fe_unpack_enqueue(u, s);
     }
+    if (ctx->has_photo) {   // (the photometric contract: behind the unpack, in front of the bin, in place, one launch for a pair)
+        FE_HIP(hipMemcpyAsync(ctx->photo_hdr.get(), ctx->h_photo_hdr.get(), sizeof(FePhotoHeader), hipMemcpyHostToDevice, s));
+        FePhotoArgs p{};
+        p.img[0] = img_input(ctx); p.img[1] = ctx->has_stereo ? right_input(ctx) : nullptr;
+        p.images = ctx->has_stereo ? 2 : 1; p.w = ctx->iw; p.h = ctx->ih;
+        p.response = ctx->photo_response.get(); p.vignette = ctx->photo_vignette.get();
+        p.hdr = ctx->photo_hdr.get(); p.state = ctx->photo_state.get(); p.set = ctx->photo;
+        fe_photo_enqueue(p, s);
+        if (ctx->photo.flags & CVO_FE_PHOTO_AUTO)   // (the frame's record, read at collect())
+            FE_HIP(hipMemcpyAsync(ctx->h_photo_rec.get(), &ctx->photo_state.get()->rec, sizeof(cvo_fe_photometric_frame),
+                                  hipMemcpyDeviceToHost, s));
+    }
     if (ctx->has_bin) {   // (the binning contract: behind those two, in front of everything else, one launch for all planes)
         FeBinArgs b{};
         b.src[0] = ctx->full_img.get(); b.dst[0] = img_landing(ctx);
@@ -1358,6 +1370,10 @@ int collect_impl(cvo_fe_ctx *ctx, float *positions, float *features, int capacit
     ctx->info.pot_used = c.pot[c.redo ? 1 : 0];
     ctx->info.canny_used = canny ? 1 : 0;
     ctx->info.num_points = c.num_points;
+    if (ctx->has_photo) {   // (no setter runs while a frame is in flight: the setting is the frame's)
+        if (ctx->photo.flags & CVO_FE_PHOTO_AUTO) ctx->photo_frame = *ctx->h_photo_rec;
+        else fe_photo_plain_record(*ctx->h_photo_hdr, &ctx->photo_frame);
+    }
     *num_points = c.num_points;
     const int ncopy = std::min(std::min(c.num_points, capacity), ctx->cap);
     float *h_pos = ctx->h_pos.get(), *h_feat = ctx->h_feat.get();
@@ -1601,6 +1617,10 @@ int submit_frame(cvo_fe_ctx *ctx, const uint8_t *img, size_t img_stride, const v
     FeCtrl c0{};
     c0.pot[0] = 3;   // a selector starts every frame at potential 3 (ref PixelSelector2.cpp:39)
     *ctx->h_ctrl = c0;
+    if (ctx->has_photo) {   // (the frame's gains and the lock's opening travel in the header the sequence copies)
+        fe_photo_header(ctx->photo, ctx->photo_gain, ctx->photo_rearm, ctx->h_photo_hdr.get());
+        ctx->photo_rearm = false;
+    }
     // a mask set since the last frame: in front of the frame, outside the captured graph (its address is the graph's)
     if (ctx->has_mask && ctx->mask_dirty) {
         FE_HIP(hipMemcpyAsync(ctx->d_mask.get(), ctx->h_mask.get(), (size_t)np, hipMemcpyHostToDevice, s));
@@ -1822,7 +1842,7 @@ int cvo_fe_read_stage(cvo_fe_ctx *ctx, int stage, void *out, size_t bytes)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the median filter, and no filter is set");
     if ((stage == CVO_FE_STAGE_SPARSE_DEPTH || stage == CVO_FE_STAGE_INFILL) && !ctx->has_infill)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: a plane of the infill stage, and the stage is not set");
-    if ((stage == CVO_FE_STAGE_INPUT_BGR || stage == CVO_FE_STAGE_INPUT_RIGHT_BGR) && !unpacks(ctx) && !ctx->has_bin)
+    if ((stage == CVO_FE_STAGE_INPUT_BGR || stage == CVO_FE_STAGE_INPUT_RIGHT_BGR) && !unpacks(ctx) && !ctx->has_bin && !ctx->has_photo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: an unpacked image, and the context's pixel format is BGR8");
     if (stage == CVO_FE_STAGE_INPUT_RIGHT_BGR && !ctx->has_stereo)
         return fail(ctx, CVO_HIP_ERR_INVALID, "read_stage: the unpacked right image, and the context has no stereo");

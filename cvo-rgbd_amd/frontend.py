@@ -113,7 +113,13 @@ SYMBOLS = ("cvo_fe_create", "cvo_fe_destroy", "cvo_fe_last_error", "cvo_fe_set_n
            "cvo_fe_lidar_twist", "cvo_fe_project_points_sweep", "cvo_fe_check_depth_format", "cvo_fe_set_depth_format",
            "cvo_fe_get_depth_format", "cvo_fe_convert_depth", "cvo_fe_submit_device", "cvo_fe_submit_stereo_device",
            "cvo_fe_check_binning", "cvo_fe_set_input_binning", "cvo_fe_get_input_binning", "cvo_fe_bin_camera",
-           "cvo_fe_bin_stereo_rig", "cvo_fe_bin_image", "cvo_fe_bin_depth")
+           "cvo_fe_bin_stereo_rig", "cvo_fe_bin_image", "cvo_fe_bin_depth",
+           "cvo_fe_check_photometric", "cvo_fe_set_photometric", "cvo_fe_get_photometric", "cvo_fe_set_photometric_gain",
+           "cvo_fe_photometric_rearm", "cvo_fe_get_photometric_frame", "cvo_fe_photometric_image",
+           "cvo_fe_response_table", "cvo_fe_vignette_gains")
+# the flags of Photometric, and of PhotometricFrame
+PHOTO_RESPONSE, PHOTO_VIGNETTE, PHOTO_GAIN, PHOTO_AUTO = 1, 2, 4, 8
+PHOTO_FALLBACK, PHOTO_LOCKED = 1, 2
 
 
 class Info(C.Structure):
@@ -225,6 +231,29 @@ class Binning(_Settings):
 
     def __init__(self, factor=2, depth_min=1, pad_=0):
         super().__init__(int(factor), int(depth_min), int(pad_))
+
+
+class Photometric(_Settings):
+    """cvo_fe_photometric: the photometric stage (the photometric contract of include/cvo_frontend.h).  `flags`: an OR
+    of PHOTO_RESPONSE, PHOTO_VIGNETTE (a table of that kind is handed over beside the settings), PHOTO_GAIN (the
+    caller's gain per frame and channel: set_photometric_gain) and PHOTO_AUTO (the gain estimated on the device from
+    the pixels whose three input bytes lie in [lo, hi], at least `min_count` of them; `target` B G R in Q8, all zero:
+    the first such frame's own statistic; `per_channel` 0: one gain for all channels).  `gain_min`, `gain_max`: Q12."""
+    _fields_ = [("flags", C.c_uint32), ("lo", C.c_int32), ("hi", C.c_int32), ("min_count", C.c_int32),
+                ("per_channel", C.c_int32), ("target", C.c_uint32 * 3), ("gain_min", C.c_int32), ("gain_max", C.c_int32),
+                ("pad_", C.c_int32)]
+
+    def __init__(self, flags=PHOTO_GAIN, lo=8, hi=247, min_count=1, per_channel=0, target=(0, 0, 0), gain_min=256,
+                 gain_max=65535, pad_=0):
+        super().__init__(int(flags), int(lo), int(hi), int(min_count), int(per_channel),
+                         (C.c_uint32 * 3)(*(int(t) for t in target)), int(gain_min), int(gain_max), int(pad_))
+
+
+class PhotometricFrame(_Settings):
+    """cvo_fe_photometric_frame: what the stage did to a frame: the gains (Q12) it was corrected with, PHOTO_FALLBACK /
+    PHOTO_LOCKED, and under PHOTO_AUTO the count k, the sums M and the target T in force behind the frame."""
+    _fields_ = [("gain", C.c_uint32 * 3), ("flags", C.c_uint32), ("count", C.c_uint64), ("sum", C.c_uint64 * 3),
+                ("target", C.c_uint32 * 3), ("pad_", C.c_uint32)]
 
 
 class DepthInfill(_Settings):
@@ -430,6 +459,17 @@ def lib():
         L.cvo_fe_bin_image.argtypes = [C.c_int, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, u8p]
         L.cvo_fe_bin_depth.argtypes = [C.c_int, u16p, C.c_size_t, C.c_int, C.c_int, C.POINTER(Binning), u16p,
                                        C.POINTER(C.c_int)]
+        pp, fp = C.POINTER(Photometric), C.POINTER(C.c_float)
+        L.cvo_fe_check_photometric.argtypes = [pp, C.c_int, C.c_int]
+        L.cvo_fe_set_photometric.argtypes = [vp, pp, u16p, u16p, C.c_size_t]
+        L.cvo_fe_get_photometric.argtypes = [vp, pp, C.POINTER(C.c_int)]
+        L.cvo_fe_set_photometric_gain.argtypes = [vp, fp]
+        L.cvo_fe_photometric_rearm.argtypes = [vp]
+        L.cvo_fe_get_photometric_frame.argtypes = [vp, C.POINTER(PhotometricFrame)]
+        L.cvo_fe_photometric_image.argtypes = [C.c_int, u8p, C.c_int, C.c_int, C.c_size_t, pp, u16p, u16p, C.c_size_t,
+                                               C.POINTER(C.c_uint32), u8p, C.POINTER(PhotometricFrame)]
+        L.cvo_fe_response_table.argtypes = [fp, u16p]
+        L.cvo_fe_vignette_gains.argtypes = [u16p, C.c_size_t, u16p]
         for name in SYMBOLS:
             if name != "cvo_fe_last_error":
                 getattr(L, name).restype = C.c_int
@@ -700,6 +740,77 @@ def bin_depth(plane, binning, device=0, stride=None):
     if not (buf == keep).all():
         raise RuntimeError("bin_depth: the source was written")
     return out, valid.value
+
+
+def _photo_tables(response, vignette, width, height, what):
+    """The two tables as the library takes them: (response 3 x 256 uint16 or None, vignette h x w uint16 or None)."""
+    if response is not None:
+        response = np.ascontiguousarray(response, np.uint16)
+        if response.shape != (3, 256):
+            raise ValueError("%s: expected a 3 x 256 uint16 response table (B, G, R)" % what)
+    if vignette is not None:
+        vignette = np.ascontiguousarray(vignette, np.uint16)
+        if vignette.shape != (height, width):
+            raise ValueError("%s: expected a %d x %d uint16 vignette, the size of the images a frame takes" % (what, height, width))
+    return response, vignette
+
+
+def _u16p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
+def check_photometric(photometric, response=False, vignette=False):
+    """True for a Photometric set_photometric() accepts beside a response table / a vignette (`response`, `vignette`:
+    whether one is handed over; cvo_fe_check_photometric); None is refused.  Host only."""
+    return lib().cvo_fe_check_photometric(None if photometric is None else C.byref(photometric),
+                                          1 if response is not None and response is not False else 0,
+                                          1 if vignette is not None and vignette is not False else 0) == 0
+
+
+def response_table(inv):
+    """A row of the response table from a channel's inverse response, 256 floats in [0, 255] -- a row of DSO's
+    pcalib.txt (cvo_fe_response_table): min(65535, uint32(v * 256 + 0.5)) in float32.  Host only."""
+    src = np.ascontiguousarray(inv, np.float32)
+    if src.shape != (256,):
+        raise ValueError("response_table: expected 256 values")
+    out = np.empty(256, np.uint16)
+    capi.check(lib().cvo_fe_response_table(src.ctypes.data_as(C.POINTER(C.c_float)), _u16p(out)), what="response_table")
+    return out
+
+
+def vignette_gains(atten):
+    """The vignette's Q12 gains from its attenuations as uint16, 65535 = none -- the plane of DSO's vignette.png
+    (cvo_fe_vignette_gains): a ? min(65535, (4096 * 65535 + a // 2) // a) : 65535, in the argument's shape.  Host only."""
+    src = np.ascontiguousarray(atten, np.uint16)
+    out = np.empty(src.shape, np.uint16)
+    capi.check(lib().cvo_fe_vignette_gains(_u16p(src), src.size, _u16p(out)), what="vignette_gains")
+    return out
+
+
+def photometric_image(bgr, photometric, response=None, vignette=None, gains_q12=None, device=0, stride=None,
+                      vignette_stride=None):
+    """The photometric contract on any h x w x 3 uint8 image (cvo_fe_photometric_image: the kernels a frame runs,
+    without a generator; under PHOTO_AUTO the image is a first frame).  Returns (the corrected image, its
+    PhotometricFrame); the argument is left as it is.  `stride`: the image is handed over in rows that many bytes apart;
+    `vignette_stride`: the vignette in rows that many uint16 apart."""
+    src = np.ascontiguousarray(bgr, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("expected an h x w x 3 uint8 image")
+    h, w = src.shape[:2]
+    response, vignette = _photo_tables(response, vignette, w, h, "photometric_image")
+    buf, pitch = _strided(src, w * 3, stride, 0xA5)
+    keep = buf.copy()
+    vbuf, vpitch = (None, 0) if vignette is None else _strided(vignette, w, vignette_stride, 0xA5A5)
+    g = None if gains_q12 is None else (C.c_uint32 * 3)(*(int(v) for v in gains_q12))
+    out, rec = np.empty((h, w, 3), np.uint8), PhotometricFrame()
+    u8p = C.POINTER(C.c_uint8)
+    capi.check(lib().cvo_fe_photometric_image(int(device), buf.ctypes.data_as(u8p), w, h, pitch,
+                                              None if photometric is None else C.byref(photometric), _u16p(response),
+                                              _u16p(vbuf), vpitch * 2, g, out.ctypes.data_as(u8p), C.byref(rec)),
+               what="photometric_image")
+    if not (buf == keep).all():
+        raise RuntimeError("photometric_image: the source was written")
+    return out, rec
 
 
 def check_depth_format(fmt, unit=1.0):
@@ -1224,6 +1335,41 @@ class PcdGenerator:
         """The Binning in force, or None."""
         return self._get_struct("input_binning", Binning)
 
+    def set_photometric(self, photometric, response=None, vignette=None):
+        """A Photometric for every following frame of any kind (the photometric contract of include/cvo_frontend.h): the
+        colour bytes -- both images of a stereo pair -- are corrected in place on the device behind the unpack and in
+        front of the bin by `response` (3 x 256 uint16, B G R; response_table() makes a row), `vignette` (uint16 Q12
+        gains of the size of the images a frame takes; vignette_gains() makes them) and the frame's gain per channel:
+        the caller's (PHOTO_GAIN, set_photometric_gain) or estimated (PHOTO_AUTO).  Both tables are copied.  None: off,
+        a new object's.  A setting of its own: it survives every other setter; with a vignette set, set_input_binning()
+        refuses a change of the input size."""
+        if photometric is None:
+            self._chk(lib().cvo_fe_set_photometric(self._h, None, None, None, 0), "set_photometric")
+            return
+        response, vignette = _photo_tables(response, vignette, self._iw, self._ih, "set_photometric")
+        self._chk(lib().cvo_fe_set_photometric(self._h, C.byref(photometric), _u16p(response), _u16p(vignette),
+                                               self._iw * 2), "set_photometric")
+
+    def photometric(self):
+        """The Photometric in force, or None (the tables are not handed back)."""
+        return self._get_struct("photometric", Photometric)
+
+    def set_photometric_gain(self, gain):
+        """The gains (one number, or B G R) of the frames submitted from now on, under PHOTO_GAIN: e.g. a reference
+        exposure time over the frame's.  Finite, in [1/16, 15.99]; they hold until changed, and no graph is dropped."""
+        g = np.broadcast_to(np.asarray(gain, np.float32), (3,))
+        self._chk(lib().cvo_fe_set_photometric_gain(self._h, (C.c_float * 3)(*(float(v) for v in g))), "set_photometric_gain")
+
+    def photometric_rearm(self):
+        """Opens the lock of PHOTO_AUTO: the next frame with enough counted pixels sets the target."""
+        self._chk(lib().cvo_fe_photometric_rearm(self._h), "photometric_rearm")
+
+    def photometric_frame(self):
+        """The PhotometricFrame of the last collected frame."""
+        out = PhotometricFrame()
+        self._chk(lib().cvo_fe_get_photometric_frame(self._h, C.byref(out)), "photometric_frame")
+        return out
+
     def set_depth_format(self, fmt, unit=1.0):
         """The DEPTH_* format of the depth image of every following frame that has one (the depth-format contract of
         include/cvo_frontend.h): under DEPTH_F32 / DEPTH_F16 the depth images are float32 / float16 planes in `unit`
@@ -1386,8 +1532,13 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
                camera=None, depth_camera=None, depth_gate=None, mask=None, stereo=None, stereo_rig=None, stereo_paths=None,
                stereo_speckle=None, select_mode=None, depth_median=None, lidar=None, depth_infill=None, pixel_format=None,
                lidar_sweep=None, lidar_motion=None, sweep_fraction=1.0, depth_format=None, device_input=False,
-               input_binning=None):
+               input_binning=None, photometric=None, exposures=None):
     """The driver loop on decoded frames: `frames` yields (name, bgr, depth).
+    `photometric`: a Photometric for the generator, or (Photometric, response, vignette) with the tables of
+    set_photometric(); the vignette has the size of the images `frames` yields.  None leaves the generator as it is.
+    `exposures`: the frames' exposure times (a sequence, frame i's at index i): frame i runs under the gain
+    exposures[0] / exposures[i] on all channels (set_photometric_gain); the Photometric must have PHOTO_GAIN, and where
+    `photometric` is None a Photometric(PHOTO_GAIN) is set.
     `input_binning`: a Binning for the generator: `frames` then yields images of the INPUT size, factor times the
     generator's each way (a first frame decides a new generator's size as shape // factor; a shape that is no multiple
     of the factor is a ValueError), and `camera`, `stereo_rig` and, where `camera` is None, the table row of
@@ -1486,6 +1637,12 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
         gen.set_lidar_sweep(lidar_sweep)
     if device_input and lidar is not None:
         raise ValueError("device_input: not for LiDAR frames (a scan is staged by the host)")
+    if exposures is not None and photometric is None:
+        photometric = Photometric(PHOTO_GAIN)
+    if photometric is not None:   # (behind input_binning: the vignette is of the input size)
+        gen.set_photometric(*(photometric if isinstance(photometric, (tuple, list)) else (photometric,)))
+    if exposures is not None and not gen.photometric().flags & PHOTO_GAIN:
+        raise ValueError("exposures: the Photometric must have PHOTO_GAIN")
     submit = gen.submit_stereo if stereo is not None else gen.submit_lidar if lidar is not None else gen.submit
     if device_input:
         submit = gen.submit_stereo_device if stereo is not None else gen.submit_device
@@ -1511,6 +1668,13 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
         def submit(bgr, points, seq, ft, name=None):
             inner0(bgr, points, seq, ft)
+    if exposures is not None:
+        exposed, frame_no = submit, [0]
+
+        def submit(bgr, second, seq, ft, name=None):
+            gen.set_photometric_gain(float(exposures[0]) / float(exposures[frame_no[0]]))
+            frame_no[0] += 1
+            exposed(bgr, second, seq, ft, name)
     gen.set_device_output(device)
     submit(cur[1], cur[2], dataset_seq, ftype, cur[0])
     while cur is not None:
@@ -1540,7 +1704,7 @@ def run_frames(registration, frames, dataset_seq, writer=None, generator=None, p
 
 def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.txt", limit=None,
                   generator=None, camera=None, depth_camera=None, depth_gate=None, mask=None, select_mode=None,
-                  depth_median=None, depth_infill=None, input_binning=None):
+                  depth_median=None, depth_infill=None, input_binning=None, photometric=None, exposures=None):
     """The reference's main loop (ref src/cvo_main.cpp:20-66, adaptive_cvo_main.cpp): every
     frame of `folder`/assoc goes through the front end and `run_cvo`; a pose line per
     frame is handed to `writer` (trajectory.TrajectoryWriter).  cvo uses the raw colour
@@ -1551,7 +1715,8 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
     `select_mode`: as in run_frames, e.g. SELECT_DEPTH beside a gate, which removes the pixels the selector likes best.
     `depth_median`: as in run_frames, e.g. DepthMedian(1, 5) for a sensor with salt and pinholes.
     `depth_infill`: as in run_frames, e.g. DepthInfill(2, 2, 0.05) for the holes a depth camera's registration leaves.
-    `input_binning`: as in run_frames, e.g. Binning(2, 2) for a 1280 x 720 recording worked on at 640 x 360."""
+    `input_binning`: as in run_frames, e.g. Binning(2, 2) for a 1280 x 720 recording worked on at 640 x 360.
+    `photometric`, `exposures`: as in run_frames, e.g. Photometric(PHOTO_AUTO) for a recording under auto exposure."""
     names, rgbs, deps = load_file_name(os.path.join(folder, assoc))
     if limit is not None:
         names, rgbs, deps = names[:limit], rgbs[:limit], deps[:limit]
@@ -1563,19 +1728,20 @@ def run_directory(registration, folder, dataset_seq, writer=None, assoc="assoc.t
 
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_camera=depth_camera, depth_gate=depth_gate, mask=mask, select_mode=select_mode,
-                      depth_median=depth_median, depth_infill=depth_infill, input_binning=input_binning)
+                      depth_median=depth_median, depth_infill=depth_infill, input_binning=input_binning,
+                      photometric=photometric, exposures=exposures)
 
 
 def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None, left="image_2", right="image_3",
                          times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
                          stereo_rig=None, stereo_paths=None, stereo_speckle=None, select_mode=None, depth_median=None,
-                         depth_infill=None, input_binning=None):
+                         depth_infill=None, input_binning=None, photometric=None, exposures=None):
     """run_directory() for the KITTI odometry layout: one line of `folder`/`times` per frame (the line is the frame's
     name), the pair in `folder`/`left`/%06d.png and `folder`/`right`/%06d.png, decoded by PIL as load_img does (B, G, R;
     a grey image is replicated).  `stereo`: the Stereo for the generator, e.g. Stereo(0.54, 128) with dataset_seq 4.
     `camera`, `depth_gate`, `mask`: as in run_frames.  `stereo_rig`: as in run_frames, for a raw recording (KITTI raw's
     image_02 / image_03 with the rig of its calib_cam_to_cam.txt).  `stereo_paths`, `stereo_speckle`, `select_mode`, `depth_median`,
-    `depth_infill`, `input_binning`: as in run_frames."""
+    `depth_infill`, `input_binning`, `photometric`, `exposures`: as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1592,13 +1758,14 @@ def run_stereo_directory(registration, folder, dataset_seq, stereo, writer=None,
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, stereo=stereo, stereo_rig=stereo_rig,
                       stereo_paths=stereo_paths, stereo_speckle=stereo_speckle, select_mode=select_mode,
-                      depth_median=depth_median, depth_infill=depth_infill, input_binning=input_binning)
+                      depth_median=depth_median, depth_infill=depth_infill, input_binning=input_binning,
+                      photometric=photometric, exposures=exposures)
 
 
 def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, image="image_2", scans="velodyne",
                         times="times.txt", limit=None, generator=None, camera=None, depth_gate=None, mask=None,
                         select_mode=None, depth_median=None, depth_infill=None, lidar_sweep=None, lidar_motion=None,
-                        sweep_fraction=1.0, input_binning=None):
+                        sweep_fraction=1.0, input_binning=None, photometric=None, exposures=None):
     """run_directory() for the KITTI odometry layout with its scans: one line of `folder`/`times` per frame (the line is
     the frame's name), the colour image in `folder`/`image`/%06d.png, decoded by PIL as load_img does (B, G, R; a grey
     image is replicated), and the scan in `folder`/`scans`/%06d.bin, records of four float32 (x y z reflectance).
@@ -1609,7 +1776,8 @@ def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, i
     `sweep_fraction`: as in run_frames, e.g. LidarSweep(SWEEP_AZIMUTH, phase0=0.5, direction=1, s_ref=0.5) and
     "constant-velocity" for records that carry no time, as KITTI's: `direction` is the scanner's sense of rotation,
     `phase0` says at which azimuth its sweep begins and `s_ref` where in the sweep the image is taken.
-    `input_binning`: as in run_frames (the colour image only; the scan is projected into the binned camera)."""
+    `input_binning`: as in run_frames (the colour image only; the scan is projected into the binned camera).
+    `photometric`, `exposures`: as in run_frames."""
     with open(os.path.join(folder, times)) as fh:
         names = [line.strip() for line in fh if line.strip()]
     if limit is not None:
@@ -1627,4 +1795,5 @@ def run_lidar_directory(registration, folder, dataset_seq, lidar, writer=None, i
     return run_frames(registration, decoded(), dataset_seq, writer=writer, generator=generator, camera=camera,
                       depth_gate=depth_gate, mask=mask, select_mode=select_mode, depth_median=depth_median, lidar=lidar,
                       depth_infill=depth_infill, lidar_sweep=lidar_sweep, lidar_motion=lidar_motion,
-                      sweep_fraction=sweep_fraction, input_binning=input_binning)
+                      sweep_fraction=sweep_fraction, input_binning=input_binning, photometric=photometric,
+                      exposures=exposures)

@@ -156,6 +156,19 @@ class registration {
     // refuses.  clear_input_binning(): off, a new object's state.
     void set_input_binning(const cvo_fe_binning &binning);
     void clear_input_binning();
+    // The photometric stage for the colour images of the image form of set_pcd() / run_cvo() of every kind of frame, both
+    // images of a stereo pair: cvo_fe_set_photometric (the photometric contract: cvo_frontend.h).  `response`: 3 x 256
+    // uint16 (B G R) with CVO_FE_PHOTO_RESPONSE, else null; `vignette`: Q12 gains of the size of the images handed over,
+    // rows `vignette_step` bytes apart, with CVO_FE_PHOTO_VIGNETTE, else null.  Both are copied.  A setting of its own,
+    // before or after the first image; throws for what the front end refuses -- a vignette of another size than the
+    // images included, which before the first image shows when that image arrives.  set_photometric_gain(): the gains
+    // (B G R) of the frames that follow under CVO_FE_PHOTO_GAIN (cvo_fe_set_photometric_gain); 1 after
+    // set_photometric().  clear_photometric(): off, a new object's state.
+    void set_photometric(const cvo_fe_photometric &photometric, const uint16_t *response = nullptr,
+                         const uint16_t *vignette = nullptr, int vignette_rows = 0, int vignette_cols = 0,
+                         size_t vignette_step = 0);
+    void clear_photometric();
+    void set_photometric_gain(const float gain[3]);
     // The format of the depth image of the image form of set_pcd() / run_cvo(): cvo_fe_set_depth_format
     // (CVO_FE_DEPTH_U16 with unit 1, a new object's; CVO_FE_DEPTH_F32 / CVO_FE_DEPTH_F16: the depth image_view's data is
     // float32 / float16 in `unit` metres per value and its step the pitch of those rows -- the depth-format contract:
@@ -272,9 +285,15 @@ class registration {
     float depth_unit_;
     cvo_fe_binning binning_;             // what set_input_binning() gave, likewise
     bool have_binning_;
+    cvo_fe_photometric photometric_;     // what set_photometric() gave, likewise, with its tables (dense rows) and the gains
+    bool have_photometric_;
+    std::vector<uint16_t> photo_response_, photo_vignette_;
+    int photo_rows_, photo_cols_;
+    float photo_gain_[3];
     void check(int status, const char *what);
     void fe_check(int status, const char *what, const char *why = nullptr);
     void apply_stored_settings();
+    void apply_photometric();
     template <class S>
     void store(int (*set)(cvo_fe_ctx *, const S *), const char *what, const S *value, S &kept, bool &have);
     void store_mask(const image_view *mask);

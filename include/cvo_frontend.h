@@ -68,7 +68,10 @@
  * cvo_fe_submit_stereo_device).  The device-input contract is stated at cvo_fe_submit_device below.  And frames in the
  * sensor's own resolution (cvo_fe_set_input_binning; cvo_fe_bin_image and cvo_fe_bin_depth for any image): the caller's
  * images are f times the context's size each way, and the first kernel of the frame bins them down to the working size.
- * The binning contract is stated at cvo_fe_binning below.
+ * The binning contract is stated at cvo_fe_binning below.  And the sensor's photometry (cvo_fe_set_photometric;
+ * cvo_fe_photometric_image for any image): a response table, a vignette and a per-frame gain per channel, the caller's
+ * or estimated on the device, correct the colour bytes in place in front of the bin.  The photometric contract is
+ * stated at cvo_fe_photometric below.
  */
 #ifndef CVO_FRONTEND_H
 #define CVO_FRONTEND_H
@@ -136,7 +139,9 @@ enum { CVO_FE_STAGE_GRAY = 0,     /* w*h uint8 */
        CVO_FE_STAGE_SPARSE_DEPTH = 28,    /* S of the infill contract: w*h uint16 */
        CVO_FE_STAGE_INFILL = 29,          /* INFILL of the infill contract: w*h uint8, CVO_FE_INFILL_* */
        /* of a frame under a pixel format (cvo_fe_set_pixel_format; CVO_HIP_ERR_INVALID on a context in
-          CVO_FE_PIXEL_BGR8, and the second on one without stereo as well) */
+          CVO_FE_PIXEL_BGR8, and the second on one without stereo as well).  With the photometric stage set
+          (cvo_fe_set_photometric) both read what that stage wrote, on a BGR8 context too; under binning
+          CVO_FE_STAGE_FULL_BGR / _FULL_RIGHT_BGR below do. */
        CVO_FE_STAGE_INPUT_BGR = 30,       /* the unpacked colour or left image, in front of any rectification: w*h*3 uint8 */
        CVO_FE_STAGE_INPUT_RIGHT_BGR = 31,     /* the unpacked right image: w*h*3 uint8 */
        /* of a frame under input binning (the binning contract at cvo_fe_binning; CVO_HIP_ERR_INVALID without it).  Under
@@ -1310,6 +1315,112 @@ int cvo_fe_project_points_sweep(int device, const void *points, size_t stride_by
                                 const float cam[5], int width, int height, uint16_t *plane, uint16_t *unculled,
                                 uint8_t *flags, int *hits, int *occluded, const cvo_fe_lidar_sweep *sw,
                                 const float twist[6], float *phase, float *moved);
+
+/*
+ * The photometric contract (cvo_fe_set_photometric; off by default).  The pair weight compares colour bytes of two
+ * frames and the selector reads grey gradients of the same bytes, so a surface should give one value in both.  A
+ * sensor's response curve, its lens's vignette and an exposure that changes between frames stand against that.  This
+ * stage corrects the B G R bytes of every colour image by a per-channel response table, a per-pixel vignette gain and
+ * a per-frame gain per channel.  It is this library's own definition, in unsigned integers; tests/fe_photometric_ref.py
+ * restates it.
+ *   Per pixel p (row-major index at the input size iw x ih) and channel c (0, 1, 2 = B, G, R as the image's bytes)
+ *   with input byte b:
+ *       L   = response ? response[c][b] : b << 8           (Q8 value, at most 65535)
+ *       V   = vignette ? vignette[p]    : 4096              (Q12 gain, 4096 = 1)
+ *       A   = L * V                                          (fits 32 bits)
+ *       out = min(255, ((uint64)A * G_c + 2^31) >> 32)       (G_c: Q12, at most 65535)
+ *   Without tables and with G_c = 4096 the stage is the identity by bytes.
+ *   G_c by the flags:
+ *     neither CVO_FE_PHOTO_GAIN nor CVO_FE_PHOTO_AUTO: 4096.
+ *     CVO_FE_PHOTO_GAIN: the gains of cvo_fe_set_photometric_gain, G = (uint32)(gain * 4096.0f + 0.5f) with each
+ *       operation in float32, clamped to [gain_min, gain_max]; 4096 until the first call.  They travel in a header
+ *       that the frame's sequence copies to the device, so a captured frame replays under gains that change.
+ *     CVO_FE_PHOTO_AUTO: estimated on the device from the image itself (the LEFT image of a stereo pair).
+ *       Pixel p counts iff all three of its INPUT bytes lie in [lo, hi] (saturation is the sensor's, so the window
+ *       tests what the sensor gave).  k = the number of such pixels, M_c = the sum over them of A_c(p) >> 12, in 64
+ *       bits.  T_c is the target: settings.target where that is not all zero, else the lock's.
+ *         k < min_count:            G = 4096 on all channels, CVO_FE_PHOTO_FALLBACK; the lock is left as it is.
+ *         target all zero and the lock open (k >= min_count): T_c = (M_c + (k >> 1)) / k, G = 4096, the lock
+ *                                   closes, CVO_FE_PHOTO_LOCKED.
+ *         else, per_channel:        G_c = clamp((T_c * k * 4096 + (M_c >> 1)) / M_c, gain_min, gain_max)
+ *         else:                     one G for all channels from T_0 + T_1 + T_2 and M_0 + M_1 + M_2 in the same way.
+ *         A divisor of zero (any of the three under per_channel): G = 4096 on all channels, CVO_FE_PHOTO_FALLBACK.
+ *       The setter opens the lock; cvo_fe_photometric_rearm opens it again.  With a closed lock T holds.
+ *   A stereo pair: both images go through the same tables and the same G.
+ * Where it sits.  In place on the image the upload, the copy of a device frame or k_fe_unpack left, at the input size
+ * iw x ih: behind the unpack, in front of k_fe_bin (a box mean then averages linearised values) and of everything else.
+ * No later stage changes or learns of it: by bits, the frame is that of a context without the stage fed the corrected
+ * image.  With the stage on CVO_FE_STAGE_INPUT_BGR / _INPUT_RIGHT_BGR (under binning CVO_FE_STAGE_FULL_BGR /
+ * _FULL_RIGHT_BGR) read what the stage wrote, and CVO_FE_STAGE_INPUT_BGR is readable on a BGR8 context too.
+ * Not part of it: tables or gains of its own for the right camera; estimating response or vignette; smoothing AUTO
+ * gains over time; more than 8 bits per channel behind the stage.
+ */
+enum { CVO_FE_PHOTO_RESPONSE = 1, CVO_FE_PHOTO_VIGNETTE = 2, CVO_FE_PHOTO_GAIN = 4, CVO_FE_PHOTO_AUTO = 8 };
+/* flags of cvo_fe_photometric_frame */
+enum { CVO_FE_PHOTO_FALLBACK = 1, CVO_FE_PHOTO_LOCKED = 2 };
+typedef struct cvo_fe_photometric {
+    uint32_t flags;        /* OR of CVO_FE_PHOTO_RESPONSE, _VIGNETTE, _GAIN, _AUTO; _GAIN and _AUTO exclude each other */
+    int32_t lo, hi;        /* 0 <= lo <= hi <= 255: the window of AUTO on the input bytes, both ends inside */
+    int32_t min_count;     /* >= 1: AUTO falls back to G = 4096 with fewer counted pixels */
+    int32_t per_channel;   /* 0: one gain for all channels; 1: one per channel */
+    uint32_t target[3];    /* T_c in Q8 times the vignette's gain, B G R, each <= 65535; all zero: the lock */
+    int32_t gain_min, gain_max;   /* Q12: 1 <= gain_min <= gain_max <= 65535 */
+    int32_t pad_;          /* must be 0 */
+} cvo_fe_photometric;      /* 44 bytes, no padding */
+typedef struct cvo_fe_photometric_frame {
+    uint32_t gain[3];      /* G_c the frame was corrected with, Q12 */
+    uint32_t flags;        /* CVO_FE_PHOTO_FALLBACK, CVO_FE_PHOTO_LOCKED */
+    uint64_t count;        /* k (0 without AUTO) */
+    uint64_t sum[3];       /* M_c (0 without AUTO) */
+    uint32_t target[3];    /* T_c in force behind the frame (0 without AUTO, and while the lock is open) */
+    uint32_t pad_;
+} cvo_fe_photometric_frame;   /* 64 bytes, no padding */
+
+/* CVO_HIP_OK for settings and tables cvo_fe_set_photometric() would accept, CVO_HIP_ERR_INVALID otherwise: NULL; a flag
+ * outside the four; _GAIN together with _AUTO; lo, hi outside 0 <= lo <= hi <= 255; min_count < 1; per_channel outside
+ * {0, 1}; a target above 65535; gain_min, gain_max outside 1 <= gain_min <= gain_max <= 65535; pad_ != 0;
+ * have_response != (flags & _RESPONSE != 0); have_vignette != (flags & _VIGNETTE != 0); flags == 0 (that, with no
+ * tables, is how the setter is told "off", and is no setting).  The one statement of what is accepted.  Host only. */
+int cvo_fe_check_photometric(const cvo_fe_photometric *p, int have_response, int have_vignette);
+/* The stage for every following frame of any kind.  `response`: 3 x 256 uint16, B G R; `vignette`: iw x ih uint16 in rows
+ * `vignette_stride` bytes apart, iw x ih the size of the images a frame takes (under input binning factor times the
+ * context's).  Both are copied before the call returns.  p == NULL, or flags == 0 with both tables NULL: off, a new
+ * context's state; the stage's memory is given back and a frame launches what it launched before.  A setting of its
+ * own: it survives every other setter in either order.  Every call opens the lock of AUTO and puts the caller's gains
+ * back to 1.  CVO_HIP_ERR_INVALID, the context keeping what it had: a null context; a frame in flight; what
+ * cvo_fe_check_photometric refuses; a vignette stride below iw * 2 or odd.  With a vignette set,
+ * cvo_fe_set_input_binning refuses a change of the input size: set the stage off first, then the binning, then the
+ * stage with a vignette of the new size. */
+int cvo_fe_set_photometric(cvo_fe_ctx *ctx, const cvo_fe_photometric *p, const uint16_t *response, const uint16_t *vignette,
+                           size_t vignette_stride);
+/* The settings in force (zeroes and *set = 0 without); the tables are not handed back. */
+int cvo_fe_get_photometric(const cvo_fe_ctx *ctx, cvo_fe_photometric *out, int *set);
+/* The gains (B, G, R) of the frames submitted from now on, under CVO_FE_PHOTO_GAIN; they hold until changed.  May be
+ * called between any two frames; no graph is dropped.  CVO_HIP_ERR_INVALID: a null argument; the stage not set with
+ * CVO_FE_PHOTO_GAIN; a gain that is not finite or outside [1/16, 15.99]. */
+int cvo_fe_set_photometric_gain(cvo_fe_ctx *ctx, const float gain[3]);
+/* Opens the lock of AUTO: the next frame with k >= min_count sets T.  CVO_HIP_ERR_INVALID without CVO_FE_PHOTO_AUTO. */
+int cvo_fe_photometric_rearm(cvo_fe_ctx *ctx);
+/* The record of the last collected frame.  CVO_HIP_ERR_INVALID: a null argument; the stage not set. */
+int cvo_fe_get_photometric_frame(const cvo_fe_ctx *ctx, cvo_fe_photometric_frame *out);
+/* The contract on any image by the kernels a frame runs, without a context: host arrays in and out.  `bgr` is width x
+ * height x 3 in rows `stride` bytes apart and is not written; `out` is dense.  `vignette` is width x height in rows
+ * `vignette_stride` bytes apart.  `gains_q12` (B, G, R; NULL: 4096) is read under CVO_FE_PHOTO_GAIN and clamped as the
+ * contract says.  Under CVO_FE_PHOTO_AUTO the image is a first frame: with a target of all zero it closes the lock.
+ * `frame_out` may be NULL.  CVO_HIP_ERR_INVALID: a null image; width or height outside [1, 8192]; a stride below the
+ * row; what cvo_fe_check_photometric refuses; CVO_HIP_ERR_NODEVICE without such a device. */
+int cvo_fe_photometric_image(int device, const uint8_t *bgr, int width, int height, size_t stride,
+                             const cvo_fe_photometric *settings, const uint16_t *response, const uint16_t *vignette,
+                             size_t vignette_stride, const uint32_t gains_q12[3], uint8_t *out,
+                             cvo_fe_photometric_frame *frame_out);
+/* A row of the response table from the inverse response of one channel (a row of DSO's pcalib.txt: the irradiance, in
+ * [0, 255], of each of the 256 pixel values): out = min(65535, (uint32)(v * 256.0f + 0.5f)), each operation in float32.
+ * CVO_HIP_ERR_INVALID: a null pointer; a value that is not finite or outside [0, 255].  Host only. */
+int cvo_fe_response_table(const float inv[256], uint16_t out[256]);
+/* The vignette's gains from its attenuations (the plane of DSO's vignette.png as 16-bit values, 65535 = none):
+ * out = a ? min(65535, (4096 * 65535 + a / 2) / a) : 65535.  `out` may be `atten`.  CVO_HIP_ERR_INVALID: a null pointer
+ * with n > 0.  Host only. */
+int cvo_fe_vignette_gains(const uint16_t *atten, size_t n, uint16_t *out);
 #ifdef __cplusplus
 }
 #endif
